@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — HEATNet4 training-step throughput on synthetic WSI graphs (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: re-executes itself under torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W          (N > 1: starts itself under torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch: forward + cross-entropy + backward of
@@ -84,7 +84,12 @@ def parse():
     ap.add_argument("--one-device", action="store_true",
                     help="TESTING ONLY: every rank uses cuda:0 (dry run of the multi-rank code path on a 1-GPU box; never for reported numbers)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend (nccl = RCCL; gloo with --one-device)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                                                          "(rank 0; see dump_outputs): two builds run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def dense_flops(N, in_dim, D, L):
@@ -108,10 +113,35 @@ def whole_model_bytes(N, E, F, D, L):
     return 3 * dense_fwd + edge_bytes(N, E, D, L)
 
 
-def launch_ranks(args, one_dev: bool) -> None:
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: check the box has N GPUs, then replace this process
-    by `torch.distributed.run --nproc-per-node N bench.py <same arguments>` (one rank per GPU over RCCL).  Never returns."""
+DUMP_SAMPLE = 1 << 22       # values kept of a flat output larger than this (16 MiB as float32): the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, logits, loss, params):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files - ``logits`` [graphs, classes], ``loss`` (a scalar),
+    ``grads`` (the gradients the step left in ``.grad``, zeros for a parameter without one) and ``params`` (the parameters after the optimizer
+    step), both flat over ``params`` in order.  A flat output of more than DUMP_SAMPLE values keeps the same seeded sample of positions in every
+    run of the same arguments.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    weights = torch.cat([p.detach().reshape(-1) for p in params])
+    if grads.numel() > DUMP_SAMPLE:
+        keep = torch.randperm(grads.numel(), generator=torch.Generator().manual_seed(611))[:DUMP_SAMPLE].sort().values.to(grads.device)
+        grads, weights = grads[keep], weights[keep]
+    arrays = {"logits": logits, "loss": loss, "grads": grads, "params": weights}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+    return sorted(arrays)
+
+
+def launch_ranks(args, one_dev: bool) -> int:
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: check the box has N GPUs, then run
+    `torch.distributed.run --nproc-per-node N bench.py <same arguments>` (one rank per GPU over RCCL) as a child process and
+    return its exit status.  A child, not an exec: a process that has opened the GPU must not replace its own program, and
+    this one does no GPU work of its own while the ranks run.  SIGTERM / SIGINT are passed on to the launcher."""
+    import signal
     import socket
+    import subprocess
     ndev = torch.cuda.device_count()
     if ndev < args.gpus and not one_dev:
         print(f"bench.py: --gpus {args.gpus} requested but this box has {ndev} GPU(s); refusing to report an {args.gpus}-GPU "
@@ -125,7 +155,11 @@ def launch_ranks(args, one_dev: bool) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     print("[bench] launching: " + " ".join(cmd), file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    proc = subprocess.Popen(cmd)
+    for sig in (signal.SIGTERM, signal.SIGINT):
+        signal.signal(sig, lambda signum, _frame: proc.send_signal(signum))
+    rc = proc.wait()
+    return 128 - rc if rc < 0 else rc
 
 
 def cpu_info():
@@ -159,15 +193,15 @@ def cpu_info():
 
 def main():
     args = parse()
-    if not torch.cuda.is_available():
-        print("bench.py needs a GPU (the HIP kernels have no CPU fallback)", file=sys.stderr)
-        sys.exit(2)
     # --one-device --backend gloo: dry-run of the multi-rank code path on a 1-GPU box
     # (all ranks share cuda:0, collectives go through gloo) - for testing only, never for reported numbers
     one_dev = args.one_device
     backend = args.backend
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        launch_ranks(args, one_dev)
+        sys.exit(launch_ranks(args, one_dev))         # before anything here initialises the GPU: the ranks check for one themselves
+    if not torch.cuda.is_available():
+        print("bench.py needs a GPU (the HIP kernels have no CPU fallback)", file=sys.stderr)
+        sys.exit(2)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -237,6 +271,8 @@ def main():
         from wsi_hgnn_amd.optim import Adam as WsiAdam
         opt = WsiAdam(bucket.params, lr=1e-5, weight_decay=5e-3)
 
+    kept = {}                                       # --dump-outputs: the logits of the latest step
+
     def step():
         opt.zero_grad(set_to_none=True)
         o = model(G)
@@ -246,6 +282,8 @@ def main():
         with ops._Timed("grad_allreduce"):          # what is left of the collective after backward
             bucket.all_reduce_mean()
         opt.step()
+        if args.dump_outputs:
+            kept["logits"] = o
         return l
 
     ops.set_gemm_precision(args.gemm)
@@ -279,6 +317,9 @@ def main():
         marks[i + 1].record()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:             # before any later leg runs another step
+        names = dump_outputs(args.dump_outputs, kept["logits"], last, bucket.params)
+        print(f"[bench] --dump-outputs: {', '.join(names)} of the last timed step -> {args.dump_outputs}", file=sys.stderr, flush=True)
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     ms_median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     if world > 1:
