@@ -1263,11 +1263,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_fp16x3g_kernel(const Gem
     }
 }
 
-// (the 2 x 2 wave-grid form of this kernel, round 5's negative result - bit-identical, 5-7 % slower - lives in gemm_emu16_ablate.inc: measurement build only)
-#ifdef WSI_ABLATE
-#include "gemm_emu16_ablate.inc"
-#endif
-
 // The fp16x3 pre-pass of a launch: the absmax bits of A per output row (absmax_rows_kernel, unless the caller supplied
 // them) and, per distinct B, ONE pack_b_frag_kernel workgroup row that finds the absmax of its 32 output columns and
 // writes their planes - every scale word a group uses is written by exactly one of the two (no clearing, no atomics).
@@ -1392,17 +1387,6 @@ void launch_gemm_fp16x3(int op, GemmParams& P, int tiles, unsigned lds_pad, floa
         P.plain_stores = 0;
 #ifdef WSI_ABLATE
         { const char* e = knob("WSI_F16G_EPI"); P.ablate_guarded = (e && e[0] == 'g') ? 1 : 0; }
-        const char* v = knob("WSI_GEMM_F16_KERNEL");
-        if (v && v[0] == 'q') { hipLaunchKernelGGL(gemm_fp16x3q_kernel, g, b, lds_pad, st, P, ws); return; }
-        if (v && v[0] == 'p') {              // persistent form: every group needs an even number of stages
-            bool ok = true;
-            for (int i = 0; i < P.ngroups; ++i) ok = ok && (P.g[i].K / GK) >= 2 && ((P.g[i].K / GK) % 2 == 0);
-            if (ok) {
-                const int slots = 512;       // 2 workgroups per CU x 256 CUs
-                hipLaunchKernelGGL(gemm_fp16x3p_kernel, dim3(tiles < slots ? tiles : slots), b, lds_pad, st, P, ws);
-                return;
-            }
-        }
 #endif
         hipLaunchKernelGGL(gemm_fp16x3g_kernel, g, b, lds_pad, st, P, ws);
     }
