@@ -9,6 +9,9 @@ HEATNet4(1024,512,2,2 layers,4 heads) on a block-diagonal batch of 8 synthetic 1
 graphs per GPU (BASELINE configs[2]/[3]), gradient all-reduce (N>1) and the Adam step
 (the reference's optimizer, parser.py:33-38) — inputs resident in HBM before the timed region.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; every other measurement
+(per-kernel pass, PMC traffic, side legs, CPU baseline) runs only with --full and is null in the line otherwise.
 """
 import argparse
 import json
@@ -56,6 +59,10 @@ def parse():
                          "bf16 split, 6 cross products; fp32 = v_mfma_f32_32x32x2_f32; auto (default, what `value` is quoted on) = per "
                          "launch fp16x3 where its pre-pass is amortised (every projection of the default workload), else bf16x6.  The "
                          "other modes are timed too and reported as other_gemm_modes")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run everything else the line reports: the per-kernel HIP-event pass (roofline, edge_phase_roofline, "
+                         "grad_allreduce.ms_per_step), the PMC passes behind roofline.traffic, fwd_bwd_only, full_depth_last_layer, training_config, "
+                         "other_gemm_modes, single_graph_step, knn_locality and cpu_baseline.  The --no-* options below drop single legs of a --full run")
     ap.add_argument("--no-alt-gemm", action="store_true", help="skip the extra timed leg in the other GEMM arithmetic")
     ap.add_argument("--no-knn", action="store_true", help="skip the extra leg on WSI-like kNN graphs in locality order (`knn_locality`)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -75,8 +82,8 @@ def parse():
     ap.add_argument("--pmc", dest="pmc", action="store_true", default=None,
                     help="measure roofline.traffic in THIS run: re-execute the workload (2 steps) twice under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` "
                          "(separate passes, no trace domains, as the MI355X guide prescribes; FETCH x2 gfx950 correction) and read the per-kernel fabric-side "
-                         "bytes from their CSVs.  DEFAULT since round 6 whenever rocprofv3 is on the box and the run is the one-GPU default workload "
-                         "(~40 s for the two child runs); --no-pmc reads the figure from the committed summary of the same passes instead (labelled)")
+                         "bytes from their CSVs.  --full only; the default of a --full run whenever rocprofv3 is on the box and the run is the one-GPU default "
+                         "workload (~40 s for the two child runs); --no-pmc reads the figure from the committed summary of the same passes instead (labelled)")
     ap.add_argument("--no-pmc", dest="pmc", action="store_false")
     ap.add_argument("--dp-overlap", type=int, default=1, choices=[0, 1],
                     help="N > 1: 1 = the gradient all-reduce goes out in pieces from autograd hooks while backward runs (GradBucket(overlap=True)), "
@@ -89,6 +96,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.pmc and not args.full:
+        ap.error("--pmc measures roofline.traffic, which only a --full run reports")
     return args
 
 
@@ -357,7 +366,7 @@ def main():
         rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
         if not os.path.exists(rocprof):
             return None
-        child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt-gemm", "--no-knn", "--no-full-depth",
+        child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt-gemm", "--no-knn", "--no-full-depth",
                  "--no-captured", "--no-training-config", "--no-kernel-timing", "--no-pmc", "--batch", str(args.batch), "--nodes", str(args.nodes), "--in-dim", str(args.in_dim),
                  "--hidden", str(args.hidden), "--layers", str(args.layers), "--heads", str(args.heads), "--model", args.model, "--dst-mode", args.dst_mode,
                  "--schema", args.schema, "--dropout", str(args.dropout), "--gemm", args.gemm]
@@ -383,8 +392,8 @@ def main():
 
     default_run = (args.schema == "synthetic" and args.model == "HEATNet4" and args.batch == 8 and args.nodes == 10000 and args.hidden == 512
                    and args.dst_mode == "uniform" and args.dropout == 0.0 and args.slide_sizes == "equal" and not args.no_kernel_timing)
-    want_pmc = args.pmc if args.pmc is not None else default_run          # default: on for the driver's plain `python bench.py`
-    if want_pmc and world == 1:
+    want_pmc = args.pmc if args.pmc is not None else default_run          # default: on for `python bench.py --full`
+    if args.full and want_pmc and world == 1:
         try:
             pmc_live = measure_pmc()
         except Exception as exc:          # (the profiler missing or refusing must not cost the bench line)
@@ -418,7 +427,7 @@ def main():
                 tot += float(r["hbm_MB_per_launch"]) * 1e6 * int(r["launches"])
                 n += int(r["launches"])
         return round(tot / n) if n else None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         ops.enable_kernel_timing(True)
         ops.set_background_weight_gradients(False)     # every launch in order on ONE stream while it is bracketed by events: a dW running under
         ksteps = max(3, min(args.steps, 10))           # an attention backward has no duration of its own
@@ -523,32 +532,34 @@ def main():
                           "traffic_source": pmc_source() + "; fabric-side bytes per attention-kernel launch, Infinity-Cache hits included"}
 
     # ---- SURVEY 8(d)'s narrower definition of the metric: forward + loss + backward only (no all-reduce, no optimizer)
-    def fb_step():
-        opt.zero_grad(set_to_none=True)
-        l = loss_fn(model(G), labels)
-        l.backward()
-        return l
-    for _ in range(2):
-        fb_step()
-    sync()
-    f0 = time.perf_counter()
-    for _ in range(args.steps):
-        fb_step()
-    sync()
-    fdt = time.perf_counter() - f0
-    if world > 1:
-        ft = torch.tensor([fdt], device=dev, dtype=torch.float64)
-        dist.all_reduce(ft, op=dist.ReduceOp.MAX)
-        fdt = ft.item()
-    fwd_bwd_only = {"value": total_edges * args.steps / fdt, "unit": "edges/s", "ms_per_step": fdt / args.steps * 1e3,
-                    "note": "forward + CrossEntropy + backward only (the timed region SURVEY 8d defines); `value` above also "
-                            "includes the gradient all-reduce and the Adam step"}
+    fwd_bwd_only = None
+    if args.full:
+        def fb_step():
+            opt.zero_grad(set_to_none=True)
+            l = loss_fn(model(G), labels)
+            l.backward()
+            return l
+        for _ in range(2):
+            fb_step()
+        sync()
+        f0 = time.perf_counter()
+        for _ in range(args.steps):
+            fb_step()
+        sync()
+        fdt = time.perf_counter() - f0
+        if world > 1:
+            ft = torch.tensor([fdt], device=dev, dtype=torch.float64)
+            dist.all_reduce(ft, op=dist.ReduceOp.MAX)
+            fdt = ft.item()
+        fwd_bwd_only = {"value": total_edges * args.steps / fdt, "unit": "edges/s", "ms_per_step": fdt / args.steps * 1e3,
+                        "note": "forward + CrossEntropy + backward only (the timed region SURVEY 8d defines); `value` above also "
+                                "includes the gradient all-reduce and the Adam step"}
 
     # ---- the same K steps with the last layer run in the reference's order of operations (DESIGN 3.7 switched off: its output formed for every
     # node, a readout pass over it, V projected, N-deep backward).  Same outputs and gradients to fp32 rounding (tests); reported beside
     # `value` so that both formulations of the same arithmetic are on record.
     full_depth = None
-    if args.model in ("HEATNet4", "HEATNet2") and getattr(model, "fuse_readout", False) and not args.no_full_depth:
+    if args.full and args.model in ("HEATNet4", "HEATNet2") and getattr(model, "fuse_readout", False) and not args.no_full_depth:
         model.fuse_readout = False
         ops.set_low_rank_readout_grad(False)
         ops.set_value_collapse(False)
@@ -582,7 +593,7 @@ def main():
     # models/HEATNet4.py:77,134).  The dropout sits between the last layer's output projection and the readout, so that layer runs at full depth
     # (DESIGN 3.7 does not apply); the masks are functions of (seed, row, column) applied in the projection epilogues (ops.CounterDropout).
     training_config = None
-    if args.model in ("HEATNet4", "HEATNet2") and args.dropout == 0.0 and not args.no_training_config:
+    if args.full and args.model in ("HEATNet4", "HEATNet2") and args.dropout == 0.0 and not args.no_training_config:
         p_ref = 0.2
         for layer in model.gcs:
             layer.drop.p = p_ref
@@ -613,7 +624,7 @@ def main():
 
     # ---- the same K steps in the other GEMM arithmetic (reported beside `value`, never as `value`)
     alts = []
-    if world == 1 and not args.no_alt_gemm:
+    if args.full and world == 1 and not args.no_alt_gemm:
         for other in [m for m in ("bf16x6", "fp16x3", "auto", "fp32") if m != args.gemm]:   # exact fp32 last: its power draw lowers the clocks of a short leg timed right after it
             ops.set_gemm_precision(other)
             for _ in range(max(2, args.warmup)):
@@ -638,7 +649,7 @@ def main():
     # issue than the GPU to run; trainer.CapturedStep records it into one hipGraph.  Eager and replayed, same model / graph / optimizer.
     # An extra field, never `value`.
     captured = None
-    if world == 1 and not args.no_captured and args.schema == "synthetic" and args.model in ("HEATNet4", "HEATNet2"):
+    if args.full and world == 1 and not args.no_captured and args.schema == "synthetic" and args.model in ("HEATNet4", "HEATNet2"):
         # in a SUBPROCESS: an invalid capture is a segfault on this ROCm, not an exception, and a side measurement must not be able to take
         # the headline line down with it
         import subprocess
@@ -666,7 +677,7 @@ def main():
     # ---- the graphs the reference actually produces: kNN in feature space (8 out-edges per patch, skewed in-degree), in locality
     # order.  An extra field, never `value` (BASELINE's metric is quoted on the uniformly random synthetic graphs above).
     knn = None
-    if world == 1 and not args.no_knn and args.schema == "synthetic" and args.model in ("HEATNet4", "HEATNet2"):
+    if args.full and world == 1 and not args.no_knn and args.schema == "synthetic" and args.model in ("HEATNet4", "HEATNet2"):
         try:
             t_build = time.perf_counter()
             kg = [synthetic.knn_slide(args.nodes, args.in_dim, seed=100 + i, device=dev, n_types=n_types) for i in range(args.batch)]
@@ -768,7 +779,7 @@ def main():
     # one graph of the workload, fwd+loss+bwd, median of 10 after 2 warm-ups, at k = 8 threads and k = all physical
     # cores; CPU model and core counts stated.
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import statistics
         from oracle import models as OM
         torch.manual_seed(611)

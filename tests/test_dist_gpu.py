@@ -244,8 +244,8 @@ def test_bench_refuses_more_gpus_than_the_box_has():
 
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it starts 2 ranks itself (here: both on cuda:0 over gloo, the
-    documented dry-run knobs) and reports n_gpus = ranks = 2 with the all-reduce timed."""
-    r = _run_bench(["--gpus", "2", "--one-device", "--backend", "gloo"] + SMALL, {})
+    documented dry-run knobs) and reports n_gpus = ranks = 2 with the all-reduce timed (by the per-kernel pass of --full)."""
+    r = _run_bench(["--gpus", "2", "--one-device", "--backend", "gloo", "--full"] + SMALL, {})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
