@@ -120,12 +120,15 @@ int wsi_heat_pool_gtab(const float* h, int64_t ldh, int32_t D, int32_t H, const 
 
 /*
  * Backward of the above (the autograd of DGL's SDDMM/SpMM/edge_softmax that loss.backward() reaches
- * from trainer/train_gnn.py:70).  Three deterministic, atomic-free passes:
- *   pass 1 (dst-major, gathers v): a[e,h] = exp(score - lse)  (written over `score`),
- *                                  ga[e,h] = (g_t[w]/R_w)[h,:] . v[src,h,:]
+ * from trainer/train_gnn.py:70).  Three deterministic, atomic-free passes; without a pool descriptor:
+ *   pass A (src-major over CSC, gathers g_t; v[u] is the wave's own row):
+ *                                  a[e,h] = exp(score - lse)  (written over `score`),
+ *                                  ga[e,h] = (g_t[w]/R_w)[h,:] . v[u,h,:],  g_v[u] = sum a*g_t[w]/R_w
  *   pass 2 (dst-major, gathers k): delta, g_s = a*(ga-delta); g_q[w]; gsc[e,h] = g_s*ea/sqrt_dk;
  *                                  gea[e,h] = g_s * (q.k)/sqrt_dk
- *   pass 3 (src-major over CSC)  : g_k[u] = sum gsc*q[w],  g_v[u] = sum a*g_t[w]/R_w
+ *   pass C (src-major over CSC, gathers q): g_k[u] = sum gsc*q[w]
+ * so that g_t, k and q each cross the fabric once per edge; with a pool descriptor (and in the generic kernels) pass 1 (dst-major,
+ * gathers v or reads a table: a, ga) and pass 3 (src-major: g_k and, generic, g_v) take the place of A and C;
  * and a fixed-shape two-stage reduction  g_e_weight = sum gea*sim,  g_e_bias = sum gea.
  * Every row of gq/gk/gv is written (zeros for nodes without edges): no memset needed.
  *   colptr[num_src+1], csc_eid[E] (CSR edge id), csc_dst[E] (global dst): CSC by source ROW of the k/v tables

@@ -1,10 +1,11 @@
 // HEAT relation attention for gfx950: fused per-relation edge softmax + neighbour aggregation (forward)
-// and its three-pass atomic-free backward.  See include/wsi_hgnn.h for the contract and the reference
+// and its three-pass atomic-free backward (non-pooled: source-major pass A, dst-major pass 2, source-major
+// pass C; pooled: passes 1, 2, 3).  See include/wsi_hgnn.h for the contract and the reference
 // call sites (models/HEATNet4.py:103-119) these kernels replace.
 //
 // Mapping (MI355X-first, not a translation of DGL's SDDMM/SpMM pair):
 //   * one 64-lane wavefront owns one destination node (forward, backward passes 1-2) or one source
-//     node (pass 3); lane l holds V = D/64 contiguous floats of every 2 KB feature row, so a row
+//     node (passes A, C, 3); lane l holds V = D/64 contiguous floats of every 2 KB feature row, so a row
 //     gather is one fully coalesced wave-wide access and head h lives in LPH = 64/H adjacent lanes;
 //   * per-head dot products reduce over those LPH lanes with DPP (quad_perm / row_mirror), no LDS;
 //   * all indices (segment pointers, edge ids, src ids, sim) are wave-uniform -> scalar (SMEM) loads,
@@ -20,6 +21,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <mutex>
+#include <type_traits>
 #include <new>
 
 namespace wsi {
@@ -533,7 +535,9 @@ __global__ __launch_bounds__(kBlock) void heat_attn_bwd_p2_kernel(
 
 // ------------------------------------------------------------------------------------------ backward pass 3
 // src-major over the CSC:  g_k[u] = sum_j gsc[eid_j]*q[w_j];   g_v[u] = sum_j a[eid_j]*g_t[w_j]/R_{w_j}
-template <int V, int LPH, int U, bool POOL = false>
+// KONLY (pass C of the source-major backward): g_k only - pass A already wrote g_v and slot 1 of the absmax table, which this wave
+// raises to max(bits(g_k), bits(g_v)); one gathered row per edge (q) instead of two.
+template <int V, int LPH, int U, bool POOL = false, bool KONLY = false>
 __global__ __launch_bounds__(kBlock) void heat_attn_bwd_p3_kernel(
     const float* __restrict__ qtab, int64_t ldq, const float* __restrict__ g_t, int64_t ldgt,
     const int32_t* __restrict__ colptr, const int32_t* __restrict__ csc_eid, const int32_t* __restrict__ csc_dst,
@@ -570,11 +574,11 @@ __global__ __launch_bounds__(kBlock) void heat_attn_bwd_p3_kernel(
                 const int eid = csc_eid[j + x];
                 const int w = csc_dst[j + x];
                 const int64_t o = (int64_t)eid * H + head;
-                aa[x] = a[o] * inv_rd[w];
+                if constexpr (!KONLY) aa[x] = a[o] * inv_rd[w];
                 gg[x] = gsc[o];
                 load_vec<V>(qq[x], qtab + (int64_t)w * ldq + col);
                 if constexpr (POOL) bin[x] = pool.ctab_ready ? -1 : pool.row_seg[w] / pool.segs_per_type;
-                else load_vec<V>(gt[x], g_t + (int64_t)(gt_row ? gt_row[w] : w) * ldgt + col);
+                else if constexpr (!KONLY) load_vec<V>(gt[x], g_t + (int64_t)(gt_row ? gt_row[w] : w) * ldgt + col);
             }
         }
 #pragma unroll
@@ -583,7 +587,7 @@ __global__ __launch_bounds__(kBlock) void heat_attn_bwd_p3_kernel(
 #pragma unroll
                 for (int i = 0; i < V; ++i) {
                     gka[i] = fmaf(gg[x], qq[x][i], gka[i]);
-                    if constexpr (!POOL) gva[i] = fmaf(aa[x], gt[x][i], gva[i]);
+                    if constexpr (!POOL && !KONLY) gva[i] = fmaf(aa[x], gt[x][i], gva[i]);
                 }
                 if constexpr (POOL) {
 #pragma unroll
@@ -625,12 +629,112 @@ __global__ __launch_bounds__(kBlock) void heat_attn_bwd_p3_kernel(
             const uint32_t bmax = wave_absmax_bits<V>(gka);
             if (lane == 0) absmax[2 * (int64_t)u + 1] = bmax;
         }
+    } else if constexpr (KONLY) {
+        if (absmax) {
+            const uint32_t b = wave_absmax_bits<V>(gka);
+            if (lane == 0) absmax[2 * (int64_t)u + 1] = max(b, absmax[2 * (int64_t)u + 1]);
+        }
     } else {
         store_vec<V>(gv + (int64_t)u * ldgv + col, gva);
         if (absmax) {
             const uint32_t b = max(wave_absmax_bits<V>(gka), wave_absmax_bits<V>(gva));
             if (lane == 0) absmax[2 * (int64_t)u + 1] = b;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ source-major backward: edge -> segment map
+// thread = CSR edge e:  seg[e] = the softmax segment s with rowptr[s] <= e < rowptr[s+1] (the last s in [node_seg[0], node_seg[N]) with
+// rowptr[s] <= e; empty segments share their rowptr value with the next one and are stepped over).  Pass A reads it to index lse.
+__global__ __launch_bounds__(256) void heat_attn_edge_seg_kernel(const int32_t* __restrict__ node_seg, const int32_t* __restrict__ rowptr,
+                                                                 int32_t num_nodes, int32_t E, int32_t* __restrict__ seg) {
+    const int e = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (e >= E) return;
+    int lo = node_seg[0], hi = node_seg[num_nodes];
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rowptr[mid] <= e) lo = mid;
+        else hi = mid;
+    }
+    seg[e] = lo;
+}
+
+// ------------------------------------------------------------------------------------------ source-major backward: pass A
+// src-major over the CSC, gathers g_t only: v[u] is the wave's own row, loaded once.  Per CSC entry (eid, w):
+//   a[eid,h] = exp(score - lse[seg(eid)])  (in place),   ga[eid,h] = (g_t[w]/R_w)[h,:] . v[u,h,:],   g_v[u] += a/R_w * g_t[w]
+// ga takes exactly the float operations of pass 1 (g_t scaled by 1/R_w first, fma over i ascending, group_sum), g_v those of pass 3
+// (a*inv_rd[w], fma over CSC j ascending): bit-identical to the dst-major pair.  Slot 1 of the absmax table gets bits(g_v); pass C
+// raises it to max(bits(g_k), bits(g_v)).  Replaces pass 1 and the g_v half of pass 3: the v gather of pass 1 is gone.
+template <int V, int LPH, int U>
+__global__ __launch_bounds__(kBlock) void heat_attn_bwd_srcA_kernel(
+    const float* __restrict__ vtab, int64_t ldv, const float* __restrict__ g_t, int64_t ldgt, const int32_t* __restrict__ gt_row,
+    const int32_t* __restrict__ node_seg, const int32_t* __restrict__ edge_seg,
+    const int32_t* __restrict__ colptr, const int32_t* __restrict__ csc_eid, const int32_t* __restrict__ csc_dst,
+    const float* __restrict__ inv_rd, const int32_t* __restrict__ order, int32_t num_nodes, int32_t xcd,
+    const float* score_in, float* score_a, const float* __restrict__ lse, float* __restrict__ ga,
+    float* __restrict__ gv, int64_t ldgv, uint32_t* __restrict__ absmax) {
+    constexpr int H = 64 / LPH;
+    const int lane = threadIdx.x & 63;
+    const int blk = xcd ? attn_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    int wave = blk * kWavesPerBlock + (int)(threadIdx.x >> 6);
+    wave = __builtin_amdgcn_readfirstlane(wave);
+    if (wave >= num_nodes) return;
+    int u = order ? order[wave] : wave;
+    u = __builtin_amdgcn_readfirstlane(u);
+    const int head = lane / LPH;
+    const bool leader = (lane % LPH) == 0;
+    const int col = lane * V;
+
+    float gva[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) gva[i] = 0.f;
+    const int j0 = colptr[u], j1 = colptr[u + 1];
+    if (j1 > j0) {
+        float vu[V];
+        load_vec<V>(vu, vtab + (int64_t)u * ldv + col);
+        for (int j = j0; j < j1; j += U) {
+            float gt[U][V];
+            float sc[U], ls[U], ir[U], ird[U];
+            int eid[U];
+#pragma unroll
+            for (int x = 0; x < U; ++x) {
+                if (j + x < j1) {
+                    eid[x] = csc_eid[j + x];
+                    const int w = csc_dst[j + x];
+                    sc[x] = score_in[(int64_t)eid[x] * H + head];
+                    ls[x] = lse[(int64_t)edge_seg[eid[x]] * H + head];
+                    ir[x] = 1.f / (float)(node_seg[w + 1] - node_seg[w]);
+                    ird[x] = inv_rd[w];
+                    load_vec<V>(gt[x], g_t + (int64_t)(gt_row ? gt_row[w] : w) * ldgt + col);
+                }
+            }
+#pragma unroll
+            for (int x = 0; x < U; ++x) {
+                if (j + x < j1) {
+                    const float a = expf(sc[x] - ls[x]);
+                    float d = 0.f;
+#pragma unroll
+                    for (int i = 0; i < V; ++i) {
+                        const float gm = gt[x][i] * ir[x];
+                        d = fmaf(gm, vu[i], d);
+                    }
+                    d = group_sum<LPH>(d);
+                    const float aa = a * ird[x];
+#pragma unroll
+                    for (int i = 0; i < V; ++i) gva[i] = fmaf(aa, gt[x][i], gva[i]);
+                    if (leader) {
+                        const int64_t o = (int64_t)eid[x] * H + head;
+                        score_a[o] = a;
+                        ga[o] = d;
+                    }
+                }
+            }
+        }
+    }
+    store_vec<V>(gv + (int64_t)u * ldgv + col, gva);
+    if (absmax) {
+        const uint32_t b = wave_absmax_bits<V>(gva);
+        if (lane == 0) absmax[2 * (int64_t)u + 1] = b;
     }
 }
 
@@ -990,6 +1094,7 @@ static void hub_join(hipStream_t st, SideStream* side) {
 template <int V, int LPH>
 struct Unroll { static constexpr int value = (V >= 8) ? 2 : 4; };
 
+
 template <int V, int LPH>
 int launch_fwd(const AttnTables& tb, const AttnGraph& g, const float* ew, const float* eb, float isd,
                float* t, int64_t ldt, float* score, float* lse, SideStream* ctx, hipStream_t st) {
@@ -1058,6 +1163,38 @@ int launch_bwd(const AttnTables& tb, const AttnGraph& gd, int32_t num_src, int32
     const int sblocks = (num_src + kWavesPerBlock - 1) / kWavesPerBlock;
     const bool ph = pool && pool->h;            // pass 1 gathers the layer input instead of v
     const bool pflat = pool && pool->gtab;      // pass 1 is a per-edge lookup: one flat launch ahead of everything else
+    // Non-pooled: source-major backward.  Pass A (src-major, gathers g_t) takes the place of pass 1 and of the g_v half of pass 3, pass C
+    // (src-major, gathers q) is pass 3 without it: g_t, k and q each cross the fabric once per edge, where pass 1 + pass 3 also gathered v.
+    // The measurement build keeps the dst-major pass 1 + two-row pass 3 behind WSI_ATTN_BWD=dst (the bit-equality reference).
+    const char* bwd_mode = knob("WSI_ATTN_BWD");
+    const bool srcmajor = !pool && !(bwd_mode && bwd_mode[0] == 'd');
+    if (srcmajor) {
+        // edge -> softmax segment map for pass A, in the gsc scratch: nothing reads gsc before pass 2 overwrites every entry of it
+        int32_t* edge_seg = reinterpret_cast<int32_t*>(gsc);
+        if (E > 0)
+            hipLaunchKernelGGL(heat_attn_edge_seg_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, gd.node_seg, gd.rowptr, gd.num_nodes, E, edge_seg);
+        if (sblocks > 0) {      // also without edges: pass A writes g_v (zeros) and slot 1 of the absmax table of every source row
+            // CSC entries in flight per wave: U, as in pass 3, though A and C gather one row per entry where it gathered two (the bench batch,
+            // D = 512: U = 2 / 4 / 8 in pass A -> 651 / 664 / 712 us for the whole backward call, pass C indifferent between 2 and 4;
+            // tools/attn_src_u_probe.py): the lower register count buys more waves per SIMD than the extra rows in flight would give
+            constexpr int UA = U;
+            auto pass_a = [&](auto uu) {
+                hipLaunchKernelGGL((heat_attn_bwd_srcA_kernel<V, LPH, decltype(uu)::value>), dim3(sblocks), dim3(kBlock), 0, st,
+                                   tb.v, tb.ldv, g_t, ldgt, gd.gt_row, gd.node_seg, (const int32_t*)edge_seg, colptr, csc_eid, csc_dst, inv_rd,
+                                   order_src, num_src, gd.xcd, gd.score_in, score_a, lse, ga, gv, ldgv, gd.absmax);
+            };
+#ifdef WSI_ABLATE
+            const char* su = knob("WSI_ATTN_SRC_U");     // measurement build: entries in flight of pass A (first digit) and pass C (second digit, default the first)
+            const int ua = su ? su[0] - '0' : UA;
+            if (ua == 2) pass_a(std::integral_constant<int, 2>{});
+            else if (ua == 4) pass_a(std::integral_constant<int, 4>{});
+            else if (ua == 8) pass_a(std::integral_constant<int, 8>{});
+            else pass_a(std::integral_constant<int, UA>{});
+#else
+            pass_a(std::integral_constant<int, UA>{});
+#endif
+        }
+    }
     if (pflat && E > 0) {
         const int64_t EH = (int64_t)E * H;
         hipLaunchKernelGGL(heat_attn_bwd_p1_flat_kernel, dim3((unsigned)((EH + 255) / 256)), dim3(256), 0, st, gd.src, pool->edge_seg, pool->seg_dst,
@@ -1071,19 +1208,19 @@ int launch_bwd(const AttnTables& tb, const AttnGraph& gd, int32_t num_src, int32
         // two independent chains (pass 2 of a node only needs pass 1 of the same node): hubs on the side stream
         SideStream* side;
         hipStream_t hs = hub_fork(st, ctx, side);
-        if (pflat) {}
+        if (pflat || srcmajor) {}
         else if (ph) hipLaunchKernelGGL((heat_attn_bwd_p1_kernel<V, LPH, kHeavyUnroll, true, true>), hb, dim3(kBlock), 0, hs, tb, gh, g_t, ldgt, score_a, lse, ga, *pool);
         else hipLaunchKernelGGL((heat_attn_bwd_p1_kernel<V, LPH, kHeavyUnroll, true>), hb, dim3(kBlock), 0, hs, tb, gh, g_t, ldgt, score_a, lse, ga, AttnPool{});
         hipLaunchKernelGGL((heat_attn_bwd_p2_kernel<V, LPH, kHeavyUnroll, true>), hb, dim3(kBlock), 0, hs,
                            tb, gh, ew, eb, isd, (const float*)score_a, (const float*)ga, gsc, gea, gq, ldgq);
-        if (pflat) {}
+        if (pflat || srcmajor) {}
         else if (ph) hipLaunchKernelGGL((heat_attn_bwd_p1_kernel<V, LPH, U, false, true>), dim3(blocks), dim3(kBlock), 0, st, tb, gl, g_t, ldgt, score_a, lse, ga, *pool);
         else hipLaunchKernelGGL((heat_attn_bwd_p1_kernel<V, LPH, U>), dim3(blocks), dim3(kBlock), 0, st, tb, gl, g_t, ldgt, score_a, lse, ga, AttnPool{});
         hipLaunchKernelGGL((heat_attn_bwd_p2_kernel<V, LPH, U>), dim3(blocks), dim3(kBlock), 0, st,
                            tb, gl, ew, eb, isd, (const float*)score_a, (const float*)ga, gsc, gea, gq, ldgq);
         hub_join(st, side);
     } else if (blocks > 0) {
-        if (pflat) {}
+        if (pflat || srcmajor) {}
         else if (ph) hipLaunchKernelGGL((heat_attn_bwd_p1_kernel<V, LPH, U, false, true>), dim3(blocks), dim3(kBlock), 0, st,
                                         tb, gd, g_t, ldgt, score_a, lse, ga, *pool);
         else hipLaunchKernelGGL((heat_attn_bwd_p1_kernel<V, LPH, U>), dim3(blocks), dim3(kBlock), 0, st,
@@ -1095,7 +1232,24 @@ int launch_bwd(const AttnTables& tb, const AttnGraph& gd, int32_t num_src, int32
         hipLaunchKernelGGL((heat_attn_bwd_p3_kernel<V, LPH, U, true>), dim3(sblocks), dim3(kBlock), 0, st,
                            tb.q, tb.ldq, g_t, ldgt, colptr, csc_eid, csc_dst, inv_rd, order_src, num_src, gd.xcd,
                            (const float*)score_a, (const float*)gsc, gk, ldgk, gv, ldgv, gd.absmax, gd.gt_row, *pool);
-    else if (sblocks > 0)
+    else if (sblocks > 0 && srcmajor) {
+        constexpr int UC = U;
+        auto pass_c = [&](auto uu) {
+            hipLaunchKernelGGL((heat_attn_bwd_p3_kernel<V, LPH, decltype(uu)::value, false, true>), dim3(sblocks), dim3(kBlock), 0, st,
+                               tb.q, tb.ldq, g_t, ldgt, colptr, csc_eid, csc_dst, inv_rd, order_src, num_src, gd.xcd,
+                               (const float*)score_a, (const float*)gsc, gk, ldgk, gv, ldgv, gd.absmax, gd.gt_row, AttnPool{});
+        };
+#ifdef WSI_ABLATE
+        const char* su = knob("WSI_ATTN_SRC_U");
+        const int uc = su ? su[su[0] && su[1] ? 1 : 0] - '0' : UC;
+        if (uc == 2) pass_c(std::integral_constant<int, 2>{});
+        else if (uc == 4) pass_c(std::integral_constant<int, 4>{});
+        else if (uc == 8) pass_c(std::integral_constant<int, 8>{});
+        else pass_c(std::integral_constant<int, UC>{});
+#else
+        pass_c(std::integral_constant<int, UC>{});
+#endif
+    } else if (sblocks > 0)
         hipLaunchKernelGGL((heat_attn_bwd_p3_kernel<V, LPH, U>), dim3(sblocks), dim3(kBlock), 0, st,
                            tb.q, tb.ldq, g_t, ldgt, colptr, csc_eid, csc_dst, inv_rd, order_src, num_src, gd.xcd,
                            (const float*)score_a, (const float*)gsc, gk, ldgk, gv, ldgv, gd.absmax, gd.gt_row, AttnPool{});
