@@ -33,6 +33,25 @@ def heat_attention_ref(kqv: torch.Tensor, e_weight: torch.Tensor, e_bias: torch.
     return t.reshape(n, D) * plan.inv_rd.to(kqv.dtype).unsqueeze(-1)
 
 
+def relation_attention_ref(q: torch.Tensor, kv: torch.Tensor, e_weight: torch.Tensor, e_bias: torch.Tensor, plan, sim_csr: torch.Tensor,
+                           D: int, H: int) -> torch.Tensor:
+    """``heat_attention_ref`` on the HGT table layout (ops.relation_attention): q [N,D] by destination node, kv [plan.num_src_rows,2D]
+    (K | V) by ``plan.src`` row, which a ``per_relation_src`` plan numbers per (relation, source node).  Returns t [N,D]."""
+    dk = D // H
+    n = plan.num_nodes
+    src = plan.src.long()
+    dst, seg = plan_edge_tables(plan)
+    qh = q.reshape(n, H, dk)
+    k = kv[:, 0:D].reshape(-1, H, dk)
+    v = kv[:, D:2 * D].reshape(-1, H, dk)
+    ea = e_weight.reshape(()) * sim_csr.to(q.dtype) + e_bias.reshape(())
+    score = (qh[dst] * k[src]).sum(-1) * ea.unsqueeze(-1) / math.sqrt(dk)      # [E,H]
+    a = S.edge_softmax_dst(score, seg, plan.num_segs)
+    msg = v[src] * a.unsqueeze(-1)
+    t = torch.zeros(n, H, dk, dtype=q.dtype).index_add_(0, dst, msg)
+    return t.reshape(n, D) * plan.inv_rd.to(q.dtype).unsqueeze(-1)
+
+
 def plan_edge_tables(plan):
     """(dst [E], seg_of_edge [E]) in the plan's CSR edge order, derived from the two-level CSR (the product plan does not
     carry per-edge destination / segment ids: the kernels never need them)."""
