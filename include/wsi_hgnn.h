@@ -34,7 +34,7 @@ extern "C" {
 #define WSI_EFAULT  (-14)   /* HIP runtime reported a launch error              */
 #define WSI_ENOMEM  (-12)   /* caller-provided workspace too small              */
 
-#define WSI_ABI_VERSION 24
+#define WSI_ABI_VERSION 25
 
 int         wsi_abi_version(void);
 const char* wsi_last_error(void);
@@ -583,6 +583,41 @@ int wsi_asap_attend_bwd(const float* a, const float* b, const float* x, int64_t 
                         const int32_t* colptr, const int32_t* csc_eid, const int32_t* csc_dst, float negative_slope,
                         const float* score, const float* g_out, int64_t ldg,
                         float* gpre, float* g_a, float* g_b, float* gx, int64_t ldgx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Multi-head GAT attention (models/GAT.py:17-92, DGL GATConv; H heads of width D, F = H*D, 1 <= H <= 16, 1 <= F <= 4096).
+ *
+ * Homogeneous edge layout of the relation-attention plan: rowptr[n+1] / src[E] = CSR by destination (edge id = CSR position),
+ * colptr[n+1] / csc_eid[E] / csc_dst[E] = CSC by source over the same edge ids; order_dst / order_src (optional, NULL = node
+ * order) = the walk orders.  Rows are head-major: column h*D + d.  No atomics, fixed summation orders: bit-reproducible.
+ *
+ * wsi_gat_scores   : eler[n, 2H] <- el | er,  el[v,h] = sum_d ft[v,h,d] attn_l[h,d],  er likewise with attn_r.
+ * wsi_gat_attn_fwd : s_e = leaky_relu(el[u] + er[v], negative_slope);  a = softmax of s over v's in-edges (max-subtracted, NO
+ *                    epsilon);  a~ = a * keep(e, h) / (1 - p)  (attn_drop: the counter-based mask of wsi_dropout_apply over an
+ *                    [E, H] tensor, row = CSR edge id, column = head; drop_threshold 0 = no dropout);
+ *                    out[v] = act(sum_e a~_e ft[u] + bias)  (bias optional; activation 0 none, 1 relu, 2 leaky_relu(act_slope));
+ *                    lse[n, 2H] <- the log-sum-exp of the scores in two parts: lse[v, h] = max_e s_e (+inf for a node without
+ *                    in-edges: out = act(bias) there), lse[v, H + h] = log sum_e exp(s_e - max); a_e = exp((s_e - max) - log_sum).
+ *                    Nothing per edge is stored: the backward recomputes a from eler and lse.
+ * wsi_gat_attn_bwd : from g_out (gradient of out) and the forward's eler / lse / out (out read only when activation != 0) and the
+ *                    SAME dropout arguments: g_ft[n, F] <- d loss / d ft (both through the aggregation and through el / er),
+ *                    g_attn_l[F], g_attn_r[F], g_bias[F] (optional) <- the parameter gradients.  workspace: at least
+ *                    wsi_gat_attn_bwd_workspace_bytes(n, E, H, D, activation) bytes (-1 for bad arguments).
+ */
+int wsi_gat_scores(const float* ft, int64_t ldf, int32_t n, int32_t H, int32_t D, const float* attn_l, const float* attn_r,
+                   float* eler, void* stream);
+int wsi_gat_attn_fwd(const float* ft, int64_t ldf, const float* eler, int32_t n, int32_t H, int32_t D,
+                     const int32_t* rowptr, const int32_t* src, const int32_t* order_dst, float negative_slope,
+                     uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold, float drop_scale,
+                     const float* bias, int32_t activation, float act_slope, float* out, int64_t ldo, float* lse, void* stream);
+int64_t wsi_gat_attn_bwd_workspace_bytes(int32_t n, int32_t E, int32_t H, int32_t D, int32_t activation);
+int wsi_gat_attn_bwd(const float* ft, int64_t ldf, const float* eler, const float* lse, const float* out, int64_t ldo,
+                     const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t H, int32_t D,
+                     const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
+                     const int32_t* csc_dst, const int32_t* order_src, const float* attn_l, const float* attn_r,
+                     float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
+                     float drop_scale, int32_t activation, float act_slope, void* workspace, int64_t workspace_bytes,
+                     float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r, float* g_bias, void* stream);
 
 /* wsi_graph_topk : pooling/ASAP.py:184  perm = topk(fitness, ratio, batch)  (torch_geometric.nn.pool.topk_pool.topk).
  *                  score[n] fp32, batch[n] int64 graph id of every node (any arrangement; ids in [0, num_graphs)),

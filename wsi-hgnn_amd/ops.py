@@ -2340,3 +2340,97 @@ class _AsapAttend(torch.autograd.Function):
 def asap_attend(a: torch.Tensor, b: torch.Tensor, x: torch.Tensor, ec: EdgeCSR, negative_slope: float):
     """(out [n,D], score [E] in the ORIGINAL edge order) of pooling/ASAP.py:167-179; ``a`` [n] already holds the bias."""
     return _AsapAttend.apply(a, b, x, ec, negative_slope)
+
+
+# ------------------------------------------------------------------------------------------------
+# GAT (DGL GATConv, models/GAT.py:17-92): counter-based feat_drop and the multi-head edge attention
+# ------------------------------------------------------------------------------------------------
+class _CounterDropoutFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, drop: CounterDropout):
+        ctx.drop = drop
+        return dropout_apply(x, drop)
+
+    @staticmethod
+    def backward(ctx, g):
+        return dropout_apply(g, ctx.drop), None
+
+
+def counter_dropout(x: torch.Tensor, drop: CounterDropout) -> torch.Tensor:
+    """nn.Dropout's forward and backward as ``drop``'s counter-based mask (``wsi_dropout_apply`` both ways: no mask tensor)."""
+    return _CounterDropoutFn.apply(x, drop)
+
+
+GAT_ACTIVATIONS = {None: 0, "none": 0, "relu": 1, "leaky_relu": 2}
+
+
+def _gat_drop_args(drop: Optional[CounterDropout]):
+    if drop is None:
+        return 0, None, 0, 1.0
+    return drop.seed, N.ptr(drop.seed_base), drop.threshold, drop.scale
+
+
+class _GatAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ft, attn_l, attn_r, bias, plan, slope: float, act: int, act_slope: float, drop: Optional[CounterDropout]):
+        N.require_cuda(ft, attn_l, attn_r, bias)
+        H, D = attn_l.shape[-2], attn_l.shape[-1]
+        n = plan.num_nodes
+        if ft.dim() != 2 or ft.shape[0] != n or ft.shape[1] != H * D:
+            raise ValueError(f"gat_attention: ft must be [{n}, {H * D}], got {tuple(ft.shape)}")
+        ft = ft.contiguous()
+        al, ar = attn_l.detach().contiguous().view(-1), attn_r.detach().contiguous().view(-1)
+        b = bias.detach().contiguous() if bias is not None else None
+        dev = ft.device
+        lib = N.load()
+        eler = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)
+        N.check(lib.wsi_gat_scores(N.ptr(ft), H * D, n, H, D, N.ptr(al), N.ptr(ar), N.ptr(eler), N.stream()), "wsi_gat_scores")
+        out = torch.empty((n, H * D), dtype=torch.float32, device=dev)
+        lse = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)       # max | log of the shifted sum, per head
+        seed, seed_base, thr, scale = _gat_drop_args(drop)
+        N.check(lib.wsi_gat_attn_fwd(N.ptr(ft), H * D, N.ptr(eler), n, H, D, N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.order_dst),
+                                     float(slope), seed, seed_base, thr, scale, N.ptr(b), int(act), float(act_slope),
+                                     N.ptr(out), H * D, N.ptr(lse), N.stream()), "wsi_gat_attn_fwd")
+        ctx.plan, ctx.slope, ctx.act, ctx.act_slope, ctx.drop, ctx.hd = plan, float(slope), int(act), float(act_slope), drop, (H, D)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(ft, al, ar, eler, lse, out if act else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        ft, al, ar, eler, lse, out = ctx.saved_tensors
+        plan = ctx.plan
+        H, D = ctx.hd
+        n, E, F = plan.num_nodes, plan.num_edges, H * D
+        g_out = g_out.contiguous()
+        dev = ft.device
+        lib = N.load()
+        ws_bytes = lib.wsi_gat_attn_bwd_workspace_bytes(n, E, H, D, ctx.act)
+        if ws_bytes < 0:
+            raise RuntimeError("wsi_gat_attn_bwd_workspace_bytes: bad arguments")
+        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
+        g_ft = torch.empty((n, F), dtype=torch.float32, device=dev)
+        g_al = torch.empty(F, dtype=torch.float32, device=dev)
+        g_ar = torch.empty(F, dtype=torch.float32, device=dev)
+        g_b = torch.empty(F, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        seed, seed_base, thr, scale = _gat_drop_args(ctx.drop)
+        N.check(lib.wsi_gat_attn_bwd(N.ptr(ft), F, N.ptr(eler), N.ptr(lse), N.ptr(out), F, N.ptr(g_out), F, n, E, H, D,
+                                     N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
+                                     N.ptr(plan.order_src), N.ptr(al), N.ptr(ar), ctx.slope, seed, seed_base, thr, scale, ctx.act, ctx.act_slope,
+                                     N.ptr(ws), int(ws_bytes), N.ptr(g_ft), F, N.ptr(g_al), N.ptr(g_ar), N.ptr(g_b), N.stream()), "wsi_gat_attn_bwd")
+        return g_ft, g_al.view(1, H, D), g_ar.view(1, H, D), g_b, None, None, None, None, None
+
+
+def gat_attention(ft: torch.Tensor, attn_l: torch.Tensor, attn_r: torch.Tensor, bias: Optional[torch.Tensor], plan,
+                  negative_slope: float, activation: Optional[str] = None, attn_drop: Optional[CounterDropout] = None,
+                  act_slope: float = 0.01) -> torch.Tensor:
+    """DGL GATConv after its projection: ``ft`` [N, H*D] (head-major rows), ``attn_l`` / ``attn_r`` [1, H, D], ``bias`` [H*D] or None;
+    ``plan`` = the graph's homogeneous GraphPlan (CSR by destination, CSC by source, walk orders).  Returns act(sum_e a_e ft[src] + bias)
+    [N, H*D] where a = edge softmax of leaky_relu(el[src] + er[dst], negative_slope) over each destination's in-edges, dropped by
+    ``attn_drop`` (a CounterDropout over the [E, H] scores: row = CSR edge id, column = head; None = no dropout).  ``activation``:
+    None, "relu" or "leaky_relu" (slope ``act_slope``), fused into the kernel."""
+    if activation not in GAT_ACTIVATIONS:
+        raise ValueError(f"gat_attention: activation {activation!r} is not one of {sorted(k for k in GAT_ACTIVATIONS if k)}")
+    if attn_l.dim() != 3 or attn_l.shape[0] != 1 or attn_r.shape != attn_l.shape:
+        raise ValueError("gat_attention: attn_l / attn_r must be [1, H, D]")
+    return _GatAttention.apply(ft, attn_l, attn_r, bias, plan, float(negative_slope), GAT_ACTIVATIONS[activation], float(act_slope), attn_drop)

@@ -1,14 +1,17 @@
 """Config -> objects, mirroring the reference's ``parser.py`` (same function names, same config keys, same error behaviour):
 
-  parse_gnn_model(cfg["GNN"])      parser.py:48-174   the in-scope branches: GCN, GCN_NTPool, HetRGCN, HGT, HEAT2, HEAT4
+  parse_gnn_model(cfg["GNN"])      parser.py:48-174   the in-scope branches: GAT, GCN, GCN_NTPool, HetRGCN, HGT, HEAT2, HEAT4
   parse_optimizer(cfg["optim"], m) parser.py:15-46    adagrad / adadelta / adam / anything else -> SGD
   parse_loss(cfg["train"])         parser.py:176-184  BCE / CE
 
 ``node_dict`` and the etype-major enumeration of ``edge_dict`` / ``etypes`` are built exactly as :107-113,122-129; a config
 without a key the reference reads raises the same ``KeyError``; names the reference does not know (``HEAT``, ``HEAT3`` of
-configs/COAD/HEAT*_staging.yml: orphan configs) raise its ``NotImplementedError``.  ``GAT`` and ``GIN`` are the
-reference's homogeneous baselines, outside the hot path: they raise ``NotImplementedError`` here too, with a message that
-says so.  tests/test_parser.py replays the calls the REFERENCE function makes on its own configs (tests/golden/
+configs/COAD/HEAT*_staging.yml: orphan configs) raise its ``NotImplementedError``.  ``GAT`` (:51-68) reads its
+keys in the reference's order (num_layers, num_heads, num_out_heads, in_dim, hidden_dim, out_dim, feat_drop, attn_drop,
+negative_slope, graph_pooling_type) and always passes ``F.leaky_relu`` and ``residual=False``; a missing key raises
+``MissingGATKey``, a ``KeyError`` with the reference's message that is also a ``NotImplementedError`` (the package refused GAT
+with the latter before it had the model).  ``GIN`` is the reference's other homogeneous baseline, outside the hot path: it
+raises ``NotImplementedError`` with a message that says so.  tests/test_parser.py replays the calls the REFERENCE function makes on its own configs (tests/golden/
 reference_surface.json, produced by executing parser.py:48-174 with recording stand-ins for the classes).
 """
 from __future__ import annotations
@@ -16,7 +19,7 @@ from __future__ import annotations
 import torch.nn.functional as F
 from torch import nn, optim
 
-from .models import GCN, HGT, HEATNet2, HEATNet4, HeteroRGCN, NTPoolGCN
+from .models import GAT, GCN, HGT, HEATNet2, HEATNet4, HeteroRGCN, NTPoolGCN
 
 
 def parse_optimizer(config_optim, model):
@@ -40,9 +43,38 @@ def _typed_schema(config_gnn):
     return node_dict, canonical_etypes
 
 
+class MissingGATKey(KeyError, NotImplementedError):
+    """A key the reference's GAT branch reads is missing: the reference's ``KeyError`` (same message), and a ``NotImplementedError``
+    as the package's earlier refusal of GAT was."""
+
+
+class _GATConfig:
+    def __init__(self, config_gnn):
+        self._cfg = config_gnn
+
+    def __getitem__(self, key):
+        try:
+            return self._cfg[key]
+        except KeyError:
+            raise MissingGATKey(key) from None
+
+
+def _parse_gat(config_gnn):
+    c = _GATConfig(config_gnn)                                      # parser.py:51-68, keys read in this order
+    n_layers = c["num_layers"]
+    n_heads = c["num_heads"]
+    n_out_heads = c["num_out_heads"]
+    heads = ([n_heads] * n_layers) + [n_out_heads]
+    return GAT(n_layers=c["num_layers"], in_dim=c["in_dim"], hidden_dim=c["hidden_dim"], out_dim=c["out_dim"], heads=heads,
+               activation=F.leaky_relu, feat_drop=c["feat_drop"], attn_drop=c["attn_drop"], negative_slope=c["negative_slope"],
+               residual=False, graph_pooling_type=c["graph_pooling_type"])
+
+
 def parse_gnn_model(config_gnn):
     gnn_name = config_gnn["name"]
-    if gnn_name in ("GAT", "GIN"):
+    if gnn_name == "GAT":
+        return _parse_gat(config_gnn)
+    if gnn_name == "GIN":
         raise NotImplementedError(f"{gnn_name} is one of the reference's homogeneous baselines, outside the hot path this package rebuilds")
     if gnn_name == "GCN":
         return GCN(in_dim=config_gnn["in_dim"], hidden_dim=config_gnn["hidden_dim"], out_dim=config_gnn["out_dim"],
