@@ -34,7 +34,7 @@ extern "C" {
 #define WSI_EFAULT  (-14)   /* HIP runtime reported a launch error              */
 #define WSI_ENOMEM  (-12)   /* caller-provided workspace too small              */
 
-#define WSI_ABI_VERSION 25
+#define WSI_ABI_VERSION 26
 
 int         wsi_abi_version(void);
 const char* wsi_last_error(void);
@@ -518,7 +518,12 @@ int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, 
  *   (edge_w: optional per-edge weight in the order of idx - the explicit edge_weight of PyG's GCNConv / LEConv in pooling/ASAP.py:45-61,157; NULL = 1)
  *   forward: (ptr, idx) = CSR by destination; backward: CSC by source with the scales swapped.  relu_ref
  *   (may be NULL): rows of x are masked by relu_ref[idx] > 0 before being summed (ReLU backward fused in).
- *   Any D <= 1024. */
+ *   Any D <= 1024.
+ * wsi_sddmm_dot: the gradient of wsi_spmm_sum's forward with respect to edge_w (GNNExplainer's per-edge message scale through GraphConv,
+ *   explainers/gnn_explainer.py:21-33), for every CSR entry e = (u -> w), u = src[e], e in [rowptr[w], rowptr[w+1]):
+ *     g_w[e] = oscale[w] * iscale[u] * sum_c gm[w,c] * x[u,c],   gm[w] = g[w] where relu_ref[w] > 0 (relu_ref NULL: gm = g)
+ *   g = gradient of spmm_sum's out, x = its input, relu_ref = its out when relu was fused.  One gather of x[u] per edge; g[w] is held by
+ *   the lane group that owns w.  g_w[E] fp32 in CSR order; no atomics.  Any D <= 1024. */
 int wsi_layernorm_fwd(const float* x, int64_t ldx, int32_t n, int32_t D, float eps,
                       const float* gamma, const float* beta, const int32_t* row_param,
                       float* y, int64_t ldy, float* stats, void* stream);
@@ -531,6 +536,9 @@ int wsi_spmm_sum(const float* x, int64_t ldx, int32_t n_out, int32_t D,
                  const int32_t* ptr, const int32_t* idx, const float* edge_w, const float* iscale, const float* oscale,
                  const float* bias, int32_t relu, const float* relu_ref, int64_t ldref,
                  float* out, int64_t ldo, void* stream);
+int wsi_sddmm_dot(const float* g, int64_t ldg, const float* x, int64_t ldx, int32_t n, int32_t D,
+                  const int32_t* rowptr, const int32_t* src, const float* iscale, const float* oscale,
+                  const float* relu_ref, int64_t ldref, float* g_w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Graph-construction edge step: exact L2 kNN + per-edge Pearson correlation.
@@ -603,6 +611,14 @@ int wsi_asap_attend_bwd(const float* a, const float* b, const float* x, int64_t 
  *                    SAME dropout arguments: g_ft[n, F] <- d loss / d ft (both through the aggregation and through el / er),
  *                    g_attn_l[F], g_attn_r[F], g_bias[F] (optional) <- the parameter gradients.  workspace: at least
  *                    wsi_gat_attn_bwd_workspace_bytes(n, E, H, D, activation) bytes (-1 for bad arguments).
+ * wsi_gat_attn_fwd_scaled / wsi_gat_attn_bwd_scaled : the same with a per-edge message scale edge_scale[E] (fp32, CSR edge order, one value
+ *                    for all heads and columns of the edge; any finite value - GNNExplainer passes sigmoid(edge_mask),
+ *                    explainers/gnn_explainer.py:21-33).  The scale multiplies the message AFTER the softmax (and after attn_drop):
+ *                      out[v] = act(sum_e a~_e s_e ft[u] + bias);  lse as above (the softmax does not see s).
+ *                    Backward, with r[e,h] = g_rst[w]_h . ft[u]_h  (g_rst = g_out * act'(out)):
+ *                      g_ft[u] = sum_e a~_e s_e g_rst[w] (+ the el / er terms);  d loss / d a~_{e,h} = s_e r[e,h];
+ *                      g_edge_scale[e] = sum_h a~_{e,h} r[e,h]   (E fp32, CSR order; heads added in order by one lane: no atomics).
+ *                    Same workspace size as the unscaled backward.  The unscaled entry points do not run this code.
  */
 int wsi_gat_scores(const float* ft, int64_t ldf, int32_t n, int32_t H, int32_t D, const float* attn_l, const float* attn_r,
                    float* eler, void* stream);
@@ -618,6 +634,19 @@ int wsi_gat_attn_bwd(const float* ft, int64_t ldf, const float* eler, const floa
                      float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
                      float drop_scale, int32_t activation, float act_slope, void* workspace, int64_t workspace_bytes,
                      float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r, float* g_bias, void* stream);
+int wsi_gat_attn_fwd_scaled(const float* ft, int64_t ldf, const float* eler, int32_t n, int32_t H, int32_t D,
+                            const int32_t* rowptr, const int32_t* src, const int32_t* order_dst, float negative_slope,
+                            uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold, float drop_scale,
+                            const float* bias, int32_t activation, float act_slope, const float* edge_scale,
+                            float* out, int64_t ldo, float* lse, void* stream);
+int wsi_gat_attn_bwd_scaled(const float* ft, int64_t ldf, const float* eler, const float* lse, const float* out, int64_t ldo,
+                            const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t H, int32_t D,
+                            const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
+                            const int32_t* csc_dst, const int32_t* order_src, const float* attn_l, const float* attn_r,
+                            float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
+                            float drop_scale, int32_t activation, float act_slope, const float* edge_scale,
+                            void* workspace, int64_t workspace_bytes, float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r,
+                            float* g_bias, float* g_edge_scale, void* stream);
 
 /* wsi_graph_topk : pooling/ASAP.py:184  perm = topk(fitness, ratio, batch)  (torch_geometric.nn.pool.topk_pool.topk).
  *                  score[n] fp32, batch[n] int64 graph id of every node (any arrangement; ids in [0, num_graphs)),

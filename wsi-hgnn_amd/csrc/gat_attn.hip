@@ -14,6 +14,12 @@
 //   B     CSR by destination v (scalar): delta = sum a g_a;  g_pre = a (g_a - delta) lrelu';  g_er[v] = sum g_pre
 //   C     by source u: g_el[u] = sum g_pre;  g_ft[u,h,:] += g_el attn_l[h] + g_er attn_r[h];  column partials of g_attn_l/r
 //   sum   the fixed-shape column partials, in order
+// Message scale (the *_scaled entry points; GNNExplainer's sigmoid(edge_mask), explainers/gnn_explainer.py:21-33): one fp32 factor s_e per
+// edge multiplies the MESSAGE a~_e ft[u] after the softmax.  SCALED is a compile-time switch of the forward, pass A and pass B:
+//   fwd   out[v] = act(sum_e a~_e s_e ft[u] + bias)
+//   A     g_ft[u] = sum a~_e s_e g_rst[w];  g_a keeps the RAW dot r[e,h] = g_rst[w]_h . ft[u]_h
+//   B     d loss / d a~ = s_e r[e,h];  g_scale[e] = sum_h a~_{e,h} r[e,h]  (the lane that owns edge e adds its heads in order)
+// The unscaled instantiations contain none of it.
 #include "gemm_common.h"
 #include <math.h>
 
@@ -137,12 +143,13 @@ __device__ __forceinline__ float act_fwd(float z, int act, float act_slope) {
     return act == GA_ACT_RELU ? fmaxf(z, 0.f) : act == GA_ACT_LEAKY ? ga_lrelu(z, act_slope) : z;
 }
 
-template <int G, int VEC, int NK>
+template <int G, int VEC, int NK, bool SCALED>
 __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restrict__ ft, int64_t ldf, const float* __restrict__ eler, int n, int H, int D,
                                                            const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src,
                                                            const int32_t* __restrict__ order, float slope, GatDrop dr,
                                                            const float* __restrict__ bias, int act, float act_slope,
-                                                           float* __restrict__ out, int64_t ldo, float* __restrict__ lse) {
+                                                           float* __restrict__ out, int64_t ldo, float* __restrict__ lse,
+                                                           const float* __restrict__ escale) {
     const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
     const int gi = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
     if (gi >= n) return;                                         // group-uniform
@@ -164,7 +171,10 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
     for (int e = e0; e < e1; ++e) {
         const int u = src[e];
         float a = 0.f;
-        if (gl < H) a = expf((ga_lrelu(eler[(int64_t)u * 2 * H + gl] + my_er, slope) - my_m) - my_ls) * edge_factor(dr, seed, e, gl, H);
+        if (gl < H) {
+            a = expf((ga_lrelu(eler[(int64_t)u * 2 * H + gl] + my_er, slope) - my_m) - my_ls) * edge_factor(dr, seed, e, gl, H);
+            if constexpr (SCALED) a *= escale[e];
+        }
         const float* __restrict__ row = ft + (int64_t)u * ldf;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
@@ -233,14 +243,15 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_act_bwd_kernel(const float* __re
     }
 }
 
-// pass A: one group per source u (in order_src); g_ft[u] = sum over out-edges of a~_e g_rst[w], g_a[e,h] = g_rst[w]_h . ft[u]_h
-template <int G, int VEC, int NK>
+// pass A: one group per source u (in order_src); g_ft[u] = sum over out-edges of a~_e (s_e) g_rst[w], g_a[e,h] = g_rst[w]_h . ft[u]_h
+template <int G, int VEC, int NK, bool SCALED>
 __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __restrict__ ft, int64_t ldf, const float* __restrict__ eler,
                                                                const float* __restrict__ lse, const float* __restrict__ g_rst, int64_t ldr,
                                                                int n, int H, int D, const int32_t* __restrict__ colptr,
                                                                const int32_t* __restrict__ csc_eid, const int32_t* __restrict__ csc_dst,
                                                                const int32_t* __restrict__ order, float slope, GatDrop dr,
-                                                               float* __restrict__ g_ft, int64_t ldgf, float* __restrict__ g_a) {
+                                                               float* __restrict__ g_ft, int64_t ldgf, float* __restrict__ g_a,
+                                                               const float* __restrict__ escale) {
     const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
     const int gi = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
     if (gi >= n) return;
@@ -262,9 +273,11 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
     for (int jj = j0; jj < j1; ++jj) {
         const int e = csc_eid[jj], w = csc_dst[jj];
         float a = 0.f;
-        if (gl < H)
+        if (gl < H) {
             a = expf((ga_lrelu(my_el + eler[(int64_t)w * 2 * H + H + gl], slope) - lse[(int64_t)w * 2 * H + gl]) - lse[(int64_t)w * 2 * H + H + gl]) *
                 edge_factor(dr, seed, e, gl, H);
+            if constexpr (SCALED) a *= escale[e];
+        }
         const float* __restrict__ row = g_rst + (int64_t)w * ldr;
         float p[NK];
 #pragma unroll
@@ -286,10 +299,13 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
         if (ok[k]) store_vec<VEC>(g_ft + (int64_t)u * ldgf + VEC * (gl + G * k), acc[k]);
 }
 
-// pass B: one 16-lane group per destination v; in place g_a (d loss / d a~) -> g_pre (d loss / d pre-activation score); g_er[v, h]
+// pass B: one 16-lane group per destination v; in place g_a (d loss / d a~, SCALED: the raw dot r) -> g_pre (d loss / d pre-activation score);
+// g_er[v, h].  SCALED: d loss / d a~ = s_e r, and g_scale[e] = sum_h a~ r is built head by head by the one lane that visits edge e.
+template <bool SCALED>
 __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __restrict__ eler, const float* __restrict__ lse, int n, int H,
                                                                const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src,
-                                                               float slope, GatDrop dr, float* __restrict__ g_a, float* __restrict__ g_er) {
+                                                               float slope, GatDrop dr, float* __restrict__ g_a, float* __restrict__ g_er,
+                                                               const float* __restrict__ escale, float* __restrict__ g_scale) {
     constexpr int G = GA_B_LANES;
     const int gl = threadIdx.x & (G - 1);
     const int v = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
@@ -301,14 +317,22 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __re
         float d = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
             const float a = expf((ga_lrelu(eler[(int64_t)src[e] * 2 * H + h] + erv, slope) - M) - LS);
-            d = fmaf(a, g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H), d);
+            if constexpr (SCALED) {
+                const float r = g_a[(int64_t)e * H + h], f = edge_factor(dr, seed, e, h, H), gs = a * f * r;
+                g_scale[e] = h ? g_scale[e] + gs : gs;
+                d = fmaf(a, r * (f * escale[e]), d);
+            } else {
+                d = fmaf(a, g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H), d);
+            }
         }
         const float delta = group_sum<G>(d);
         float gr = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
             const float pre = eler[(int64_t)src[e] * 2 * H + h] + erv;
             const float a = expf((ga_lrelu(pre, slope) - M) - LS);
-            const float gp = a * (g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H) - delta) * (pre > 0.f ? 1.f : slope);
+            float gp;
+            if constexpr (SCALED) gp = a * (g_a[(int64_t)e * H + h] * (edge_factor(dr, seed, e, h, H) * escale[e]) - delta) * (pre > 0.f ? 1.f : slope);
+            else gp = a * (g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H) - delta) * (pre > 0.f ? 1.f : slope);
             g_a[(int64_t)e * H + h] = gp;
             gr += gp;
         }
@@ -392,6 +416,53 @@ __global__ __launch_bounds__(256) void gat_colsum_kernel(const float* __restrict
     else if (g_b) g_b[c - 2 * F] = s;
 }
 
+// GraphConv edge-weight gradient (wsi_sddmm_dot): g_w[e] = oscale[w] iscale[u] <g[w], x[u]> for every CSR entry e = (u -> w).  The layout of
+// the forward above with one head: a group per destination w keeps g[w] (masked by relu_ref[w] > 0) in registers and gathers x[u] once per edge.
+template <int G, int VEC, int NK>
+__global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __restrict__ g, int64_t ldg, const float* __restrict__ x, int64_t ldx, int n, int D,
+                                                             const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src,
+                                                             const float* __restrict__ iscale, const float* __restrict__ oscale,
+                                                             const float* __restrict__ relu_ref, int64_t ldref, float* __restrict__ g_w) {
+    const int gl = threadIdx.x & (G - 1);
+    const int w = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    if (w >= n) return;                                          // group-uniform
+    float gw[NK][VEC];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int c = VEC * (gl + G * k);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) gw[k][j] = 0.f;
+        if (c < D) {
+            ga_load<VEC>(gw[k], g + (int64_t)w * ldg + c);
+            if (relu_ref) {
+                float y[VEC];
+                ga_load<VEC>(y, relu_ref + (int64_t)w * ldref + c);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) gw[k][j] = y[j] > 0.f ? gw[k][j] : 0.f;
+            }
+        }
+    }
+    const float os = oscale ? oscale[w] : 1.f;
+    const int e0 = rowptr[w], e1 = rowptr[w + 1];
+    for (int e = e0; e < e1; ++e) {
+        const int u = src[e];
+        const float* __restrict__ row = x + (int64_t)u * ldx;
+        float p = 0.f;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int c = VEC * (gl + G * k);
+            if (c < D) {
+                float v[VEC];
+                ga_load<VEC>(v, row + c);
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) p = fmaf(gw[k][j], v[j], p);
+            }
+        }
+        p = group_sum<G>(p);
+        if (gl == 0) g_w[e] = os * (iscale ? iscale[u] : 1.f) * p;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- host side
 struct GaCfg {
     int G, VEC, NK;
@@ -458,26 +529,45 @@ extern "C" int wsi_gat_scores(const float* ft, int64_t ldf, int32_t n, int32_t H
     return check_launch("gat_scores");
 }
 
-extern "C" int wsi_gat_attn_fwd(const float* ft, int64_t ldf, const float* eler, int32_t n, int32_t H, int32_t D,
-                                const int32_t* rowptr, const int32_t* src, const int32_t* order_dst, float negative_slope,
-                                uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold, float drop_scale,
-                                const float* bias, int32_t activation, float act_slope, float* out, int64_t ldo, float* lse, void* stream) {
-    if (int rc = ga_check_shape("gat_attn_fwd", n, H, D)) return rc;
+// both forward entry points; SCALED picks the instantiation that reads edge_scale (checked non-null by the caller)
+template <bool SCALED>
+static int ga_fwd(const char* what, const float* ft, int64_t ldf, const float* eler, int32_t n, int32_t H, int32_t D,
+                  const int32_t* rowptr, const int32_t* src, const int32_t* order_dst, float negative_slope,
+                  uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold, float drop_scale,
+                  const float* bias, int32_t activation, float act_slope, const float* edge_scale, float* out, int64_t ldo, float* lse, void* stream) {
+    if (int rc = ga_check_shape(what, n, H, D)) return rc;
     const int64_t F = (int64_t)H * D;
-    if (ldf < F || ldo < F) { set_error("gat_attn_fwd: row stride below heads*D"); return WSI_EINVAL; }
-    if (activation < 0 || activation > 2) { set_error("gat_attn_fwd: activation %d (0 none, 1 relu, 2 leaky_relu)", activation); return WSI_EINVAL; }
-    if (drop_threshold > 65535u) { set_error("gat_attn_fwd: drop_threshold %u > 65535", drop_threshold); return WSI_EINVAL; }
-    if (!ft || !eler || !rowptr || !src || !out || !lse) { set_error("gat_attn_fwd: null pointer"); return WSI_EINVAL; }
+    if (ldf < F || ldo < F) { set_error("%s: row stride below heads*D", what); return WSI_EINVAL; }
+    if (activation < 0 || activation > 2) { set_error("%s: activation %d (0 none, 1 relu, 2 leaky_relu)", what, activation); return WSI_EINVAL; }
+    if (drop_threshold > 65535u) { set_error("%s: drop_threshold %u > 65535", what, drop_threshold); return WSI_EINVAL; }
+    if (!ft || !eler || !rowptr || !src || !out || !lse || (SCALED && !edge_scale)) { set_error("%s: null pointer", what); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
     const GaCfg cfg = ga_cfg(H, D, ldf % 4 == 0 && ldo % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(bias));
     const GatDrop dr{drop_seed, drop_threshold, drop_seed_base, drop_scale};
     hipStream_t st = (hipStream_t)stream;
     const int per = GA_BLOCK / cfg.G;
-#define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_fwd_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, eler, n, H, D, \
-                                            rowptr, src, order_dst, negative_slope, dr, bias, (int)activation, act_slope, out, ldo, lse)
+#define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_fwd_kernel<G_, V_, K_, SCALED>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, eler, n, H, D, \
+                                            rowptr, src, order_dst, negative_slope, dr, bias, (int)activation, act_slope, out, ldo, lse, edge_scale)
     GA_DISPATCH(cfg, CALL);
 #undef CALL
-    return check_launch("gat_attn_fwd");
+    return check_launch(what);
+}
+
+extern "C" int wsi_gat_attn_fwd(const float* ft, int64_t ldf, const float* eler, int32_t n, int32_t H, int32_t D,
+                                const int32_t* rowptr, const int32_t* src, const int32_t* order_dst, float negative_slope,
+                                uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold, float drop_scale,
+                                const float* bias, int32_t activation, float act_slope, float* out, int64_t ldo, float* lse, void* stream) {
+    return ga_fwd<false>("gat_attn_fwd", ft, ldf, eler, n, H, D, rowptr, src, order_dst, negative_slope, drop_seed, drop_seed_base, drop_threshold,
+                         drop_scale, bias, activation, act_slope, nullptr, out, ldo, lse, stream);
+}
+
+extern "C" int wsi_gat_attn_fwd_scaled(const float* ft, int64_t ldf, const float* eler, int32_t n, int32_t H, int32_t D,
+                                       const int32_t* rowptr, const int32_t* src, const int32_t* order_dst, float negative_slope,
+                                       uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold, float drop_scale,
+                                       const float* bias, int32_t activation, float act_slope, const float* edge_scale,
+                                       float* out, int64_t ldo, float* lse, void* stream) {
+    return ga_fwd<true>("gat_attn_fwd_scaled", ft, ldf, eler, n, H, D, rowptr, src, order_dst, negative_slope, drop_seed, drop_seed_base,
+                        drop_threshold, drop_scale, bias, activation, act_slope, edge_scale, out, ldo, lse, stream);
 }
 
 // workspace: g_rst [n, F] (only when activation != none), g_a / g_pre [E, H], g_er [n, H], column partials [rows(G), 3F]
@@ -500,27 +590,29 @@ extern "C" int64_t wsi_gat_attn_bwd_workspace_bytes(int32_t n, int32_t E, int32_
     return ga_ws_layout(n, E, H, D, activation, off);
 }
 
-extern "C" int wsi_gat_attn_bwd(const float* ft, int64_t ldf, const float* eler, const float* lse, const float* out, int64_t ldo,
-                                const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t H, int32_t D,
-                                const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
-                                const int32_t* csc_dst, const int32_t* order_src, const float* attn_l, const float* attn_r,
-                                float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
-                                float drop_scale, int32_t activation, float act_slope, void* workspace, int64_t workspace_bytes,
-                                float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r, float* g_bias, void* stream) {
-    if (int rc = ga_check_shape("gat_attn_bwd", n, H, D)) return rc;
+// both backward entry points; SCALED: edge_scale in, g_edge_scale [E] out (same workspace)
+template <bool SCALED>
+static int ga_bwd(const char* what, const float* ft, int64_t ldf, const float* eler, const float* lse, const float* out, int64_t ldo,
+                  const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t H, int32_t D,
+                  const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
+                  const int32_t* csc_dst, const int32_t* order_src, const float* attn_l, const float* attn_r,
+                  float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
+                  float drop_scale, int32_t activation, float act_slope, const float* edge_scale, void* workspace, int64_t workspace_bytes,
+                  float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r, float* g_bias, float* g_edge_scale, void* stream) {
+    if (int rc = ga_check_shape(what, n, H, D)) return rc;
     const int64_t F = (int64_t)H * D;
-    if (E < 0) { set_error("gat_attn_bwd: E=%d", E); return WSI_EINVAL; }
-    if (ldf < F || ldo < F || ldg < F || ldgf < F) { set_error("gat_attn_bwd: row stride below heads*D"); return WSI_EINVAL; }
-    if (activation < 0 || activation > 2) { set_error("gat_attn_bwd: activation %d (0 none, 1 relu, 2 leaky_relu)", activation); return WSI_EINVAL; }
-    if (drop_threshold > 65535u) { set_error("gat_attn_bwd: drop_threshold %u > 65535", drop_threshold); return WSI_EINVAL; }
+    if (E < 0) { set_error("%s: E=%d", what, E); return WSI_EINVAL; }
+    if (ldf < F || ldo < F || ldg < F || ldgf < F) { set_error("%s: row stride below heads*D", what); return WSI_EINVAL; }
+    if (activation < 0 || activation > 2) { set_error("%s: activation %d (0 none, 1 relu, 2 leaky_relu)", what, activation); return WSI_EINVAL; }
+    if (drop_threshold > 65535u) { set_error("%s: drop_threshold %u > 65535", what, drop_threshold); return WSI_EINVAL; }
     if (!ft || !eler || !lse || !g_out || !rowptr || !src || !colptr || !csc_eid || !csc_dst || !attn_l || !attn_r || !workspace ||
-        !g_ft || !g_attn_l || !g_attn_r || (activation && !out)) {
-        set_error("gat_attn_bwd: null pointer");
+        !g_ft || !g_attn_l || !g_attn_r || (activation && !out) || (SCALED && (!edge_scale || !g_edge_scale))) {
+        set_error("%s: null pointer", what);
         return WSI_EINVAL;
     }
     int64_t off[4];
     const int64_t need = ga_ws_layout(n, E, H, D, activation, off);
-    if (workspace_bytes < need) { set_error("gat_attn_bwd: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need); return WSI_ENOMEM; }
+    if (workspace_bytes < need) { set_error("%s: workspace %lld < %lld bytes", what, (long long)workspace_bytes, (long long)need); return WSI_ENOMEM; }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* g_rst = activation ? (float*)(ws + off[0]) : nullptr;
@@ -539,12 +631,13 @@ extern "C" int wsi_gat_attn_bwd(const float* ft, int64_t ldf, const float* eler,
                                             (int)activation, act_slope, g_rst, part)
         GA_DISPATCH(cfg, CALL);
 #undef CALL
-#define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_bwd_src_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, eler, lse, rst, ldr, \
-                                            n, H, D, colptr, csc_eid, csc_dst, order_src, negative_slope, dr, g_ft, ldgf, g_a)
+#define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_bwd_src_kernel<G_, V_, K_, SCALED>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, eler, lse, rst, ldr, \
+                                            n, H, D, colptr, csc_eid, csc_dst, order_src, negative_slope, dr, g_ft, ldgf, g_a, edge_scale)
         GA_DISPATCH(cfg, CALL);
 #undef CALL
         constexpr int per_b = GA_BLOCK / GA_B_LANES;
-        hipLaunchKernelGGL(gat_bwd_dst_kernel, dim3((n + per_b - 1) / per_b), dim3(GA_BLOCK), 0, st, eler, lse, n, H, rowptr, src, negative_slope, dr, g_a, g_er);
+        hipLaunchKernelGGL((gat_bwd_dst_kernel<SCALED>), dim3((n + per_b - 1) / per_b), dim3(GA_BLOCK), 0, st, eler, lse, n, H, rowptr, src, negative_slope, dr, g_a, g_er,
+                           edge_scale, g_edge_scale);
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_bwd_attn_kernel<G_, V_, K_>), dim3(GA_PART_BLOCKS), dim3(GA_BLOCK), 0, st, ft, ldf, (const float*)g_a, \
                                             (const float*)g_er, n, H, D, colptr, csc_eid, attn_l, attn_r, g_ft, ldgf, part)
         GA_DISPATCH(cfg, CALL);
@@ -554,7 +647,49 @@ extern "C" int wsi_gat_attn_bwd(const float* ft, int64_t ldf, const float* eler,
     } else {
         if (hipMemsetAsync(g_attn_l, 0, F * 4, st) != hipSuccess || hipMemsetAsync(g_attn_r, 0, F * 4, st) != hipSuccess ||
             (g_bias && hipMemsetAsync(g_bias, 0, F * 4, st) != hipSuccess))
-            return check_launch("gat_attn_bwd(memset)");
+            return check_launch(SCALED ? "gat_attn_bwd_scaled(memset)" : "gat_attn_bwd(memset)");
     }
-    return check_launch("gat_attn_bwd");
+    return check_launch(what);
+}
+
+extern "C" int wsi_gat_attn_bwd(const float* ft, int64_t ldf, const float* eler, const float* lse, const float* out, int64_t ldo,
+                                const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t H, int32_t D,
+                                const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
+                                const int32_t* csc_dst, const int32_t* order_src, const float* attn_l, const float* attn_r,
+                                float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
+                                float drop_scale, int32_t activation, float act_slope, void* workspace, int64_t workspace_bytes,
+                                float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r, float* g_bias, void* stream) {
+    return ga_bwd<false>("gat_attn_bwd", ft, ldf, eler, lse, out, ldo, g_out, ldg, n, E, H, D, rowptr, src, colptr, csc_eid, csc_dst, order_src,
+                         attn_l, attn_r, negative_slope, drop_seed, drop_seed_base, drop_threshold, drop_scale, activation, act_slope, nullptr,
+                         workspace, workspace_bytes, g_ft, ldgf, g_attn_l, g_attn_r, g_bias, nullptr, stream);
+}
+
+extern "C" int wsi_gat_attn_bwd_scaled(const float* ft, int64_t ldf, const float* eler, const float* lse, const float* out, int64_t ldo,
+                                       const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t H, int32_t D,
+                                       const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
+                                       const int32_t* csc_dst, const int32_t* order_src, const float* attn_l, const float* attn_r,
+                                       float negative_slope, uint32_t drop_seed, const uint32_t* drop_seed_base, uint32_t drop_threshold,
+                                       float drop_scale, int32_t activation, float act_slope, const float* edge_scale,
+                                       void* workspace, int64_t workspace_bytes, float* g_ft, int64_t ldgf, float* g_attn_l, float* g_attn_r,
+                                       float* g_bias, float* g_edge_scale, void* stream) {
+    return ga_bwd<true>("gat_attn_bwd_scaled", ft, ldf, eler, lse, out, ldo, g_out, ldg, n, E, H, D, rowptr, src, colptr, csc_eid, csc_dst, order_src,
+                        attn_l, attn_r, negative_slope, drop_seed, drop_seed_base, drop_threshold, drop_scale, activation, act_slope, edge_scale,
+                        workspace, workspace_bytes, g_ft, ldgf, g_attn_l, g_attn_r, g_bias, g_edge_scale, stream);
+}
+
+extern "C" int wsi_sddmm_dot(const float* g, int64_t ldg, const float* x, int64_t ldx, int32_t n, int32_t D,
+                             const int32_t* rowptr, const int32_t* src, const float* iscale, const float* oscale,
+                             const float* relu_ref, int64_t ldref, float* g_w, void* stream) {
+    if (n < 0 || D <= 0 || D > 1024) { set_error("sddmm_dot: bad shape n=%d D=%d (1 <= D <= 1024)", n, D); return WSI_EINVAL; }
+    if (ldg < D || ldx < D || (relu_ref && ldref < D)) { set_error("sddmm_dot: row stride below D"); return WSI_EINVAL; }
+    if (n == 0) return WSI_OK;
+    if (!g || !x || !rowptr || !src || !g_w) { set_error("sddmm_dot: null pointer"); return WSI_EINVAL; }
+    const GaCfg cfg = ga_cfg(1, D, ldg % 4 == 0 && ldx % 4 == 0 && (!relu_ref || ldref % 4 == 0) && aligned16(g) && aligned16(x) && aligned16(relu_ref));
+    hipStream_t st = (hipStream_t)stream;
+    const int per = GA_BLOCK / cfg.G;
+#define CALL(G_, V_, K_) hipLaunchKernelGGL((sddmm_dot_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, g, ldg, x, ldx, n, D, \
+                                            rowptr, src, iscale, oscale, relu_ref, ldref, g_w)
+    GA_DISPATCH(cfg, CALL);
+#undef CALL
+    return check_launch("sddmm_dot");
 }

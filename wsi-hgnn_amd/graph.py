@@ -964,6 +964,36 @@ def batch(graphs: Sequence[HeteroGraph]) -> HeteroGraph:
     return out
 
 
+@contextlib.contextmanager
+def message_scale(g: HeteroGraph, scale: torch.Tensor):
+    """For the duration of the block, every message of every ``GraphConv`` / ``GATConv`` forward on ``g`` is multiplied by
+    ``scale[e]`` (``scale``: [E], in the graph's EDGE order, any finite values; gradients flow back to it).  This is what the
+    reference's ``ExplainGraph.update_all`` does with ``sigmoid(edge_mask)`` (explainers/gnn_explainer.py:21-33); degree norms and
+    the readout poolings are those of the unmasked graph, as there.  The tensor is kept permuted into the plan's CSR edge order
+    (plain indexing: autograd carries the gradient back to edge order) and removed on exit, also when the block raises.
+    Homogeneous graphs only: the reference's hijack works on a ``DGLGraph`` with a single edge frame."""
+    if not g.is_homogeneous:
+        raise ValueError("message_scale needs a homogeneous graph (one node type, one relation): the reference's update_all hijack "
+                         "does not reach multi_update_all")
+    E = g.num_edges()
+    if scale.dim() != 1 or scale.numel() != E:
+        raise ValueError(f"message_scale: scale must be [{E}] (one value per edge, in edge order), got {tuple(scale.shape)}")
+    previous = g.__dict__.get("_message_scale")
+    g.__dict__["_message_scale"] = scale.to(torch.float32)[g._csr_perm().to(scale.device)] if E else scale.to(torch.float32)
+    try:
+        yield g
+    finally:
+        if previous is None:
+            g.__dict__.pop("_message_scale", None)
+        else:
+            g.__dict__["_message_scale"] = previous
+
+
+def message_scale_of(g: HeteroGraph) -> Optional[torch.Tensor]:
+    """The scale attached by an enclosing ``message_scale`` block, in CSR edge order, or None."""
+    return g.__dict__.get("_message_scale")
+
+
 def to_homogeneous(g: HeteroGraph, add_self_loop: bool = False) -> HeteroGraph:
     """``dgl.to_homogeneous(g, ndata=['feat', ...])`` (+ ``dgl.add_self_loop``): one node type holding all nodes in
     type-major order (DGL's order), one relation holding every edge (relations concatenated in canonical order);

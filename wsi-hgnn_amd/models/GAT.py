@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..graph import message_scale_of
 from .heat_net import make_pool
 
 
@@ -90,7 +91,8 @@ class GATConv(nn.Module):
         ft = ops.linear(x, self.fc.weight, None)
         act = _fused_activation(self.activation)
         rst = ops.gat_attention(ft, self.attn_l, self.attn_r, self.bias, plan, self.leaky_relu.negative_slope,
-                                activation=act or None, attn_drop=self._draw(self.attn_drop.p, x.device))
+                                activation=act or None, attn_drop=self._draw(self.attn_drop.p, x.device),
+                                edge_scale=message_scale_of(g))         # graph.message_scale (GNNExplainer): None outside such a block
         if act is False:
             rst = self.activation(rst)
         return rst.view(-1, self._num_heads, self._out_feats)

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..graph import message_scale_of
 from .heat_net import make_pool
 
 
@@ -19,6 +20,7 @@ class HomoPlan:
     def __init__(self, g):
         p = g.plan()
         self.rowptr, self.src, self.colptr, self.csc_dst = p.rowptr, p.src, p.colptr, p.csc_dst
+        self.csc_eid, self.num_edges = p.csc_eid, p.num_edges            # (the edge-scaled aggregation: ops.graph_conv_aggregate(edge_scale=))
         n = p.num_nodes
         indeg = (p.rowptr[1:n + 1] - p.rowptr[:n]).to(torch.float32)
         outdeg = (p.colptr[1:] - p.colptr[:-1]).to(torch.float32)
@@ -84,12 +86,13 @@ class GraphConv(nn.Module):
 
     def forward(self, g, x):
         hp = homo_plan(g)
+        scale = message_scale_of(g)                      # graph.message_scale (GNNExplainer): None outside such a block
         relu = self._activation is not None and getattr(self._activation, "__name__", "") == "relu"
         if self._in_feats > self._out_feats:
-            y = ops.graph_conv_aggregate(_MatmulNN.apply(x, self.weight), self.bias, hp, relu)
+            y = ops.graph_conv_aggregate(_MatmulNN.apply(x, self.weight), self.bias, hp, relu, edge_scale=scale)
             fused_act = relu
         else:
-            y = _MatmulNN.apply(ops.graph_conv_aggregate(x, None, hp, False), self.weight) + self.bias
+            y = _MatmulNN.apply(ops.graph_conv_aggregate(x, None, hp, False, edge_scale=scale), self.weight) + self.bias
             fused_act = False
         if self._activation is not None and not fused_act:
             y = self._activation(y)
