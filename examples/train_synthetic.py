@@ -5,7 +5,7 @@
   graph files (io.save_graph / load_graph)  ->  GraphBatchLoader (replaces GraphDataLoader + g.to(device))  ->
   HEATNet4 + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate.
 
-Run on one GPU:            python examples/train_synthetic.py --epochs 2
+Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation)
 Run data-parallel on N:    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_synthetic.py
 """
 import argparse
@@ -16,7 +16,7 @@ import tempfile
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from wsi_hgnn_amd import data, dist, io, models, synthetic, trainer  # noqa: E402
+from wsi_hgnn_amd import data, dist, io, models, synthetic, trainer, transforms  # noqa: E402
 
 
 def main(argv=None):
@@ -29,6 +29,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--dropout", type=float, default=0.2)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--augment", action="store_true",
+                    help="train on augmented graphs as the reference does (data.py:16-23: DropNode, DropEdge, NodeShuffle, FeatMask at p = 0.5)")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -58,7 +60,10 @@ def main(argv=None):
     mine = dist.shard(paths, rank, world)                                   # WSI-sharded data parallelism
     graphs = [io.load_graph(p) for p in mine]
     labels = [io.label_tumour_vs_normal(p, normal) for p in mine]
-    loader = data.GraphBatchLoader(graphs, labels, args.batch, dev, shuffle=True, drop_last=False, seed=611 + rank)
+    loader = data.GraphBatchLoader(graphs, labels, args.batch, dev, shuffle=True, drop_last=False, seed=611 + rank,
+                                   transform=transforms.reference_train_transform() if args.augment else None)
+    # evaluation sees the stored graphs: the reference augments type_ == "train" only (data.py:116-117)
+    eval_loader = data.GraphBatchLoader(graphs, labels, args.batch, dev, shuffle=False, drop_last=False) if args.augment else loader
 
     # 2. model / optimizer / loss exactly as parser.py builds them (Adam lr 1e-5 wd 5e-3; CrossEntropyLoss)
     nd = {"0": 0, "1": 1, "2": 2}
@@ -77,7 +82,7 @@ def main(argv=None):
             loss, acc, *_ = trainer.train_one_step(gnn, opt, loss_fn, G, y, dev, bucket=bucket, sync=True)
             tot, n = tot + loss, n + 1
         gnn.eval()
-        metrics = io.evaluate(gnn, loader)
+        metrics = io.evaluate(gnn, eval_loader)
         if rank == 0:
             print(f"epoch {epoch}: train loss {tot / max(n, 1):.4f}  eval {metrics}")
             store.save_model(gnn.state_dict(), version=epoch + 1, stats={"epoch": epoch, "loss": tot / max(n, 1), **metrics})

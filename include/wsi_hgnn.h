@@ -671,6 +671,55 @@ int wsi_stas(int32_t fill, int32_t kN, const int64_t* perm, const int32_t* n_idx
              const int32_t* colptr, const int32_t* csc_eid, const int32_t* csc_dst,
              int32_t* row_count, const int64_t* row_start, int64_t* out_col, float* out_val, int32_t* overflow, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Train-time graph augmentation (data.py:16-23,116-117: Compose([DropNode(0.5), DropEdge(0.5), NodeShuffle(), FeatMask(0.5, ['feat'])]) through
+ * dgl.transforms, applied to every TRAINING graph each time it is loaded).  Host side: wsi-hgnn_amd/transforms.py, ops.augment_graph.
+ *
+ * The draw contract (beside the dropout contract above; same fmix32, same 16-bit threshold = round(p * 65536), all arithmetic modulo 2^32).
+ * One call of a pipeline has ONE 32-bit draw seed.  Transform number k of the pipeline (0 for a transform called on its own), acting on
+ * stream j, uses the sub-seed
+ *     sub(seed, k, j) = fmix32(fmix32(seed + (k + 1) * 0x9E3779B1) + (j + 1) * 0x85EBCA6B)
+ * and element i of that stream the hash  h(i) = fmix32(i * 0x9E3779B1 + sub):
+ *     DropNode   stream j = index of the node type in g.ntypes,          i = node id;       node i is REMOVED iff (h(i) & 0xffff) < threshold
+ *     DropEdge   stream j = index of the relation in g.canonical_etypes, i = edge position; edge i is REMOVED iff (h(i) & 0xffff) < threshold
+ *     NodeShuffle stream j = index of the node type,                     i = node id;       perm = stable argsort of the 32-bit keys h(i)
+ *                (equal keys in index order); every node field x becomes x[perm]
+ *     FeatMask   stream j = 65536 * (position of the field name in its list) + (32768 for an edge field) + index of the type / relation,
+ *                i = feature column;  column i is ZEROED iff (h(i) & 0xffff) < threshold
+ * i always counts in the graph THE TRANSFORM RECEIVES: behind DropNode, DropEdge indexes the surviving edges of a relation in their (stable)
+ * order and NodeShuffle the surviving nodes.  Probability of removal = threshold / 65536 (p quantised to 1/65536; p = 1 removes everything).
+ * A pure function of (seed, k, j, i): the CPU formulation in transforms.py and these kernels produce the same graph bit for bit.
+ *
+ * Segment descriptors: DEVICE int64 tables, one row per node type / relation, in order.  A segment of n elements owns ceil(n / 1024) TILES;
+ * first_tile = tiles of the segments before it; ntiles = their total.  Outputs of a segment are written at its OWN offset `off` (capacity n):
+ * no output position depends on another segment's count, and none on an atomic: two-level exclusive scans, stable order, reproducible.
+ *
+ * wsi_augment_nodes : rows of 6 words [n, off, first_tile, sub-seed, threshold, 0].  new_id[off + i] <- new id of node i of the type (survivors
+ *                     keep their order) or -1; kept[off + r] <- old id of the type's r-th survivor; counts[s] <- survivors of segment s.
+ *                     tile_sum: scratch, ntiles + 1 int32.
+ * wsi_augment_edges : rows of 14 words [n, off, first_tile, u, v, sim, src_off, dst_off, sub-seed, threshold, mode, n_src, n_dst, 0]; u, v: device
+ *                     pointers to the relation's int64 endpoints (local ids), sim: to its fp32 edge scalar or 0; src_off / dst_off: offsets of
+ *                     the endpoint types in new_id (new_id NULL: no node was removed).  Stage 1 keeps the edges whose endpoints both survive
+ *                     (an endpoint outside [0, n_src) / [0, n_dst) removes the edge) and ranks them; mode 0 draws DropEdge by the edge's
+ *                     ORIGINAL position (DropEdge in front of DropNode), mode 1 by that rank (behind it); threshold 0: no DropEdge.
+ *                     out_u / out_v [off + r] <- renumbered endpoints of the relation's r-th final survivor, out_sim its sim, out_eid its original
+ *                     position; counts[s] <- final survivors.  tile_sum: scratch, 2 * (ntiles + 1) int32; rank1: scratch, one int32 per edge.
+ * wsi_augment_keys  : rows as for wsi_augment_nodes (threshold unused): keys[off + i] <- (segment << 32) | h(i): ONE stable ascending sort of
+ *                     keys orders every node type at once.
+ * wsi_gather_rows_masked : out[i, c] = zeroed(c) ? 0 : x[row_of[i], c] for i < rows, c < F  (row_of NULL: row i; an index outside
+ *                     [0, src_rows) gives a zero row; zeroed(c) = (fmix32(c * 0x9E3779B1 + mask_seed) & 0xffff) < mask_threshold, 0 = no mask):
+ *                     DropNode's compaction, NodeShuffle's permutation (composed into row_of) and FeatMask in ONE pass over the surviving
+ *                     rows.  One wave per row, 16 bytes per lane and access when F % 4 == 0 and both tables are 16-byte aligned with strides
+ *                     that are multiples of 4; any other width / alignment takes an element-per-lane path.
+ *                     Traffic: rows * F * 4 bytes read + rows * F * 4 written + rows * 8 of indices. */
+int wsi_augment_nodes(const int64_t* desc, int32_t nseg, int32_t ntiles, int32_t* tile_sum, int32_t* new_id, int64_t* kept,
+                      int32_t* counts, void* stream);
+int wsi_augment_edges(const int64_t* desc, int32_t nseg, int32_t ntiles, const int32_t* new_id, int32_t* tile_sum, int32_t* rank1,
+                      int64_t* out_u, int64_t* out_v, float* out_sim, int64_t* out_eid, int32_t* counts, void* stream);
+int wsi_augment_keys(const int64_t* desc, int32_t nseg, int32_t ntiles, int64_t* keys, void* stream);
+int wsi_gather_rows_masked(const float* x, int64_t ldx, int64_t src_rows, const int64_t* row_of, float* out, int64_t ldo, int64_t rows,
+                           int32_t F, uint32_t mask_seed, uint32_t mask_threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

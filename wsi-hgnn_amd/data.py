@@ -16,6 +16,9 @@ graph's own plan (``graph.PlanPieces``, built once per stored graph): the batch 
 so the plan of a batch is a concatenation of pieces plus offset additions — ~45 small launches, **no sort**, no host
 sync — and the returned ``HeteroGraph`` carries the plan, the CSR-ordered ``sim`` and the already-concatenated feature
 table, so the model does no further preprocessing.
+``transform=`` (``transforms.Compose`` ...) augments every slide drawn for a batch on the loader's device, as the reference's TRAINING data set
+does each time a graph is loaded (data.py:16-23,116-117); such batches take the general route (``graph.batch``, then the model's ``plan()``)
+because the stored pieces describe the unaugmented slide.  Evaluation loaders take no transform: the reference augments ``type_ == "train"`` only.
 Dataset parsing (DGL pickles, labels from TCGA barcodes — data.py:67-123) stays out of scope; graphs arrive as
 ``HeteroGraph`` objects (see INTEGRATION.md for the one-off DGL conversion).
 """
@@ -28,6 +31,12 @@ import torch
 
 from . import graph as _graph_mod
 from .graph import HeteroGraph, PlanHeader, PlanPieces, _resolve_device, assemble_plan, host_to_device
+
+
+def augment_draw(seed: int, counter: int, slide: int) -> int:
+    """The 32-bit draw of slide number ``slide`` in batch number ``counter`` (running over the loader's life) of a loader seeded with ``seed``."""
+    from .ops import _fmix32
+    return _fmix32(_fmix32(_fmix32(int(seed)) + int(counter) * 0x9E3779B1) + int(slide) * 0x85EBCA6B)
 
 
 class StoredGraph:
@@ -92,7 +101,11 @@ class GraphBatchLoader:
 
     def __init__(self, graphs: Sequence[HeteroGraph], labels: Sequence[int], batch_size: int, device,
                  shuffle: bool = True, drop_last: bool = False, seed: int = 611, resident: Optional[bool] = None, passes: int = 1,
-                 assemble_on_side_stream: bool = False):
+                 assemble_on_side_stream: bool = False, transform=None):
+        """``transform``: a callable ``(HeteroGraph, draw=seed) -> HeteroGraph`` (``transforms.reference_train_transform()``) applied to every
+        slide each time it is drawn, on ``device`` (pinned-host data sets: after the transfer), with the draw ``augment_draw(seed, running batch
+        counter, slide index)``: two loaders with one seed yield identical batches, successive passes different ones.  ``None`` (default, and what an
+        evaluation loader passes): the stored slides, through the assembled-plan path."""
         if len(graphs) != len(labels):
             raise ValueError("graphs and labels differ in length")
         if len(graphs) == 0:
@@ -117,6 +130,7 @@ class GraphBatchLoader:
         # cost is paid every other step.)
         self.passes = max(1, int(passes))
         self.gen = torch.Generator().manual_seed(seed)
+        self.transform, self.seed, self._batches_drawn = transform, int(seed), 0
         self.in_dim = self.items[0].feat[0].shape[1]
         # pinned-host mode: the transfers travel on ops' "work" side stream - idle while this loader feeds steps (it blocks the side streams then,
         # __iter__) - rather than on one more stream of its own: a fourth hardware queue in use stretches the step (ops._SIDE_STREAMS)
@@ -244,6 +258,19 @@ class GraphBatchLoader:
                     feat[row:row + k].copy_(it.feat[t], non_blocking=True)
                 row += k
 
+    def _augmented(self, idxs: List[int]):
+        """A batch of augmented slides: every slide as a single graph on the device, ``transform`` with its own draw, then the general route -
+        ``graph.batch``; the model builds the plan (``HeteroGraph.plan``).  The stored pieces describe the unaugmented slide and are not used."""
+        dev = self.device
+        counter, self._batches_drawn = self._batches_drawn, self._batches_drawn + 1
+        gs = []
+        for i in idxs:
+            it = self.items[i]
+            feats = it.feat if self.resident else [f.to(dev, non_blocking=True) for f in it.feat]
+            g = HeteroGraph.from_coo(OrderedDict(zip(it.ntypes, it.num_nodes)), it.edges, feat=dict(zip(it.ntypes, feats)), sim=it.sims)
+            gs.append(self.transform(g, draw=augment_draw(self.seed, counter, i)))
+        return _graph_mod.batch(gs), host_to_device([self.items[i].label for i in idxs], torch.int64, dev)
+
     def __iter__(self) -> Iterator[Tuple[HeteroGraph, torch.Tensor]]:
         batches = []
         for _ in range(self.passes):
@@ -258,6 +285,10 @@ class GraphBatchLoader:
                 one = [one[j] for j in torch.randperm(len(one), generator=self.gen).tolist()]
             batches += one
         if not batches:
+            return
+        if self.transform is not None:
+            for idxs in batches:
+                yield self._augmented(idxs)
             return
         # pinned-host mode: while this iterator feeds steps, every launch of those steps stays on the caller's stream (ops.block_side_streams: beside
         # H2D transfers a second compute stream stretches the step from 6.7 to 10 ms; the transfer bounds it at ~6 ms either way)
@@ -280,7 +311,7 @@ class GraphBatchLoader:
                 if not self.resident and bi + 1 < len(batches):
                     slot ^= 1
                     nxt = self._assemble(batches[bi + 1], slot)
-                cur = torch.cuda.current_stream(self.device)
+                cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
                 if ready is not None:
                     cur.wait_event(ready)
                 yield G, labels

@@ -2548,3 +2548,228 @@ def gat_attention(ft: torch.Tensor, attn_l: torch.Tensor, attn_r: torch.Tensor, 
     _check_edge_scale("gat_attention", edge_scale, plan)
     return _GatAttentionScaled.apply(ft, attn_l, attn_r, bias, edge_scale, plan, float(negative_slope), GAT_ACTIVATIONS[activation],
                                      float(act_slope), attn_drop)
+
+
+# ------------------------------------------------------------------------------------------------
+# train-time graph augmentation (wsi_augment_* / wsi_gather_rows_masked; the draw contract is in include/wsi_hgnn.h)
+# ------------------------------------------------------------------------------------------------
+AUG_TILE = 1024
+AUG_KINDS = ("drop_node", "drop_edge", "node_shuffle", "feat_mask")
+
+
+def _fmix32(h: int) -> int:
+    h &= 0xffffffff
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & 0xffffffff
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & 0xffffffff
+    h ^= h >> 16
+    return h
+
+
+def augment_subseed(seed: int, k: int, j: int) -> int:
+    """sub(seed, k, j) of the draw contract: transform number ``k`` of the pipeline acting on stream ``j`` (host integers)."""
+    return _fmix32(_fmix32(int(seed) + (int(k) + 1) * 0x9E3779B1) + (int(j) + 1) * 0x85EBCA6B)
+
+
+def augment_threshold(p: float) -> int:
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("probability must be in [0, 1]")
+    return int(round(float(p) * 65536.0))
+
+
+def augment_hash(n: int, sub: int, device="cpu") -> torch.Tensor:
+    """h(i) = fmix32(i * 0x9E3779B1 + sub) for i < n as an int64 tensor of 32-bit values: the contract replayed with integer tensor arithmetic
+    (any device; independent of the kernels)."""
+    i = torch.arange(int(n), dtype=torch.int64, device=device)
+    h = (_mul32(i & 0xffffffff, 0x9E3779B1) + int(sub)) & 0xffffffff
+    h = h ^ (h >> 16)
+    h = _mul32(h, 0x85EBCA6B)
+    h = h ^ (h >> 13)
+    h = _mul32(h, 0xC2B2AE35)
+    return h ^ (h >> 16)
+
+
+def augment_drawn(n: int, sub: int, threshold: int, device="cpu") -> torch.Tensor:
+    """Boolean [n]: element i is removed / zeroed by a Bernoulli(threshold / 65536) draw of stream ``sub``."""
+    return (augment_hash(n, sub, device) & 0xffff) < int(threshold)
+
+
+def mask_columns(x: torch.Tensor, sub: int, threshold: int) -> torch.Tensor:
+    """FeatMask on one field as tensor operations: a copy of ``x`` with the drawn columns (last dimension) set to 0."""
+    if x.dim() < 2:
+        raise ValueError("FeatMask needs a field with a feature dimension (at least 2-D)")
+    out = x.clone()
+    if threshold:
+        out[..., augment_drawn(x.shape[-1], sub, threshold, x.device)] = 0
+    return out
+
+
+def gather_rows_masked(x: torch.Tensor, row_of: Optional[torch.Tensor], mask_seed: int = 0, mask_threshold: int = 0) -> torch.Tensor:
+    """out[i, c] = zeroed(c) ? 0 : x[row_of[i], c] (``wsi_gather_rows_masked``): x fp32 [n, F] with unit column stride, row_of int64 [rows] or
+    None (= every row in place)."""
+    N.require_cuda(x, row_of)
+    if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("gather_rows_masked: an fp32 [n, F] table with contiguous rows")
+    rows = x.shape[0] if row_of is None else int(row_of.numel())
+    if row_of is not None:
+        row_of = row_of.to(torch.int64).contiguous()
+    out = torch.empty((rows, x.shape[1]), dtype=torch.float32, device=x.device)
+    with _Timed("augment_gather"):
+        N.check(N.load().wsi_gather_rows_masked(N.ptr(x), x.stride(0) if x.shape[0] > 1 else max(x.shape[1], 1), x.shape[0], N.ptr(row_of), N.ptr(out),
+                                                max(x.shape[1], 1), rows, x.shape[1], int(mask_seed) & 0xffffffff, int(mask_threshold), N.stream()),
+                "wsi_gather_rows_masked")
+    return out
+
+
+def _segment_rows(counts: Sequence[int], extra) -> Tuple[List[int], int, List[int]]:
+    """Descriptor rows [n, off, first_tile, *extra(j)] of consecutive segments; returns (words, tiles, offsets)."""
+    words, off, tiles, offs = [], 0, 0, []
+    for j, n in enumerate(counts):
+        words += [int(n), off, tiles] + list(extra(j))
+        offs.append(off)
+        off += int(n)
+        tiles += (int(n) + AUG_TILE - 1) // AUG_TILE
+    return words, tiles, offs
+
+
+def _shuffle_perms(counts: Sequence[int], subs: Sequence[int], dev) -> List[torch.Tensor]:
+    """NodeShuffle's permutation of every node type: the 32-bit hash keys of all types in one table ((type << 32) | key), ONE stable sort."""
+    total = sum(counts)
+    words, tiles, offs = _segment_rows(counts, lambda j: (subs[j], 0, 0))
+    keys = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        desc = host_to_device(words, torch.int64, dev)
+        N.check(N.load().wsi_augment_keys(N.ptr(desc), len(counts), tiles, N.ptr(keys), N.stream()), "wsi_augment_keys")
+    idx = torch.sort(keys, stable=True).indices
+    return [idx[a:a + c] - a for a, c in zip(offs, counts)]
+
+
+def augment_graph(g, stages, seed: int):
+    """The fused device path of ``transforms``: at most one each of DropNode, DropEdge, NodeShuffle and FeatMask, in ANY order, applied to a
+    single graph on the GPU with a launch count that does not depend on how many of them there are.  ``stages``: tuples
+    ``(kind, k, p, node_names, edge_names)`` in pipeline order, ``kind`` one of ``AUG_KINDS``, ``k`` the transform's number in the pipeline.
+    The result equals the members applied one after another (transforms.py's tensor formulation) bit for bit.
+
+    Node ids come from one flag + scan pass over all node types, the surviving edges from two over all relations (endpoints, then DropEdge by
+    rank), every fp32 [n, F] node field from ONE gather through the composed row index with the column mask applied on the way; the other
+    fields follow by indexing.  One device->host read-back per call: the [T] node and [R] edge counts together (HeteroGraph keeps counts on the
+    host); none when neither DropNode nor DropEdge is present."""
+    from collections import OrderedDict
+    from .graph import HeteroGraph
+    kinds = [s[0] for s in stages]
+    if any(k not in AUG_KINDS for k in kinds) or len(set(kinds)) != len(kinds):
+        raise ValueError(f"augment_graph fuses at most one each of {AUG_KINDS}; got {kinds}")
+    if g._batch_num_nodes is not None and g.batch_size > 1:
+        raise ValueError("graph transforms work on single graphs (augment the slides, then batch them)")
+    dev = g.device
+    if dev.type != "cuda":
+        raise RuntimeError("ops.augment_graph runs on the GPU only (HIP kernels); transforms.py holds the CPU formulation")
+    g = g.to(dev)
+    lib = N.load()
+    order = {s[0]: i for i, s in enumerate(stages)}
+    st = {s[0]: s for s in stages}
+    ntypes, rels = g.ntypes, g.canonical_etypes
+    T, R = len(ntypes), len(rels)
+    tindex = {t: i for i, t in enumerate(ntypes)}
+    n = [g.num_nodes(t) for t in ntypes]
+    edges = g._edges
+    e = [int(edges[r][0].numel()) for r in rels]
+    Ntot, Etot = sum(n), sum(e)
+    if Ntot >= 2 ** 31 - 1 or Etot >= 2 ** 31 - 1:
+        raise ValueError("graph too large for the int32 augmentation kernels")
+    dn, de, ns, fm = (st.get(k) for k in AUG_KINDS)
+    dn_thr = augment_threshold(dn[2]) if dn is not None else 0
+    de_thr = augment_threshold(de[2]) if de is not None else 0
+    fm_thr = augment_threshold(fm[2]) if fm is not None else 0
+    node_changed, edge_changed = dn_thr > 0, dn_thr > 0 or de_thr > 0
+    counts_dev = torch.zeros(T + R, dtype=torch.int32, device=dev)
+    i32 = lambda m: torch.empty(max(int(m), 1), dtype=torch.int32, device=dev)
+    i64 = lambda m: torch.empty(max(int(m), 1), dtype=torch.int64, device=dev)
+    with _Timed("augment_index"):
+        new_id = kept = None
+        if node_changed:
+            words, tiles, noff = _segment_rows(n, lambda j: (augment_subseed(seed, dn[1], j), dn_thr, 0))
+            desc_n = host_to_device(words, torch.int64, dev)
+            new_id, kept, tsum_n = i32(Ntot), i64(Ntot), i32(tiles + 1)
+            N.check(lib.wsi_augment_nodes(N.ptr(desc_n), T, tiles, N.ptr(tsum_n), N.ptr(new_id), N.ptr(kept), N.ptr(counts_dev), N.stream()),
+                    "wsi_augment_nodes")
+        else:
+            _, _, noff = _segment_rows(n, lambda j: ())
+        sim_in_kernel = {}
+        if edge_changed and R > 0:
+            by_rank = 1 if (node_changed and de_thr > 0 and order["drop_edge"] > order["drop_node"]) else 0
+            uv = [(edges[r][0].contiguous(), edges[r][1].contiguous()) for r in rels]
+            sims = []
+            for r, m in zip(rels, e):
+                x = g._eframes[r].get("sim")
+                ok = x is not None and x.dtype == torch.float32 and x.dim() == 1 and x.numel() == m and x.is_contiguous()
+                sims.append(x if ok else None)
+                sim_in_kernel[r] = ok
+
+            def extra(j):
+                s, _, d = rels[j]
+                return (uv[j][0].data_ptr(), uv[j][1].data_ptr(), 0 if sims[j] is None else sims[j].data_ptr(), noff[tindex[s]], noff[tindex[d]],
+                        augment_subseed(seed, de[1], j) if de is not None else 0, de_thr, by_rank, n[tindex[s]], n[tindex[d]], 0)
+
+            words, tiles, eoff = _segment_rows(e, extra)
+            desc_e = host_to_device(words, torch.int64, dev)
+            out_u, out_v, out_eid = i64(Etot), i64(Etot), i64(Etot)
+            out_sim = torch.empty(max(Etot, 1), dtype=torch.float32, device=dev)
+            tsum_e, rank1 = i32(2 * (tiles + 1)), i32(Etot)             # (scratch held in names: two temporaries could share one block)
+            N.check(lib.wsi_augment_edges(N.ptr(desc_e), R, tiles, N.ptr(new_id), N.ptr(tsum_e), N.ptr(rank1), N.ptr(out_u), N.ptr(out_v),
+                                          N.ptr(out_sim), N.ptr(out_eid), N.ptr(counts_dev[T:]), N.stream()), "wsi_augment_edges")
+        shuffle_first = ns is not None and (not node_changed or order["node_shuffle"] < order["drop_node"])
+        perms = None
+        if shuffle_first:
+            perms = _shuffle_perms(n, [augment_subseed(seed, ns[1], j) for j in range(T)], dev)
+        if node_changed or (edge_changed and R > 0):
+            got = counts_dev.tolist()           # THE read-back: [T] node counts and [R] edge counts in one copy
+        n2 = got[:T] if node_changed else n
+        e2 = got[T:] if (edge_changed and R > 0) else e
+        if ns is not None and not shuffle_first:
+            perms = _shuffle_perms(n2, [augment_subseed(seed, ns[1], j) for j in range(T)], dev)
+        row_of = []
+        for j in range(T):
+            kj = kept[noff[j]:noff[j] + n2[j]] if node_changed else None
+            if perms is None:
+                row_of.append(kj)
+            elif kj is None:
+                row_of.append(perms[j])
+            else:
+                row_of.append(perms[j][kj] if shuffle_first else kj[perms[j]])
+    new_edges = OrderedDict()
+    for j, r in enumerate(rels):
+        if edge_changed:
+            new_edges[r] = (out_u[eoff[j]:eoff[j] + e2[j]], out_v[eoff[j]:eoff[j] + e2[j]])
+        else:
+            new_edges[r] = edges[r]
+    out = HeteroGraph(OrderedDict(zip(ntypes, n2)), new_edges)
+    node_names = list(fm[3] or []) if fm is not None else []
+    edge_names = list(fm[4] or []) if fm is not None else []
+    for j, t in enumerate(ntypes):
+        for key, x in g._nframes[t].items():
+            if key == "_pos" and ns is not None:
+                continue                        # the locality positions describe the topology, not the rows that now sit on it
+            masked = key in node_names and fm_thr > 0
+            sub = augment_subseed(seed, fm[1], 65536 * node_names.index(key) + j) if masked else 0
+            if masked and x.dim() < 2:
+                raise ValueError("FeatMask needs a field with a feature dimension (at least 2-D)")
+            if row_of[j] is None and not masked:
+                out._nframes[t][key] = x
+            elif x.dim() == 2 and x.dtype == torch.float32 and (x.shape[1] <= 1 or x.stride(1) == 1):
+                out._nframes[t][key] = gather_rows_masked(x, row_of[j], sub, fm_thr if masked else 0)
+            else:
+                y = x if row_of[j] is None else x[row_of[j]]
+                out._nframes[t][key] = mask_columns(y, sub, fm_thr) if masked else y
+    for j, r in enumerate(rels):
+        for key, x in g._eframes[r].items():
+            masked = key in edge_names and fm_thr > 0
+            if not edge_changed:
+                y = x
+            elif key == "sim" and sim_in_kernel.get(r):
+                y = out_sim[eoff[j]:eoff[j] + e2[j]]
+            else:
+                y = x[out_eid[eoff[j]:eoff[j] + e2[j]]]
+            out._eframes[r][key] = mask_columns(y, augment_subseed(seed, fm[1], 65536 * edge_names.index(key) + 32768 + j), fm_thr) if masked else y
+    return out
