@@ -541,7 +541,10 @@ int wsi_sddmm_dot(const float* g, int64_t ldg, const float* x, int64_t ldx, int3
                   const float* relu_ref, int64_t ldref, float* g_w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Graph-construction edge step: exact L2 kNN + per-edge Pearson correlation.
+ * Graph-construction edge step: L2 kNN + per-edge Pearson correlation.  The kNN is an exact
+ * re-ranking (wsi_pair_stats) of a shortlist (wsi_knn_select) whose membership is reliable down to neighbour gaps of about
+ * slack = 8 e, e = the absolute fp32 error of the key sqnorm[j] - 2 dots[i,j] (a few ulp of |x|^2; about 4e-4 at 1024
+ * columns and |x|^2 = 350): a returned distance exceeds the exact one at its position by at most slack.
  *
  * Replaces, behind wsi-hgnn_amd/construct.py::construct_graph,
  *   construct_graph/graph_constructor.py:265-273   Hnsw(space='l2').fit(features); query(features[v], topn=radius)[1:]
@@ -551,9 +554,12 @@ int wsi_sddmm_dot(const float* g, int64_t ldg, const float* x, int64_t ldx, int3
  * wsi_knn_select : `dots` = rows [row0, row0+rows) of X X^T (ld = ldd, N columns; from wsi_gemm_grouped NT).  For every
  *                  row writes the kc (<= 32) columns j != row0+i with the smallest sqnorm[j] - 2 dots[i,j] (i.e. the
  *                  smallest |x_i - x_j|^2 up to the GEMM's rounding), ascending, ties -> smaller j; -1 pads when N-1 < kc.
- * wsi_pair_stats : for every row i and each of its kc (<= 64) candidates j: exact d2 = sum (x_i-x_j)^2 and Pearson r
- *                  from centred sums (NaN if either vector is constant, as scipy); keeps the `keep` candidates with the
- *                  smallest (d2, j), ascending, into nbr / dist2 / corr [n, keep] (caller pre-fills nbr with -1).
+ *                  A column whose key is +inf (an overflowed norm) is never listed; -1 stands in its place.
+ * wsi_pair_stats : for every row i and each of its kc (<= 64) candidates j (entries < 0 are skipped): exact
+ *                  d2 = sum (x_i-x_j)^2 and Pearson r from centred sums (NaN if either vector is constant, i.e. every
+ *                  element equals the first, as scipy tests it); keeps the `keep` candidates with the smallest (d2, j),
+ *                  ascending, into nbr / dist2 / corr [n, keep].  With fewer than `keep` valid candidates the remaining
+ *                  slots are not written (caller pre-fills nbr with -1).
  */
 int wsi_row_sqnorm(const float* x, int64_t ldx, int32_t n, int32_t F, float* out, void* stream);
 int wsi_knn_select(const float* dots, int64_t ldd, const float* sqnorm, int32_t row0, int32_t rows, int32_t N,

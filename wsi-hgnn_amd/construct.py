@@ -11,8 +11,14 @@ per-patch features and node types exist (the CNN encoders / HoVer-Net / openslid
 
 Here: ``X X^T`` row blocks on the matrix cores (the grouped GEMM of the hot path), a streaming top-(k+pad) shortlist per row
 (``wsi_knn_select``) and one gather kernel that computes, for the shortlisted pairs, the EXACT squared distance and the
-Pearson correlation and keeps the ``radius-1`` nearest (``wsi_pair_stats``).  HNSW is an approximate index; this is the
-exact k-NN it approximates (recall 1.0 by construction), ties broken towards the smaller index.
+Pearson correlation and keeps the ``radius-1`` nearest (``wsi_pair_stats``).  HNSW is an approximate index; this is an exact
+re-ranking of a shortlist whose membership is reliable down to neighbour gaps of about ``slack``: the shortlist ranks by
+``|x_j|^2 - 2 x_i.x_j`` in fp32, whose absolute error ``e`` is a few ulp of ``|x|^2`` (about 4e-4 at F = 1024, ``|x|^2`` = 350),
+and ``slack = 8 e``.  Every returned distance lies within ``slack`` above the exact one at the same position, and the list is
+the exact one wherever the exact distances of the ``radius-1``-th and the ``(radius+pad)``-th neighbour differ by more than
+``slack``; inside a tight cluster far from the origin (near-duplicate patches) the neighbours returned are near but need not
+be the nearest.  Ties are broken towards the smaller index.  A constant feature row gives ``corr`` = nan, as
+``scipy.stats.pearsonr`` does, and its edges are typed ``neg``.
 There is no CPU fallback: the kernels live in libwsi_hgnn.so.
 """
 from __future__ import annotations
@@ -34,7 +40,8 @@ def knn_pearson(features: torch.Tensor, radius: int, pad: int = 8, block_rows: O
     """For every row of ``features`` [N, F] (fp32, CUDA) its ``radius - 1`` nearest OTHER rows under L2.
 
     Returns ``(nbr [N, radius-1] int64, corr [N, radius-1] float32, dist2 [N, radius-1] float32)``, neighbours ascending by
-    (distance, index).  ``pad`` extra candidates are shortlisted from the GEMM form of the distance and re-ranked exactly.
+    (distance, index).  ``pad`` extra candidates are shortlisted from the GEMM form of the distance and re-ranked exactly
+    (the module docstring states how far the shortlist can be trusted).  ``block_rows``: rows of ``X X^T`` per GEMM launch.
     """
     N.require_cuda(features)
     if features.dim() != 2 or features.dtype != torch.float32:

@@ -1,12 +1,19 @@
-// Graph-construction edge step on the GPU: exact L2 k-nearest-neighbour selection and the per-edge
-// Pearson correlation that types the edges.  Replaces, behind wsi-hgnn_amd/construct.py,
+// Graph-construction edge step on the GPU: L2 k-nearest-neighbour selection (exact re-ranking of a
+// shortlist whose membership is reliable down to neighbour gaps of about `slack`, see below) and the per-edge Pearson
+// correlation that types the edges.  Replaces, behind wsi-hgnn_amd/construct.py,
 //   construct_graph/graph_constructor.py:265-273  nmslib HNSW(space='l2') fit + one knnQuery per patch (approximate)
 //   construct_graph/graph_constructor.py:276-282  scipy.stats.pearsonr in a Python loop over all E pairs of 1024-d vectors
 // Pipeline (host side in construct.py):  X X^T row blocks on the matrix cores (wsi_gemm_grouped NT)  ->
 // wsi_knn_select: per row the kc = k+pad columns with the smallest |x_j|^2 - 2 x_i.x_j  (one streaming pass, HBM-bound) ->
 // wsi_pair_stats: for those candidates the EXACT sum (x_i-x_j)^2 and Pearson r from centred sums (gathers of 4 KB rows),
 // final top-k by the exact distance.  The GEMM form of the distance cancels catastrophically for near neighbours; it is
-// only used to shortlist, never to rank the output.
+// only used to shortlist, never to rank the output.  The shortlist is therefore NOT exact: its fp32 key carries an absolute
+// error e of a few ulp of |x|^2 (about 5e-4 at F = 1024, |x|^2 = 330), and a true neighbour can be displaced by a row whose
+// exact distance is up to slack = 8 e larger.  What holds for every output position c is
+//   d2_exact[c] (1 - 2e-5) <= d2[c] <= d2_exact[c] + slack,
+// and the list equals the exact one wherever the exact distances of the keep-th and the (kc+1)-th neighbour are further
+// than slack apart (tests/test_construct_kernels_gpu.py::test_resolution_limit).  Tight clusters far from the
+// origin (near-duplicate patches) are where the lists differ.
 #include "common.h"
 #include <limits.h>
 #include <math.h>
@@ -94,8 +101,13 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const float* __restrict
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= n) return;
     const float* xi = x + (int64_t)i * ldx;
+    // constancy as scipy.stats.pearsonr tests it, (x == x[0]).all(), voted over the wave while the row is read: the centred
+    // sum of squares of a constant row is NOT exactly 0 in fp32 (1024 x 0.7f: the rounded mean is 0.69999987, sxx = 1.5e-11)
+    const float xi0 = xi[0];
+    bool same_i = true;
     float si = 0.f;
-    for (int c = lane; c < F; c += 64) si += xi[c];
+    for (int c = lane; c < F; c += 64) { const float a = xi[c]; same_i &= (a == xi0); si += a; }
+    const bool const_i = __all(same_i);
     const float mi = wave_sum(si) / (float)F;
     float sxx = 0.f;
     for (int c = lane; c < F; c += 64) { const float a = xi[c] - mi; sxx = fmaf(a, a, sxx); }
@@ -107,8 +119,11 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const float* __restrict
         const int j = cand[(int64_t)i * kc + cidx];
         if (j < 0) continue;                                   // wave-uniform
         const float* xj = x + (int64_t)j * ldx;
+        const float xj0 = xj[0];
+        bool same_j = true;
         float sj = 0.f;
-        for (int c = lane; c < F; c += 64) sj += xj[c];
+        for (int c = lane; c < F; c += 64) { const float b = xj[c]; same_j &= (b == xj0); sj += b; }
+        const bool const_j = __all(same_j);
         const float mj = wave_sum(sj) / (float)F;
         float sxy = 0.f, syy = 0.f, d2 = 0.f;
         for (int c = lane; c < F; c += 64) {
@@ -122,9 +137,10 @@ __global__ __launch_bounds__(256) void pair_stats_kernel(const float* __restrict
         if (lane == cidx) {
             my_d2 = d2; my_j = j;
             // scipy.stats.pearsonr: r = <xm/|xm|, ym/|ym|> clipped to [-1, 1]; a constant vector gives nan (kept: the
-            // reference then types the edge 'neg' because `nan > 0` is False)
-            my_r = fminf(1.f, fmaxf(-1.f, sxy / (sqrtf(sxx) * sqrtf(syy))));
-            if (sxx == 0.f || syy == 0.f) my_r = NAN;
+            // reference then types the edge 'neg' because `nan > 0` is False).  The normalisation runs in double, where
+            // sxx * syy is exact and cannot leave the range: two identical rows (sxy == sxx == syy) give exactly 1.
+            const double r = (double)sxy / sqrt((double)sxx * (double)syy);
+            my_r = (const_i || const_j) ? NAN : (float)(r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r));      // a nan r stays nan
         }
     }
     // rank of this lane's candidate among all candidates by (exact d2, column)
