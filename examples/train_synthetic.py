@@ -5,7 +5,8 @@
   graph files (io.save_graph / load_graph)  ->  GraphBatchLoader (replaces GraphDataLoader + g.to(device))  ->
   HEATNet4 + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate.
 
-Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation)
+Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation;
+                           --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers)
 Run data-parallel on N:    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_synthetic.py
 """
 import argparse
@@ -16,7 +17,7 @@ import tempfile
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from wsi_hgnn_amd import data, dist, io, models, synthetic, trainer, transforms  # noqa: E402
+from wsi_hgnn_amd import data, dist, io, models, parser, synthetic, trainer, transforms  # noqa: E402
 
 
 def main(argv=None):
@@ -31,6 +32,9 @@ def main(argv=None):
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--augment", action="store_true",
                     help="train on augmented graphs as the reference does (data.py:16-23: DropNode, DropEdge, NodeShuffle, FeatMask at p = 0.5)")
+    ap.add_argument("--optimizer", choices=("adam", "sgd", "adagrad", "adadelta"), default=None,
+                    help="step with the package's own optimizer of that name (parser.parse_optimizer(..., native=True): one HIP launch per step); "
+                         "default: torch.optim.Adam")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -69,7 +73,10 @@ def main(argv=None):
     nd = {"0": 0, "1": 1, "2": 2}
     torch.manual_seed(611)
     gnn = models.HEATNet4(args.in_dim, args.hidden, 2, 2, 4, nd, args.dropout, "mean").to(dev)
-    opt = torch.optim.Adam(gnn.parameters(), lr=1e-5, weight_decay=5e-3)
+    if args.optimizer is None:
+        opt = torch.optim.Adam(gnn.parameters(), lr=1e-5, weight_decay=5e-3)
+    else:
+        opt = parser.parse_optimizer({"opt_method": args.optimizer, "lr": 1e-5, "weight_decay": 5e-3}, gnn, native=True)
     loss_fn = torch.nn.CrossEntropyLoss()
     bucket = dist.GradBucket.from_model(gnn) if world > 1 else None         # every parameter the architecture reaches, with used flags
     store = io.CheckpointStore(os.path.join(work, "ckpt"))

@@ -433,6 +433,34 @@ typedef struct wsi_adam_tensor { float* p; const float* g; float* m; float* v; i
 int wsi_adam_step(const wsi_adam_tensor_t* tensors, int32_t count, double lr, double beta1, double beta2, double eps,
                   double weight_decay, int64_t step, void* stream);      /* (hyper-parameters in double, as torch holds them: 1 - beta2 is taken in double) */
 
+/* The other optimizers parser.parse_optimizer can build (parser.py:15-46: Adagrad, Adadelta, SGD for anything else) and an Adam whose step
+ * count lives on the device, each in ONE launch over all `count` tensors (more than the kernel's table holds: several launches; zero-element
+ * tensors are skipped).  fp32 arithmetic per element in torch.optim's order, scalar factors taken in double:
+ *   WSI_OPTIM_SGD       g += wd p;  momentum != 0: buf = (flags & WSI_OPTIM_FIRST) ? g : momentum buf + (1 - dampening) g,
+ *                       g = nesterov ? g + momentum buf : buf;  p -= lr g                            (s0 = buf; NULL when momentum == 0)
+ *   WSI_OPTIM_ADAGRAD   g += wd p;  sum += g^2;  p -= lr / (1 + (t - 1) lr_decay) * g / (sqrt(sum) + eps)                     (s0 = sum)
+ *   WSI_OPTIM_ADADELTA  g += wd p;  sq = rho sq + (1 - rho) g^2;  d = sqrt(acc + eps) / sqrt(sq + eps) * g;
+ *                       acc = rho acc + (1 - rho) d^2;  p -= lr d                                                  (s0 = sq, s1 = acc)
+ *   WSI_OPTIM_ADAM      wsi_adam_step's arithmetic                                                           (s0 = exp_avg, s1 = exp_avg_sq)
+ * t is the 1-based count AFTER this step.  A tensor with `step` != NULL keeps it on the device (a 0-dim fp32 word, torch's capturable layout):
+ * the launch reads t - 1 from it and leaves t there, which is what lets a captured graph replay the step; `ticket` is an int32 word of the
+ * caller's, zero before the first call and left zero by every call (the workgroups of a tensor count themselves through it: the last one
+ * stores the new count).  With `step` == NULL, t = hyper->host_step.  SGD and Adadelta never read t but advance a `step` word they are given.
+ * `nesterov` is 0 or 1 and needs momentum > 0 and dampening == 0, as torch demands. */
+#define WSI_OPTIM_SGD      0
+#define WSI_OPTIM_ADAGRAD  1
+#define WSI_OPTIM_ADADELTA 2
+#define WSI_OPTIM_ADAM     3
+#define WSI_OPTIM_FIRST    1   /* flags: this tensor's first step under SGD with momentum (s0 is written, not read) */
+typedef struct wsi_optim_tensor {
+    float* p; const float* g; float* s0; float* s1;
+    float* step; int32_t* ticket; int64_t n; int32_t flags;
+} wsi_optim_tensor_t;
+typedef struct wsi_optim_hyper {
+    double lr, weight_decay, momentum, dampening, nesterov, lr_decay, eps, rho, beta1, beta2, host_step;
+} wsi_optim_hyper_t;
+int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper, void* stream);
+
 /* Mean cross entropy of logits [B, C] against int64 labels and its gradient factor in ONE launch (torch.nn.CrossEntropyLoss() with its
  * defaults, parser.py:182-183, applied at trainer/train_gnn.py:67):  *loss = mean over the VALID rows b of (logsumexp(logits[b]) - logits[b, y_b]);
  * dlogits[b, c] = (softmax(logits[b])[c] - [c == y_b]) / #valid  (the caller multiplies it by the incoming gradient of the loss).

@@ -38,6 +38,22 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
+class OptimTensor(ctypes.Structure):
+    """wsi_optim_tensor_t (include/wsi_hgnn.h)."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("s0", ctypes.c_void_p), ("s1", ctypes.c_void_p),
+                ("step", ctypes.c_void_p), ("ticket", ctypes.c_void_p), ("n", ctypes.c_int64), ("flags", ctypes.c_int32)]
+
+
+class OptimHyper(ctypes.Structure):
+    """wsi_optim_hyper_t (include/wsi_hgnn.h)."""
+    _fields_ = [(f, ctypes.c_double) for f in ("lr", "weight_decay", "momentum", "dampening", "nesterov", "lr_decay", "eps", "rho",
+                                                "beta1", "beta2", "host_step")]
+
+
+WSI_OPTIM_SGD, WSI_OPTIM_ADAGRAD, WSI_OPTIM_ADADELTA, WSI_OPTIM_ADAM = 0, 1, 2, 3
+WSI_OPTIM_FIRST = 1
+
+
 class GemmGroup(ctypes.Structure):
     """struct wsi_gemm_group (include/wsi_hgnn.h)."""
     _fields_ = [
@@ -123,6 +139,7 @@ EXPORTS = {
     "wsi_cross_entropy": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wsi_adam_step": (ctypes.c_int, [c_void_p, c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                      c_int64, c_void_p]),
+    "wsi_optim_step": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "wsi_layernorm_fwd": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_int64, c_void_p, c_void_p]),
     "wsi_layernorm_bwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,

@@ -6,6 +6,13 @@ arithmetic (L2 penalty added to the gradient, bias-corrected moments, ``amsgrad=
 (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter: checkpoints move between the two), stepping every parameter of a group through
 ``wsi_adam_step`` (csrc/optim.hip): one kernel, 28 bytes of HBM traffic per element, where torch's fused path takes two launches at half
 the bandwidth on this model's 54 tensors.  GPU only - there is no CPU path.
+
+The other three branches of ``parse_optimizer`` (parser.py:15-46) - :class:`Adagrad` (``lr_decay = weight_decay``, :23), :class:`Adadelta` and
+:class:`SGD` for anything else - and ``Adam(..., capturable=True)`` step through ``wsi_optim_step``: one kernel template over the rule, again one
+launch over all tensors, with torch's arithmetic, constructor arguments and ``state_dict`` layout (``momentum_buffer`` / ``step``, ``sum`` /
+``step``, ``square_avg``, ``acc_delta``).  ``capturable=True`` keeps ``state["step"]`` as a 0-dim fp32 device word, torch's capturable layout,
+which the kernel itself advances: that is what ``trainer.CapturedStep`` needs to replay the step from a hipGraph.  SGD and Adadelta never read a
+count, so their groups always carry ``capturable=True``.
 """
 from __future__ import annotations
 
@@ -17,11 +24,144 @@ import torch
 from . import _native as N
 
 
-class Adam(torch.optim.Optimizer):
-    def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
-        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
-            raise ValueError("Adam: invalid hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+def _refuse(name: str, **unsupported) -> None:
+    """torch.optim's keywords that select another algorithm or another implementation: accepted at their defaults, refused otherwise."""
+    for k, v in unsupported.items():
+        if v:
+            raise ValueError(f"wsi_hgnn_amd.optim.{name} has one implementation (one HIP launch) and one algorithm: {k}={v!r} is not supported")
+
+
+def _check_param(name: str, p: torch.Tensor) -> None:
+    if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+        raise RuntimeError(f"wsi_hgnn_amd.optim.{name} steps contiguous fp32 parameters on the GPU only (no CPU path)")
+    if p.grad.is_sparse:
+        raise RuntimeError(f"wsi_hgnn_amd.optim.{name} does not take sparse gradients")
+
+
+class _OneLaunch(torch.optim.Optimizer):
+    """What the optimizers that step through ``wsi_optim_step`` share: the per-group descriptor table, the ticket words, the step contract."""
+
+    RULE = None                 # N.WSI_OPTIM_*
+    STATE = ()                  # state tensors in the order of wsi_optim_tensor_t's s0, s1
+    READS_COUNT = False         # the rule's arithmetic depends on the step count (Adagrad's clr, Adam's bias corrections)
+
+    def _new_state(self, p: torch.Tensor, group: dict) -> dict:
+        """Create ``self.state[p]`` in torch's layout for this rule and return it."""
+        st = self.state[p]
+        if "step" in self._state_keys(group):
+            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if group["capturable"] else 0
+        for k in self.STATE:
+            st[k] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st
+
+    def _state_keys(self, group: dict):
+        return ("step",) + tuple(self.STATE)
+
+    def _ensure_state(self, p: torch.Tensor, group: dict, st: dict) -> int:
+        """State of a parameter about to be stepped; returns its wsi_optim_tensor_t flags."""
+        if len(st) == 0:
+            self._new_state(p, group)
+        return 0
+
+    def _hyper(self, group: dict, h) -> None:
+        raise NotImplementedError
+
+    def _tickets(self, device: torch.device) -> torch.Tensor:
+        # one int32 word per parameter, zero between launches (the workgroups of a tensor count themselves through it); on the optimizer, not in
+        # `state`: state_dict() stays torch's
+        bufs = self.__dict__.setdefault("_wsi_tickets", {})
+        buf = bufs.get(device)
+        if buf is None:
+            n = sum(len(g["params"]) for g in self.param_groups)
+            buf = bufs[device] = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+        return buf
+
+    def _ticket_index(self) -> dict:
+        idx = self.__dict__.get("_wsi_ticket_index")
+        n = sum(len(g["params"]) for g in self.param_groups)
+        if idx is None or len(idx) != n:
+            idx = self.__dict__["_wsi_ticket_index"] = {id(p): i for i, p in enumerate(p for g in self.param_groups for p in g["params"])}
+            self.__dict__.pop("_wsi_tickets", None)               # (a parameter group was added: larger buffers,
+            self.__dict__.pop("_wsi_tables", None)                #  and tables that point into the old ones go)
+        return idx
+
+    def load_state_dict(self, state_dict) -> None:
+        # torch replaces the groups by the saved ones and keeps a saved count as it finds it: where the count lives is this OBJECT'S choice
+        # (a checkpoint written by torch.optim, host counts, loads into a capturable optimizer and the other way round)
+        capturable = [g["capturable"] for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for group, cap in zip(self.param_groups, capturable):
+            group["capturable"] = cap
+            for p in group["params"]:
+                st = self.state.get(p)
+                if st and "step" in st:
+                    if cap:
+                        st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32).reshape(()).to(p.device)
+                    else:
+                        st["step"] = int(st["step"])
+        self.__dict__.pop("_wsi_tables", None)
+
+    def _step_group(self, lib, gi: int, group: dict) -> None:
+        name = type(self).__name__
+        cap = group["capturable"]
+        host_counts = self.READS_COUNT and not cap
+        keys = self._state_keys(group)
+        by_step = {}
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            _check_param(name, p)
+            st = self.state[p] if keys else {}                  # (SGD without momentum keeps no state, and like torch leaves no empty entry)
+            flags = self._ensure_state(p, group, st)
+            t = 0
+            if host_counts:                                      # a plain Python number, as Adam's (a state loaded from torch brings a tensor: converted once)
+                t = int(st["step"]) + 1
+                st["step"] = t
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            by_step.setdefault(t, []).append((p, g, st, flags))
+        if not by_step:
+            return
+        tables = self.__dict__.setdefault("_wsi_tables", {})      # (on the optimizer, not in param_groups: state_dict() stays plain data)
+        index = self._ticket_index()
+        has_step = "step" in keys and not host_counts
+        hyper = self.__dict__.get("_wsi_hyper")
+        if hyper is None:
+            hyper = self.__dict__["_wsi_hyper"] = N.OptimHyper()
+        self._hyper(group, hyper)
+        for t, items in by_step.items():                        # (one launch when every parameter has been stepped equally often, or counts on the device)
+            # the descriptor table is kept between steps and only the pointers that move are refreshed (gradients; a state a checkpoint replaced)
+            key = tuple(id(p) for p, _, _, _ in items)
+            cached = tables.get(gi)
+            if cached is None or cached[0] != key:
+                arr = (N.OptimTensor * len(items))()
+                tick = self._tickets(items[0][0].device)
+                written, empty = [], []                        # every tensor the launch writes; the step words of zero-element tensors
+                for a, (p, _, st, _) in zip(arr, items):
+                    a.n = p.numel()
+                    written.append(p)
+                    written.extend(st[k] for k in self.STATE)
+                    if has_step:                                 # (a step word is only ever replaced by load_state_dict, which drops this table)
+                        if p.device != tick.device:
+                            tick = self._tickets(p.device)
+                        a.step, a.ticket = st["step"].data_ptr(), tick.data_ptr() + 4 * index[id(p)]
+                        written.append(st["step"])
+                        if a.n == 0:
+                            empty.append(st["step"])
+                cached = tables[gi] = (key, arr, ctypes.cast(arr, ctypes.c_void_p), written, empty)
+            _, arr, arr_p, written, empty = cached
+            s0, s1 = (tuple(self.STATE) + (None, None))[:2]
+            for a, (p, g, st, flags) in zip(arr, items):
+                a.p, a.g, a.flags = p.data_ptr(), g.data_ptr(), flags
+                if s0 is not None:
+                    a.s0 = st[s0].data_ptr()
+                    if s1 is not None:
+                        a.s1 = st[s1].data_ptr()
+            for word in empty:
+                word += 1                                        # (no workgroup of the launch covers a zero-element tensor; torch counts its steps too)
+            hyper.host_step = float(t)
+            N.check(lib.wsi_optim_step(self.RULE, arr_p, len(items), ctypes.addressof(hyper), N.stream()), "wsi_optim_step")
+            # the kernel wrote through raw pointers: move the version counters as torch.optim's in-place ops would (see Adam.step)
+            torch.autograd.graph.increment_version(written)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -33,6 +173,130 @@ class Adam(torch.optim.Optimizer):
         from . import ops
         ops._background_recover()       # a backward pass that raised never joined its side stream: order this step behind it (no-op otherwise)
         for gi, group in enumerate(self.param_groups):
+            self._step_group(lib, gi, group)
+        ops.repack_weights()            # the packed fp16 planes of the weights the projections read (ops._PACKED): all of them in one launch per op
+        return loss
+
+
+class SGD(_OneLaunch):
+    """``torch.optim.SGD`` (the fall-through of parser.py:15-46) in one launch; momentum, dampening, nesterov and weight decay as torch's."""
+    RULE = N.WSI_OPTIM_SGD
+
+    def __init__(self, params: Iterable, lr: float = 1e-3, momentum: float = 0, dampening: float = 0, weight_decay: float = 0,
+                 nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None):
+        _refuse("SGD", maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+            raise ValueError("SGD: invalid hyper-parameter")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                      capturable=True,       # (no count is read: nothing a capture could freeze)
+                                      maximize=False, foreach=None, differentiable=False, fused=None))      # (torch's group keys: checkpoints move both ways)
+
+    def _state_keys(self, group):
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _new_state(self, p, group):
+        st = self.state[p]
+        st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)      # written, not read, by the first step
+        return st
+
+    def _ensure_state(self, p, group, st):
+        if group["momentum"] == 0:
+            return 0                                             # (no state at all, as torch)
+        if st.get("momentum_buffer") is None:
+            self._new_state(p, group)
+            return N.WSI_OPTIM_FIRST
+        return 0
+
+    def _step_group(self, lib, gi, group):
+        self.STATE = self._state_keys(group)
+        super()._step_group(lib, gi, group)
+
+    def _hyper(self, group, h):
+        h.lr, h.weight_decay, h.momentum = float(group["lr"]), float(group["weight_decay"]), float(group["momentum"])
+        h.dampening, h.nesterov = float(group["dampening"]), float(bool(group["nesterov"]))
+
+
+class Adagrad(_OneLaunch):
+    """``torch.optim.Adagrad`` (parser.py:20-24; the reference passes ``lr_decay = weight_decay``) in one launch."""
+    RULE = N.WSI_OPTIM_ADAGRAD
+    STATE = ("sum",)
+    READS_COUNT = True
+
+    def __init__(self, params: Iterable, lr: float = 1e-2, lr_decay: float = 0, weight_decay: float = 0, initial_accumulator_value: float = 0,
+                 eps: float = 1e-10, foreach=None, *, maximize: bool = False, differentiable: bool = False, fused=None, capturable: bool = False):
+        _refuse("Adagrad", maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        if lr < 0.0 or lr_decay < 0.0 or weight_decay < 0.0 or initial_accumulator_value < 0.0 or eps < 0.0:
+            raise ValueError("Adagrad: invalid hyper-parameter")
+        super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
+                                      initial_accumulator_value=initial_accumulator_value, capturable=bool(capturable),
+                                      foreach=None, maximize=False, differentiable=False, fused=None))
+        for group in self.param_groups:                          # torch.optim.Adagrad creates its state in the constructor
+            for p in group["params"]:
+                self._new_state(p, group)
+
+    def _new_state(self, p, group):
+        st = super()._new_state(p, group)
+        if group["initial_accumulator_value"]:
+            st["sum"].fill_(float(group["initial_accumulator_value"]))
+        return st
+
+    def _hyper(self, group, h):
+        h.lr, h.weight_decay, h.lr_decay, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["lr_decay"]), float(group["eps"])
+
+
+class Adadelta(_OneLaunch):
+    """``torch.optim.Adadelta`` (parser.py:25-30) in one launch; ``state["step"]`` is a device word the kernel advances (the rule never reads it)."""
+    RULE = N.WSI_OPTIM_ADADELTA
+    STATE = ("square_avg", "acc_delta")
+
+    def __init__(self, params: Iterable, lr: float = 1.0, rho: float = 0.9, eps: float = 1e-6, weight_decay: float = 0, foreach=None, *,
+                 capturable: bool = True, maximize: bool = False, differentiable: bool = False):
+        _refuse("Adadelta", maximize=maximize, foreach=foreach, differentiable=differentiable)
+        if not capturable:
+            raise ValueError("Adadelta: the count is kept on the device and the rule never reads it - there is no non-capturable form")
+        if lr < 0.0 or not (0.0 <= rho <= 1.0) or eps < 0.0 or weight_decay < 0.0:
+            raise ValueError("Adadelta: invalid hyper-parameter")
+        super().__init__(params, dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay, capturable=True,      # (always: no count is read)
+                                      maximize=False, foreach=None, differentiable=False))
+
+    def _hyper(self, group, h):
+        h.lr, h.weight_decay, h.rho, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["rho"]), float(group["eps"])
+
+
+class Adam(_OneLaunch):
+    RULE = N.WSI_OPTIM_ADAM
+    STATE = ("exp_avg", "exp_avg_sq")
+    READS_COUNT = True
+
+    def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 amsgrad: bool = False, *, foreach=None, maximize: bool = False, capturable: bool = False, differentiable: bool = False,
+                 fused=None, decoupled_weight_decay: bool = False):
+        _refuse("Adam", amsgrad=amsgrad, foreach=foreach, maximize=maximize, differentiable=differentiable, fused=fused,
+                decoupled_weight_decay=decoupled_weight_decay)
+        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
+            raise ValueError("Adam: invalid hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, capturable=bool(capturable),
+                                      amsgrad=False, maximize=False, foreach=None, differentiable=False, fused=None, decoupled_weight_decay=False))
+
+    def _hyper(self, group, h):
+        h.lr, h.weight_decay, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
+        h.beta1, h.beta2 = float(group["betas"][0]), float(group["betas"][1])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = N.load()
+        from . import ops
+        ops._background_recover()       # a backward pass that raised never joined its side stream: order this step behind it (no-op otherwise)
+        for gi, group in enumerate(self.param_groups):
+            if group.get("capturable", False):                  # the count on the device: wsi_optim_step (the default path below is as it was)
+                self._step_group(lib, gi, group)
+                continue
             by_step = {}
             for p in group["params"]:
                 if p.grad is None:

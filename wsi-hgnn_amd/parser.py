@@ -1,7 +1,7 @@
 """Config -> objects, mirroring the reference's ``parser.py`` (same function names, same config keys, same error behaviour):
 
   parse_gnn_model(cfg["GNN"])      parser.py:48-174   the in-scope branches: GAT, GCN, GCN_NTPool, HetRGCN, HGT, HEAT2, HEAT4
-  parse_optimizer(cfg["optim"], m) parser.py:15-46    adagrad / adadelta / adam / anything else -> SGD
+  parse_optimizer(cfg["optim"], m) parser.py:15-46    adagrad / adadelta / adam / anything else -> SGD (native=True: wsi_hgnn_amd.optim's)
   parse_loss(cfg["train"])         parser.py:176-184  BCE / CE
 
 ``node_dict`` and the etype-major enumeration of ``edge_dict`` / ``etypes`` are built exactly as :107-113,122-129; a config
@@ -22,17 +22,23 @@ from torch import nn, optim
 from .models import GAT, GCN, HGT, HEATNet2, HEATNet4, HeteroRGCN, NTPoolGCN
 
 
-def parse_optimizer(config_optim, model):
+def parse_optimizer(config_optim, model, native=False):
+    """parser.py:15-46.  ``native=False``: the ``torch.optim`` classes, as the reference builds them.  ``native=True``: the same branch with the
+    same arguments from ``wsi_hgnn_amd.optim`` - every parameter of the model stepped in one HIP launch."""
     opt_method = config_optim["opt_method"].lower()
     alpha = config_optim["lr"]
     weight_decay = config_optim["weight_decay"]
+    if native:
+        from . import optim as O
+    else:
+        O = optim
     if opt_method == "adagrad":
-        return optim.Adagrad(model.parameters(), lr=alpha, lr_decay=weight_decay, weight_decay=weight_decay)    # (lr_decay = weight_decay: parser.py:23)
+        return O.Adagrad(model.parameters(), lr=alpha, lr_decay=weight_decay, weight_decay=weight_decay)    # (lr_decay = weight_decay: parser.py:23)
     if opt_method == "adadelta":
-        return optim.Adadelta(model.parameters(), lr=alpha, weight_decay=weight_decay)
+        return O.Adadelta(model.parameters(), lr=alpha, weight_decay=weight_decay)
     if opt_method == "adam":
-        return optim.Adam(model.parameters(), lr=alpha, weight_decay=weight_decay)
-    return optim.SGD(model.parameters(), lr=alpha, weight_decay=weight_decay)
+        return O.Adam(model.parameters(), lr=alpha, weight_decay=weight_decay)
+    return O.SGD(model.parameters(), lr=alpha, weight_decay=weight_decay)
 
 
 def _typed_schema(config_gnn):

@@ -81,11 +81,12 @@ class CapturedStep:
     own, never allocates or synchronises (``include/wsi_hgnn.h``), and the hub kernels' side stream forks from and joins that stream with events -
     so the whole step records as one graph.  What the capture bakes in: the graph's kernel plan and every shape, i.e. one ``CapturedStep`` per
     resident batch (captures may share a memory ``pool``); the optimizer must keep its step count on the device
-    (``torch.optim.Adam(..., capturable=True)``).  A model stepped eagerly before is fine - as long as the caller holds no tensor of those
-    steps' autograd graphs any more (a previous loss, logits).  At the benchmark's size the step is GPU-bound and replay changes nothing
+    (``wsi_hgnn_amd.optim.Adam(..., capturable=True)``: the whole optimizer step is then ONE node of the graph; ``optim.SGD`` and
+    ``optim.Adadelta`` read no count and are taken as they are; ``torch.optim``'s capturable optimizers work too).  A model stepped eagerly
+    before is fine - as long as the caller holds no tensor of those steps' autograd graphs any more (a previous loss, logits).  At the benchmark's size the step is GPU-bound and replay changes nothing
     (6.87 vs 6.93 ms).
 
-    >>> step = CapturedStep(model, torch.optim.Adam(model.parameters(), lr=1e-4, capturable=True), torch.nn.CrossEntropyLoss(), G, labels)
+    >>> step = CapturedStep(model, wsi_hgnn_amd.optim.Adam(model.parameters(), lr=1e-4, capturable=True), torch.nn.CrossEntropyLoss(), G, labels)
     >>> for _ in range(epochs): loss = step()          # a device tensor, overwritten by the next replay
     """
 
@@ -95,7 +96,7 @@ class CapturedStep:
             raise RuntimeError("CapturedStep: the batch and its labels must be resident on the GPU")
         for group in optimizer.param_groups:
             if not group.get("capturable", False):
-                raise RuntimeError("CapturedStep: the optimizer must be capturable (torch.optim.Adam(..., capturable=True)): its step count has to "
+                raise RuntimeError("CapturedStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step count has to "
                                    "live on the device, a host count would be frozen into the graph")
         # Train-mode dropout: the HEAT layers draw their masks as a function of (host seed + a DEVICE word, row, column) - ops.CounterDropout.  The
         # capture freezes the host seeds; the recorded step itself advances the word, so every replay drops other entries (forward and backward of a
