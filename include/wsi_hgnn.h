@@ -644,7 +644,7 @@ int wsi_asap_attend_bwd(const float* a, const float* b, const float* x, int64_t 
  * wsi_gat_attn_bwd : from g_out (gradient of out) and the forward's eler / lse / out (out read only when activation != 0) and the
  *                    SAME dropout arguments: g_ft[n, F] <- d loss / d ft (both through the aggregation and through el / er),
  *                    g_attn_l[F], g_attn_r[F], g_bias[F] (optional) <- the parameter gradients.  workspace: at least
- *                    wsi_gat_attn_bwd_workspace_bytes(n, E, H, D, activation) bytes (-1 for bad arguments).
+ *                    wsi_gat_attn_bwd_workspace_bytes(n, E, H, D, activation) bytes (-1 for bad arguments), 16-byte aligned (else WSI_EINVAL).
  * wsi_gat_attn_fwd_scaled / wsi_gat_attn_bwd_scaled : the same with a per-edge message scale edge_scale[E] (fp32, CSR edge order, one value
  *                    for all heads and columns of the edge; any finite value - GNNExplainer passes sigmoid(edge_mask),
  *                    explainers/gnn_explainer.py:21-33).  The scale multiplies the message AFTER the softmax (and after attn_drop):

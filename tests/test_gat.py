@@ -151,3 +151,77 @@ def test_capi_rejects_null_pointers_strides_and_modes():
     assert bwd(E=-1) == EINVAL
     assert bwd(act=-1) == EINVAL
     assert bwd(ws_bytes=ws - 1) == -12              # WSI_ENOMEM: workspace too small
+
+
+def test_capi_rejects_a_misaligned_workspace():
+    """g_rst and the column partials are carved out of the workspace and take the 16-byte accesses of the vector-4 kernels: a workspace
+    that is not 16-byte aligned is refused before anything is launched (the contract in include/wsi_hgnn.h)."""
+    lib = _lib()
+    H, D = 4, 8
+    ws = lib.wsi_gat_attn_bwd_workspace_bytes(10, 20, H, D, 2)
+    for off in (4, 8, 12, 1):                       # offset 0 would pass the check and launch on the fake address: only refusals are made
+        w = ctypes.c_void_p((1 << 40) + off)
+        assert lib.wsi_gat_attn_bwd(P, 32, P, P, P, 32, P, 32, 10, 20, H, D, P, P, P, P, P, None, P, P, 0.2, 0, None, 0, 1.0, 2, 0.01,
+                                    w, ws + 16, P, 32, P, P, None, None) == EINVAL
+        assert "16-byte aligned" in lib.wsi_last_error().decode()
+        assert lib.wsi_gat_attn_bwd_scaled(P, 32, P, P, P, 32, P, 32, 10, 20, H, D, P, P, P, P, P, None, P, P, 0.2, 0, None, 0, 1.0, 2, 0.01,
+                                           P, w, ws + 16, P, 32, P, P, None, P, None) == EINVAL
+        assert "16-byte aligned" in lib.wsi_last_error().decode()
+
+
+# ---------------------------------------------------------------------------------------------------- dispatch coverage
+# Every (heads, width, fused activation) the kernel sweep of tests/test_gat_kernels_gpu.py runs, and every width its wsi_sddmm_dot sweep
+# runs next to those of tests/test_gnn_explainer_gpu.py.  The lists live here so that the test below, which needs no GPU, sees them.
+GA_SWEEP = [(4, 4, None), (8, 4, "relu"), (16, 4, "leaky_relu"), (5, 24, "relu"), (2, 100, "leaky_relu"), (6, 64, None),
+            (3, 300, "relu"), (7, 260, "leaky_relu"), (16, 256, "leaky_relu"), (5, 500, "relu"),
+            (4, 1, "leaky_relu"), (2, 3, "relu"), (8, 1, None), (16, 1, "relu"), (3, 10, "leaky_relu"), (7, 9, None), (5, 25, "relu"),
+            (3, 67, "leaky_relu"), (2, 250, None), (1, 1001, "relu"), (11, 150, "leaky_relu"), (16, 255, "relu")]
+SDDMM_WIDTHS = [16, 28, 60, 120, 200, 7, 13, 30, 63, 125, 201, 501, 1001]
+SDDMM_WIDTHS_ELSEWHERE = [1, 3, 40, 64, 512, 1000]            # test_gnn_explainer_gpu.py: the aggregate's widths and the direct call's
+
+
+def ga_cfg(H, D, vec4_ok=True):
+    """csrc/gat_attn.hip's ga_cfg and GA_DISPATCH's code, restated: VEC * 100000 + G * 100 + NK."""
+    vec = 4 if vec4_ok and D % 4 == 0 else 1
+    G = next(g for g in (4, 8, 16, 32, 64) if g == 64 or (g >= H * D // vec and g >= H))
+    NK = next(k for k in (1, 2, 4, 8, 16, 32, 64, 128) if k * G >= H * D // vec)
+    return vec * 100000 + G * 100 + NK
+
+
+def ga_group(H, D, vec4_ok=True):
+    return ga_cfg(H, D, vec4_ok) // 100 % 1000
+
+
+def _dispatch_codes():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "wsi-hgnn_amd", "csrc", "gat_attn.hip")) as f:
+        text = f.read()
+    table = text[text.index("#define GA_DISPATCH"):text.index("static int ga_check_shape")]
+    return sorted(int(c) for c in re.findall(r"case (\d+):", table))
+
+
+def test_sweeps_reach_every_dispatch_code():
+    codes = _dispatch_codes()
+    assert len(codes) == len(set(codes)) == 20
+    reached = {}
+    for H, D, _ in GA_SWEEP:
+        reached.setdefault(ga_cfg(H, D), []).append((H, D))
+    assert sorted(reached) == codes, f"not reached: {sorted(set(codes) - set(reached))}; unknown: {sorted(set(reached) - set(codes))}"
+    assert len(set(GA_SWEEP)) == len(GA_SWEEP)
+    # the cases the sweep is there for: heads == lanes of a group in both families, the full width, ragged last chunks, every activation
+    for H in (8, 16):
+        assert any(h == H and ga_group(h, d) == H and d % 4 == 0 for h, d, _ in GA_SWEEP)
+        assert any(h == H and ga_group(h, d) == H and d % 4 != 0 for h, d, _ in GA_SWEEP)
+    assert any(h * d == 4096 for h, d, _ in GA_SWEEP) and any(ga_cfg(h, d) == 406416 and h * d < 4096 for h, d, _ in GA_SWEEP)
+    assert any(ga_cfg(h, d) == 100801 and h < 8 for h, d, _ in GA_SWEEP)
+    for vec4 in (True, False):
+        acts = {a for h, d, a in GA_SWEEP if (d % 4 == 0) == vec4}
+        assert acts == {None, "relu", "leaky_relu"}
+    # wsi_sddmm_dot: every code ga_cfg(1, D) produces for a legal width
+    want = {ga_cfg(1, D) for D in range(1, 1025)}
+    assert want <= set(codes)
+    got = {ga_cfg(1, D) for D in SDDMM_WIDTHS + SDDMM_WIDTHS_ELSEWHERE}
+    assert got == want, f"wsi_sddmm_dot codes not reached: {sorted(want - got)}"
+    assert len({ga_cfg(1, D) for D in SDDMM_WIDTHS}) == len(SDDMM_WIDTHS)          # no width of the new list repeats another's kernel

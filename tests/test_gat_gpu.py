@@ -72,7 +72,9 @@ def ref_attention(ft, al, ar, bias, src, dst, n, slope, act, keep=None, scale=1.
     rst = torch.zeros((n, H, D), dtype=ft.dtype).index_add(0, dst, a[:, :, None] * f3[src]).reshape(n, H * D)
     if bias is not None:
         rst = rst + bias
-    if act == "relu":
+    if act == "relu" and pos is not None:
+        rst = torch.where(pos, rst, torch.zeros_like(rst))
+    elif act == "relu":
         rst = F.relu(rst)
     elif act == "leaky_relu" and pos is not None:                    # the side of the kink the GPU run took, replayed (see _model_check)
         rst = torch.where(pos, rst, 0.01 * rst)

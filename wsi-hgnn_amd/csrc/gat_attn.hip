@@ -299,7 +299,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
         if (ok[k]) store_vec<VEC>(g_ft + (int64_t)u * ldgf + VEC * (gl + G * k), acc[k]);
 }
 
-// pass B: one 16-lane group per destination v; in place g_a (d loss / d a~, SCALED: the raw dot r) -> g_pre (d loss / d pre-activation score);
+// pass B: one 16-lane group per destination v; in place g_a (d loss / d a~, SCALED: the raw dot r) -> d loss / d a -> g_pre (d loss / d pre-activation score);
 // g_er[v, h].  SCALED: d loss / d a~ = s_e r, and g_scale[e] = sum_h a~ r is built head by head by the one lane that visits edge e.
 template <bool SCALED>
 __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __restrict__ eler, const float* __restrict__ lse, int n, int H,
@@ -317,22 +317,26 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __re
         float d = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
             const float a = expf((ga_lrelu(eler[(int64_t)src[e] * 2 * H + h] + erv, slope) - M) - LS);
+            // t = d loss / d a: g_a times the factors of a~, rounded ONCE and kept in g_a for the second sweep.  delta and g_pre then see the
+            // same number: a destination with one in-edge (a = 1, delta = t) gets a score gradient of exactly zero, as a softmax of one term
+            // has (g_a * f - delta contracted into one fma would leave the rounding of the product there)
+            float t;
             if constexpr (SCALED) {
                 const float r = g_a[(int64_t)e * H + h], f = edge_factor(dr, seed, e, h, H), gs = a * f * r;
                 g_scale[e] = h ? g_scale[e] + gs : gs;
-                d = fmaf(a, r * (f * escale[e]), d);
+                t = r * (f * escale[e]);
             } else {
-                d = fmaf(a, g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H), d);
+                t = g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H);
             }
+            g_a[(int64_t)e * H + h] = t;
+            d = fmaf(a, t, d);
         }
         const float delta = group_sum<G>(d);
         float gr = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
             const float pre = eler[(int64_t)src[e] * 2 * H + h] + erv;
             const float a = expf((ga_lrelu(pre, slope) - M) - LS);
-            float gp;
-            if constexpr (SCALED) gp = a * (g_a[(int64_t)e * H + h] * (edge_factor(dr, seed, e, h, H) * escale[e]) - delta) * (pre > 0.f ? 1.f : slope);
-            else gp = a * (g_a[(int64_t)e * H + h] * edge_factor(dr, seed, e, h, H) - delta) * (pre > 0.f ? 1.f : slope);
+            const float gp = a * (g_a[(int64_t)e * H + h] - delta) * (pre > 0.f ? 1.f : slope);
             g_a[(int64_t)e * H + h] = gp;
             gr += gp;
         }
@@ -610,6 +614,8 @@ static int ga_bwd(const char* what, const float* ft, int64_t ldf, const float* e
         set_error("%s: null pointer", what);
         return WSI_EINVAL;
     }
+    // g_rst and the column partials live in the workspace at 256-byte offsets and take the 16-byte accesses of the vector-4 kernels
+    if (!aligned16(workspace)) { set_error("%s: workspace %p is not 16-byte aligned", what, workspace); return WSI_EINVAL; }
     int64_t off[4];
     const int64_t need = ga_ws_layout(n, E, H, D, activation, off);
     if (workspace_bytes < need) { set_error("%s: workspace %lld < %lld bytes", what, (long long)workspace_bytes, (long long)need); return WSI_ENOMEM; }
