@@ -754,6 +754,31 @@ int wsi_augment_keys(const int64_t* desc, int32_t nseg, int32_t ntiles, int64_t*
 int wsi_gather_rows_masked(const float* x, int64_t ldx, int64_t src_rows, const int64_t* row_of, float* out, int64_t ldo, int64_t rows,
                            int32_t F, uint32_t mask_seed, uint32_t mask_threshold, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Leave-one-node-out batches (explainers/GEM.py:31-50, explainers/gem_het.py:30-39: the model is run on the graph WITHOUT node r, once per node).
+ * Host side: graph.leave_one_out_tables / graph.leave_one_out_batch, ops.leave_one_out_batch.  Copy b of the batch is the graph without node r_b
+ * of ONE node type t; the result equals graph.batch([graph.remove_nodes(g, [r_b], t) for b]) value for value.  The host knows every copy's
+ * surviving edge count in advance (per-node out-degree, in-degree and self-loop count of each relation, read back ONCE per graph and type), so every
+ * output offset is exact and a call needs no device->host read.  Entry points added to ABI 26.
+ *
+ * Descriptors: DEVICE int64 tables with tiles as for wsi_augment_* (a row of n input elements owns ceil(n / 1024) tiles, first_tile = tiles of the
+ * rows before it, ntiles = their total).
+ *
+ * wsi_loo_edges : rows of 12 words [n, off, first_tile, u, v, sim, r_src, r_dst, add_src, add_dst, cap, 0], one per (relation j, copy b), relation-major
+ *                 and copy-major inside a relation.  n: edges of the relation; u, v: device pointers to its int64 endpoints (local ids); sim: to its
+ *                 fp32 edge scalar or 0; r_src = r_b when the source type is t, else INT64_MAX (never equal, never below an id), r_dst likewise.
+ *                 Edge i survives iff u[i] != r_src && v[i] != r_dst.  The row's p-th survivor (input order) is written at off + p:
+ *                 out_u <- u - (u > r_src) + add_src, out_v <- v - (v > r_dst) + add_dst (add = b * nodes of that type per copy), out_eid <- i,
+ *                 out_sim <- sim[i] (rows with sim only).  cap = the count the host predicted for the row: a survivor with p >= cap is NOT written,
+ *                 so a row never leaves its range.  counts[row] <- survivors found (== cap unless the host's tables are wrong).
+ *                 tile_sum: scratch, ntiles + 1 int32.  Count per tile, one-block scan, stable scatter: no atomics, bit-reproducible.
+ * wsi_loo_rows  : rows of 6 words [n, off, first_tile, per, is_t, 0], one per node type: per = nodes of the type in ONE copy, n = ncopies * per.
+ *                 row_of[off + b * per + i] <- i + (is_t && i >= removed[b])   (removed: DEVICE int64 [ncopies], the r_b): the source row of every node
+ *                 of the batch, for wsi_gather_rows_masked (threshold 0) and plain indexing. */
+int wsi_loo_edges(const int64_t* desc, int32_t nrow, int32_t ntiles, int32_t* tile_sum, int64_t* out_u, int64_t* out_v, float* out_sim,
+                  int64_t* out_eid, int32_t* counts, void* stream);
+int wsi_loo_rows(const int64_t* desc, int32_t nrow, int32_t ntiles, const int64_t* removed, int32_t ncopies, int64_t* row_of, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,8 @@ EXPORTS = {
     "wsi_augment_keys": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "wsi_gather_rows_masked": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32,
                                               ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
+    "wsi_loo_edges": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wsi_loo_rows": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
     "wsi_segment_reduce_bwd": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32,
                                               c_void_p, c_void_p, c_int32, c_void_p, c_int32,
                                               c_void_p, c_void_p, c_int64, c_void_p]),

@@ -1065,6 +1065,112 @@ def remove_nodes(g: HeteroGraph, nids: torch.Tensor, ntype: Optional[str] = None
     return out
 
 
+class LeaveOneOutTables:
+    """Host-side degree tables of one (graph, node type): what ``leave_one_out_batch`` needs to size every copy without asking the device.
+
+    ``out_degree[j]``, ``in_degree[j]``, ``self_loops[j]``: int64 CPU tensors ``[n_t]`` for relation j of ``g.canonical_etypes`` — edges whose
+    source / destination / both ends are node i of ``ntype`` — or None where that side of the relation has another type (self loops: unless both
+    have it).  Removing node r takes ``out(r) + in(r) - loops(r)`` edges of the relation away (a self loop is in both degrees)."""
+
+    def __init__(self, ntype: str, num_nodes: int, num_edges: List[int], out_degree, in_degree, self_loops, signature):
+        self.ntype, self.num_nodes, self.num_edges = ntype, int(num_nodes), list(num_edges)
+        self.out_degree, self.in_degree, self.self_loops = out_degree, in_degree, self_loops
+        self.signature = signature
+        removed = torch.zeros((len(num_edges), self.num_nodes), dtype=torch.int64)
+        for j in range(len(num_edges)):
+            if out_degree[j] is not None:
+                removed[j] += out_degree[j]
+            if in_degree[j] is not None:
+                removed[j] += in_degree[j]
+            if self_loops[j] is not None:
+                removed[j] -= self_loops[j]
+        self._removed = removed
+
+    def surviving_edges(self, nid: int) -> List[int]:
+        """Edges of every relation (canonical order) in the graph without node ``nid`` of the type:
+        ``E_j - out_j(r)[s==t] - in_j(r)[d==t] + loops_j(r)[s==t==d]``."""
+        if self.num_nodes == 0:
+            raise IndexError("the node type has no node")
+        return [e - r for e, r in zip(self.num_edges, self._removed[:, int(nid)].tolist())]
+
+
+def _edge_signature(g: HeteroGraph):
+    return tuple((u.data_ptr(), v.data_ptr(), int(u.numel()), u._version, v._version) for u, v in g._edges.values())
+
+
+def leave_one_out_tables(g: HeteroGraph, ntype: Optional[str] = None) -> LeaveOneOutTables:
+    """Per-node out-degree, in-degree and self-loop count of every relation that touches ``ntype``: counted on the graph's device, brought to
+    the host in ONE copy.  Compute once per (graph, type) and pass to every ``leave_one_out_batch`` call on it."""
+    if ntype is None:
+        if len(g.ntypes) != 1:
+            raise ValueError("ntype is required for a multi-type graph")
+        ntype = g.ntypes[0]
+    ntype = str(ntype)
+    n = g.num_nodes(ntype)
+    dev = g.device
+    rows, where = [], []            # where[k] = (relation index, 0 out / 1 in / 2 loops)
+    num_edges = []
+    for j, (s, e, d) in enumerate(g.canonical_etypes):
+        u, v = g._edges[(s, e, d)]
+        u, v = u.to(dev), v.to(dev)
+        num_edges.append(int(u.numel()))
+        if s == ntype:
+            rows.append(_count(u, n))
+            where.append((j, 0))
+        if d == ntype:
+            rows.append(_count(v, n))
+            where.append((j, 1))
+        if s == ntype and d == ntype:       # (index_add_ of the flag, not a boolean selection: that would read its size back)
+            rows.append(torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, u, (u == v).to(torch.int64)))
+            where.append((j, 2))
+    R = len(num_edges)
+    out_d, in_d, loops = [None] * R, [None] * R, [None] * R
+    if rows:
+        host = torch.stack(rows).cpu()          # THE device->host copy
+        for k, (j, kind) in enumerate(where):
+            (out_d, in_d, loops)[kind][j] = host[k]
+    return LeaveOneOutTables(ntype, n, num_edges, out_d, in_d, loops, _edge_signature(g))
+
+
+def leave_one_out_batch(g: HeteroGraph, nids, ntype: Optional[str] = None, tables: Optional[LeaveOneOutTables] = None,
+                        check: bool = False) -> HeteroGraph:
+    """``batch([remove_nodes(g, [i], ntype) for i in nids])``: one copy of ``g`` per entry of ``nids`` (any host sequence of node ids of
+    ``ntype``; repeats allowed, order kept), each without that one node — the batches of the GEM explainers.  Same ``num_nodes``,
+    ``batch_num_nodes``, edges and node / edge fields as the composition, value for value.
+
+    On a CPU graph the result IS that composition.  On a GPU graph it comes from ``csrc/loo.hip`` (``ops.leave_one_out_batch``) with no
+    device->host read: every size comes from ``tables`` (``leave_one_out_tables(g, ntype)``; built on first use and kept with the graph when
+    not passed).  ``check=True`` reads the kernel's per-copy edge counts back and raises when one differs from the tables' prediction
+    (tests and debugging)."""
+    if g._batch_num_nodes is not None and g.batch_size > 1:
+        raise ValueError("leave_one_out_batch works on single graphs, as remove_nodes does")
+    if ntype is None:
+        if len(g.ntypes) != 1:
+            raise ValueError("ntype is required for a multi-type graph")
+        ntype = g.ntypes[0]
+    ntype = str(ntype)
+    if ntype not in g._num_nodes:
+        raise KeyError(f"unknown node type {ntype!r}")
+    nids = [int(i) for i in nids]
+    if not nids:
+        raise ValueError("leave_one_out_batch needs at least one node id")
+    n = g.num_nodes(ntype)
+    for i in nids:
+        if not 0 <= i < n:
+            raise IndexError(f"node id {i} outside [0, {n}) of node type {ntype!r}")
+    if g.device.type != "cuda":
+        return batch([remove_nodes(g, torch.tensor([i]), ntype) for i in nids])
+    if tables is None:
+        cache = g.__dict__.setdefault("_loo_tables", {})
+        tables = cache.get(ntype)
+        if tables is None or tables.signature != _edge_signature(g):
+            tables = cache[ntype] = leave_one_out_tables(g, ntype)
+    elif tables.ntype != ntype or tables.num_nodes != n or tables.num_edges != [int(u.numel()) for u, _ in g._edges.values()]:
+        raise ValueError("leave_one_out_batch: the tables were built for another graph or node type")
+    from . import ops
+    return ops.leave_one_out_batch(g, nids, ntype, tables, check)
+
+
 def permute_nodes(g: HeteroGraph, perm: Dict[str, torch.Tensor]) -> HeteroGraph:
     """The same graph with the nodes of every type renumbered: new node i of type t is old node ``perm[t][i]``.
     Node fields follow their nodes, edges are relabelled, edge order and edge fields are untouched, so every model output

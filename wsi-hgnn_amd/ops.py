@@ -2773,3 +2773,97 @@ def augment_graph(g, stages, seed: int):
                 y = x[out_eid[eoff[j]:eoff[j] + e2[j]]]
             out._eframes[r][key] = mask_columns(y, augment_subseed(seed, fm[1], 65536 * edge_names.index(key) + 32768 + j), fm_thr) if masked else y
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# leave-one-node-out batches (csrc/loo.hip; graph.leave_one_out_batch)
+# ------------------------------------------------------------------------------------------------
+_LOO_NEVER = 2 ** 63 - 1        # "no node of this side is removed": never equal to an id, never below one
+
+
+def leave_one_out_batch(g, nids: Sequence[int], ntype: str, tables, check: bool = False):
+    """The device path of ``graph.leave_one_out_batch`` (which validates the arguments): B = len(nids) copies of the single graph ``g``, copy b
+    without node ``nids[b]`` of ``ntype``, as ONE block-diagonal ``HeteroGraph`` equal to ``batch([remove_nodes(g, [i], ntype) for i in nids])``.
+
+    Edges: one ``wsi_loo_edges`` call over a descriptor row per (relation, copy) writes the renumbered survivors of every copy straight into the
+    batch's relation-major, copy-major edge arrays (+ ``sim`` and the original edge index for the other edge fields); every row's offset and
+    capacity comes from ``tables``.  Nodes: one ``wsi_loo_rows`` launch writes the source row of every node of the batch; fp32 [n, F] fields go
+    through ``gather_rows_masked``, the rest through indexing.  One small upload, no device->host read (``check=True``: one, of the counts)."""
+    from collections import OrderedDict
+    from .graph import HeteroGraph
+    dev = g.device
+    if dev.type != "cuda":
+        raise RuntimeError("ops.leave_one_out_batch runs on the GPU only (HIP kernels); graph.leave_one_out_batch composes CPU graphs")
+    g = g.to(dev)
+    lib = N.load()
+    ntypes, rels = g.ntypes, g.canonical_etypes
+    T, R, B = len(ntypes), len(rels), len(nids)
+    n = [g.num_nodes(t) for t in ntypes]
+    per = [m - (1 if t == ntype else 0) for t, m in zip(ntypes, n)]             # nodes of every type in ONE copy
+    tindex = {t: i for i, t in enumerate(ntypes)}
+    edges = g._edges
+    e = [int(edges[r][0].numel()) for r in rels]
+    surv = [tables.surviving_edges(i) for i in nids]                            # [B][R]
+    etot = [sum(surv[b][j] for b in range(B)) for j in range(R)]
+    Etot, Ntot = sum(etot), B * sum(per)
+    tiles_e = B * sum((m + AUG_TILE - 1) // AUG_TILE for m in e)
+    if Ntot >= 2 ** 31 - 1 or Etot >= 2 ** 31 - 1 or B * sum(e) >= 2 ** 31 - 1 or tiles_e >= 2 ** 31 - 1:
+        raise ValueError("batch too large for the int32 leave-one-out kernels")
+    uv = [(edges[r][0].contiguous(), edges[r][1].contiguous()) for r in rels]
+    sims = []
+    for r, m in zip(rels, e):
+        x = g._eframes[r].get("sim")
+        sims.append(x if (x is not None and x.dtype == torch.float32 and x.dim() == 1 and x.numel() == m and x.is_contiguous()) else None)
+    # ---- descriptor tables: edge rows, node rows and the removed ids in one upload
+    words, roff, off, tiles = [], [], 0, 0
+    for j, (s, _, d) in enumerate(rels):
+        roff.append(off)
+        for b in range(B):
+            words += [e[j], off, tiles, uv[j][0].data_ptr(), uv[j][1].data_ptr(), 0 if sims[j] is None else sims[j].data_ptr(),
+                      nids[b] if s == ntype else _LOO_NEVER, nids[b] if d == ntype else _LOO_NEVER,
+                      b * per[tindex[s]], b * per[tindex[d]], surv[b][j], 0]
+            off += surv[b][j]
+            tiles += (e[j] + AUG_TILE - 1) // AUG_TILE
+    nwords, noff, no, ntiles_n = [], [], 0, 0
+    for j, t in enumerate(ntypes):
+        nwords += [B * per[j], no, ntiles_n, per[j], 1 if t == ntype else 0, 0]
+        noff.append(no)
+        no += B * per[j]
+        ntiles_n += (B * per[j] + AUG_TILE - 1) // AUG_TILE
+    desc = host_to_device(words + nwords + list(nids), torch.int64, dev)
+    desc_n, removed = desc[len(words):], desc[len(words) + len(nwords):]
+    i64 = lambda m: torch.empty(max(int(m), 1), dtype=torch.int64, device=dev)
+    with _Timed("loo_index"):
+        out_u, out_v, out_eid = i64(Etot), i64(Etot), i64(Etot)
+        out_sim = torch.empty(max(Etot, 1), dtype=torch.float32, device=dev)
+        tsum = torch.empty(tiles + 1, dtype=torch.int32, device=dev)
+        counts = torch.empty(max(R * B, 1), dtype=torch.int32, device=dev)
+        if R > 0:
+            N.check(lib.wsi_loo_edges(N.ptr(desc), R * B, tiles, N.ptr(tsum), N.ptr(out_u), N.ptr(out_v), N.ptr(out_sim), N.ptr(out_eid),
+                                      N.ptr(counts), N.stream()), "wsi_loo_edges")
+        row_of = i64(Ntot)
+        N.check(lib.wsi_loo_rows(N.ptr(desc_n), T, ntiles_n, N.ptr(removed), B, N.ptr(row_of), N.stream()), "wsi_loo_rows")
+    if check and R > 0:
+        got, want = counts[:R * B].tolist(), [surv[b][j] for j in range(R) for b in range(B)]
+        if got != want:
+            bad = [(rels[k // B], nids[k % B], want[k], got[k]) for k in range(R * B) if got[k] != want[k]]
+            raise RuntimeError(f"leave_one_out_batch: the kernel's surviving edge counts differ from the tables' prediction "
+                               f"(relation, removed node, predicted, found): {bad[:8]}")
+    out = HeteroGraph(OrderedDict((t, B * per[j]) for j, t in enumerate(ntypes)),
+                      OrderedDict((r, (out_u[roff[j]:roff[j] + etot[j]], out_v[roff[j]:roff[j] + etot[j]])) for j, r in enumerate(rels)),
+                      {t: torch.full((B,), per[j], dtype=torch.int64) for j, t in enumerate(ntypes)})
+    for j, t in enumerate(ntypes):
+        rows = row_of[noff[j]:noff[j] + B * per[j]]
+        for key, x in g._nframes[t].items():
+            if x.dim() == 2 and x.dtype == torch.float32 and (x.shape[1] <= 1 or x.stride(1) == 1):
+                out._nframes[t][key] = gather_rows_masked(x, rows, 0, 0)
+            else:
+                out._nframes[t][key] = x[rows]
+    for j, r in enumerate(rels):
+        for key, x in g._eframes[r].items():
+            if key == "sim" and sims[j] is not None:
+                out._eframes[r][key] = out_sim[roff[j]:roff[j] + etot[j]]
+            else:
+                out._eframes[r][key] = x[out_eid[roff[j]:roff[j] + etot[j]]]
+    out._loo_desc = desc                # (the descriptor table must outlive the launches that read it: held by the graph)
+    return out
