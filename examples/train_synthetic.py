@@ -35,6 +35,9 @@ def main(argv=None):
     ap.add_argument("--optimizer", choices=("adam", "sgd", "adagrad", "adadelta"), default=None,
                     help="step with the package's own optimizer of that name (parser.parse_optimizer(..., native=True): one HIP launch per step); "
                          "default: torch.optim.Adam")
+    ap.add_argument("--captured-slots", type=int, default=0, metavar="K",
+                    help="train through trainer.CapturedSlotStep over K padded batch slots by slide size (DESIGN 3.15): one captured step per slot, "
+                         "replayed over every new batch that fits; needs --optimizer adam, sgd or adadelta (capturable) and no --augment")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -81,11 +84,32 @@ def main(argv=None):
     bucket = dist.GradBucket.from_model(gnn) if world > 1 else None         # every parameter the architecture reaches, with used flags
     store = io.CheckpointStore(os.path.join(work, "ckpt"))
 
+    slot_step = None
+    if args.captured_slots:
+        if world > 1 or args.augment or args.optimizer not in ("adam", "sgd", "adadelta"):
+            raise SystemExit("--captured-slots: single process, no --augment (augmented batches change shape), and --optimizer adam | sgd | adadelta")
+        if args.optimizer == "adam":
+            from wsi_hgnn_amd import optim
+            opt = optim.Adam(gnn.parameters(), lr=1e-5, weight_decay=5e-3, capturable=True)         # the step count on the device
+        # slot k holds any `batch` slides out of the smallest (k + 1) / K of the data set; the last one every batch
+        its, K = sorted(loader.items, key=lambda it: sum(it.num_nodes)), args.captured_slots
+        top = lambda xs: sum(sorted(xs, reverse=True)[:args.batch])
+        caps = []
+        for k in range(K):
+            part = its[:max(args.batch, (len(its) * (k + 1) + K - 1) // K)]
+            caps.append(([top([it.num_nodes[t] for it in part]) + 1 for t in range(len(its[0].num_nodes))], [top([it.pieces.ecount[t] for it in part]) for t in range(len(its[0].num_nodes))], args.batch))
+        gnn.train()
+        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c) for c in caps])
+
     # 3. epochs
     for epoch in range(args.epochs):
         gnn.train()
         tot, n = 0.0, 0
-        for G, y in loader:
+        if slot_step is not None:
+            order = torch.randperm(len(graphs), generator=loader.gen).tolist()
+            losses = [slot_step.step(order[i:i + args.batch])[0].clone() for i in range(0, len(order), args.batch)]     # no host sync inside the epoch
+            tot, n = float(torch.stack(losses).sum().item()), len(losses)
+        for G, y in (loader if slot_step is None else ()):
             loss, acc, *_ = trainer.train_one_step(gnn, opt, loss_fn, G, y, dev, bucket=bucket, sync=True)
             tot, n = tot + loss, n + 1
         gnn.eval()

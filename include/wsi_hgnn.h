@@ -533,6 +533,21 @@ int wsi_pool_bwd_bias(const float* gt_seg, int32_t T, int32_t S, int32_t D, int3
 int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fill of a padded batch slot (data.BatchSlot): plan, readout tables, labels and type-major features of "the real slides, empty graphs up to the
+ * slot's capacity, one filler graph" written into caller-owned STATIC buffers, so that a step captured over them replays over every batch that
+ * fits.  One launch over a descriptor table in wsi_plan_assemble's format (same 10 words, same block_start rule), with these modes:
+ *   mode 0  as wsi_plan_assemble                 mode 1  4-byte copy out[i] = in1[i]            mode 2  4-byte fill with the low 32 bits of add
+ *   mode 3 (int32 out):  out[i] = desc[tab_off + key + i]                    mode 4 (int64 out):  out[i] = desc[tab_off + key + i]
+ *   mode 5 (16-byte elements, both pointers 16-byte aligned):  out[i] = in1[i], or zero when in1 is NULL (the feature rows)
+ *   modes 10 / 11 / 13 (int32 out): rowptr of the filler's segments / src of its edges / colptr of its sources, for node type `key`, by index
+ *   arithmetic from the filler block at desc + tab_off: [T, then per node type: nf, ef, first filler node, first filler CSR edge, source type of
+ *   relation slot 0, relation slots, first filler CSC entry] (csrc/slot_math.h; the filler graph: graph.filler_graph)
+ *   mode 14 (int32 out): out[i] = add + stride * (local destination of the filler's i-th edge into node type `key`)
+ *   mode 12: element i = the filler's i-th edge into node type `key`; writes its CSC entry into the WHOLE tables out (csc_eid) and in1 (csc_dst)
+ * No allocation, no synchronisation, no read-back; everything on `stream`. */
+int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Row-wise kernels of the HGT / GCN siblings of the path.
  *
  * wsi_layernorm_*: torch.nn.LayerNorm(out_dim) per node type, models/HGT.py:57 (creation), :124 (use).

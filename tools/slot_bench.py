@@ -1,0 +1,158 @@
+#!/usr/bin/env python
+"""What replaying ONE captured step over new slides costs (data.BatchSlot + trainer.CapturedSlotStep) -> profiles/r12_slot_step.json.
+
+The reference's regime: one or two new slides per step (trainer/train_gnn.py:48-79).  HEATNet4 at the benchmark's model size over a resident data
+set of 64 synthetic slides of 6k-12k nodes, batch_size 1 and 2, feat_drop 0 and 0.2 (train mode), three legs over the SAME sequence of batches, in
+one process, alternating round by round:
+  (i)   eager: the loader's assembled batch (graph.assemble_plan), forward, loss, backward, optimizer step - the yardstick;
+  (ii)  CapturedSlotStep over ONE slot sized for the largest batch;
+  (iii) CapturedSlotStep over THREE slots by size class.
+Every leg has a model and an optimizer of its own (same initial values, wsi_hgnn_amd.optim.Adam(capturable=True)).  A round is one pass over the
+batches behind a device synchronise and ends in one; reported: median / fastest / slowest round in wall ms per step, the fill alone (wall ms per
+``slot.load`` with the device idle - host arithmetic, upload and kernel - and the device time of upload + kernel by events, queued behind a few ms
+of unrelated work), the share of the slot's rows and edges the filler takes, and which
+slot the batches went to.  A GPU is required: nothing is estimated."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+ND = {"0": 0, "1": 1, "2": 2}
+
+
+def _stats(v):
+    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+
+
+def _class_capacities(loader, batch_size, classes):
+    """Capacities of `classes` slots by slide size: slot k holds any `batch_size` slides out of the smallest (k + 1) / classes of the data set."""
+    its = sorted(loader.items, key=lambda it: sum(it.num_nodes))
+    T = len(its[0].num_nodes)
+    caps = []
+    for k in range(classes):
+        part = its[:max(batch_size, (len(its) * (k + 1) + classes - 1) // classes)]
+        top = lambda xs: sum(sorted(xs, reverse=True)[:batch_size])
+        caps.append(([top([it.num_nodes[t] for it in part]) + 1 for t in range(T)], [top([it.pieces.ecount[t] for it in part]) for t in range(T)], batch_size))
+    return caps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slides", type=int, default=64)
+    ap.add_argument("--min-nodes", type=int, default=6000)
+    ap.add_argument("--max-nodes", type=int, default=12000)
+    ap.add_argument("--in-dim", type=int, default=1024)
+    ap.add_argument("--hidden", type=int, default=512)
+    ap.add_argument("--rounds", type=int, default=11)
+    ap.add_argument("--gemm", default="auto", choices=["fp32", "bf16x6", "fp16x3", "auto"])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_slot_step.json"))
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/slot_bench.py measures on the GPU; none is visible (nothing is estimated on the CPU)")
+    import __graft_entry__
+    __graft_entry__.build()
+    from wsi_hgnn_amd import models, ops, synthetic, optim as O
+    from wsi_hgnn_amd.data import BatchSlot, GraphBatchLoader
+    from wsi_hgnn_amd.trainer import CapturedSlotStep, apply_loss
+    dev = torch.device("cuda:0")
+    ops.set_gemm_precision(args.gemm)
+    gen = torch.Generator().manual_seed(611)
+    sizes = torch.randint(args.min_nodes, args.max_nodes + 1, (args.slides,), generator=gen).tolist()
+    graphs = [synthetic.hetero_graph(n, args.in_dim, seed=3000 + i) for i, n in enumerate(sizes)]
+    labels = torch.randint(0, 2, (args.slides,), generator=gen).tolist()
+    lf = torch.nn.CrossEntropyLoss()
+    busy = torch.randn(4096, 4096, device=dev)
+    busy_out = torch.empty_like(busy)
+    result = {"workload": f"HEATNet4({args.in_dim}, {args.hidden}, 2 layers, 4 heads), {args.slides} synthetic slides of {args.min_nodes}-{args.max_nodes} nodes "
+                          f"(mean {sum(sizes) / len(sizes):.0f}), resident, gemm={args.gemm}, wsi_hgnn_amd.optim.Adam(capturable=True), train mode",
+              "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "configs": []}
+
+    def make(drop):
+        torch.manual_seed(611)
+        m = models.HEATNet4(args.in_dim, args.hidden, 2, 2, 4, ND, drop, "mean").to(dev).train()
+        return m, O.Adam(m.parameters(), lr=1e-5, weight_decay=5e-3, capturable=True)
+
+    for bs in (1, 2):
+        loader = GraphBatchLoader(graphs, labels, bs, dev, shuffle=False, resident=True)
+        order = torch.randperm(args.slides, generator=gen).tolist()
+        batches = [order[i:i + bs] for i in range(0, len(order), bs)]
+        for drop in (0.0, 0.2):
+            m_e, o_e = make(drop)
+
+            def eager_round():
+                for idxs in batches:
+                    G, y, _ = loader._assemble(idxs, 0)
+                    o_e.zero_grad(set_to_none=True)
+                    loss = apply_loss(lf, m_e(G), y)
+                    loss.backward()
+                    o_e.step()
+
+            m1, o1 = make(drop)
+            one = CapturedSlotStep(m1, o1, lf, [BatchSlot(loader)], warmup=2)
+            m3, o3 = make(drop)
+            three = CapturedSlotStep(m3, o3, lf, [BatchSlot(loader, c) for c in _class_capacities(loader, bs, 3)], warmup=2)
+            legs = {"eager": eager_round,
+                    "one_slot": lambda: [one.step(idxs) for idxs in batches],
+                    "three_slots": lambda: [three.step(idxs) for idxs in batches]}
+            for fn in legs.values():                         # one untimed pass each: caches, allocator pools
+                fn()
+            times = {k: [] for k in legs}
+            for _ in range(args.rounds):
+                for k, fn in legs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    times[k].append((time.perf_counter() - t0) / len(batches) * 1e3)
+            entry = {"batch_size": bs, "feat_drop": drop, "steps_per_round": len(batches), "legs": {k: _stats(v) for k, v in times.items()}}
+            # the fill alone, and what the filler takes
+            for name, step in (("one_slot", one), ("three_slots", three)):
+                wall, devt, rows, edges, routed = [], [], [], [], [0] * len(step.slots)
+                for idxs in batches:
+                    i = step.slot_for(idxs)
+                    if i is None:
+                        continue
+                    slot = step.slots[i]
+                    routed[i] += 1
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    slot.load(idxs)
+                    torch.cuda.synchronize()
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    # device time: behind a few ms of unrelated work, so that the upload and the kernel are queued before the GPU reaches them
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    for _ in range(3):
+                        torch.mm(busy, busy, out=busy_out)
+                    a.record()
+                    slot.load(idxs)
+                    b.record()
+                    torch.cuda.synchronize()
+                    devt.append(a.elapsed_time(b))
+                    r, e = slot.padded_share()
+                    rows.append(r)
+                    edges.append(e)
+                entry[name] = {"fill_wall_ms": _stats(wall), "fill_device_ms": _stats(devt), "padded_row_share": round(sum(rows) / len(rows), 4),
+                               "padded_edge_share": round(sum(edges) / len(edges), 4), "batches_per_slot": routed,
+                               "slot_rows": [s.layout.N for s in step.slots], "eager_fallbacks_per_round": len(batches) - sum(routed)}
+            e_ms = entry["legs"]["eager"]["median_ms"]
+            entry["speedup_one_slot"] = round(e_ms / entry["legs"]["one_slot"]["median_ms"], 3)
+            entry["speedup_three_slots"] = round(e_ms / entry["legs"]["three_slots"]["median_ms"], 3)
+            result["configs"].append(entry)
+            print(json.dumps(entry), flush=True)
+            del one, three, m1, m3, m_e
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()

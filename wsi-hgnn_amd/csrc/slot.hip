@@ -1,0 +1,91 @@
+// Fill of a padded batch slot (data.BatchSlot, graph.slot_fill): the kernel plan, the readout tables, the labels and the type-major
+// feature table of "the real slides, then empty graphs, then one filler graph" written into the slot's STATIC buffers, so that a training step
+// captured once over those buffers replays over any batch that fits.  ONE launch over a table of segment descriptors, in the format of
+// wsi_plan_assemble (csrc/plan.hip) with more modes: the real slides' parts are offset copies of their stored pieces, the filler's parts are
+// index arithmetic (csrc/slot_math.h), the features a 16-byte streaming copy.  Contract: include/wsi_hgnn.h (wsi_slot_fill).
+#include "common.h"
+#include "slot_math.h"
+
+namespace wsi {
+
+constexpr int SLOT_ROW = 10;              // int64 words per segment descriptor
+constexpr int SLOT_BLOCK = 1024;          // elements per workgroup (modes 5: 16-byte elements)
+
+// desc (device, int64): per segment  [out, in1, in2, tab_off, key, add, stride, n, mode, block_start], then the tables the tab_off's point into.
+//  mode 0  int32 out[i] = add + i * stride + in1[i] + tab[in2[i]]        (in1, in2: int64 arrays or null; tab = desc + tab_off + key)
+//  mode 1  4-byte copy out[i] = in1[i]                                   mode 2  4-byte fill out[i] = (uint32) add
+//  mode 3  int32 out[i] = tab[i]                                         mode 4  int64 out[i] = tab[i]
+//  mode 5  16-byte copy out[i] = in1[i], or zero fill when in1 is null (n counts 16-byte elements; both pointers 16-byte aligned)
+//  filler modes, tab = the filler block of slot_math.h, key = node type:
+//  mode 10 rowptr of the filler's segments      mode 11 src of the filler's edges      mode 13 colptr of the filler's sources
+//  mode 14 out[i] = add + stride * (destination of the filler's i-th edge): the softmax segment of every filler edge
+//  mode 12 CSC entries of the filler's edges: out = csc_eid and in1 = csc_dst, the WHOLE tables (the entry's position is computed)
+__global__ __launch_bounds__(256) void slot_fill_kernel(const int64_t* __restrict__ desc, int nsegs) {
+    const int b = blockIdx.x;
+    int lo = 0, hi = nsegs - 1;           // last segment whose block_start <= b
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[(int64_t)mid * SLOT_ROW + 9] <= b) lo = mid; else hi = mid - 1;
+    }
+    const int64_t* d = desc + (int64_t)lo * SLOT_ROW;
+    const int64_t n = d[7];
+    const int mode = (int)d[8];
+    const int64_t i0 = ((int64_t)b - d[9]) * SLOT_BLOCK;
+    const int64_t* tab = d[3] >= 0 ? desc + d[3] : nullptr;
+    const int64_t key = d[4], add = d[5], stride = d[6];
+#pragma unroll
+    for (int r = 0; r < SLOT_BLOCK / 256; ++r) {
+        const int64_t i = i0 + r * 256 + threadIdx.x;          // a wave's 64 lanes: 64 consecutive elements (modes 5: one contiguous KB)
+        if (i >= n) break;
+        switch (mode) {
+        case 0: {
+            const int64_t* in1 = reinterpret_cast<const int64_t*>(d[1]);
+            const int64_t* in2 = reinterpret_cast<const int64_t*>(d[2]);
+            int64_t v = add + i * stride;
+            if (in1) v += in1[i];
+            if (tab) v += tab[key + (in2 ? in2[i] : 0)];
+            reinterpret_cast<int32_t*>(d[0])[i] = (int32_t)v;
+            break;
+        }
+        case 1: reinterpret_cast<uint32_t*>(d[0])[i] = reinterpret_cast<const uint32_t*>(d[1])[i]; break;
+        case 2: reinterpret_cast<uint32_t*>(d[0])[i] = (uint32_t)add; break;
+        case 3: reinterpret_cast<int32_t*>(d[0])[i] = (int32_t)tab[key + i]; break;
+        case 4: reinterpret_cast<int64_t*>(d[0])[i] = tab[key + i]; break;
+        case 5: {
+            const uint4* in = reinterpret_cast<const uint4*>(d[1]);
+            reinterpret_cast<uint4*>(d[0])[i] = in ? in[i] : make_uint4(0u, 0u, 0u, 0u);
+            break;
+        }
+        case 10: reinterpret_cast<int32_t*>(d[0])[i] = (int32_t)filler_rowptr(tab, key, i); break;
+        case 11: reinterpret_cast<int32_t*>(d[0])[i] = (int32_t)filler_src(tab, key, i); break;
+        case 12: {
+            int64_t slot, eid, dst;
+            filler_csc(tab, key, i, &slot, &eid, &dst);
+            reinterpret_cast<int32_t*>(d[0])[slot] = (int32_t)eid;
+            reinterpret_cast<int32_t*>(d[1])[slot] = (int32_t)dst;
+            break;
+        }
+        case 13: reinterpret_cast<int32_t*>(d[0])[i] = (int32_t)filler_colptr(tab, key, i); break;
+        case 14: {
+            const int64_t* f = filler_type(tab, key);
+            int64_t node, k;
+            filler_owner(i, f[FP_EF], f[FP_NF], &node, &k);
+            reinterpret_cast<int32_t*>(d[0])[i] = (int32_t)(add + node * stride);
+            break;
+        }
+        default: break;
+        }
+    }
+}
+
+}  // namespace wsi
+
+using namespace wsi;
+
+extern "C" int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
+    if (nsegs < 0 || total_blocks < 0) { set_error("slot_fill: bad argument"); return WSI_EINVAL; }
+    if (nsegs == 0 || total_blocks == 0) return WSI_OK;
+    if (!desc) { set_error("slot_fill: null pointer"); return WSI_EINVAL; }
+    hipLaunchKernelGGL(slot_fill_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, desc, (int)nsegs);
+    return check_launch("slot_fill");
+}

@@ -325,3 +325,141 @@ class GraphBatchLoader:
         finally:
             if pinned:
                 ops.block_side_streams(False, who)
+
+
+class BatchSlot:
+    """A batch of FIXED shape fed from a resident loader: the static tables of one padded batch - up to ``b_cap`` real slides, empty
+    graphs up to ``b_cap``, one filler graph labelled -100 that takes what the slides leave of the capacities - and ONE ``HeteroGraph`` whose kernel
+    plan and feature frames are views of those tables.  ``load(idxs)`` rewrites the tables for another batch (one descriptor upload, one launch:
+    ``graph.slot_fill``); the graph object, its plan, its readout plan and every shape stay, so a step captured over ``slot.graph`` and
+    ``slot.labels`` replays over the new batch (``trainer.CapturedSlotStep``).
+
+    ``capacity``: ``(n_cap, e_cap)`` - nodes per node type, edges per destination node type - or ``(n_cap, e_cap, b_cap)``; ``None`` derives a
+    bound every batch of the loader's bucket fits: per type the sum of the ``batch_size`` largest counts, plus one node.  Resident data sets
+    without a transform only: a pinned-host data set has no device-side features to copy from, augmented batches change shape."""
+
+    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0):
+        if not loader.resident:
+            raise RuntimeError("BatchSlot needs a device-resident data set (GraphBatchLoader(..., resident=True)): the fill copies the slides' features "
+                               "device to device; a pinned-host loader stays on its own double-buffered path")
+        if loader.transform is not None:
+            raise RuntimeError("BatchSlot: a loader with transform= yields augmented batches, whose shapes change from draw to draw; step them eagerly")
+        self.loader, self.device = loader, loader.device
+        key = list(loader.buckets)[bucket]
+        self.members = set(loader.buckets[key])
+        ntypes, rels = list(key[0]), [tuple(r) for r in key[1]]
+        its = [loader.items[i] for i in loader.buckets[key]]
+        T = len(ntypes)
+        if capacity is None:
+            bs = loader.batch_size
+            top = lambda xs: sum(sorted(xs, reverse=True)[:bs])
+            n_cap = [top([it.num_nodes[t] for it in its]) + 1 for t in range(T)]
+            e_cap = [top([it.pieces.ecount[t] for it in its]) for t in range(T)]
+            b_cap = bs
+        else:
+            n_cap, e_cap = capacity[0], capacity[1]
+            b_cap = capacity[2] if len(capacity) > 2 else loader.batch_size
+        self.layout = _graph_mod.SlotLayout(ntypes, rels, n_cap, e_cap, b_cap, loader.in_dim)
+        self.bufs = self.layout.buffers(self.device)
+        locality = [it.pieces.locality for it in its]
+        if any(locality) and not all(locality):
+            raise ValueError("a data set mixes locality-ordered and plain graphs: apply graph.apply_locality_order to all of its slides or none")
+        lay, hd = self.layout, self.layout.hd
+        plan = _graph_mod.slot_plan(lay, self.bufs, locality=bool(locality and locality[0]))
+        G = HeteroGraph._from_plan(OrderedDict(zip(ntypes, lay.n_cap)), rels,
+                                   {t: torch.zeros(lay.graphs, dtype=torch.int64) for t in ntypes}, plan, None)
+        feat = self.bufs["feat"]
+        parts = []
+        for i, t in enumerate(ntypes):
+            v = feat[hd.type_off[i]:hd.type_off[i + 1]]
+            G._nframes[t]["feat"] = v
+            parts.append(v)
+        # the caches that key on (data_ptr, _version) stay valid across fills - the kernel writes behind the version counters and the cached
+        # objects ARE the static tables: the feature concatenation, the CSR-ordered sim, the features' row scales
+        cache = G.__dict__.setdefault("_cat_cache", {})
+        cache["feat"] = (tuple((p.data_ptr(), tuple(p.shape), p.dtype, p._version) for p in parts), feat)
+        cache[("e", "sim")] = ((), self.bufs["sim"])
+        if self.device.type == "cuda":
+            from . import ops
+            ops.attach_row_scales(feat, self.bufs["scales"])
+            # the readout's plan (pooling.readout.all_types_plan caches it on the graph): static tables, refreshed by every fill
+            rp = _slot_reduce_plan(ops)()
+            rp.device, rp.num_segs, rp.num_chunks, rp.num_rows, rp.first_row = self.device, lay.num_segs, lay.c_cap, lay.N, 0
+            rp.chunk_row, rp.chunk_seg, rp.seg_chunk = self.bufs["chunk_row"], self.bufs["chunk_seg"], self.bufs["seg_chunk"]
+            rp._counts, rp._inv_counts, rp._nonempty = self.bufs["seg_counts"], self.bufs["seg_inv_counts"], self.bufs["seg_nonempty"]
+            rp._row_seg = self.bufs["row_seg"]
+            rp.type_rows = [(hd.type_off[i], hd.type_off[i + 1]) for i in range(T)]
+            rp.type_segments = [(i * lay.graphs, (i + 1) * lay.graphs) for i in range(T)]
+            G.__dict__.setdefault("_readout_plans", {})[("all", str(self.device))] = rp
+            self.readout_plan = rp
+        else:
+            self.readout_plan = None
+        self.graph, self.labels = G, self.bufs["labels"]
+        self.num_real, self.batch, self.idxs = 0, None, None
+
+    def _counts(self, idxs):
+        its = [self.loader.items[i] for i in idxs]
+        return [it.num_nodes for it in its], [it.pieces.ecount for it in its]
+
+    def fits(self, idxs: Sequence[int]) -> bool:
+        """Does the batch of the loader's slides ``idxs`` fit: same schema bucket, at most ``b_cap`` slides, and per node type at least one
+        node and no fewer than zero edges left for the filler."""
+        idxs = list(idxs)
+        if not idxs or any(i not in self.members for i in idxs):
+            return False
+        return _graph_mod.SlotBatch.fits(self.layout, *self._counts(idxs))
+
+    def load(self, idxs: Sequence[int]) -> "BatchSlot":
+        """Fill the slot with the batch of slides ``idxs`` (in that order) on the current stream.  Raises ValueError when it does not fit."""
+        idxs = list(idxs)
+        if not self.fits(idxs):
+            raise ValueError(f"BatchSlot.load: the batch {idxs} does not fit the slot (capacities: {self.layout.n_cap} nodes, {self.layout.e_cap} edges, "
+                             f"{self.layout.b_cap} slides)")
+        its = [self.loader.items[i] for i in idxs]
+        T = self.layout.T
+        scales = None
+        if self.device.type == "cuda":
+            scales = [[it.feat_scale(t) for t in range(T)] for it in its]
+        sb = _graph_mod.slot_fill(self.layout, self.bufs, [it.pieces for it in its], [it.label for it in its], [it.feat for it in its], scales)
+        G, lay = self.graph, self.layout
+        for i, t in enumerate(G.ntypes):
+            G._batch_num_nodes[t] = torch.tensor(sb.counts[i], dtype=torch.int64)
+        # per-relation COO / edge fields of the padded batch: rebuilt on demand only (HeteroGraph._edges); the HEAT path never asks
+        ntypes, rels, dev = G.ntypes, G.canonical_etypes, self.device
+        nf, ef, n = list(sb.nf), list(sb.ef), list(sb.n)
+
+        def coo():
+            edges, efields = _batch_coo(its, ntypes, rels)
+            fg = _graph_mod.filler_graph(ntypes, rels, nf, ef, 0)
+            tix = {t: i for i, t in enumerate(ntypes)}
+            for r in rels:
+                u, v = fg.edges(r)
+                edges[r] = (torch.cat([edges[r][0], u.to(dev) + n[tix[r[0]]]]), torch.cat([edges[r][1], v.to(dev) + n[tix[r[2]]]]))
+                efields[r] = {"sim": torch.cat([efields[r]["sim"], torch.zeros(u.numel(), dtype=torch.float32, device=dev)])}
+            return edges, efields
+
+        G._edges_store, G._edge_thunk = None, coo
+        for r in rels:
+            G._eframes[r].clear()
+        if self.readout_plan is not None:
+            self.readout_plan.ranges = list(sb.ranges)
+            from . import ops
+            ops.refresh_constant_cols(self.bufs["feat"])      # scaled GEMM modes: the features' cached column statistics describe the previous batch
+        self.num_real, self.batch, self.idxs = sb.B, sb, idxs
+        return self
+
+    def padded_share(self):
+        """(share of the slot's rows, share of its edges) that the current batch's filler takes."""
+        sb, lay = self.batch, self.layout
+        return sum(sb.nf) / max(lay.N, 1), sum(sb.ef) / max(lay.E, 1)
+
+
+def _slot_reduce_plan(ops):
+    class SlotReducePlan(ops.ReducePlan):
+        """The readout plan of a slot: its tables are static buffers the fill rewrites, so nothing a step decides on the HOST may depend on the
+        current batch - a slot always counts as having empty segments (the mask of empty segments is then always applied; it is exact)."""
+
+        def has_empty(self) -> bool:
+            return True
+
+    return SlotReducePlan

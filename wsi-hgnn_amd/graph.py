@@ -908,6 +908,394 @@ def assemble_plan_torch(hd: PlanHeader, pieces: Sequence[PlanPieces], dev, batch
     return p, sim
 
 
+# ------------------------------------------------------------------ padded batch slots
+# A SLOT is a batch of fixed shape: up to ``b_cap`` real slides, empty graphs up to ``b_cap``, and one FILLER graph that takes every node and
+# edge the real slides leave of the slot's capacities.  The filler's label is -100, so it adds nothing to the loss or to any gradient, and a
+# block-diagonal batch keeps it away from the real slides' logits: a training step captured once over the slot's static buffers replays over
+# every batch that fits (data.BatchSlot, trainer.CapturedSlotStep).
+
+def filler_graph(ntypes: Sequence[str], rels: Sequence[CanonicalEType], nf: Sequence[int], ef: Sequence[int], in_dim: int) -> HeteroGraph:
+    """The filler of a slot as an ordinary graph: ``nf[t]`` all-zero nodes of node type ``ntypes[t]`` (sorted, as ``HeteroGraph.ntypes``) and,
+    for every destination type t with ``ef[t] > 0``, ``ef[t]`` edges with ``sim = 0`` in the first relation (sorted order) whose destination
+    type is t: edge j runs from source ``j mod nf[s]`` to destination ``j mod nf[t]`` - spread over both endpoints, so that neither the
+    destination-major nor the source-major kernels meet a hub.  Every other relation is present and empty."""
+    ntypes = [str(t) for t in ntypes]
+    rels = sorted(tuple(str(x) for x in r) for r in rels)
+    hd = PlanHeader(ntypes, rels, [int(x) for x in nf])
+    edges, sim = OrderedDict(), {}
+    for ri, (s, e, d) in enumerate(rels):
+        td, ts = hd.tindex[d], hd.tindex[s]
+        k = int(ef[td]) if hd.slot_of_rel[ri] == 0 else 0
+        if k and (nf[td] < 1 or nf[ts] < 1):
+            raise ValueError("filler_graph: edges need at least one node at both ends")
+        j = torch.arange(k, dtype=torch.int64)
+        edges[(s, e, d)] = (j % max(int(nf[ts]), 1), j % max(int(nf[td]), 1))
+        sim[(s, e, d)] = torch.zeros(k, dtype=torch.float32)
+    for t in range(len(ntypes)):
+        if ef[t] and hd.R[t] == 0:
+            raise ValueError(f"filler_graph: node type {ntypes[t]!r} has no incoming relation to carry edges")
+    feat = {t: torch.zeros((int(nf[i]), int(in_dim)), dtype=torch.float32) for i, t in enumerate(ntypes)}
+    return HeteroGraph.from_coo(OrderedDict(zip(ntypes, [int(x) for x in nf])), edges, feat=feat, sim=sim)
+
+
+READOUT_CHUNK = 128     # rows per chunk of the readout's ReducePlan (ops.ReducePlan.from_ptr's default, which pooling.readout uses)
+
+
+class SlotLayout:
+    """Capacities of a slot and what follows from them alone: ``n_cap[t]`` nodes per node type, ``e_cap[t]`` edges per DESTINATION node type
+    (0 where the type has no incoming relation), ``b_cap`` slides.  All shapes of the padded batch are functions of these."""
+
+    def __init__(self, ntypes: Sequence[str], rels: Sequence[CanonicalEType], n_cap: Sequence[int], e_cap: Sequence[int], b_cap: int, in_dim: int):
+        self.ntypes, self.rels = [str(t) for t in ntypes], [tuple(str(x) for x in r) for r in rels]
+        if self.ntypes != sorted(self.ntypes) or self.rels != sorted(self.rels):
+            raise ValueError("SlotLayout: node types and relations in sorted order (HeteroGraph.ntypes / canonical_etypes)")
+        self.n_cap, self.e_cap, self.b_cap, self.in_dim = [int(x) for x in n_cap], [int(x) for x in e_cap], int(b_cap), int(in_dim)
+        self.T, self.graphs = len(self.ntypes), self.b_cap + 1
+        self.hd = hd = PlanHeader(self.ntypes, self.rels, self.n_cap)
+        if self.b_cap < 1 or any(n < 1 for n in self.n_cap) or any(e < 0 for e in self.e_cap):
+            raise ValueError("SlotLayout: b_cap >= 1, n_cap >= 1 (the filler keeps one node of every type), e_cap >= 0")
+        self.src_type = [-1] * self.T                      # source type of relation slot 0 of every destination type: where filler edges come from
+        for ri, (s, e, d) in enumerate(self.rels):
+            if hd.slot_of_rel[ri] == 0:
+                self.src_type[hd.tindex[d]] = hd.tindex[s]
+        if any(self.e_cap[t] and hd.R[t] == 0 for t in range(self.T)):
+            raise ValueError("SlotLayout: e_cap must be 0 for a node type without incoming relation")
+        self.ebase = [0]
+        for e in self.e_cap:
+            self.ebase.append(self.ebase[-1] + e)
+        self.N, self.S, self.E = hd.N, hd.S, self.ebase[-1]
+        if self.E >= 2 ** 31 - 1 or self.S >= 2 ** 31 - 1:
+            raise ValueError("slot too large for the int32 kernel plan")
+        self.num_segs = self.T * self.graphs               # readout segments (node type, graph)
+        # every graph adds at most one short chunk per node type to the ceil(n / chunk) full ones
+        self.c_cap = sum((n + READOUT_CHUNK - 1) // READOUT_CHUNK + self.graphs for n in self.n_cap)
+
+    def buffers(self, device) -> Dict[str, torch.Tensor]:
+        """The slot's static tables (uninitialised): written by ``slot_fill``, read by every step on the slot."""
+        dev = torch.device(device)
+        mk = lambda n, dt: torch.empty(max(int(n), 1), dtype=dt, device=dev)[:int(n)]
+        i32, f32 = torch.int32, torch.float32
+        N, S, E, K, C = self.N, self.S, self.E, self.num_segs, self.c_cap
+        return {"rowptr": mk(S + 1, i32), "colptr": mk(N + 1, i32), "node_seg": mk(N + 1, i32), "src": mk(E, i32), "csc_eid": mk(E, i32),
+                "csc_dst": mk(E, i32), "order_dst": mk(N, i32), "order_src": mk(N, i32), "sim": mk(E, f32), "inv_rd": mk(N, f32),
+                "readout_ptr": mk(K + 1, i32), "labels": mk(self.graphs, torch.int64), "feat": mk(N * self.in_dim, f32).view(N, self.in_dim),
+                "scales": mk(N, i32).view(N, 1), "edge_seg": mk(E, i32), "row_seg": mk(N, i32),
+                "chunk_row": mk(C + 1, i32), "chunk_seg": mk(C, i32), "seg_chunk": mk(K + 1, i32),
+                "seg_counts": mk(K, f32).view(K, 1), "seg_inv_counts": mk(K, f32).view(K, 1), "seg_nonempty": mk(K, f32).view(K, 1)}
+
+
+class SlotBatch:
+    """Host arithmetic of ONE batch placed in a slot: where every piece of every table goes.  Raises ValueError when the batch does not fit:
+    more than ``b_cap`` slides, or for some node type t fewer than one node (``nf[t] = n_cap[t] - n[t] >= 1``) or fewer than zero edges
+    (``ef[t] = e_cap[t] - e[t] >= 0``) left for the filler."""
+
+    @staticmethod
+    def fits(lay: SlotLayout, counts: Sequence[Sequence[int]], ecounts: Sequence[Sequence[int]]) -> bool:
+        """``counts[b][t]`` / ``ecounts[b][t]``: nodes / edges (by destination type) of slide b."""
+        if not 1 <= len(counts) <= lay.b_cap:
+            return False
+        # a node type NO slide of the batch has is not padded: the models skip such a type's prediction head altogether (models/HEATNet4.py:216-221,
+        # ``h[k].shape[0] > 0``), the filler's nodes would switch it on - such a batch does not fit and is stepped eagerly
+        if any(sum(c[t] for c in counts) < 1 for t in range(lay.T)):
+            return False
+        return all(lay.n_cap[t] - sum(c[t] for c in counts) >= 1 and lay.e_cap[t] - sum(e[t] for e in ecounts) >= 0 for t in range(lay.T))
+
+    def __init__(self, lay: SlotLayout, pieces: Sequence[PlanPieces]):
+        T, hd, B = lay.T, lay.hd, len(pieces)
+        if not SlotBatch.fits(lay, [pc.counts for pc in pieces], [pc.ecount for pc in pieces]):
+            raise ValueError("the batch does not fit the slot")
+        self.B = B
+        self.n = [sum(pc.counts[t] for pc in pieces) for t in range(T)]
+        self.e = [sum(pc.ecount[t] for pc in pieces) for t in range(T)]
+        self.nf = [lay.n_cap[t] - self.n[t] for t in range(T)]
+        self.ef = [lay.e_cap[t] - self.e[t] for t in range(T)]
+        self.pre = [[0] * T for _ in range(B + 1)]
+        for b in range(B):
+            for t in range(T):
+                self.pre[b + 1][t] = self.pre[b][t] + pieces[b].counts[t]
+        self.node_tab = [hd.type_off[t] + self.pre[b][t] for b in range(B) for t in range(T)]          # [b*T + t]: first global id of (slide, type)
+        self.fb = [hd.type_off[t] + self.n[t] for t in range(T)]                                        # first filler node of the type
+        self.feb = [lay.ebase[t] + self.e[t] for t in range(T)]                                         # first filler CSR edge into the type
+        self.eoff, self.coff, self.cfb, acc_c = {}, {}, [], 0
+        for t in range(T):
+            acc_e = lay.ebase[t]
+            for b in range(B):
+                self.eoff[(t, b)], self.coff[(t, b)] = acc_e, acc_c
+                acc_e += pieces[b].ecount[t]
+                acc_c += pieces[b].ccount[t]
+            self.cfb.append(acc_c)                                                                      # first CSC entry of the type's filler sources
+            acc_c += sum(self.ef[d] for d in range(T) if lay.src_type[d] == t)
+        if acc_c != lay.E:
+            raise ValueError("slot: the pieces' CSR and CSC edge counts disagree")
+        self.edge_tab = [self.eoff[(t, b)] for b in range(B) for t in range(T)]
+        self.counts = [[pc.counts[t] for pc in pieces] + [0] * (lay.b_cap - B) + [self.nf[t]] for t in range(T)]    # [t][graph]
+        self.readout_ptr = [0]
+        for t in range(T):
+            for c in self.counts[t]:
+                self.readout_ptr.append(self.readout_ptr[-1] + c)
+        self.filler_block = [T] + [w for t in range(T) for w in (self.nf[t], self.ef[t], self.fb[t], self.feb[t], lay.src_type[t], hd.R[t], self.cfb[t])]
+        # the readout's ReducePlan (ops.ReducePlan.from_ranges over readout_ptr), padded to the slot's chunk capacity with empty chunks that no
+        # segment owns: the launches over chunks keep one grid, the second stages never read them
+        self.ranges = [(self.readout_ptr[i], self.readout_ptr[i + 1]) for i in range(lay.num_segs)]
+        chunk_row, chunk_seg, seg_chunk = [], [], [0]
+        for s_, (a, b_) in enumerate(self.ranges):
+            r = a
+            while r < b_:
+                chunk_row.append(r)
+                chunk_seg.append(s_)
+                r = min(b_, r + READOUT_CHUNK)
+            seg_chunk.append(len(chunk_row))
+        pad = lay.c_cap - len(chunk_seg)
+        if pad < 0:
+            raise ValueError("slot: readout chunk capacity exceeded")
+        self.chunk_row = chunk_row + [lay.N] * (pad + 1)
+        self.chunk_seg = chunk_seg + [lay.num_segs - 1] * pad
+        self.seg_chunk = seg_chunk
+        self.seg_counts = [float(b_ - a) for a, b_ in self.ranges]
+        self.seg_inv_counts = [1.0 / (b_ - a) if b_ > a else 0.0 for a, b_ in self.ranges]
+        self.seg_nonempty = [1.0 if b_ > a else 0.0 for a, b_ in self.ranges]
+
+
+def _piece_edge_seg(pc: PlanPieces, t: int, R: int) -> torch.Tensor:
+    """int64 [ecount[t]]: the softmax segment (local: node * R + slot) of every CSR edge into node type t of a stored graph; expanded on the
+    device once per stored graph (output size known: no synchronisation)."""
+    cache = pc.__dict__.setdefault("_edge_seg", {})
+    if t not in cache:
+        rp = pc.rp[t]
+        cnt = torch.cat([rp[1:], rp.new_full((1,), int(pc.ecount[t]))]) - rp if rp.numel() else rp
+        cache[t] = torch.repeat_interleave(torch.arange(rp.numel(), dtype=torch.int64, device=rp.device), cnt, output_size=int(pc.ecount[t]))
+    return cache[t]
+
+
+def _float_bits(xs: Sequence[float]) -> List[int]:
+    return torch.tensor(list(xs), dtype=torch.float32).view(torch.int32).tolist()
+
+
+def slot_fill(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: Sequence[PlanPieces], labels: Sequence[int],
+              feats: Sequence[Sequence[torch.Tensor]], scales: Optional[Sequence[Sequence[torch.Tensor]]] = None) -> SlotBatch:
+    """Write the padded batch of the stored graphs ``pieces`` (labels ``labels``, per-type fp32 feature tables ``feats[b][t]`` and, optionally,
+    their row scales ``scales[b][t]``) into the slot's static tables ``bufs`` (``SlotLayout.buffers``): on the GPU ONE upload (a descriptor
+    table) and ONE launch (``wsi_slot_fill``), no allocation inside the library, no read-back, no synchronisation, on the current stream; the
+    filler's tables come from index arithmetic in the kernel.  On the CPU: ``slot_fill_torch`` copied into ``bufs``.  Features and plan share
+    the launch: every mode works on 1024-element blocks (the feature copy on 16-byte elements).  The fill writes behind PyTorch's version
+    counters - see DESIGN 3.15 for what that means for caches."""
+    dev = bufs["rowptr"].device
+    if dev.type != "cuda":
+        out = slot_fill_torch(lay, pieces, labels, feats, scales, dev)
+        with torch.no_grad():
+            for k, v in out.items():
+                if k != "batch":
+                    bufs[k].copy_(v)
+        return out["batch"]
+    from . import _native as N
+    sb, words, nsegs, blocks = _slot_descriptors(lay, bufs, pieces, labels, feats, scales)
+    desc = host_to_device(words, torch.int64, dev)
+    N.check(N.load().wsi_slot_fill(N.ptr(desc), nsegs, blocks, N.stream()), "wsi_slot_fill")
+    bufs["_desc"] = desc            # (stream-ordered: the table must outlive the launch; the next fill replaces it behind this one)
+    return sb
+
+
+def _slot_descriptors(lay: SlotLayout, bufs, pieces, labels, feats, scales):
+    """The descriptor table of ``slot_fill`` (include/wsi_hgnn.h, wsi_slot_fill): (SlotBatch, words, segments, 1024-element blocks).  Every
+    segment is checked against the bounds of the table it writes before anything is launched."""
+    dev = bufs["rowptr"].device
+    sb = SlotBatch(lay, pieces)
+    T, hd, B, G = lay.T, lay.hd, sb.B, lay.graphs
+    F = lay.in_dim
+    # tables behind the descriptors, in words from the start of the table area
+    tabs, tab_off = [], {}
+    for name, words in (("node", sb.node_tab), ("edge", sb.edge_tab), ("fill", sb.filler_block), ("readout_ptr", sb.readout_ptr),
+                        ("labels", [int(y) for y in labels] + [-100] * (G - B)), ("chunk_row", sb.chunk_row), ("chunk_seg", sb.chunk_seg),
+                        ("seg_chunk", sb.seg_chunk), ("seg_counts", _float_bits(sb.seg_counts)), ("seg_inv_counts", _float_bits(sb.seg_inv_counts)),
+                        ("seg_nonempty", _float_bits(sb.seg_nonempty))):
+        tab_off[name] = len(tabs)
+        tabs += list(words)
+    segs: List[List[int]] = []
+
+    def seg(out, off, n, in1=None, in2=None, tab=None, key=0, add=0, stride=0, mode=0, esize=4):
+        if n > 0:
+            if off < 0 or (int(off) + int(n)) * esize > bufs[out].numel() * bufs[out].element_size():
+                raise RuntimeError(f"slot_fill: a segment of {out} leaves the table ({off} + {n} elements of {esize} bytes)")
+            if in1 is not None and not isinstance(in1, int) and mode in (0, 1, 5) and in1.numel() * in1.element_size() < int(n) * (8 if mode == 0 else esize):
+                raise RuntimeError(f"slot_fill: a segment of {out} reads past its source")
+            p1 = in1 if isinstance(in1, int) else (0 if in1 is None else in1.data_ptr())
+            segs.append([bufs[out].data_ptr() + int(off) * esize, p1, 0 if in2 is None else in2.data_ptr(),
+                         -1 if tab is None else tab_off[tab], int(key), int(add), int(stride), int(n), mode, 0])
+
+    nreal = sum(sb.n)
+    H = sum(pc.num_heavy for pc in pieces)
+    ho, lo, oo = 0, H, 0
+    for b, pc in enumerate(pieces):             # the real nodes in the order of the unpadded batch's plan (graph.assemble_plan) ...
+        nh, nl, no = int(pc.heavy_l.numel()), int(pc.light_l.numel()), int(pc.so_l.numel())
+        seg("order_dst", ho, nh, in1=pc.heavy_l, in2=pc.heavy_t, tab="node", key=b * T)
+        seg("order_dst", lo, nl, in1=pc.light_l, in2=pc.light_t, tab="node", key=b * T)
+        seg("order_src", oo, no, in1=pc.so_l, in2=pc.so_t, tab="node", key=b * T)
+        ho, lo, oo = ho + nh, lo + nl, oo + no
+    pos = nreal
+    for t in range(T):                          # ... the filler's last
+        seg("order_dst", pos, sb.nf[t], add=sb.fb[t], stride=1)
+        seg("order_src", pos, sb.nf[t], add=sb.fb[t], stride=1)
+        pos += sb.nf[t]
+    for t in range(T):
+        R = hd.R[t]
+        for b, pc in enumerate(pieces):
+            row, eo, co = sb.node_tab[b * T + t], sb.eoff[(t, b)], sb.coff[(t, b)]
+            so = hd.seg_off[t] + sb.pre[b][t] * R
+            nc, ne, ncc = pc.counts[t], pc.ecount[t], pc.ccount[t]
+            seg("rowptr", so, nc * R, in1=pc.rp[t], add=eo)
+            seg("colptr", row, nc, in1=pc.cp[t], add=co)
+            seg("src", eo, ne, in1=pc.src_l[t], in2=pc.src_t[t], tab="node", key=b * T)
+            seg("sim", eo, ne, in1=pc.sim[t], mode=1)
+            seg("edge_seg", eo, ne, in1=_piece_edge_seg(pc, t, R) if ne else None, add=so)
+            seg("csc_eid", co, ncc, in1=pc.eid_l[t], in2=pc.ent_t[t], tab="edge", key=b * T)
+            seg("csc_dst", co, ncc, in1=pc.dst_l[t], in2=pc.ent_t[t], tab="node", key=b * T)
+            x = feats[b][t]
+            if nc:
+                if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (nc, F) or x.device != dev:
+                    raise ValueError("slot_fill: features must be contiguous fp32 [nodes, in_dim] tables on the slot's device")
+                wide = F % 4 == 0 and x.data_ptr() % 16 == 0 and bufs["feat"].data_ptr() % 16 == 0
+                if wide:
+                    seg("feat", row * F // 4, nc * F // 4, in1=x, mode=5, esize=16)
+                else:
+                    seg("feat", row * F, nc * F, in1=x, mode=1)
+                if scales is not None:
+                    seg("scales", row, nc, in1=scales[b][t], mode=1)
+        so = hd.seg_off[t] + sb.n[t] * R
+        seg("rowptr", so, sb.nf[t] * R, tab="fill", key=t, mode=10)
+        seg("colptr", sb.fb[t], sb.nf[t], tab="fill", key=t, mode=13)
+        seg("src", sb.feb[t], sb.ef[t], tab="fill", key=t, mode=11)
+        seg("sim", sb.feb[t], sb.ef[t], add=0, mode=2)
+        seg("edge_seg", sb.feb[t], sb.ef[t], tab="fill", key=t, add=so, stride=R, mode=14)
+        seg("csc_eid", 0, sb.ef[t], in1=bufs["csc_dst"].data_ptr(), tab="fill", key=t, mode=12)
+        if F % 4 == 0 and bufs["feat"].data_ptr() % 16 == 0:
+            seg("feat", sb.fb[t] * F // 4, sb.nf[t] * F // 4, mode=5, esize=16)       # (in1 null: zero rows)
+        else:
+            seg("feat", sb.fb[t] * F, sb.nf[t] * F, add=0, mode=2)
+        seg("scales", sb.fb[t], sb.nf[t], add=0, mode=2)                               # the scale of an all-zero row: absmax bits 0
+        seg("node_seg", hd.type_off[t], hd.counts[t], add=hd.seg_off[t], stride=R)
+        seg("inv_rd", hd.type_off[t], hd.counts[t], add=_float_bits([(1.0 / R) if R > 0 else 0.0])[0], mode=2)
+    seg("rowptr", lay.S, 1, add=lay.E)
+    seg("colptr", lay.N, 1, add=lay.E)
+    seg("node_seg", lay.N, 1, add=lay.S)
+    seg("labels", 0, G, tab="labels", mode=4, esize=8)
+    for name in ("readout_ptr", "chunk_row", "chunk_seg", "seg_chunk", "seg_counts", "seg_inv_counts", "seg_nonempty"):
+        seg(name, 0, bufs[name].numel(), tab=name, mode=3)
+    for s_, (a, b_) in enumerate(sb.ranges):
+        seg("row_seg", a, b_ - a, add=s_)
+    blocks = 0
+    tab0 = len(segs) * 10
+    for s_ in segs:
+        if s_[3] >= 0:
+            s_[3] += tab0
+        s_[9] = blocks
+        blocks += (s_[7] + 1023) // 1024
+    return sb, [w for s_ in segs for w in s_] + tabs, len(segs), blocks
+
+
+def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]],
+                    scales: Optional[Sequence[Sequence[torch.Tensor]]] = None, device="cpu") -> Dict[str, object]:
+    """``slot_fill`` as tensor operations: the CPU path and the kernel's test oracle (the GPU test compares the two bit for bit).  The real
+    slides' parts are offset copies of their pieces; the filler's parts come from SORTING its explicit edge list (``filler_graph``'s
+    ``j -> (j mod nf[s], j mod nf[t])``), not from the kernel's closed forms.  Returns the tables by the names of ``SlotLayout.buffers``, plus
+    ``"batch"``: the ``SlotBatch``."""
+    dev = torch.device(device)
+    sb = SlotBatch(lay, pieces)
+    T, hd, B, G, F = lay.T, lay.hd, sb.B, lay.graphs, lay.in_dim
+    N, S, E = lay.N, lay.S, lay.E
+    i64 = lambda n: torch.zeros(int(n), dtype=torch.int64, device=dev)
+    ar = lambda n: torch.arange(int(n), dtype=torch.int64, device=dev)
+    on = lambda x: x.to(dev)
+    rowptr, colptr = i64(S + 1), i64(N + 1)
+    src, csc_eid, csc_dst = i64(E), i64(E), i64(E)
+    sim = torch.zeros(E, dtype=torch.float32, device=dev)
+    feat = torch.zeros((N, F), dtype=torch.float32, device=dev)
+    scl = torch.zeros((N, 1), dtype=torch.int32, device=dev)
+    node_tab = torch.tensor(sb.node_tab, dtype=torch.int64, device=dev)
+    edge_tab = torch.tensor(sb.edge_tab, dtype=torch.int64, device=dev)
+    for t in range(T):
+        R = hd.R[t]
+        for b, pc in enumerate(pieces):
+            row, eo, co = sb.node_tab[b * T + t], sb.eoff[(t, b)], sb.coff[(t, b)]
+            so = hd.seg_off[t] + sb.pre[b][t] * R
+            nc, ne, ncc = pc.counts[t], pc.ecount[t], pc.ccount[t]
+            rowptr[so:so + nc * R] = on(pc.rp[t]) + eo
+            colptr[row:row + nc] = on(pc.cp[t]) + co
+            src[eo:eo + ne] = on(pc.src_l[t]) + node_tab[b * T + on(pc.src_t[t])]
+            sim[eo:eo + ne] = on(pc.sim[t])
+            ent = b * T + on(pc.ent_t[t])
+            csc_eid[co:co + ncc] = on(pc.eid_l[t]) + edge_tab[ent]
+            csc_dst[co:co + ncc] = on(pc.dst_l[t]) + node_tab[ent]
+            if nc:
+                feat[row:row + nc] = on(feats[b][t])
+                if scales is not None:
+                    scl[row:row + nc] = on(scales[b][t])
+    # the filler: its edges in CSR order (destination type, destination, j), then a stable sort by source for the CSC side
+    f_eid, f_src, f_dst = [i64(0)], [i64(0)], [i64(0)]
+    for t in range(T):
+        R, nf, ef = hd.R[t], sb.nf[t], sb.ef[t]
+        deg = i64(nf * R)
+        if ef:
+            s_ = lay.src_type[t]
+            j = ar(ef)
+            d, u = j % nf, j % sb.nf[s_]
+            o = torch.sort(d, stable=True).indices
+            src[sb.feb[t]:sb.feb[t] + ef] = sb.fb[s_] + u[o]
+            f_eid.append(sb.feb[t] + ar(ef)); f_src.append(sb.fb[s_] + u[o]); f_dst.append(sb.fb[t] + d[o])
+            deg[::R] = _count(d, nf)
+        so = hd.seg_off[t] + sb.n[t] * R
+        rowptr[so:so + nf * R] = sb.feb[t] + torch.cumsum(deg, 0) - deg
+    rowptr[S] = E
+    f_eid, f_src, f_dst = torch.cat(f_eid), torch.cat(f_src), torch.cat(f_dst)
+    o = torch.sort(f_src, stable=True).indices
+    f_eid, f_src, f_dst = f_eid[o], f_src[o], f_dst[o]
+    for s_ in range(T):
+        m = (f_src >= sb.fb[s_]) & (f_src < sb.fb[s_] + sb.nf[s_])
+        k = int(m.sum())
+        csc_eid[sb.cfb[s_]:sb.cfb[s_] + k] = f_eid[m]
+        csc_dst[sb.cfb[s_]:sb.cfb[s_] + k] = f_dst[m]
+        od = _count(f_src[m] - sb.fb[s_], sb.nf[s_])
+        colptr[sb.fb[s_]:sb.fb[s_] + sb.nf[s_]] = sb.cfb[s_] + torch.cumsum(od, 0) - od
+    colptr[N] = E
+    frame = plan_frame(hd, dev, sb.counts)            # node_seg, inv_rd, readout_ptr of the padded batch's node counts
+    H = sum(pc.num_heavy for pc in pieces)
+    tabs = node_tab
+    cat = lambda xs: torch.cat([on(x) for x in xs]) if xs else i64(0)
+    bkey = lambda sizes: torch.repeat_interleave(ar(B) * T, torch.tensor(sizes, dtype=torch.int64, device=dev))
+    heavy = cat([pc.heavy_l for pc in pieces]) + tabs[bkey([int(pc.heavy_l.numel()) for pc in pieces]) + cat([pc.heavy_t for pc in pieces])]
+    light = cat([pc.light_l for pc in pieces]) + tabs[bkey([int(pc.light_l.numel()) for pc in pieces]) + cat([pc.light_t for pc in pieces])]
+    osrc = cat([pc.so_l for pc in pieces]) + tabs[bkey([int(pc.so_l.numel()) for pc in pieces]) + cat([pc.so_t for pc in pieces])]
+    fill_nodes = torch.cat([sb.fb[t] + ar(sb.nf[t]) for t in range(T)])
+    i32 = lambda x: x.to(torch.int32)
+    rp32 = i32(rowptr)
+    edge_seg = torch.repeat_interleave(torch.arange(S, dtype=torch.int32, device=dev), (rowptr[1:] - rowptr[:-1]), output_size=E)
+    row_seg = torch.repeat_interleave(torch.arange(lay.num_segs, dtype=torch.int32, device=dev),
+                                      torch.tensor([b_ - a for a, b_ in sb.ranges], dtype=torch.int64, device=dev), output_size=N)
+    col = lambda xs: torch.tensor(xs, dtype=torch.float32, device=dev).view(-1, 1)
+    t32 = lambda xs: torch.tensor(xs, dtype=torch.int32, device=dev)
+    return {"batch": sb, "rowptr": rp32, "colptr": i32(colptr), "node_seg": frame.node_seg, "src": i32(src), "csc_eid": i32(csc_eid),
+            "csc_dst": i32(csc_dst), "order_dst": i32(torch.cat([heavy, light, fill_nodes])), "order_src": i32(torch.cat([osrc, fill_nodes])),
+            "sim": sim, "inv_rd": frame.inv_rd, "readout_ptr": t32(sb.readout_ptr),
+            "labels": torch.tensor([int(y) for y in labels] + [-100] * (G - B), dtype=torch.int64, device=dev), "feat": feat, "scales": scl,
+            "edge_seg": edge_seg, "row_seg": row_seg, "chunk_row": t32(sb.chunk_row), "chunk_seg": t32(sb.chunk_seg), "seg_chunk": t32(sb.seg_chunk),
+            "seg_counts": col(sb.seg_counts), "seg_inv_counts": col(sb.seg_inv_counts), "seg_nonempty": col(sb.seg_nonempty)}
+
+
+def slot_plan(lay: SlotLayout, bufs: Dict[str, torch.Tensor], locality: bool = False) -> GraphPlan:
+    """The kernel plan whose tables ARE the slot's static buffers.  ``num_heavy = 0``: every destination takes the light path (correct for any
+    degree); a hub prefix of fixed size is not part of a slot."""
+    hd = lay.hd
+    p = GraphPlan()
+    p.device = bufs["rowptr"].device
+    p.type_off, p.num_nodes, p.rel_slots, p.num_segs, p.rel_rows = hd.type_off, hd.N, hd.R, hd.S, list(hd.rel_rows)
+    p.num_edges, p.num_src_rows, p.batch_size = lay.E, hd.N, lay.graphs
+    for k in ("rowptr", "colptr", "node_seg", "src", "csc_eid", "csc_dst", "order_dst", "order_src", "inv_rd", "readout_ptr"):
+        setattr(p, k, bufs[k])
+    p.num_heavy, p.locality = 0, bool(locality)
+    p.heavy_degree = HEAVY_DEGREE_LOCALITY if locality else HEAVY_DEGREE
+    p.__dict__["_edge_seg"] = bufs["edge_seg"]       # (ops._edge_segments: derived from rowptr once per plan - here refreshed by every fill)
+    return p
+
+
 def _build_plan(g: HeteroGraph, per_relation_src: bool = False) -> GraphPlan:
     dev = g.device
     hd = PlanHeader(g.ntypes, g.canonical_etypes, [g.num_nodes(t) for t in g.ntypes])

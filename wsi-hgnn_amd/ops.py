@@ -381,6 +381,22 @@ def remember_constant_cols(x: torch.Tensor, rows: Sequence[Tuple[int, int]]) -> 
         attach_col_stats(x, ColStats(torch.stack(bits_rows), None, ranges))
 
 
+def refresh_constant_cols(x: torch.Tensor) -> None:
+    """``x`` was rewritten BEHIND its version counter (a batch slot's feature table, ``graph.slot_fill``): recompute the column statistics
+    ``remember_constant_cols`` attached, into the same tables - a step recorded into a hipGraph reads them by address.  Nothing to do when
+    none are attached."""
+    st = _annotation(x, "_wsi_col_stats")
+    if st is None or st.sums is not None:
+        return
+    lib = N.load()
+    width = x.shape[1]
+    for (a, b), (p0, _) in st.ranges.items():
+        nbytes = lib.wsi_col_absmax_workspace_bytes(b - a, width)
+        ws = torch.empty(max(nbytes // 4, 4), dtype=torch.int32, device=x.device)
+        N.check(lib.wsi_col_absmax(N.ptr(x, a * x.stride(0) * 4), x.stride(0), b - a, width, N.ptr(st.bits, p0 * st.bits.shape[1] * 4), N.ptr(ws), nbytes,
+                                   N.stream()), "wsi_col_absmax")
+
+
 # ------------------------------------------------------------------------------------------------
 # weights packed once per optimizer step (wsi_gemm_group_t.b_packed)
 # ------------------------------------------------------------------------------------------------

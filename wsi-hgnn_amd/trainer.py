@@ -158,3 +158,124 @@ class CapturedStep:
     def pool(self):
         """The memory pool of this capture, for further ``CapturedStep(..., pool=...)`` over other resident batches."""
         return self.cuda_graph.pool()
+
+
+class CapturedSlotStep:
+    """One captured training step per batch SLOT (``data.BatchSlot``), replayed over NEW slides every step: the regime the reference trains in
+    (one or two slides per step, ``trainer/train_gnn.py:48-79``), where the host takes longer to issue the step's launches than the GPU to run them.
+    ``CapturedStep`` bakes a resident batch into its graph; a slot's tables have one shape for every batch that fits, so one capture serves them
+    all.  Per step the host uploads one descriptor table, launches one fill kernel into the slot's static tables and replays.
+
+    ``slots``: one ``BatchSlot`` or several of different capacity over the same loader (small slides then do not pay for the largest);
+    ``step(idxs)`` takes the smallest slot (fewest node rows) that fits.  A batch no slot fits runs eagerly through the loader's ordinary
+    assembly.  The captures share one memory pool.  As with ``CapturedStep`` the ``warmup`` steps before each capture ARE optimisation steps -
+    here on ``warmup_batches[i]`` for slot i (default: the slot's first fitting batch of one slide) - the optimizer must be capturable, and
+    train-mode dropout must be the HEAT layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4 with a sum / mean /
+    max readout: HGT builds its per-relation-source plan from the batch's COO on the host, and the attention readout reads host-side node
+    counts - both are refused."""
+
+    def __init__(self, gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_fcn, slots, warmup: int = 1, warmup_batches=None):
+        from .data import BatchSlot
+        from .models.heat_net import HEATTrunk
+        from .pooling import GlobalAttentionPooling
+        self.slots = [slots] if isinstance(slots, BatchSlot) else list(slots)
+        if not self.slots:
+            raise ValueError("CapturedSlotStep: no slot")
+        if not isinstance(gnn, HEATTrunk):
+            raise RuntimeError(f"CapturedSlotStep: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4 only (HGT derives a per-relation-source plan "
+                               "from the batch's COO on the host for every new batch, which a replay cannot redo); step it eagerly")
+        if isinstance(gnn.pools[0], GlobalAttentionPooling):
+            raise RuntimeError("CapturedSlotStep: the attention readout ('att') expands host-side node counts per batch; use a sum / mean / max readout "
+                               "or step eagerly")
+        self.loader = self.slots[0].loader
+        if any(s.loader is not self.loader for s in self.slots):
+            raise ValueError("CapturedSlotStep: all slots must be fed by one loader")
+        dev = self.loader.device
+        if dev.type != "cuda":
+            raise RuntimeError("CapturedSlotStep: the slots must live on the GPU")
+        for group in optimizer.param_groups:
+            if not group.get("capturable", False):
+                raise RuntimeError("CapturedSlotStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step count has "
+                                   "to live on the device, a host count would be frozen into the graph")
+        self.seed_base = None
+        if gnn.training and any(isinstance(mod, torch.nn.Dropout) and mod.p > 0.0 for mod in gnn.modules()):
+            from .models.heat_layer import HEATLayer
+            owners = [m_ for m_ in gnn.modules() if any(isinstance(c, torch.nn.Dropout) and c.p > 0.0 for c in m_.children())]
+            if not all(isinstance(m_, HEATLayer) and getattr(m_, "counter_dropout", False) for m_ in owners):
+                raise RuntimeError("CapturedSlotStep: the model draws dropout masks outside the HEAT layers' counter-based draw (train mode, p > 0); their "
+                                   "generator state is a host value a capture would freeze - every replay would drop the same entries.  Step such a "
+                                   "model eagerly")
+            self.seed_base = torch.empty((), dtype=torch.int64).random_(-(1 << 31), 1 << 31).to(torch.int32).reshape(1).to(dev)
+        self.gnn, self.optimizer, self.loss_fcn = gnn, optimizer, loss_fcn
+        order = sorted(range(len(self.slots)), key=lambda i: self.slots[i].layout.N)          # smallest first: what step() tries in turn
+        self.slots = [self.slots[i] for i in order]
+        if warmup_batches is not None:
+            warmup_batches = [list(warmup_batches[i]) for i in order]
+        optimizer.zero_grad(set_to_none=True)
+        self.params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
+        self.steps_taken, self.replays, self.eager_steps = 0, 0, 0
+        self.graphs, self.outputs = [], []
+        pool = None
+        for i, slot in enumerate(self.slots):
+            first = warmup_batches[i] if warmup_batches is not None else next(([j] for j in sorted(slot.members) if slot.fits([j])), None)
+            if first is None:
+                raise ValueError(f"CapturedSlotStep: no slide of the data set fits slot {i}")
+            slot.load(first)
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):                      # (plans, caches and allocator pools settle before the capture; these ARE steps)
+                for _ in range(max(1, warmup)):
+                    self._eager(slot.graph, slot.labels)
+                    self.steps_taken += 1
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            cg = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
+                    out = self._eager(slot.graph, slot.labels)
+            except Exception as exc:
+                raise RuntimeError("CapturedSlotStep: the step could not be captured into a hipGraph (is a tensor of an earlier eager step's autograd "
+                                   "graph - a previous loss or logits - still alive in the caller?); run the step eagerly instead") from exc
+            pool = cg.pool()
+            self.graphs.append(cg)
+            self.outputs.append(out)
+
+    def _eager(self, graph: HeteroGraph, label: torch.Tensor):
+        from . import ops
+        self.optimizer.zero_grad(set_to_none=True)
+        with ops.dropout_seed_base(self.seed_base):
+            pred = self.gnn(graph)
+            loss = self.loss_fcn(pred, label)
+            grads = torch.autograd.grad(loss, self.params, allow_unused=True)
+        for p, g in zip(self.params, grads):
+            p.grad = g
+        self.optimizer.step()
+        if self.seed_base is not None:
+            ops.advance_dropout_seed_base(self.seed_base)
+        return loss.detach(), pred.detach()
+
+    def slot_for(self, idxs: Sequence[int]):
+        """Index of the smallest slot the batch fits, or None."""
+        for i, slot in enumerate(self.slots):
+            if slot.fits(idxs):
+                return i
+        return None
+
+    def step(self, idxs: Sequence[int]):
+        """One optimisation step on the loader's slides ``idxs``.  Returns ``(loss, logits[:len(idxs)])`` as device tensors; those of a replayed
+        step are overwritten by the next replay of the same slot."""
+        idxs = list(idxs)
+        i = self.slot_for(idxs)
+        self.steps_taken += 1
+        if i is None:                                          # fits no slot: the loader's ordinary batch, stepped eagerly
+            G, labels, ready = self.loader._assemble(idxs, 0)
+            if ready is not None:
+                torch.cuda.current_stream(self.loader.device).wait_event(ready)
+            self.eager_steps += 1
+            return self._eager(G, labels)
+        slot = self.slots[i]
+        slot.load(idxs)
+        self.graphs[i].replay()
+        self.replays += 1
+        loss, pred = self.outputs[i]
+        return loss, pred[:slot.num_real]
