@@ -15,10 +15,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "wsi-hgnn_amd")
 
 
-def test_library_exports_every_declared_symbol():
+def _native_built():
     import __graft_entry__
     __graft_entry__.build()
     from wsi_hgnn_amd import _native
+    return _native
+
+
+def _gcc(source, *flags, run=False, extra=None):
+    """Compile ``source`` (C, sees include/) with gcc; ``run``: link it, run it and return the integers it prints."""
+    import subprocess, tempfile
+    with tempfile.TemporaryDirectory() as td:
+        for name, text in {"t.c": source, **(extra or {})}.items():
+            open(os.path.join(td, name), "w").write(text)
+        cmd = ["gcc", "-I", td, "-I", os.path.join(ROOT, "include"), *flags, os.path.join(td, "t.c")]
+        if not run:
+            return subprocess.run(cmd + ["-fsyntax-only"], capture_output=True, text=True)
+        subprocess.check_call(cmd + ["-o", os.path.join(td, "t")])
+        return [int(x) for x in subprocess.check_output([os.path.join(td, "t")]).split()]
+
+
+def test_library_exports_every_declared_symbol():
+    _native = _native_built()
     header = open(os.path.join(ROOT, "include", "wsi_hgnn.h")).read()
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     declared = set(re.findall(r"\b(wsi_[a-z0-9_]+)\s*\(", header))
@@ -26,21 +44,128 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(_native.LIB_PATH)
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/wsi_hgnn.h but not exported"
-    assert declared == set(_native.EXPORTS), (declared ^ set(_native.EXPORTS))
+    assert declared == set(_native.EXPORTS), (declared ^ set(_native.EXPORTS))     # (two readings of one file: the C compiler's are below)
     assert _native.load().wsi_abi_version() == _native.WSI_ABI_VERSION
-    # struct layout agrees with the header: ask the C compiler
-    import subprocess, tempfile
-    for ctype, cname in ((_native.GemmGroup, "wsi_gemm_group_t"),):
+
+
+def test_struct_layouts_agree_with_the_header():
+    """Every struct the binding derives from include/wsi_hgnn.h (all five today; one added later is covered as it appears) against the C
+    compiler's sizeof / offsetof of the same header, and the public class names the host code uses."""
+    _native = _native_built()
+    assert {c: t.__name__ for c, t in _native.STRUCTS.items()} == {
+        "wsi_attn_pool_t": "AttnPool", "wsi_gemm_group_t": "GemmGroup", "wsi_adam_tensor_t": "AdamTensor",
+        "wsi_optim_tensor_t": "OptimTensor", "wsi_optim_hyper_t": "OptimHyper"}
+    assert [len(_native.STRUCTS[c]._fields_) for c in ("wsi_attn_pool_t", "wsi_gemm_group_t", "wsi_adam_tensor_t", "wsi_optim_tensor_t",
+                                                       "wsi_optim_hyper_t")] == [16, 43, 5, 8, 11]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "wsi_hgnn.h"\nint main(void){'
+    for cname, ctype in _native.STRUCTS.items():
+        assert getattr(_native, ctype.__name__) is ctype
+        src += 'printf("%%zu", sizeof(%s));' % cname + "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, f) for f, _ in ctype._fields_)
+        src += 'printf("\\n");'
+    nums = _gcc(src + "return 0;}", run=True)
+    for cname, ctype in _native.STRUCTS.items():
         fields = [f for f, _ in ctype._fields_]
-        src = '#include <stdio.h>\n#include <stddef.h>\n#include "wsi_hgnn.h"\nint main(void){printf("%%zu", sizeof(%s));' % cname + \
-              "".join('printf(" %%zu", offsetof(%s, %s));' % (cname, f) for f in fields) + "return 0;}"
-        with tempfile.TemporaryDirectory() as td:
-            c = os.path.join(td, "layout.c")
-            open(c, "w").write(src)
-            subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", os.path.join(td, "layout")])
-            nums = [int(x) for x in subprocess.check_output([os.path.join(td, "layout")]).split()]
-        assert nums[0] == ctypes.sizeof(ctype), cname
-        assert nums[1:] == [getattr(ctype, f).offset for f in fields], cname
+        mine, nums = nums[:1 + len(fields)], nums[1 + len(fields):]
+        assert mine[0] == ctypes.sizeof(ctype), cname
+        assert mine[1:] == [getattr(ctype, f).offset for f in fields], cname
+    assert not nums
+
+
+_C_SPELLING = {ctypes.c_void_p: "void*", ctypes.c_int64: "int64_t", ctypes.c_int32: "int32_t", ctypes.c_uint32: "uint32_t",
+               ctypes.c_float: "float", ctypes.c_double: "double", ctypes.c_int: "int", ctypes.c_char_p: "const char*", None: "void"}
+
+
+def _prototype_check(exports):
+    """One C file with, for every entry, a function-pointer variable whose type is spelled from the derived ctypes signature and which is
+    initialised with the address of the declared function: gcc refuses a difference in the number, the order, the class (integer / floating /
+    pointer) or the width of any argument or of the result.  C has no initialisation that forgives only WHAT a pointer points to, so the
+    file includes the header with every pointer type but ``const char*`` rewritten to ``void*`` (one substitution outside the preprocessor
+    lines; it can turn no scalar into a pointer and change no width) - which is all the binding claims of a pointer."""
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wsi_hgnn.h")).read(), flags=re.S)
+    erased = "\n".join(ln if ln.lstrip().startswith("#") else re.sub(r"(?:\bconst\s+)?\b(?!char\b)\w+(?:\s*\*(?:\s*const\b)?)+", "void* ", ln)
+                       for ln in header.split("\n"))
+    assert "float*" not in erased.replace(" ", "") and "const char*" in erased
+    src = '#include "erased.h"\n' + "".join("%s (*p_%s)(%s) = &%s;\n" % (_C_SPELLING[res], name, ", ".join(_C_SPELLING[a] for a in args) or "void", name)
+                                           for name, (res, args) in exports.items())
+    return _gcc(src, "-Werror=incompatible-pointer-types", "-Werror=int-conversion", extra={"erased.h": erased})
+
+
+def test_prototypes_agree_with_the_header():
+    """restype and argtypes of every entry of _native.EXPORTS against the C compiler's reading of the prototypes (see _prototype_check)."""
+    _native = _native_built()
+    assert len(_native.EXPORTS) >= 63
+    done = _prototype_check(_native.EXPORTS)
+    assert done.returncode == 0, done.stderr
+
+
+def test_prototype_check_sees_a_wrong_width_a_wrong_class_and_a_dropped_argument():
+    """The check above is not vacuous: an int64_t typed c_int32, a double typed c_float, a pointer typed as an integer and a dropped argument
+    are each refused, with the entry's name in gcc's message."""
+    _native = _native_built()
+    res, args = _native.EXPORTS["wsi_adam_step"]          # (tensors, int32 count, 5 doubles, int64 step, stream)
+    assert args[1] is ctypes.c_int32 and args[2] is ctypes.c_double and args[7] is ctypes.c_int64
+    swap = lambda i, t: args[:i] + [t] + args[i + 1:]
+    for bad in (swap(7, ctypes.c_int32), swap(2, ctypes.c_float), swap(0, ctypes.c_int64), args[:-1], swap(1, ctypes.c_int64)):
+        done = _prototype_check({"wsi_adam_step": (res, bad)})
+        assert done.returncode != 0 and "p_wsi_adam_step" in done.stderr, bad
+    assert _prototype_check({"wsi_adam_step": (ctypes.c_int64, args)}).returncode != 0
+    assert _prototype_check({"wsi_adam_step": (res, args)}).returncode == 0
+
+
+def test_constants_and_macro_restatements_agree_with_the_header():
+    """Every integer constant the binding derives, and the two function-like macros the host code restates by hand
+    (_native.gemm_absmax_parts, ops._attn_flags), against the values the C compiler gives the header's own macros."""
+    import types
+    _native = _native_built()
+    from wsi_hgnn_amd import ops
+    names = sorted(_native.CONSTANTS)
+    assert {"WSI_OK", "WSI_EINVAL", "WSI_ABI_VERSION", "WSI_EPI_GATED_SKIP", "WSI_GEMM_MAX_GROUPS", "WSI_OPTIM_ADAM", "WSI_ATTN_XCD_CONTIGUOUS"} <= set(names)
+    assert all(getattr(_native, n) == _native.CONSTANTS[n] for n in names)
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "wsi_hgnn.h")).read(), flags=re.S)
+    assert set(names) == set(re.findall(r"^#define\s+(WSI_\w+)[ \t]+\S", header, flags=re.M))           # none missed; function-like ones skipped
+    parts_n, hub_d = (1, 127, 128, 129, 512), (0, 128, 65535)
+    exprs = names + ["WSI_GEMM_ABSMAX_PARTS(%d)" % n for n in parts_n] + ["WSI_ATTN_XCD_CONTIGUOUS | WSI_ATTN_HUB_DEGREE(%d)" % d for d in hub_d] + \
+        ["WSI_ATTN_HUB_DEGREE(%d)" % d for d in hub_d]
+    nums = _gcc('#include <stdio.h>\n#include "wsi_hgnn.h"\nint main(void){' + "".join('printf("%%lld\\n", (long long)(%s));' % e for e in exprs) + "return 0;}",
+                run=True)
+    assert len(nums) == len(exprs)
+    assert dict(zip(names, nums)) == _native.CONSTANTS
+    assert _native.WSI_EINVAL == -22 and _native.WSI_EPI_GATED_SKIP == 1 | 4 | 16 | 32
+    nums = nums[len(names):]
+    assert nums[:5] == [_native.gemm_absmax_parts(n) for n in parts_n]
+    plan = lambda d, loc: types.SimpleNamespace(locality=loc, heavy_degree=d)
+    assert nums[5:8] == [ops._attn_flags(plan(d, True)) for d in hub_d]
+    assert nums[8:] == [ops._attn_flags(plan(d, False)) for d in hub_d]
+
+
+_BAD_HEADERS = {"an array member": ("int32_t reserved;", "int32_t reserved[2];"),
+                "a type outside the table": ("int64_t  ldm;", "size_t  ldm;"),
+                "a function pointer": ("void*           b_packed;", "void (*b_packed)(int);"),
+                "a nested struct": ("int32_t reserved;", "struct { int a; } reserved;"),
+                "two pointer declarators": ("float* r_out; int64_t ldr;", "float *r_out, *r2; int64_t ldr;"),
+                "a parameter type outside the table": ("float* y, int64_t n, void* stream);", "float* y, long n, void* stream);"),
+                "a return type outside the table": ("int64_t wsi_gemm_packed_b_bytes", "long wsi_gemm_packed_b_bytes"),
+                "a division in a constant": ("#define WSI_RED_MAX  2", "#define WSI_RED_MAX  (4 / 2)"),
+                "an unknown name in a constant": ("#define WSI_RED_MAX  2", "#define WSI_RED_MAX  WSI_RED_MIN"),
+                "an enum": ("#define WSI_RED_MAX  2", "enum wsi_red { WSI_RED_MAX = 2 };"),
+                "an unknown directive": ("#define WSI_RED_MAX  2", "#pragma pack(1)")}
+
+
+@pytest.mark.parametrize("what", sorted(_BAD_HEADERS))
+def test_header_parser_refuses_what_it_does_not_know(what, tmp_path):
+    """The parser of the binding raises on anything outside the header's idiom and names the line (a nested struct: the line its typedef starts on)."""
+    _native = _native_built()
+    old, new = _BAD_HEADERS[what]
+    header = open(_native.HEADER_PATH).read()
+    assert header.count(old) == 1
+    line = header[:header.index(old)].count("\n") + 1
+    if what == "a nested struct":
+        line = header[:header.index("typedef struct wsi_gemm_group {")].count("\n") + 1
+    (tmp_path / "bad.h").write_text(header.replace(old, new))
+    with pytest.raises(RuntimeError, match=r"bad\.h:%d: " % line):
+        _native._parse_header(str(tmp_path / "bad.h"))
+    (tmp_path / "good.h").write_text(header)
+    assert _native._parse_header(str(tmp_path / "good.h"))[0] == _native.CONSTANTS
 
 
 def test_product_never_imports_the_oracle():

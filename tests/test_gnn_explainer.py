@@ -225,7 +225,7 @@ def test_abi_26_in_header_library_and_binding():
     assert int(re.search(r"#define WSI_ABI_VERSION (\d+)", header).group(1)) == 26
     assert lib.wsi_abi_version() == 26 == _native.WSI_ABI_VERSION
     for name in ("wsi_gat_attn_fwd_scaled", "wsi_gat_attn_bwd_scaled", "wsi_sddmm_dot"):
-        assert name in _native.EXPORTS and re.search(r"\b%s\(" % name, header)
+        assert hasattr(lib, name) and re.search(r"\b%s\(" % name, header)
 
 
 def test_capi_scaled_gat_rejects_bad_arguments():

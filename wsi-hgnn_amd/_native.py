@@ -7,194 +7,104 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_void_p
+import re
+from ctypes import c_char_p, c_float, c_int32, c_int64, c_void_p
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libwsi_hgnn.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "wsi_hgnn.h")
 
-WSI_GEMM_NT, WSI_GEMM_NN, WSI_GEMM_TN = 0, 1, 2
-WSI_EPI_BIAS, WSI_EPI_ACCUMULATE, WSI_EPI_SCALE_GATE, WSI_EPI_GELU, WSI_EPI_ADD_R, WSI_EPI_R_1MG, WSI_EPI_MUL_M, WSI_EPI_BACKGROUND, WSI_EPI_DROPOUT = 1, 2, 4, 8, 16, 32, 64, 128, 256
-WSI_EPI_GATED_SKIP = WSI_EPI_BIAS | WSI_EPI_SCALE_GATE | WSI_EPI_ADD_R | WSI_EPI_R_1MG
-WSI_RED_SUM, WSI_RED_MEAN, WSI_RED_MAX = 0, 1, 2
-WSI_GEMM_MAX_GROUPS = 24
-WSI_ABI_VERSION = 26
-WSI_GEMM_FP32, WSI_GEMM_BF16X6, WSI_GEMM_FP16X3, WSI_GEMM_AUTO = 0, 1, 2, 3
-WSI_ATTN_XCD_CONTIGUOUS = 1
-
-
-class AttnPool(ctypes.Structure):
-    """wsi_attn_pool_t (include/wsi_hgnn.h)."""
-    _fields_ = [("row_seg", ctypes.c_void_p), ("segs_per_type", ctypes.c_int32), ("n_types", ctypes.c_int32),
-                ("y", ctypes.c_void_p), ("g_row", ctypes.c_void_p), ("omg", ctypes.c_void_p),
-                ("r_out", ctypes.c_void_p), ("ldr", ctypes.c_int64), ("ctab", ctypes.c_void_p), ("ctab_ready", ctypes.c_int32),
-                ("h", ctypes.c_void_p), ("ldh", ctypes.c_int64), ("beta", ctypes.c_void_p),
-                ("gtab", ctypes.c_void_p), ("edge_seg", ctypes.c_void_p), ("seg_dst", ctypes.c_void_p)]
+# ------------------------------------------------------------------------------------------------
+# The binding is DERIVED from include/wsi_hgnn.h at import: every object-like `#define WSI_* <integer expression>` becomes a module
+# attribute, every `typedef struct ... { ... } wsi_x_y_t;` a ctypes.Structure named XY (AttnPool, AdamTensor, OptimTensor, OptimHyper,
+# GemmGroup), every prototype an entry of EXPORTS (restype, argtypes).  Any pointer is a c_void_p.  The parser knows the header's own
+# idiom and nothing else: whatever it does not understand raises here, with the header's line number - it never guesses.
+# tests/test_boundary.py holds every derived layout, signature and value against the C compiler's reading of the same file.
+# ------------------------------------------------------------------------------------------------
+_SCALARS = {"int": ctypes.c_int, "int32_t": c_int32, "int64_t": c_int64, "uint32_t": ctypes.c_uint32, "float": c_float,
+            "double": ctypes.c_double}
+_RETURNS = {"int": ctypes.c_int, "int32_t": c_int32, "int64_t": c_int64, "void": None, "const char*": c_char_p}
+_DECL = re.compile(r"\s*(?:const\s+)?(\w+)((?:\s*\*(?:\s*const\b)?)*)\s*(\w+(?:\s*,\s*\w+)*)\s*")
 
 
-class AdamTensor(ctypes.Structure):
-    """wsi_adam_tensor_t (include/wsi_hgnn.h)."""
-    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("n", ctypes.c_int64)]
+def _parse_header(path: str):
+    lines_only = lambda m: "\n" * m.group().count("\n")        # what is taken out leaves its newlines: an offset still names its line
+    text = re.sub(r"/\*.*?\*/", lines_only, open(path).read(), flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus\n.*?#endif", lines_only, text, flags=re.S)          # the extern "C" brackets
+    constants, structs, exports, pointees = {}, {}, {}, {"void", "char", *_SCALARS}
+
+    def fail(pos: int, what: str):
+        raise RuntimeError(f"{path}:{text.count(chr(10), 0, pos) + 1}: the binding cannot read {' '.join(what.split())[:100]!r} "
+                           "(wsi_hgnn_amd/_native.py understands the header's own idiom only and does not guess)")
+
+    def pieces(lo: int, hi: int, sep: str):
+        """(offset, text) of the non-blank pieces of text[lo:hi] between ``sep``s."""
+        for m in re.compile(f"[^{sep}]*[^{sep}\\s][^{sep}]*").finditer(text, lo, hi):
+            yield m.start() + len(m.group()) - len(m.group().lstrip()), m.group()
+
+    def declaration(pos: int, decl: str, many: bool):
+        """``[const] T [* [const]]... name[, name...]`` -> (ctype, names): T from _SCALARS, any pointer to a known type a c_void_p."""
+        m = _DECL.fullmatch(decl)
+        names = re.split(r"\s*,\s*", m.group(3)) if m else []
+        if not m or m.group(1) not in (pointees if m.group(2) else _SCALARS) or (len(names) > 1 and (m.group(2) or not many)):
+            fail(pos, decl)
+        return (c_void_p if m.group(2) else _SCALARS[m.group(1)]), names
+
+    def directive(m):
+        d = re.fullmatch(r"\s*#define\s+(WSI_\w+)(\(.*?\))?(.*)", m.group())
+        if d and not d.group(2) and d.group(3).strip():         # object-like, with a value (function-like macros and the include guard: skipped)
+            try:                                                # earlier constants under operators that mean the same in C and in Python
+                ok = re.fullmatch(r"[\w\s()|&<+*-]+", d.group(3)) and eval(d.group(3), {"__builtins__": {}}, dict(constants))
+            except Exception:
+                ok = None
+            if type(ok) is not int:
+                fail(m.start(), m.group())
+            constants[d.group(1)] = ok
+        elif not d and not re.match(r"\s*#(ifndef|include|endif)\b", m.group()):
+            fail(m.start(), m.group())
+        return ""
+
+    def opaque(m):
+        pointees.add(m.group(1))
+        return lines_only(m)
+
+    def struct(m):
+        name = re.fullmatch(r"wsi_(\w+)_t", m.group(2)) or fail(m.start(2), m.group(2))
+        if not m.group(1).rstrip().endswith(";"):
+            fail(m.end(1), m.group(1)[-40:])
+        fields = [(n, ctype) for pos, decl in pieces(m.start(1), m.end(1), ";") for ctype, names in [declaration(pos, decl, True)] for n in names]
+        structs[m.group(2)] = type(name.group(1).title().replace("_", ""), (ctypes.Structure,),
+                                   {"_fields_": fields, "__doc__": f"{m.group(2)} (include/wsi_hgnn.h)."})
+        pointees.add(m.group(2))
+        return lines_only(m)
+
+    text = re.sub(r"^[ \t]*#.*$", directive, text, flags=re.M)
+    text = re.sub(r"\btypedef\s+struct\s+\w+\s+(\w+)\s*;", opaque, text)
+    text = re.sub(r"\btypedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    if text.rstrip()[-1:] not in ("", ";"):
+        fail(len(text.rstrip()), text.rstrip()[-40:])
+    for pos, stmt in pieces(0, len(text), ";"):                 # whatever is left must be prototypes
+        m = re.fullmatch(r"\s*(const\s+char\s*\*|\w+)\s+(wsi_\w+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        ret = m and re.sub(r"\s+", " ", m.group(1)).replace(" *", "*")
+        if ret not in _RETURNS or not m.group(3).strip():
+            fail(pos, stmt)
+        lo = pos - (len(stmt) - len(stmt.lstrip()))
+        exports[m.group(2)] = (_RETURNS[ret], [] if m.group(3).strip() == "void" else
+                               [declaration(p, decl, False)[0] for p, decl in pieces(lo + m.start(3), lo + m.end(3), ",")])
+    return constants, structs, exports
 
 
-class OptimTensor(ctypes.Structure):
-    """wsi_optim_tensor_t (include/wsi_hgnn.h)."""
-    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("s0", ctypes.c_void_p), ("s1", ctypes.c_void_p),
-                ("step", ctypes.c_void_p), ("ticket", ctypes.c_void_p), ("n", ctypes.c_int64), ("flags", ctypes.c_int32)]
-
-
-class OptimHyper(ctypes.Structure):
-    """wsi_optim_hyper_t (include/wsi_hgnn.h)."""
-    _fields_ = [(f, ctypes.c_double) for f in ("lr", "weight_decay", "momentum", "dampening", "nesterov", "lr_decay", "eps", "rho",
-                                                "beta1", "beta2", "host_step")]
-
-
-WSI_OPTIM_SGD, WSI_OPTIM_ADAGRAD, WSI_OPTIM_ADADELTA, WSI_OPTIM_ADAM = 0, 1, 2, 3
-WSI_OPTIM_FIRST = 1
-
-
-class GemmGroup(ctypes.Structure):
-    """struct wsi_gemm_group (include/wsi_hgnn.h)."""
-    _fields_ = [
-        ("A", c_void_p), ("B", c_void_p), ("C", c_void_p),
-        ("bias", c_void_p), ("R", c_void_p), ("gate", c_void_p),
-        ("B1", c_void_p), ("B2", c_void_p),
-        ("lda", c_int64), ("ldb", c_int64), ("ldc", c_int64), ("ldr", c_int64),
-        ("M", c_int32), ("N", c_int32), ("K", c_int32), ("b_chunk", c_int32),
-        ("Mm", c_void_p), ("ldm", c_int64),
-        ("colsum_out", c_void_p),
-        ("a_absmax", c_void_p), ("c_absmax", c_void_p),
-        ("a_absmax_parts", c_int32), ("c_absmax_parts", c_int32), ("c_absmax_first", c_int32), ("reserved", c_int32),
-        ("drop_seed", ctypes.c_uint32), ("drop_threshold", ctypes.c_uint32), ("drop_scale", c_float),
-        ("drop_row0", c_int32), ("drop_cols", c_int32), ("drop_col0", c_int32),
-        ("drop_seed_base", c_void_p),
-        ("c_colmax", c_void_p), ("c_colsum", c_void_p), ("c_col_ld", c_int64),
-        ("a_colmax", c_void_p), ("a_colsum", c_void_p), ("b_colmax", c_void_p),
-        ("a_col_ld", c_int64), ("b_col_ld", c_int64), ("a_col_parts", c_int32), ("b_col_parts", c_int32),
-        ("b_packed", c_void_p),
-    ]
+CONSTANTS, STRUCTS, EXPORTS = _parse_header(HEADER_PATH)
+globals().update(CONSTANTS)
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})
 
 
 def gemm_absmax_parts(n_cols: int) -> int:
     """WSI_GEMM_ABSMAX_PARTS: slots per row a group of ``n_cols`` output columns writes into c_absmax."""
     return 2 * ((int(n_cols) + 127) // 128)
 
-
-EXPORTS = {
-    "wsi_abi_version": (ctypes.c_int, []),
-    "wsi_last_error": (c_char_p, []),
-    "wsi_heat_attn_fwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                         c_int32, c_int32, c_int32,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                         c_void_p, c_void_p,
-                                         c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_heat_attn_scores_fwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
-                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
-                                                c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_heat_pool_gtab": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
-                                          c_int32, c_int32, c_void_p, c_void_p]),
-    "wsi_heat_pool_coeff": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
-    "wsi_heat_attn_bwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                         c_int32, c_int32, c_int32, c_int32, c_int32,
-                                         c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_int32, c_void_p, c_int32,
-                                         c_void_p, c_void_p,
-                                         c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_context_create": (ctypes.c_int, [POINTER(c_void_p)]),
-    "wsi_context_destroy": (None, [c_void_p]),
-    "wsi_gemm_workspace_bytes": (c_int64, [c_int32, c_int32, POINTER(GemmGroup), c_int32]),
-    "wsi_gemm_kernel_precision": (c_int32, [c_int32, c_int32, POINTER(GemmGroup), c_int32]),
-    "wsi_row_absmax": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
-    "wsi_gemm_grouped": (ctypes.c_int, [c_int32, c_int32, c_int32, POINTER(GemmGroup), c_int32, c_void_p, c_int64, c_void_p]),
-    "wsi_gemm_writes_colstats": (c_int32, [c_int32, c_int32, POINTER(GemmGroup), c_int32]),
-    "wsi_gemm_packed_b_bytes": (c_int64, [c_int32, c_int32]),
-    "wsi_gemm_pack_b": (ctypes.c_int, [c_int32, POINTER(GemmGroup), c_int32, c_void_p]),
-    "wsi_col_stats_parts": (c_int32, [c_int32]),
-    "wsi_col_stats": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
-    "wsi_col_absmax_workspace_bytes": (c_int64, [c_int32, c_int32]),
-    "wsi_col_absmax": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
-    "wsi_segment_reduce_fwd": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32,
-                                              c_void_p, c_int32, c_void_p, c_int32,
-                                              c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "wsi_segment_dot_diff": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32,
-                                            c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-    "wsi_segment_weighted_sums": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32,
-                                                 c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-    "wsi_gate_grad": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32,
-                                     c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
-    "wsi_pool_factors": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32,
-                                        c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_pool_tmean": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_pool_bwd_prep": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
-                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_pool_bwd_bias": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_gemm_small_pair": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
-    "wsi_plan_assemble": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p]),
-    "wsi_slot_fill": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p]),
-    "wsi_cross_entropy": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_adam_step": (ctypes.c_int, [c_void_p, c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                     c_int64, c_void_p]),
-    "wsi_optim_step": (ctypes.c_int, [c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
-    "wsi_layernorm_fwd": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_int64, c_void_p, c_void_p]),
-    "wsi_layernorm_bwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "wsi_dropout_apply": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                         ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_float, c_void_p]),
-    "wsi_gelu_fwd": (ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    "wsi_gelu_bwd": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "wsi_spmm_sum": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                    c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    "wsi_sddmm_dot": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_int64, c_void_p, c_void_p]),
-    "wsi_row_sqnorm": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
-    "wsi_knn_select": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
-    "wsi_pair_stats": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32,
-                                      c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_csr_gather_max_fwd": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "wsi_csr_gather_max_bwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_int64, c_void_p]),
-    "wsi_asap_attend_fwd": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_float,
-                                           c_void_p, c_void_p, c_int64, c_void_p]),
-    "wsi_asap_attend_bwd": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    "wsi_gat_scores": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_gat_attn_fwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float,
-                                        ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_float, c_void_p, c_int32, c_float,
-                                        c_void_p, c_int64, c_void_p, c_void_p]),
-    "wsi_gat_attn_bwd_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
-    "wsi_gat_attn_bwd": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                        c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_float, ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_float, c_int32, c_float,
-                                        c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_gat_attn_fwd_scaled": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float,
-                                               ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_float, c_void_p, c_int32, c_float, c_void_p,
-                                               c_void_p, c_int64, c_void_p, c_void_p]),
-    "wsi_gat_attn_bwd_scaled": (ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                               c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                               c_void_p, c_void_p, c_float, ctypes.c_uint32, c_void_p, ctypes.c_uint32, c_float, c_int32, c_float,
-                                               c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_graph_topk": (ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_stas": (ctypes.c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_augment_nodes": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_augment_edges": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_augment_keys": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
-    "wsi_gather_rows_masked": (ctypes.c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32,
-                                              ctypes.c_uint32, ctypes.c_uint32, c_void_p]),
-    "wsi_loo_edges": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wsi_loo_rows": (ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
-    "wsi_segment_reduce_bwd": (ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32,
-                                              c_void_p, c_void_p, c_int32, c_void_p, c_int32,
-                                              c_void_p, c_void_p, c_int64, c_void_p]),
-}
 
 _lib = None
 _ablate = False

@@ -2204,72 +2204,44 @@ def layer_norm(x, gamma, beta, row_param, rplan, seg_param, eps=1e-5):
 
 
 class _GraphConvAggregate(torch.autograd.Function):
-    """y = act(indeg^-1/2 * sum_{u->w} outdeg^-1/2[u] * z[u] + bias)   (DGL GraphConv norm='both', after/before the GEMM)."""
-
-    @staticmethod
-    def forward(ctx, z, bias, hp, relu: bool):
-        N.require_cuda(z)
-        z = z.contiguous()
-        n, D = z.shape
-        y = torch.empty_like(z)
-        N.check(N.load().wsi_spmm_sum(N.ptr(z), D, n, D, N.ptr(hp.rowptr), N.ptr(hp.src), N.ptr(getattr(hp, "edge_w", None)), N.ptr(hp.out_norm), N.ptr(hp.in_norm),
-                                      N.ptr(bias), 1 if relu else 0, None, 0, N.ptr(y), D, N.stream()), "wsi_spmm_sum")
-        ctx.hp, ctx.relu, ctx.has_bias = hp, relu, bias is not None
-        ctx.save_for_backward(y)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (y,) = ctx.saved_tensors
-        hp = ctx.hp
-        gy = gy.contiguous()
-        n, D = y.shape
-        gz = torch.empty_like(y)
-        N.check(N.load().wsi_spmm_sum(N.ptr(gy), D, n, D, N.ptr(hp.colptr), N.ptr(hp.csc_dst), N.ptr(getattr(hp, "edge_w_csc", None)), N.ptr(hp.in_norm), N.ptr(hp.out_norm),
-                                      None, 0, N.ptr(y) if ctx.relu else None, D, N.ptr(gz), D, N.stream()), "wsi_spmm_sum")
-        gb = None
-        if ctx.has_bias:
-            gb = (gy * (y > 0).to(gy.dtype)).sum(0) if ctx.relu else gy.sum(0)
-        return gz, gb, None, None
-
-
-class _GraphConvAggregateScaled(torch.autograd.Function):
-    """_GraphConvAggregate with a per-edge message scale s (CSR order) that receives a gradient:
-    y = act(indeg^-1/2 * sum_{e: u->w} s_e * outdeg^-1/2[u] * z[u] + bias);  g_s[e] = indeg^-1/2[w] outdeg^-1/2[u] <g_y[w] * act', z[u]>
-    (``wsi_sddmm_dot``).  Saves z as well as y (the plain function needs only y)."""
+    """y = act(indeg^-1/2 * sum_{e: u->w} s_e * outdeg^-1/2[u] * z[u] + bias)   (DGL GraphConv norm='both', after/before the GEMM).
+    ``edge_scale`` None: s = the plan's constant edge weights (or 1); only y is saved.  ``edge_scale`` [E] (CSR order): it receives a gradient,
+    g_s[e] = indeg^-1/2[w] outdeg^-1/2[u] <g_y[w] * act', z[u]> (``wsi_sddmm_dot``), for which z is saved as well."""
 
     @staticmethod
     def forward(ctx, z, bias, edge_scale, hp, relu: bool):
         N.require_cuda(z, bias, edge_scale)
-        if getattr(hp, "edge_w", None) is not None:
+        if edge_scale is not None and getattr(hp, "edge_w", None) is not None:
             raise RuntimeError("graph_conv_aggregate: edge_scale on a plan that already carries constant edge weights (EdgeCSR.with_weights)")
         z = z.contiguous()
-        s = edge_scale.detach().to(torch.float32).contiguous()
+        s = edge_scale.detach().to(torch.float32).contiguous() if edge_scale is not None else None
         n, D = z.shape
         y = torch.empty_like(z)
-        N.check(N.load().wsi_spmm_sum(N.ptr(z), D, n, D, N.ptr(hp.rowptr), N.ptr(hp.src), N.ptr(s), N.ptr(hp.out_norm), N.ptr(hp.in_norm),
+        N.check(N.load().wsi_spmm_sum(N.ptr(z), D, n, D, N.ptr(hp.rowptr), N.ptr(hp.src), N.ptr(getattr(hp, "edge_w", None) if s is None else s),
+                                      N.ptr(hp.out_norm), N.ptr(hp.in_norm),
                                       N.ptr(bias), 1 if relu else 0, None, 0, N.ptr(y), D, N.stream()), "wsi_spmm_sum")
-        ctx.hp, ctx.relu, ctx.has_bias = hp, relu, bias is not None
-        ctx.save_for_backward(z, y, s)
+        ctx.hp, ctx.relu, ctx.has_bias, ctx.scaled = hp, relu, bias is not None, s is not None
+        ctx.save_for_backward(*((y,) if s is None else (y, z, s)))
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        z, y, s = ctx.saved_tensors
+        y, *zs = ctx.saved_tensors
         hp = ctx.hp
         gy = gy.contiguous()
         n, D = y.shape
         gz = gb = gs = None
-        if ctx.needs_input_grad[0]:
+        need = ctx.needs_input_grad if ctx.scaled else (True, True, False)     # (without a scale gz and gb are written whether asked for or not)
+        if need[0]:
             gz = torch.empty_like(y)
-            s_csc = s[hp.csc_eid.long()]
-            N.check(N.load().wsi_spmm_sum(N.ptr(gy), D, n, D, N.ptr(hp.colptr), N.ptr(hp.csc_dst), N.ptr(s_csc), N.ptr(hp.in_norm), N.ptr(hp.out_norm),
+            w_csc = zs[1][hp.csc_eid.long()] if ctx.scaled else getattr(hp, "edge_w_csc", None)
+            N.check(N.load().wsi_spmm_sum(N.ptr(gy), D, n, D, N.ptr(hp.colptr), N.ptr(hp.csc_dst), N.ptr(w_csc), N.ptr(hp.in_norm), N.ptr(hp.out_norm),
                                           None, 0, N.ptr(y) if ctx.relu else None, D, N.ptr(gz), D, N.stream()), "wsi_spmm_sum")
-        if ctx.has_bias and ctx.needs_input_grad[1]:
+        if ctx.has_bias and need[1]:
             gb = (gy * (y > 0).to(gy.dtype)).sum(0) if ctx.relu else gy.sum(0)
-        if ctx.needs_input_grad[2]:
-            gs = torch.empty_like(s)
-            N.check(N.load().wsi_sddmm_dot(N.ptr(gy), D, N.ptr(z), D, n, D, N.ptr(hp.rowptr), N.ptr(hp.src), N.ptr(hp.out_norm), N.ptr(hp.in_norm),
+        if need[2]:
+            gs = torch.empty_like(zs[1])
+            N.check(N.load().wsi_sddmm_dot(N.ptr(gy), D, N.ptr(zs[0]), D, n, D, N.ptr(hp.rowptr), N.ptr(hp.src), N.ptr(hp.out_norm), N.ptr(hp.in_norm),
                                            N.ptr(y) if ctx.relu else None, D, N.ptr(gs), N.stream()), "wsi_sddmm_dot")
         return gz, gb, gs, None, None
 
@@ -2282,10 +2254,9 @@ def _check_edge_scale(what: str, edge_scale: torch.Tensor, plan) -> None:
 def graph_conv_aggregate(z, bias, hplan, relu: bool, edge_scale: Optional[torch.Tensor] = None):
     """``edge_scale`` [E] (the plan's CSR edge order; None = the plain aggregation, unchanged): every message is multiplied by it and it
     receives a gradient (GNNExplainer's sigmoid(edge_mask): ``graph.message_scale``)."""
-    if edge_scale is None:
-        return _GraphConvAggregate.apply(z, bias, hplan, relu)
-    _check_edge_scale("graph_conv_aggregate", edge_scale, hplan)
-    return _GraphConvAggregateScaled.apply(z, bias, edge_scale, hplan, relu)
+    if edge_scale is not None:
+        _check_edge_scale("graph_conv_aggregate", edge_scale, hplan)
+    return _GraphConvAggregate.apply(z, bias, edge_scale, hplan, relu)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2438,59 +2409,9 @@ def _gat_drop_args(drop: Optional[CounterDropout]):
 
 
 class _GatAttention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ft, attn_l, attn_r, bias, plan, slope: float, act: int, act_slope: float, drop: Optional[CounterDropout]):
-        N.require_cuda(ft, attn_l, attn_r, bias)
-        H, D = attn_l.shape[-2], attn_l.shape[-1]
-        n = plan.num_nodes
-        if ft.dim() != 2 or ft.shape[0] != n or ft.shape[1] != H * D:
-            raise ValueError(f"gat_attention: ft must be [{n}, {H * D}], got {tuple(ft.shape)}")
-        ft = ft.contiguous()
-        al, ar = attn_l.detach().contiguous().view(-1), attn_r.detach().contiguous().view(-1)
-        b = bias.detach().contiguous() if bias is not None else None
-        dev = ft.device
-        lib = N.load()
-        eler = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)
-        N.check(lib.wsi_gat_scores(N.ptr(ft), H * D, n, H, D, N.ptr(al), N.ptr(ar), N.ptr(eler), N.stream()), "wsi_gat_scores")
-        out = torch.empty((n, H * D), dtype=torch.float32, device=dev)
-        lse = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)       # max | log of the shifted sum, per head
-        seed, seed_base, thr, scale = _gat_drop_args(drop)
-        N.check(lib.wsi_gat_attn_fwd(N.ptr(ft), H * D, N.ptr(eler), n, H, D, N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.order_dst),
-                                     float(slope), seed, seed_base, thr, scale, N.ptr(b), int(act), float(act_slope),
-                                     N.ptr(out), H * D, N.ptr(lse), N.stream()), "wsi_gat_attn_fwd")
-        ctx.plan, ctx.slope, ctx.act, ctx.act_slope, ctx.drop, ctx.hd = plan, float(slope), int(act), float(act_slope), drop, (H, D)
-        ctx.has_bias = bias is not None
-        ctx.save_for_backward(ft, al, ar, eler, lse, out if act else None)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        ft, al, ar, eler, lse, out = ctx.saved_tensors
-        plan = ctx.plan
-        H, D = ctx.hd
-        n, E, F = plan.num_nodes, plan.num_edges, H * D
-        g_out = g_out.contiguous()
-        dev = ft.device
-        lib = N.load()
-        ws_bytes = lib.wsi_gat_attn_bwd_workspace_bytes(n, E, H, D, ctx.act)
-        if ws_bytes < 0:
-            raise RuntimeError("wsi_gat_attn_bwd_workspace_bytes: bad arguments")
-        ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
-        g_ft = torch.empty((n, F), dtype=torch.float32, device=dev)
-        g_al = torch.empty(F, dtype=torch.float32, device=dev)
-        g_ar = torch.empty(F, dtype=torch.float32, device=dev)
-        g_b = torch.empty(F, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        seed, seed_base, thr, scale = _gat_drop_args(ctx.drop)
-        N.check(lib.wsi_gat_attn_bwd(N.ptr(ft), F, N.ptr(eler), N.ptr(lse), N.ptr(out), F, N.ptr(g_out), F, n, E, H, D,
-                                     N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
-                                     N.ptr(plan.order_src), N.ptr(al), N.ptr(ar), ctx.slope, seed, seed_base, thr, scale, ctx.act, ctx.act_slope,
-                                     N.ptr(ws), int(ws_bytes), N.ptr(g_ft), F, N.ptr(g_al), N.ptr(g_ar), N.ptr(g_b), N.stream()), "wsi_gat_attn_bwd")
-        return g_ft, g_al.view(1, H, D), g_ar.view(1, H, D), g_b, None, None, None, None, None
-
-
-class _GatAttentionScaled(torch.autograd.Function):
-    """_GatAttention with a per-edge message scale (CSR order) applied after the softmax: out = act(sum_e a~_e s_e ft[u] + bias)
-    (``wsi_gat_attn_fwd_scaled`` / ``wsi_gat_attn_bwd_scaled``); returns a gradient for the scale as well."""
+    """``edge_scale`` None: wsi_gat_attn_fwd / _bwd.  ``edge_scale`` [E] (CSR order), a per-edge message scale applied after the softmax,
+    out = act(sum_e a~_e s_e ft[u] + bias): wsi_gat_attn_fwd_scaled / _bwd_scaled, which take the scale as one more pointer, save it and
+    return its gradient as well."""
 
     @staticmethod
     def forward(ctx, ft, attn_l, attn_r, bias, edge_scale, plan, slope: float, act: int, act_slope: float, drop: Optional[CounterDropout]):
@@ -2502,25 +2423,26 @@ class _GatAttentionScaled(torch.autograd.Function):
         ft = ft.contiguous()
         al, ar = attn_l.detach().contiguous().view(-1), attn_r.detach().contiguous().view(-1)
         b = bias.detach().contiguous() if bias is not None else None
-        s = edge_scale.detach().to(torch.float32).contiguous()
+        s = (edge_scale.detach().to(torch.float32).contiguous(),) if edge_scale is not None else ()
         dev = ft.device
         lib = N.load()
         eler = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)
         N.check(lib.wsi_gat_scores(N.ptr(ft), H * D, n, H, D, N.ptr(al), N.ptr(ar), N.ptr(eler), N.stream()), "wsi_gat_scores")
         out = torch.empty((n, H * D), dtype=torch.float32, device=dev)
-        lse = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)
+        lse = torch.empty((n, 2 * H), dtype=torch.float32, device=dev)       # max | log of the shifted sum, per head
         seed, seed_base, thr, scale = _gat_drop_args(drop)
-        N.check(lib.wsi_gat_attn_fwd_scaled(N.ptr(ft), H * D, N.ptr(eler), n, H, D, N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.order_dst),
-                                            float(slope), seed, seed_base, thr, scale, N.ptr(b), int(act), float(act_slope), N.ptr(s),
-                                            N.ptr(out), H * D, N.ptr(lse), N.stream()), "wsi_gat_attn_fwd_scaled")
+        fwd, what = (lib.wsi_gat_attn_fwd_scaled, "wsi_gat_attn_fwd_scaled") if s else (lib.wsi_gat_attn_fwd, "wsi_gat_attn_fwd")
+        N.check(fwd(N.ptr(ft), H * D, N.ptr(eler), n, H, D, N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.order_dst),
+                    float(slope), seed, seed_base, thr, scale, N.ptr(b), int(act), float(act_slope), *map(N.ptr, s),
+                    N.ptr(out), H * D, N.ptr(lse), N.stream()), what)
         ctx.plan, ctx.slope, ctx.act, ctx.act_slope, ctx.drop, ctx.hd = plan, float(slope), int(act), float(act_slope), drop, (H, D)
         ctx.has_bias = bias is not None
-        ctx.save_for_backward(ft, al, ar, eler, lse, s, out if act else None)
+        ctx.save_for_backward(ft, al, ar, eler, lse, *s, out if act else None)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        ft, al, ar, eler, lse, s, out = ctx.saved_tensors
+        ft, al, ar, eler, lse, *s, out = ctx.saved_tensors
         plan = ctx.plan
         H, D = ctx.hd
         n, E, F = plan.num_nodes, plan.num_edges, H * D
@@ -2535,14 +2457,15 @@ class _GatAttentionScaled(torch.autograd.Function):
         g_al = torch.empty(F, dtype=torch.float32, device=dev)
         g_ar = torch.empty(F, dtype=torch.float32, device=dev)
         g_b = torch.empty(F, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        g_s = torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E]
+        g_s = tuple(torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E] for _ in s)
         seed, seed_base, thr, scale = _gat_drop_args(ctx.drop)
-        N.check(lib.wsi_gat_attn_bwd_scaled(N.ptr(ft), F, N.ptr(eler), N.ptr(lse), N.ptr(out), F, N.ptr(g_out), F, n, E, H, D,
-                                            N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
-                                            N.ptr(plan.order_src), N.ptr(al), N.ptr(ar), ctx.slope, seed, seed_base, thr, scale, ctx.act, ctx.act_slope,
-                                            N.ptr(s), N.ptr(ws), int(ws_bytes), N.ptr(g_ft), F, N.ptr(g_al), N.ptr(g_ar), N.ptr(g_b), N.ptr(g_s),
-                                            N.stream()), "wsi_gat_attn_bwd_scaled")
-        return g_ft, g_al.view(1, H, D), g_ar.view(1, H, D), g_b, g_s, None, None, None, None, None
+        bwd, what = (lib.wsi_gat_attn_bwd_scaled, "wsi_gat_attn_bwd_scaled") if s else (lib.wsi_gat_attn_bwd, "wsi_gat_attn_bwd")
+        N.check(bwd(N.ptr(ft), F, N.ptr(eler), N.ptr(lse), N.ptr(out), F, N.ptr(g_out), F, n, E, H, D,
+                    N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
+                    N.ptr(plan.order_src), N.ptr(al), N.ptr(ar), ctx.slope, seed, seed_base, thr, scale, ctx.act, ctx.act_slope,
+                    *map(N.ptr, s), N.ptr(ws), int(ws_bytes), N.ptr(g_ft), F, N.ptr(g_al), N.ptr(g_ar), N.ptr(g_b), *map(N.ptr, g_s),
+                    N.stream()), what)
+        return g_ft, g_al.view(1, H, D), g_ar.view(1, H, D), g_b, (g_s[0] if s else None), None, None, None, None, None
 
 
 def gat_attention(ft: torch.Tensor, attn_l: torch.Tensor, attn_r: torch.Tensor, bias: Optional[torch.Tensor], plan,
@@ -2559,11 +2482,9 @@ def gat_attention(ft: torch.Tensor, attn_l: torch.Tensor, attn_r: torch.Tensor, 
         raise ValueError(f"gat_attention: activation {activation!r} is not one of {sorted(k for k in GAT_ACTIVATIONS if k)}")
     if attn_l.dim() != 3 or attn_l.shape[0] != 1 or attn_r.shape != attn_l.shape:
         raise ValueError("gat_attention: attn_l / attn_r must be [1, H, D]")
-    if edge_scale is None:
-        return _GatAttention.apply(ft, attn_l, attn_r, bias, plan, float(negative_slope), GAT_ACTIVATIONS[activation], float(act_slope), attn_drop)
-    _check_edge_scale("gat_attention", edge_scale, plan)
-    return _GatAttentionScaled.apply(ft, attn_l, attn_r, bias, edge_scale, plan, float(negative_slope), GAT_ACTIVATIONS[activation],
-                                     float(act_slope), attn_drop)
+    if edge_scale is not None:
+        _check_edge_scale("gat_attention", edge_scale, plan)
+    return _GatAttention.apply(ft, attn_l, attn_r, bias, edge_scale, plan, float(negative_slope), GAT_ACTIVATIONS[activation], float(act_slope), attn_drop)
 
 
 # ------------------------------------------------------------------------------------------------
