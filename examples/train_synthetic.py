@@ -37,7 +37,8 @@ def main(argv=None):
                          "default: torch.optim.Adam")
     ap.add_argument("--captured-slots", type=int, default=0, metavar="K",
                     help="train through trainer.CapturedSlotStep over K padded batch slots by slide size (DESIGN 3.15): one captured step per slot, "
-                         "replayed over every new batch that fits; needs --optimizer adam, sgd or adadelta (capturable) and no --augment")
+                         "replayed over every new batch that fits; needs --optimizer adam, sgd or adadelta (capturable).  With --augment the slots draw the "
+                         "augmentation on the device in front of every replay (DESIGN 3.16)")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -86,8 +87,8 @@ def main(argv=None):
 
     slot_step = None
     if args.captured_slots:
-        if world > 1 or args.augment or args.optimizer not in ("adam", "sgd", "adadelta"):
-            raise SystemExit("--captured-slots: single process, no --augment (augmented batches change shape), and --optimizer adam | sgd | adadelta")
+        if world > 1 or args.optimizer not in ("adam", "sgd", "adadelta"):
+            raise SystemExit("--captured-slots: single process and --optimizer adam | sgd | adadelta")
         if args.optimizer == "adam":
             from wsi_hgnn_amd import optim
             opt = optim.Adam(gnn.parameters(), lr=1e-5, weight_decay=5e-3, capturable=True)         # the step count on the device

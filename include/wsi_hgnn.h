@@ -794,6 +794,50 @@ int wsi_loo_edges(const int64_t* desc, int32_t nrow, int32_t ntiles, int32_t* ti
                   int64_t* out_eid, int32_t* counts, void* stream);
 int wsi_loo_rows(const int64_t* desc, int32_t nrow, int32_t ntiles, const int64_t* removed, int32_t ncopies, int64_t* row_of, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fill of a padded batch slot with AUGMENTED slides (data.BatchSlot over a loader with transform=; graph.slot_fill_augmented): the tables
+ * wsi_slot_fill writes, for the batch [transform(slide_0, draw_0), .., empty graphs, filler], from survivor counts that stay on the device - no
+ * read-back, no synchronisation, no atomics, no allocation; a launch count that depends on neither the draw nor the pipeline.  Entry points
+ * added to ABI 26.  A stored slide's plan pieces are in CSR order and DropNode renumbers monotonically, so the augmented slide's pieces are
+ * stable compactions of the stored ones; the processing orders are the stored order lists restricted to the survivors (a processing order
+ * changes no result), the filler's nodes behind them.
+ *
+ * Sequence of one fill, all on `stream`: wsi_augment_nodes over the rows at off_node (B * T rows, (slide, type), slide-major; counts = ncnt),
+ * wsi_augment_edges over the rows at off_edge (B * R rows, (slide, relation); rank1 = rank1, new_id = new_id), wsi_slot_aug_keys, ONE stable
+ * ascending sort of keys whose indices are perm, wsi_slot_aug_scan, wsi_slot_aug_write.
+ *
+ * desc: ONE device int64 table; the off_* fields are word offsets into it.
+ *   off_node   wsi_augment_nodes rows;  off_edge  wsi_augment_edges rows (slide b's rows cover ITS concatenated COO: off = coo_base[b] + ...)
+ *   off_flag   nflag rows of 8 words [n, off, first_tile, kind, p0, p1, slide, 0] (tiles of 1024 as for wsi_augment_*; off into frank):
+ *              kind 0: p0 = int64 [n], entry i = (relation << 40) | index of the entry's edge in the slide's concatenated COO - kept iff the edge
+ *              survives;  kind 1: p0 / p1 = int64 [n] local id / node type of an order list's entry - kept iff the node survives.
+ *              Rows, in order: CSR edges into (b, t) at [b T + t], CSC entries out of (b, t) at [B T + b T + t], then per slide its
+ *              heavy-destination, light-destination and source order lists at [2 B T + b], [2 B T + B + b], [2 B T + 2 B + b]: nflag = 2 B T + 3 B.
+ *   off_push   npush rows of 10 words [n, first_block, kind, slide, type, p0, p1, p2, p3, flag row] (blocks of 1024; rows with n = 0 not listed):
+ *              kind 0 nodes of (b, t): p0 = stored rowptr piece (int64 [n R]), p1 = stored colptr piece;  kind 1 CSR edges into (b, t): p0 = src_l,
+ *              p1 = src_t, p2 = sim (fp32), p3 = local softmax segment node * R + slot;  kind 2 CSC entries out of (b, t): p0 = eid_l, p1 = ent_t,
+ *              p2 = dst_l;  kinds 3 / 4 / 5 the slide's heavy / light / source order list: p0 = local id, p1 = node type (all int64 but sim)
+ *   off_feat   B * T rows of 3 words [fp32 feature table of (b, t), its rows, FeatMask's sub-seed]
+ *   off_shape  the shape block of csrc/slot_layout.h: [T, B, b_cap, chunk, c_cap, per type: n_cap, e_cap, type_off, ebase, src_type, R, seg_off]
+ *   off_misc   noff[B T] (offset of (b, t) in new_id / kept / keys / perm), stored rows [B T], coo_base[B], labels[G], NodeShuffle sub-seeds [B T]
+ * ns_mode: 0 no NodeShuffle, 1 in front of DropNode (or no DropNode): perm over the stored nodes, 2 behind it: over the survivors - positions at
+ * or beyond the survivors' count carry a key above every real one.  mask_thr: FeatMask's threshold (0: none).  feat_aligned: every feature
+ * table is 16-byte aligned (with F % 4 == 0: 16-byte accesses; else the element path).
+ * Scratch (caller-owned): new_id int32 / kept int64 / keys int64 / perm int64 [nodes_stored], ncnt int32 [B T], rank1 int32 [COO edges],
+ * ftile int32 [flag_tiles + 1], frank int32 [flag entries], fcnt int32 [nflag], L int64 [4 B T + 9 T + 3 B + 2] (slot_layout.h).
+ * wsi_slot_aug_scan: flags -> ranks and counts (three launches), then the layout kernel: L, readout_ptr, the readout's chunk tables and
+ * segment counts, labels.  wsi_slot_aug_write: the real slides push, the filler and tails are pulled, the features are gathered (three launches);
+ * every element of every table is written by every fill (scales: wsi_row_absmax over feat afterwards).
+ * args: a HOST array of 55 int64 words, read during the call (pointers as integers), the same for the three calls:
+ *   [0] desc   [1..7] off_node, off_edge, off_flag, off_push, off_feat, off_shape, off_misc   [8..14] B, T, R, N, S, E, G (= b_cap + 1)
+ *   [15..23] nflag, flag_tiles, npush, push_blocks, nodes_stored, ns_mode, F, mask_thr, feat_aligned
+ *   [24..33] scratch: new_id, kept, ncnt, rank1, ftile, frank, fcnt, keys, perm, L
+ *   [34..54] the slot's tables: rowptr, colptr, node_seg, src, csc_eid, csc_dst, order_dst, order_src, sim, inv_rd, readout_ptr, labels, feat,
+ *            edge_seg, row_seg, chunk_row, chunk_seg, seg_chunk, seg_counts, seg_inv_counts, seg_nonempty */
+int wsi_slot_aug_keys(const int64_t* args, void* stream);
+int wsi_slot_aug_scan(const int64_t* args, void* stream);
+int wsi_slot_aug_write(const int64_t* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,13 @@ Every leg has a model and an optimizer of its own (same initial values, wsi_hgnn
 batches behind a device synchronise and ends in one; reported: median / fastest / slowest round in wall ms per step, the fill alone (wall ms per
 ``slot.load`` with the device idle - host arithmetic, upload and kernel - and the device time of upload + kernel by events, queued behind a few ms
 of unrelated work), the share of the slot's rows and edges the filler takes, and which
-slot the batches went to.  A GPU is required: nothing is estimated."""
+slot the batches went to.  A GPU is required: nothing is estimated.
+
+``--augment`` -> profiles/r13_slot_augment.json: the same data set, rounds and alternation with the reference's training pipeline
+(``transforms.reference_train_transform()``) on the loader.  The yardstick leg is then the only way to train augmented without slots -
+``GraphBatchLoader(transform=...)``'s batch (fused device augmentation, one read-back per slide, ``graph.batch``, ``plan()``) stepped eagerly - and
+the slots draw the augmentation on the device in front of every replay; also reported: the kernel launches of one fill (torch.profiler) and the
+filler's share from ``BatchSlot.counts()``, read outside the timed windows."""
 import argparse
 import json
 import os
@@ -51,13 +57,16 @@ def main(argv=None):
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--rounds", type=int, default=11)
     ap.add_argument("--gemm", default="auto", choices=["fp32", "bf16x6", "fp16x3", "auto"])
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_slot_step.json"))
+    ap.add_argument("--augment", action="store_true", help="the reference's train-time augmentation on the loader: eager augmented batches against augmented slots")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r13_slot_augment.json" if args.augment else "r12_slot_step.json")
     if not torch.cuda.is_available():
         raise SystemExit("tools/slot_bench.py measures on the GPU; none is visible (nothing is estimated on the CPU)")
     import __graft_entry__
     __graft_entry__.build()
-    from wsi_hgnn_amd import models, ops, synthetic, optim as O
+    from wsi_hgnn_amd import models, ops, synthetic, transforms, optim as O
     from wsi_hgnn_amd.data import BatchSlot, GraphBatchLoader
     from wsi_hgnn_amd.trainer import CapturedSlotStep, apply_loss
     dev = torch.device("cuda:0")
@@ -72,6 +81,8 @@ def main(argv=None):
     result = {"workload": f"HEATNet4({args.in_dim}, {args.hidden}, 2 layers, 4 heads), {args.slides} synthetic slides of {args.min_nodes}-{args.max_nodes} nodes "
                           f"(mean {sum(sizes) / len(sizes):.0f}), resident, gemm={args.gemm}, wsi_hgnn_amd.optim.Adam(capturable=True), train mode",
               "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "configs": []}
+    if args.augment:
+        result["workload"] += ", transform = Compose([DropNode(0.5), DropEdge(0.5), NodeShuffle(), FeatMask(0.5, ['feat'])]) drawn anew every step"
 
     def make(drop):
         torch.manual_seed(611)
@@ -79,7 +90,8 @@ def main(argv=None):
         return m, O.Adam(m.parameters(), lr=1e-5, weight_decay=5e-3, capturable=True)
 
     for bs in (1, 2):
-        loader = GraphBatchLoader(graphs, labels, bs, dev, shuffle=False, resident=True)
+        loader = GraphBatchLoader(graphs, labels, bs, dev, shuffle=False, resident=True,
+                                  transform=transforms.reference_train_transform() if args.augment else None)
         order = torch.randperm(args.slides, generator=gen).tolist()
         batches = [order[i:i + bs] for i in range(0, len(order), bs)]
         for drop in (0.0, 0.2):
@@ -87,7 +99,7 @@ def main(argv=None):
 
             def eager_round():
                 for idxs in batches:
-                    G, y, _ = loader._assemble(idxs, 0)
+                    G, y = loader._augmented(idxs) if args.augment else loader._assemble(idxs, 0)[:2]
                     o_e.zero_grad(set_to_none=True)
                     loss = apply_loss(lf, m_e(G), y)
                     loss.backward()
@@ -140,6 +152,18 @@ def main(argv=None):
                 entry[name] = {"fill_wall_ms": _stats(wall), "fill_device_ms": _stats(devt), "padded_row_share": round(sum(rows) / len(rows), 4),
                                "padded_edge_share": round(sum(edges) / len(edges), 4), "batches_per_slot": routed,
                                "slot_rows": [s.layout.N for s in step.slots], "eager_fallbacks_per_round": len(batches) - sum(routed)}
+                if args.augment:                             # kernel launches of ONE fill (the sort's and the column statistics' included)
+                    try:
+                        from torch.profiler import ProfilerActivity, profile
+                        idxs = next(b_ for b_ in batches if step.slot_for(b_) is not None)
+                        torch.cuda.synchronize()
+                        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                            step.slots[step.slot_for(idxs)].load(idxs)
+                            torch.cuda.synchronize()
+                        entry[name]["launches_per_fill"] = sum(ev.count for ev in prof.key_averages() if "memcpy" not in ev.key.lower() and "memset" not in ev.key.lower())
+                    except Exception as exc:                 # (no tracer in this build: the count is then documented arithmetic only)
+                        entry[name]["launches_per_fill"] = None
+                        entry[name]["launches_note"] = f"torch.profiler unavailable: {type(exc).__name__}"
             e_ms = entry["legs"]["eager"]["median_ms"]
             entry["speedup_one_slot"] = round(e_ms / entry["legs"]["one_slot"]["median_ms"], 3)
             entry["speedup_three_slots"] = round(e_ms / entry["legs"]["three_slots"]["median_ms"], 3)

@@ -327,6 +327,53 @@ class GraphBatchLoader:
                 ops.block_side_streams(False, who)
 
 
+def slot_augment_spec(transform):
+    """The ``graph.AugmentSpec`` of a slot-compatible pipeline: a ``transforms.Compose`` whose members are DropNode, DropEdge, NodeShuffle and
+    FeatMask, each kind at most once, in any order (the set one ``ops.augment_graph`` call fuses), FeatMask naming at most the node field
+    ``"feat"`` and no edge field.  Anything else raises RuntimeError."""
+    from . import transforms as _tr
+    refuse = lambda why: RuntimeError(f"BatchSlot: the loader's transform is not slot-compatible ({why}); a slot draws the augmentation on the device for "
+                                      "a Compose of at most one each of DropNode, DropEdge, NodeShuffle and FeatMask(node_feat_names=['feat']) - step "
+                                      "other pipelines eagerly")
+    if not isinstance(transform, _tr.Compose):
+        raise refuse("not a transforms.Compose")
+    found = {}
+    for k, t in enumerate(transform.transforms):
+        if not isinstance(t, _tr.BaseTransform) or type(t) not in (_tr.DropNode, _tr.DropEdge, _tr.NodeShuffle, _tr.FeatMask):
+            raise refuse(f"member {k} is not one of the four transforms")
+        if t.kind in found:
+            raise refuse(f"{type(t).__name__} occurs twice")
+        if isinstance(t, _tr.FeatMask):
+            if t.edge_feat_names:
+                raise refuse("FeatMask over an edge field")
+            if list(t.node_feat_names or []) not in ([], ["feat"]):
+                raise refuse("FeatMask over a node field other than 'feat'")
+            found[t.kind] = (k, t.threshold) if t.node_feat_names else None
+        else:
+            found[t.kind] = (k, getattr(t, "threshold", 0))
+    return _graph_mod.AugmentSpec(**{k: v for k, v in found.items() if v is not None})
+
+
+class _DeviceOnly:
+    """Stands where a host copy of an augmented GPU slot's counts would be: those counts live on the device, and reading them fails loudly."""
+
+    def __init__(self, what: str):
+        self.what = what
+
+    def _fail(self, *a, **k):
+        raise RuntimeError(f"BatchSlot: {self.what} of an augmented slot exists on the device only (the draw is not read back); "
+                           "BatchSlot.counts() is the one explicit read-back")
+
+    __iter__ = __len__ = __getitem__ = __bool__ = __call__ = _fail
+
+
+class _DeviceOnlyCounts(dict):
+    """``HeteroGraph._batch_num_nodes`` of an augmented GPU slot: the number of graphs is known (``batch_size``), the node counts are not."""
+
+    def __getitem__(self, key):
+        _DeviceOnly("batch_num_nodes")._fail()
+
+
 class BatchSlot:
     """A batch of FIXED shape fed from a resident loader: the static tables of one padded batch - up to ``b_cap`` real slides, empty
     graphs up to ``b_cap``, one filler graph labelled -100 that takes what the slides leave of the capacities - and ONE ``HeteroGraph`` whose kernel
@@ -336,14 +383,19 @@ class BatchSlot:
 
     ``capacity``: ``(n_cap, e_cap)`` - nodes per node type, edges per destination node type - or ``(n_cap, e_cap, b_cap)``; ``None`` derives a
     bound every batch of the loader's bucket fits: per type the sum of the ``batch_size`` largest counts, plus one node.  Resident data sets
-    without a transform only: a pinned-host data set has no device-side features to copy from, augmented batches change shape."""
+    only: a pinned-host data set has no device-side features to copy from.
+
+    A loader with ``transform=`` a slot-compatible pipeline (``slot_augment_spec``) gives an AUGMENTED slot: ``load(idxs, draws)``
+    fills it with ``[transform(slide_b, draws[b]).., empty graphs.., filler]`` - on the GPU the draw is taken on the device and the tables are
+    written from device-side counts (``graph.slot_fill_augmented``: no read-back), on the CPU through the tensor formulation.  Capacities are
+    those of the unaugmented batch (augmentation only removes), ``fits`` uses the stored counts plus one rule (see ``fits``), the host mirrors of
+    the counts fail loudly on a GPU slot and ``counts()`` is the explicit read-back."""
 
     def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0):
         if not loader.resident:
             raise RuntimeError("BatchSlot needs a device-resident data set (GraphBatchLoader(..., resident=True)): the fill copies the slides' features "
                                "device to device; a pinned-host loader stays on its own double-buffered path")
-        if loader.transform is not None:
-            raise RuntimeError("BatchSlot: a loader with transform= yields augmented batches, whose shapes change from draw to draw; step them eagerly")
+        self.spec = slot_augment_spec(loader.transform) if loader.transform is not None else None
         self.loader, self.device = loader, loader.device
         key = list(loader.buckets)[bucket]
         self.members = set(loader.buckets[key])
@@ -395,7 +447,7 @@ class BatchSlot:
         else:
             self.readout_plan = None
         self.graph, self.labels = G, self.bufs["labels"]
-        self.num_real, self.batch, self.idxs = 0, None, None
+        self.num_real, self.batch, self.idxs, self.draws = 0, None, None, None
 
     def _counts(self, idxs):
         its = [self.loader.items[i] for i in idxs]
@@ -407,14 +459,32 @@ class BatchSlot:
         idxs = list(idxs)
         if not idxs or any(i not in self.members for i in idxs):
             return False
-        return _graph_mod.SlotBatch.fits(self.layout, *self._counts(idxs))
+        counts, ecounts = self._counts(idxs)
+        if not _graph_mod.SlotBatch.fits(self.layout, counts, ecounts):
+            return False
+        if self.spec is not None and self.spec.node_thr > 0:
+            # augmented slot: the models switch a node type's head off when the batch has no node of the type - a host-side branch frozen into a
+            # capture - so a draw that empties a type must be impossible in practice: p_node ** n[t] <= 2 ** -32 for every type (n >= 32 at 0.5)
+            p = self.spec.node_thr / 65536.0
+            if any(p ** sum(c[t] for c in counts) > 2.0 ** -32 for t in range(self.layout.T)):
+                return False
+        return True
 
-    def load(self, idxs: Sequence[int]) -> "BatchSlot":
-        """Fill the slot with the batch of slides ``idxs`` (in that order) on the current stream.  Raises ValueError when it does not fit."""
+    def load(self, idxs: Sequence[int], draws: Optional[Sequence[int]] = None) -> "BatchSlot":
+        """Fill the slot with the batch of slides ``idxs`` (in that order) on the current stream.  Raises ValueError when it does not fit.
+        Augmented slot: ``draws[b]`` is the 32-bit draw of slide ``idxs[b]``; ``None`` takes ``augment_draw(loader.seed, counter, idxs[b])`` with
+        the loader's running batch counter, which it advances by one - as ``GraphBatchLoader._augmented`` does."""
         idxs = list(idxs)
         if not self.fits(idxs):
             raise ValueError(f"BatchSlot.load: the batch {idxs} does not fit the slot (capacities: {self.layout.n_cap} nodes, {self.layout.e_cap} edges, "
                              f"{self.layout.b_cap} slides)")
+        if self.spec is not None:
+            if draws is None:
+                counter, self.loader._batches_drawn = self.loader._batches_drawn, self.loader._batches_drawn + 1
+                draws = [augment_draw(self.loader.seed, counter, i) for i in idxs]
+            return self.load_augmented(idxs, draws)
+        if draws is not None:
+            raise ValueError("BatchSlot.load: draws= needs a loader with a transform")
         its = [self.loader.items[i] for i in idxs]
         T = self.layout.T
         scales = None
@@ -448,10 +518,86 @@ class BatchSlot:
         self.num_real, self.batch, self.idxs = sb.B, sb, idxs
         return self
 
+    def load_augmented(self, idxs: Sequence[int], draws: Sequence[int]) -> "BatchSlot":
+        """``load`` of an augmented slot WITHOUT the ``fits`` rule on the node counts (the stored batch must fit the capacities): the fill itself is
+        defined for every draw, one that empties a node type included (the filler then takes the whole type) - tests and diagnostics call this."""
+        idxs, draws = list(idxs), [int(d) & 0xffffffff for d in draws]
+        if self.spec is None:
+            raise RuntimeError("BatchSlot.load_augmented: the loader has no transform")
+        if len(draws) != len(idxs):
+            raise ValueError("BatchSlot.load_augmented: one draw per slide")
+        its = [self.loader.items[i] for i in idxs]
+        lay, G = self.layout, self.graph
+        if any(i not in self.members for i in idxs) or not _graph_mod.SlotBatch.fits(lay, *self._counts(idxs), True):
+            raise ValueError(f"BatchSlot.load_augmented: the batch {idxs} does not fit the slot")
+        ntypes, rels = G.ntypes, G.canonical_etypes
+        if self.device.type == "cuda":
+            _graph_mod.slot_fill_augmented(lay, self.bufs, [it.pieces for it in its], [[it.edges[r] for r in rels] for it in its],
+                                           [it.label for it in its], [it.feat for it in its], draws, self.spec)
+            # host mirrors of the counts: not current without a read-back - they fail loudly instead (the step reads none of them)
+            G._batch_num_nodes = _DeviceOnlyCounts((t, torch.zeros(lay.graphs, dtype=torch.int64)) for t in ntypes)
+            G._edges_store, G._edge_thunk = None, _DeviceOnly("the per-relation COO")
+            self.batch = _DeviceOnly("the host layout (BatchSlot.batch)")
+            self.readout_plan.ranges = _DeviceOnly("the readout plan's row ranges")
+            from . import ops
+            ops.refresh_constant_cols(self.bufs["feat"])
+        else:
+            # tensor route (and the kernels' oracle): every slide through the tensor formulation of the pipeline, stored anew, then the ordinary fill
+            aug, keeps = [], []
+            for it, d in zip(its, draws):
+                g = HeteroGraph.from_coo(OrderedDict(zip(it.ntypes, it.num_nodes)), it.edges, feat=dict(zip(it.ntypes, it.feat)), sim=it.sims)
+                aug.append(StoredGraph(self.loader.transform(g, draw=d, fused=False), it.label, self.device, True))
+                keeps.append(self.spec.node_keep(d, it.num_nodes, self.device))
+            out = _graph_mod.slot_fill_torch(lay, [a.pieces for a in aug], [a.label for a in aug], [a.feat for a in aug], None, self.device, True)
+            sb = out["batch"]
+            out["order_dst"], out["order_src"] = _graph_mod.restricted_orders(lay, [it.pieces for it in its], keeps, sb)
+            with torch.no_grad():
+                for k, v in out.items():
+                    if k != "batch":
+                        self.bufs[k].copy_(v)
+            for i, t in enumerate(ntypes):
+                G._batch_num_nodes[t] = torch.tensor(sb.counts[i], dtype=torch.int64)
+            nf, ef, n, dev = list(sb.nf), list(sb.ef), list(sb.n), self.device
+
+            def coo():
+                edges, efields = _batch_coo(aug, ntypes, rels)
+                fg = _graph_mod.filler_graph(ntypes, rels, nf, ef, 0)
+                tix = {t: i for i, t in enumerate(ntypes)}
+                for r in rels:
+                    u, v = fg.edges(r)
+                    edges[r] = (torch.cat([edges[r][0], u.to(dev) + n[tix[r[0]]]]), torch.cat([edges[r][1], v.to(dev) + n[tix[r[2]]]]))
+                    efields[r] = {"sim": torch.cat([efields[r]["sim"], torch.zeros(u.numel(), dtype=torch.float32, device=dev)])}
+                return edges, efields
+
+            G._edges_store, G._edge_thunk = None, coo
+            self.batch = sb
+        for r in rels:
+            G._eframes[r].clear()
+        self.num_real, self.idxs, self.draws = len(idxs), idxs, draws
+        return self
+
+    def counts(self):
+        """``(nodes, edges)`` of the last fill, ``[b][t]`` per real slide and node type (edges by destination type).  On an augmented GPU slot
+        this is THE read-back of the device-side counts (one synchronising copy): for diagnostics and benchmarks, never inside a step."""
+        if self.idxs is None:
+            raise RuntimeError("BatchSlot.counts: nothing loaded")
+        B, T = len(self.idxs), self.layout.T
+        if self.spec is not None and self.device.type == "cuda":
+            sc = self.bufs["_aug"]
+            got = torch.cat([sc["ncnt"][:B * T], sc["fcnt"][:B * T]]).tolist()
+            return [got[b * T:(b + 1) * T] for b in range(B)], [got[(B + b) * T:(B + b + 1) * T] for b in range(B)]
+        if self.spec is not None:
+            sb = self.batch
+            return ([[sb.counts[t][b] for t in range(T)] for b in range(B)],
+                    [[sb.eoff[(t, b + 1)] - sb.eoff[(t, b)] if b + 1 < B else sb.feb[t] - sb.eoff[(t, b)] for t in range(T)] for b in range(B)])
+        n, e = self._counts(self.idxs)
+        return [list(x) for x in n], [list(x) for x in e]
+
     def padded_share(self):
-        """(share of the slot's rows, share of its edges) that the current batch's filler takes."""
-        sb, lay = self.batch, self.layout
-        return sum(sb.nf) / max(lay.N, 1), sum(sb.ef) / max(lay.E, 1)
+        """(share of the slot's rows, share of its edges) that the current batch's filler takes (``counts()``: a read-back on an augmented GPU slot)."""
+        lay = self.layout
+        n, e = self.counts()
+        return (lay.N - sum(map(sum, n))) / max(lay.N, 1), (lay.E - sum(map(sum, e))) / max(lay.E, 1)
 
 
 def _slot_reduce_plan(ops):

@@ -706,6 +706,26 @@ class PlanPieces:
             self.so_l, self.so_t = self.so_l[o], self.so_t[o]
         self.num_heavy = sum(nheavy)
         self.max_in_degree = int(indeg.max().item()) if indeg.numel() else 0
+        # what an augmented slot fill needs of the plan's sort (slot_fill_augmented): CSR position -> position in the slide's concatenated COO
+        # (relations in sorted order), global CSC entry -> CSR position, the CSR / CSC range of every type; the packed maps are built on first use
+        self._perm, self._csc_eid, self._e_start, self._c_start = getattr(plan, "perm", None), eid, e_start, c_start
+        self._coo_maps = None
+
+    def coo_maps(self, rel_sizes: Sequence[int]):
+        """(csr_map[t], csc_map[t]): int64 per CSR edge into / CSC entry out of node type t, ``(relation << 40) | index in the slide's concatenated
+        COO`` (relations in sorted order, ``rel_sizes`` edges each): which COO edge an entry of the stored pieces is.  Built once per stored graph."""
+        if self._coo_maps is None:
+            if self._perm is None:
+                raise RuntimeError("PlanPieces.coo_maps: the plan was not built from COO (no sort permutation kept)")
+            dev = self._perm.device
+            perm = self._perm.to(torch.int64)
+            bounds = torch.tensor([sum(rel_sizes[:j + 1]) for j in range(len(rel_sizes))], dtype=torch.int64, device=dev)
+            packed = perm | (torch.bucketize(perm, bounds, right=True) << 40) if perm.numel() else perm
+            by_csc = packed[self._csc_eid] if perm.numel() else perm
+            T = len(self.counts)
+            self._coo_maps = ([packed[self._e_start[t]:self._e_start[t + 1]].contiguous() for t in range(T)],
+                              [by_csc[self._c_start[t]:self._c_start[t + 1]].contiguous() for t in range(T)])
+        return self._coo_maps
 
 
 def plan_frame(hd: PlanHeader, dev, batch_counts: List[List[int]]) -> GraphPlan:
@@ -990,19 +1010,23 @@ class SlotBatch:
     (``ef[t] = e_cap[t] - e[t] >= 0``) left for the filler."""
 
     @staticmethod
-    def fits(lay: SlotLayout, counts: Sequence[Sequence[int]], ecounts: Sequence[Sequence[int]]) -> bool:
-        """``counts[b][t]`` / ``ecounts[b][t]``: nodes / edges (by destination type) of slide b."""
+    def fits(lay: SlotLayout, counts: Sequence[Sequence[int]], ecounts: Sequence[Sequence[int]], allow_empty_type: bool = False) -> bool:
+        """``counts[b][t]`` / ``ecounts[b][t]``: nodes / edges (by destination type) of slide b.  ``allow_empty_type``: the layout of a batch in
+        which some node type has no real node is still defined (an augmented batch after an unlucky draw: the filler takes the whole type) -
+        ``BatchSlot.fits`` never lets such a batch be STEPPED on a slot."""
         if not 1 <= len(counts) <= lay.b_cap:
             return False
+        if allow_empty_type:
+            return all(lay.n_cap[t] - sum(c[t] for c in counts) >= 1 and lay.e_cap[t] - sum(e[t] for e in ecounts) >= 0 for t in range(lay.T))
         # a node type NO slide of the batch has is not padded: the models skip such a type's prediction head altogether (models/HEATNet4.py:216-221,
         # ``h[k].shape[0] > 0``), the filler's nodes would switch it on - such a batch does not fit and is stepped eagerly
         if any(sum(c[t] for c in counts) < 1 for t in range(lay.T)):
             return False
         return all(lay.n_cap[t] - sum(c[t] for c in counts) >= 1 and lay.e_cap[t] - sum(e[t] for e in ecounts) >= 0 for t in range(lay.T))
 
-    def __init__(self, lay: SlotLayout, pieces: Sequence[PlanPieces]):
+    def __init__(self, lay: SlotLayout, pieces: Sequence[PlanPieces], allow_empty_type: bool = False):
         T, hd, B = lay.T, lay.hd, len(pieces)
-        if not SlotBatch.fits(lay, [pc.counts for pc in pieces], [pc.ecount for pc in pieces]):
+        if not SlotBatch.fits(lay, [pc.counts for pc in pieces], [pc.ecount for pc in pieces], allow_empty_type):
             raise ValueError("the batch does not fit the slot")
         self.B = B
         self.n = [sum(pc.counts[t] for pc in pieces) for t in range(T)]
@@ -1193,13 +1217,13 @@ def _slot_descriptors(lay: SlotLayout, bufs, pieces, labels, feats, scales):
 
 
 def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]],
-                    scales: Optional[Sequence[Sequence[torch.Tensor]]] = None, device="cpu") -> Dict[str, object]:
+                    scales: Optional[Sequence[Sequence[torch.Tensor]]] = None, device="cpu", allow_empty_type: bool = False) -> Dict[str, object]:
     """``slot_fill`` as tensor operations: the CPU path and the kernel's test oracle (the GPU test compares the two bit for bit).  The real
     slides' parts are offset copies of their pieces; the filler's parts come from SORTING its explicit edge list (``filler_graph``'s
     ``j -> (j mod nf[s], j mod nf[t])``), not from the kernel's closed forms.  Returns the tables by the names of ``SlotLayout.buffers``, plus
     ``"batch"``: the ``SlotBatch``."""
     dev = torch.device(device)
-    sb = SlotBatch(lay, pieces)
+    sb = SlotBatch(lay, pieces, allow_empty_type)
     T, hd, B, G, F = lay.T, lay.hd, sb.B, lay.graphs, lay.in_dim
     N, S, E = lay.N, lay.S, lay.E
     i64 = lambda n: torch.zeros(int(n), dtype=torch.int64, device=dev)
@@ -1278,6 +1302,171 @@ def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Seque
             "labels": torch.tensor([int(y) for y in labels] + [-100] * (G - B), dtype=torch.int64, device=dev), "feat": feat, "scales": scl,
             "edge_seg": edge_seg, "row_seg": row_seg, "chunk_row": t32(sb.chunk_row), "chunk_seg": t32(sb.chunk_seg), "seg_chunk": t32(sb.seg_chunk),
             "seg_counts": col(sb.seg_counts), "seg_inv_counts": col(sb.seg_inv_counts), "seg_nonempty": col(sb.seg_nonempty)}
+
+
+# ------------------------------------------------------------------ augmented slides in a slot
+class AugmentSpec:
+    """What a slot-compatible pipeline (``transforms.Compose`` of at most one each of DropNode, DropEdge, NodeShuffle, FeatMask(['feat'])) comes
+    down to: per kind ``(number in the pipeline, 16-bit threshold)`` or None.  ``data.slot_augment_spec`` builds it."""
+
+    def __init__(self, drop_node=None, drop_edge=None, node_shuffle=None, feat_mask=None):
+        self.drop_node, self.drop_edge, self.node_shuffle, self.feat_mask = drop_node, drop_edge, node_shuffle, feat_mask
+        self.node_thr = drop_node[1] if drop_node else 0
+        self.edge_thr = drop_edge[1] if drop_edge else 0
+        self.mask_thr = feat_mask[1] if feat_mask else 0
+        # DropEdge behind an effective DropNode draws by the rank among the relation's surviving edges (ops.augment_graph's rule)
+        self.by_rank = int(self.node_thr > 0 and self.edge_thr > 0 and drop_edge[0] > drop_node[0])
+        # NodeShuffle: 0 none, 1 over the stored nodes (in front of DropNode, or no effective DropNode), 2 over DropNode's survivors
+        self.ns_mode = 0 if node_shuffle is None else (1 if (self.node_thr == 0 or node_shuffle[0] < drop_node[0]) else 2)
+
+    def node_keep(self, draw: int, counts: Sequence[int], device="cpu") -> List[torch.Tensor]:
+        """DropNode's keep flags of every node type under ``draw``, by the draw contract (bool [counts[t]])."""
+        from . import ops
+        if self.node_thr == 0:
+            return [torch.ones(int(n), dtype=torch.bool, device=device) for n in counts]
+        return [~ops.augment_drawn(int(n), ops.augment_subseed(draw, self.drop_node[0], t), self.node_thr, device) for t, n in enumerate(counts)]
+
+
+def restricted_orders(lay: SlotLayout, pieces: Sequence[PlanPieces], keeps: Sequence[Sequence[torch.Tensor]], sb: SlotBatch):
+    """The processing orders of an augmented slot: the order tables the unaugmented fill writes for the same slides (heavy destinations of every
+    slide, then the light ones; sources apart), restricted to the surviving nodes in the same relative order and renumbered; the filler's nodes
+    follow, ascending.  ``pieces``: the STORED slides'; ``keeps[b][t]``: DropNode's keep flags; ``sb``: the augmented batch's layout."""
+    T = lay.T
+    dev = keeps[0][0].device
+    node_tab = torch.tensor(sb.node_tab, dtype=torch.int64, device=dev)
+    new_id = [[torch.cumsum(k.to(torch.int64), 0) - 1 for k in kb] for kb in keeps]
+
+    def pick(b, l, t):
+        l, t = l.to(dev), t.to(dev)
+        out = []
+        for i in range(int(l.numel())):
+            li, ti = int(l[i]), int(t[i])
+            if bool(keeps[b][ti][li]):
+                out.append(int(node_tab[b * T + ti]) + int(new_id[b][ti][li]))
+        return out
+
+    dst = [x for b, pc in enumerate(pieces) for x in pick(b, pc.heavy_l, pc.heavy_t)] + [x for b, pc in enumerate(pieces) for x in pick(b, pc.light_l, pc.light_t)]
+    src = [x for b, pc in enumerate(pieces) for x in pick(b, pc.so_l, pc.so_t)]
+    fill = [sb.fb[t] + i for t in range(T) for i in range(sb.nf[t])]
+    return torch.tensor(dst + fill, dtype=torch.int32, device=dev), torch.tensor(src + fill, dtype=torch.int32, device=dev)
+
+
+def slot_fill_augmented(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: Sequence[PlanPieces], edges: Sequence[Sequence[Tuple[torch.Tensor, torch.Tensor]]],
+                        labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]], draws: Sequence[int], spec: AugmentSpec) -> None:
+    """Write the padded batch ``[transform(slide_b, draws[b]).., empty graphs.., filler]`` of the STORED slides ``pieces`` (per-relation COO
+    ``edges[b][j]`` in sorted relation order, fp32 feature tables ``feats[b][t]``) into the GPU slot's tables ``bufs``, drawing the augmentation on
+    the device: ONE descriptor upload, no read-back, no synchronisation, no atomics, scratch sized by the stored counts, ~20 launches whatever
+    the draw and the pipeline (csrc/slot_aug.hip; include/wsi_hgnn.h, wsi_slot_aug_*).  ``bufs["_aug"]`` keeps the scratch of the last fill
+    (``ncnt`` / ``fcnt``: the survivors' counts, for ``BatchSlot.counts``).  ``bufs["scales"]`` = row absmax of the filled feature table."""
+    from . import _native as N
+    from . import ops
+    dev = bufs["rowptr"].device
+    if dev.type != "cuda":
+        raise RuntimeError("slot_fill_augmented runs on the GPU only (HIP kernels); a CPU slot takes the tensor route (data.BatchSlot.load)")
+    if not SlotBatch.fits(lay, [pc.counts for pc in pieces], [pc.ecount for pc in pieces], True):
+        raise ValueError("the stored batch does not fit the slot")
+    T, hd, B, G, F = lay.T, lay.hd, len(pieces), lay.graphs, lay.in_dim
+    R = len(lay.rels)
+    tix = hd.tindex
+    seed = lambda st, draw, j: ops.augment_subseed(draw, st[0], j) if st else 0
+    n_st = [pc.counts[t] for pc in pieces for t in range(T)]                      # [b * T + t]
+    rel_sizes = [[int(edges[b][j][0].numel()) for j in range(R)] for b in range(B)]
+    # ---- wsi_augment_nodes / wsi_augment_edges rows
+    nwords, ntiles, noff = ops._segment_rows(n_st, lambda s: (seed(spec.drop_node, draws[s // T], s % T), spec.node_thr, 0))
+    nodes_stored = sum(n_st)
+
+    def erow(s):
+        b, j = divmod(s, R)
+        u, v = edges[b][j]
+        if u.dtype != torch.int64 or v.dtype != torch.int64 or not u.is_contiguous() or not v.is_contiguous() or u.device != dev:
+            raise ValueError("slot_fill_augmented: contiguous int64 COO on the slot's device")
+        sr, _, ds = lay.rels[j]
+        return (u.data_ptr(), v.data_ptr(), 0, noff[b * T + tix[sr]], noff[b * T + tix[ds]], seed(spec.drop_edge, draws[b], j), spec.edge_thr,
+                spec.by_rank, pieces[b].counts[tix[sr]], pieces[b].counts[tix[ds]], 0)
+
+    ewords, etiles, eoff = ops._segment_rows([m for rs in rel_sizes for m in rs], erow)
+    coo_total = sum(sum(rs) for rs in rel_sizes)
+    coo_base = [eoff[b * R] if R else 0 for b in range(B)]
+    # ---- flag segments (what is scanned) and push segments (what the real slides write)
+    maps = [pc.coo_maps(rel_sizes[b]) for b, pc in enumerate(pieces)]
+    flag_n, flag_extra = [], []
+    for b, pc in enumerate(pieces):
+        for t in range(T):
+            flag_n.append(pc.ecount[t]); flag_extra.append((0, maps[b][0][t].data_ptr(), 0, b, 0))
+    for b, pc in enumerate(pieces):
+        for t in range(T):
+            flag_n.append(pc.ccount[t]); flag_extra.append((0, maps[b][1][t].data_ptr(), 0, b, 0))
+    for l_, t_ in (("heavy_l", "heavy_t"), ("light_l", "light_t"), ("so_l", "so_t")):
+        for b, pc in enumerate(pieces):
+            flag_n.append(int(getattr(pc, l_).numel())); flag_extra.append((1, getattr(pc, l_).data_ptr(), getattr(pc, t_).data_ptr(), b, 0))
+    fwords, ftiles, foff = ops._segment_rows(flag_n, lambda s: flag_extra[s])
+    flag_total = sum(flag_n)
+    pwords, blocks, npush = [], 0, 0
+
+    def push(n, kind, b, t, ptrs, fseg):
+        nonlocal blocks, npush
+        if n > 0:
+            pwords.extend([int(n), blocks, kind, b, t] + [p.data_ptr() for p in ptrs] + [0] * (4 - len(ptrs)) + [fseg])
+            blocks += (int(n) + 1023) // 1024
+            npush += 1
+
+    aligned = bufs["feat"].data_ptr() % 16 == 0
+    xwords = []
+    for b, pc in enumerate(pieces):
+        for t in range(T):
+            Rt = hd.R[t]
+            push(pc.counts[t], 0, b, t, [pc.rp[t], pc.cp[t]], 0)
+            push(pc.ecount[t], 1, b, t, [pc.src_l[t], pc.src_t[t], pc.sim[t], _piece_edge_seg(pc, t, Rt) if pc.ecount[t] else pc.src_l[t]], b * T + t)
+            push(pc.ccount[t], 2, b, t, [pc.eid_l[t], pc.ent_t[t], pc.dst_l[t]], B * T + b * T + t)
+            x = feats[b][t]
+            if pc.counts[t] and (x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (pc.counts[t], F) or x.device != dev):
+                raise ValueError("slot_fill_augmented: features must be contiguous fp32 [nodes, in_dim] tables on the slot's device")
+            aligned = aligned and (pc.counts[t] == 0 or x.data_ptr() % 16 == 0)
+            xwords += [x.data_ptr() if pc.counts[t] else 0, pc.counts[t], seed(spec.feat_mask, draws[b], t)]
+        push(int(pc.heavy_l.numel()), 3, b, 0, [pc.heavy_l, pc.heavy_t], 2 * B * T + b)
+        push(int(pc.light_l.numel()), 4, b, 0, [pc.light_l, pc.light_t], 2 * B * T + B + b)
+        push(int(pc.so_l.numel()), 5, b, 0, [pc.so_l, pc.so_t], 2 * B * T + 2 * B + b)
+    shape = [T, B, lay.b_cap, READOUT_CHUNK, lay.c_cap]
+    for t in range(T):
+        shape += [lay.n_cap[t], lay.e_cap[t], hd.type_off[t], lay.ebase[t], lay.src_type[t], hd.R[t], hd.seg_off[t]]
+    misc = list(noff) + n_st + coo_base + [int(y) for y in labels] + [-100] * (G - B) + [seed(spec.node_shuffle, draws[s // T], s % T) for s in range(B * T)]
+    words, offs = [], {}
+    for name, part in (("node", nwords), ("edge", ewords), ("flag", fwords), ("push", pwords), ("feat", xwords), ("shape", shape), ("misc", misc)):
+        offs[name] = len(words)
+        words += part
+    desc = host_to_device(words, torch.int64, dev)
+    i32 = lambda m: torch.empty(max(int(m), 1), dtype=torch.int32, device=dev)
+    i64 = lambda m: torch.empty(max(int(m), 1), dtype=torch.int64, device=dev)
+    sc = {"desc": desc, "new_id": i32(nodes_stored), "kept": i64(nodes_stored), "ncnt": i32(B * T), "tsum_n": i32(ntiles + 1), "rank1": i32(coo_total),
+          "tsum_e": i32(2 * (etiles + 1)), "out_u": i64(coo_total), "out_v": i64(coo_total), "out_eid": i64(coo_total),
+          "out_sim": torch.empty(max(coo_total, 1), dtype=torch.float32, device=dev), "ecnt_rel": i32(B * R), "ftile": i32(ftiles + 1),
+          "frank": i32(flag_total), "fcnt": i32(len(flag_n)), "keys": i64(nodes_stored), "L": i64(4 * B * T + 9 * T + 3 * B + 2), "maps": maps}
+    lib = N.load()
+    st = N.stream()
+    dp = desc.data_ptr()
+    N.check(lib.wsi_augment_nodes(dp + 8 * offs["node"], B * T, ntiles, N.ptr(sc["tsum_n"]), N.ptr(sc["new_id"]), N.ptr(sc["kept"]), N.ptr(sc["ncnt"]), st),
+            "wsi_augment_nodes")
+    if R > 0:
+        N.check(lib.wsi_augment_edges(dp + 8 * offs["edge"], B * R, etiles, N.ptr(sc["new_id"]), N.ptr(sc["tsum_e"]), N.ptr(sc["rank1"]), N.ptr(sc["out_u"]),
+                                      N.ptr(sc["out_v"]), N.ptr(sc["out_sim"]), N.ptr(sc["out_eid"]), N.ptr(sc["ecnt_rel"]), st), "wsi_augment_edges")
+    import ctypes
+    names = ("desc", "off_node", "off_edge", "off_flag", "off_push", "off_feat", "off_shape", "off_misc", "B", "T", "R", "N", "S", "E", "G", "nflag",
+             "flag_tiles", "npush", "push_blocks", "nodes_stored", "ns_mode", "F", "mask_thr", "feat_aligned", "new_id", "kept", "ncnt", "rank1", "ftile",
+             "frank", "fcnt", "keys", "perm", "L", "rowptr", "colptr", "node_seg", "src", "csc_eid", "csc_dst", "order_dst", "order_src", "sim", "inv_rd",
+             "readout_ptr", "labels", "feat", "edge_seg", "row_seg", "chunk_row", "chunk_seg", "seg_chunk", "seg_counts", "seg_inv_counts", "seg_nonempty")
+    val = {"desc": dp, "B": B, "T": T, "R": R, "N": lay.N, "S": lay.S, "E": lay.E, "G": G, "nflag": len(flag_n), "flag_tiles": ftiles, "npush": npush,
+           "push_blocks": blocks, "nodes_stored": nodes_stored, "ns_mode": spec.ns_mode, "F": F, "mask_thr": spec.mask_thr, "feat_aligned": int(aligned), "perm": 0}
+    val.update({"off_" + k: v for k, v in offs.items()})
+    val.update({k: sc[k].data_ptr() for k in ("new_id", "kept", "ncnt", "rank1", "ftile", "frank", "fcnt", "keys", "L")})
+    val.update({k: bufs[k].data_ptr() for k in names[34:]})
+    args = (ctypes.c_int64 * len(names))(*[val[k] for k in names])                # the 55 argument words of wsi_slot_aug_* (include/wsi_hgnn.h)
+    N.check(lib.wsi_slot_aug_keys(ctypes.addressof(args), st), "wsi_slot_aug_keys")
+    sc["perm"] = torch.sort(sc["keys"][:nodes_stored], stable=True).indices if nodes_stored else sc["keys"]
+    args[names.index("perm")] = sc["perm"].data_ptr()
+    N.check(lib.wsi_slot_aug_scan(ctypes.addressof(args), st), "wsi_slot_aug_scan")
+    N.check(lib.wsi_slot_aug_write(ctypes.addressof(args), st), "wsi_slot_aug_write")
+    N.check(lib.wsi_row_absmax(N.ptr(bufs["feat"]), F, lay.N, F, N.ptr(bufs["scales"]), st), "wsi_row_absmax")
+    bufs["_aug"] = sc                # (stream-ordered: descriptors and scratch must outlive the launches; the next fill replaces them behind this one)
 
 
 def slot_plan(lay: SlotLayout, bufs: Dict[str, torch.Tensor], locality: bool = False) -> GraphPlan:

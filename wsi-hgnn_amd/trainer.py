@@ -172,7 +172,11 @@ class CapturedSlotStep:
     here on ``warmup_batches[i]`` for slot i (default: the slot's first fitting batch of one slide) - the optimizer must be capturable, and
     train-mode dropout must be the HEAT layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4 with a sum / mean /
     max readout: HGT builds its per-relation-source plan from the batch's COO on the host, and the attention readout reads host-side node
-    counts - both are refused."""
+    counts - both are refused.
+
+    Slots over a loader with a slot-compatible ``transform=`` (``data.slot_augment_spec``) are AUGMENTED: every ``step`` fills its slot with a fresh
+    draw taken on the device (no read-back) in front of the replay, a batch no slot fits goes through ``loader._augmented``, and either way the
+    loader's batch counter advances exactly once per step - under one seed the trajectory follows the eager loader's draws."""
 
     def __init__(self, gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_fcn, slots, warmup: int = 1, warmup_batches=None):
         from .data import BatchSlot
@@ -268,9 +272,12 @@ class CapturedSlotStep:
         i = self.slot_for(idxs)
         self.steps_taken += 1
         if i is None:                                          # fits no slot: the loader's ordinary batch, stepped eagerly
-            G, labels, ready = self.loader._assemble(idxs, 0)
-            if ready is not None:
-                torch.cuda.current_stream(self.loader.device).wait_event(ready)
+            if self.loader.transform is not None:              # (augmented: the general route; it advances the loader's batch counter as a fill does)
+                G, labels = self.loader._augmented(idxs)
+            else:
+                G, labels, ready = self.loader._assemble(idxs, 0)
+                if ready is not None:
+                    torch.cuda.current_stream(self.loader.device).wait_event(ready)
             self.eager_steps += 1
             return self._eager(G, labels)
         slot = self.slots[i]
