@@ -521,22 +521,11 @@ int wsi_pool_bwd_bias(const float* gt_seg, int32_t T, int32_t S, int32_t D, int3
                       float* beta, float* gbv, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Kernel plan of a block-diagonal batch (`dgl.batch` + `g.to(device)` in front of every step of a loader-fed run: trainer/train_gnn.py:48-65):
- * every table of the batch's plan (rowptr, colptr, src, csc_eid, csc_dst, sim, the processing orders, node_seg, inv_rd) is a concatenation of
- * per-graph pieces with per-piece offsets - ONE launch over a table of segment descriptors.  desc: DEVICE array of int64, nsegs rows of 10 words
+ * Segment descriptor tables (csrc/segment_table.hip): tables written from pieces in ONE launch.  desc: DEVICE array of int64, nsegs rows of 10 words
  *   [out, in1, in2, tab_off, key, add, stride, n, mode, block_start]
- * followed by the lookup tables the tab_off's index (in words from desc).  Segment s writes n elements:
+ * followed by the lookup tables the tab_off's index (in words from desc; tab_off < 0: none).  Segment s writes n elements:
  *   mode 0 (int32 out):  out[i] = (in1 ? in1[i] : 0) + add + i * stride + (tab_off >= 0 ? desc[tab_off + key + (in2 ? in2[i] : 0)] : 0)     (in1, in2: int64)
- *   mode 1 (float out):  out[i] = ((const float*)in1)[i]
- *   mode 2 (float out):  out[i] = the float whose bits are the low 32 bits of add
- * block_start = number of 1024-element blocks of the segments before it (segments with n = 0 are not listed); total_blocks = their sum. */
-int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
-
-/* ------------------------------------------------------------------------------------------------
- * Fill of a padded batch slot (data.BatchSlot): plan, readout tables, labels and type-major features of "the real slides, empty graphs up to the
- * slot's capacity, one filler graph" written into caller-owned STATIC buffers, so that a step captured over them replays over every batch that
- * fits.  One launch over a descriptor table in wsi_plan_assemble's format (same 10 words, same block_start rule), with these modes:
- *   mode 0  as wsi_plan_assemble                 mode 1  4-byte copy out[i] = in1[i]            mode 2  4-byte fill with the low 32 bits of add
+ *   mode 1  4-byte copy out[i] = in1[i]                                      mode 2  4-byte fill with the low 32 bits of add
  *   mode 3 (int32 out):  out[i] = desc[tab_off + key + i]                    mode 4 (int64 out):  out[i] = desc[tab_off + key + i]
  *   mode 5 (16-byte elements, both pointers 16-byte aligned):  out[i] = in1[i], or zero when in1 is NULL (the feature rows)
  *   modes 10 / 11 / 13 (int32 out): rowptr of the filler's segments / src of its edges / colptr of its sources, for node type `key`, by index
@@ -544,7 +533,17 @@ int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, 
  *   relation slot 0, relation slots, first filler CSC entry] (csrc/slot_math.h; the filler graph: graph.filler_graph)
  *   mode 14 (int32 out): out[i] = add + stride * (local destination of the filler's i-th edge into node type `key`)
  *   mode 12: element i = the filler's i-th edge into node type `key`; writes its CSC entry into the WHOLE tables out (csc_eid) and in1 (csc_dst)
- * No allocation, no synchronisation, no read-back; everything on `stream`. */
+ * block_start = number of 1024-element blocks of the segments before it (segments with n = 0 are not listed); total_blocks = their sum.
+ * No allocation, no synchronisation, no read-back; everything on `stream`.  Host side: graph.SegmentTable.
+ *
+ * wsi_plan_assemble - kernel plan of a block-diagonal batch (`dgl.batch` + `g.to(device)` in front of every step of a loader-fed run:
+ * trainer/train_gnn.py:48-65): every table of the batch's plan (rowptr, colptr, src, csc_eid, csc_dst, sim, the processing orders, node_seg,
+ * inv_rd) is a concatenation of per-graph pieces with per-piece offsets.  Accepts modes 0-2.
+ *
+ * wsi_slot_fill - fill of a padded batch slot (data.BatchSlot): plan, readout tables, labels and type-major features of "the real slides, empty
+ * graphs up to the slot's capacity, one filler graph" written into caller-owned STATIC buffers, so that a step captured over them replays over
+ * every batch that fits.  Accepts every mode. */
+int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
 int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
-"""Padded batch slots on the GPU: the fill kernel (csrc/slot.hip) against graph.slot_fill_torch bit for bit, and one captured step
-per slot (trainer.CapturedSlotStep) replayed over new slides against eager steps on the same slots.  Fixture: tests/slot_cases.py."""
+"""Padded batch slots on the GPU: the fill kernel (csrc/segment_table.hip) against graph.slot_fill_torch bit for bit, its descriptor
+contract (include/wsi_hgnn.h, graph.SegmentTable) by hand, and one captured step per slot (trainer.CapturedSlotStep) replayed over new slides
+against eager steps on the same slots.  Fixture: tests/slot_cases.py."""
 import pytest
 import torch
 
@@ -45,6 +46,110 @@ def test_slot_fill_kernel_equals_the_tensor_operations_bit_for_bit(ld):
                 assert torch.equal(got.view(torch.int32) if got.dtype == torch.float32 else got, v.view(torch.int32) if v.dtype == torch.float32 else v), (idxs, k)
         assert torch.equal(slot.bufs["scales"], ops.row_absmax(slot.bufs["feat"])), idxs      # a valid scale on every row, the zero rows included
         assert slot.num_real == len(idxs) and slot.labels.tolist()[:len(idxs)] == [C.LABELS[i] for i in idxs]
+
+
+POISON = -0x5A5A5A5B                          # int32 0xA5A5A5A5: what an element no segment owns must still hold
+
+
+def _hand_table(out):
+    """A SegmentTable by hand over ``out`` (int32, poisoned) and what the header's formulas give for it, evaluated directly: mode 0 in the four
+    combinations of in1 and in2 + tab, modes 1 and 2; lengths at the 1024-element block edges, interleaved; one unowned element between any two
+    segments.  Two lookup tables, the second behind the first, so that ``tab_off`` differs from the handle's offset alone."""
+    from wsi_hgnn_amd import graph as G
+    dev = out.device
+    tb = G.SegmentTable("test")
+    lut = [7, -3, 100]
+    far = [1000, 2000, -4000, 8000]
+    h_lut, h_far = tb.table("lut", lut), tb.table("far", far)
+    assert (h_lut, h_far) == (0, 3)
+    words = lut + far
+    exp = torch.full((out.numel(),), POISON, dtype=torch.int64)
+    gen = torch.Generator().manual_seed(5)
+    keep = []                                 # the sources stay alive until the caller has synchronised
+    lengths = [1, 1023, 1024, 1025, 2049]
+    nan, neg0 = 0x7FC12345, -0x80000000       # a quiet NaN with a payload; -0.0 as the signed word graph._float_bits gives
+    off = 1
+    for k in range(12):
+        n, kind = lengths[(2 * k + k // 6) % 5], k % 6
+        i = torch.arange(n, dtype=torch.int64)
+        if kind < 4:                          # mode 0: add + i * stride + in1[i] + tab[key + in2[i]]
+            add, stride = 11 + k, 3 - k
+            in1 = torch.randint(-500, 500, (n,), generator=gen, dtype=torch.int64) if kind & 1 else None
+            v = add + i * stride + (in1 if in1 is not None else 0)
+            kw = {}
+            if kind & 2:
+                tab, key, size = ((h_lut, 1, 3) if k < 6 else (h_far, 2, 4))
+                in2 = torch.randint(0, size - key, (n,), generator=gen, dtype=torch.int64)
+                v = v + torch.tensor(words, dtype=torch.int64)[tab + key + in2]
+                kw = dict(in2=in2.to(dev), tab=tab, key=key)
+                keep.append(kw["in2"])
+            if in1 is not None:
+                kw["in1"] = in1.to(dev)
+                keep.append(kw["in1"])
+            tb.seg(out, off, n, add=add, stride=stride, mode=0, **kw)
+        elif kind == 4:                       # mode 1: the same 32 bits, whatever float they spell
+            bits = torch.randint(-2 ** 31, 2 ** 31, (n,), generator=gen, dtype=torch.int64)
+            bits[0], bits[n - 1] = nan, neg0
+            v = bits
+            src = bits.to(torch.int32).view(torch.float32).to(dev)
+            keep.append(src)
+            tb.seg(out, off, n, in1=src, mode=1)
+        else:                                 # mode 2: the low 32 bits of add
+            add = nan if k < 6 else neg0
+            v = torch.full((n,), add, dtype=torch.int64)
+            tb.seg(out, off, n, add=add, mode=2)
+        before = tb.nsegs
+        tb.seg(out, off, 0, add=1)            # n = 0: no row
+        assert tb.nsegs == before == k + 1
+        exp[off:off + n] = v
+        off += n + 1
+    assert off <= out.numel()
+    wrap = lambda x: ((x + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)
+    assert tb.blocks == sum((s_[7] + 1023) // 1024 for s_ in tb.segs) and {s_[7] for s_ in tb.segs} == set(lengths)
+    return tb, wrap(exp), keep
+
+
+def test_segment_descriptor_contract_through_both_entry_points(ld):
+    """The descriptor contract of include/wsi_hgnn.h itself, not through the graph functions: one hand-built table launched through
+    wsi_plan_assemble and through wsi_slot_fill into separate outputs; both equal the direct evaluation of the header's formulas and each other,
+    exactly (every unowned element still poisoned).  An empty table is OK without a launch; a segment that leaves its output raises before
+    anything is launched, in assemble_plan and in ReducePlan.row_segment as well."""
+    from wsi_hgnn_amd import _native as N, graph as G, ops
+    dev = _dev()
+    lib = N.load()
+    total = 12 + 2 * (1 + 1023 + 1024 + 1025 + 2049) + 2049 + 8
+    outs = {}
+    for name in ("wsi_plan_assemble", "wsi_slot_fill"):
+        out = torch.full((total,), POISON, dtype=torch.int32, device=dev)
+        tb, exp, keep = _hand_table(out)          # (keep: the sources, alive until the synchronise below)
+        desc = tb.upload(dev)
+        N.check(getattr(lib, name)(N.ptr(desc), tb.nsegs, tb.blocks, N.stream()), name)
+        torch.cuda.synchronize()
+        outs[name] = out.cpu()
+        assert torch.equal(outs[name], exp), name
+        # nothing to do: OK, and nothing written
+        empty = G.SegmentTable("test")
+        empty.seg(out, 0, 0)
+        assert empty.nsegs == 0 and empty.blocks == 0
+        assert getattr(lib, name)(None, 0, 0, N.stream()) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(out.cpu(), exp), name
+        with pytest.raises(RuntimeError, match="leaves the table"):
+            tb.seg(out, total - 4, 5, add=1)
+        with pytest.raises(RuntimeError, match="reads past its source"):
+            tb.seg(out, 0, 5, in1=torch.zeros(4, dtype=torch.int64, device=dev))
+    assert torch.equal(outs["wsi_plan_assemble"], outs["wsi_slot_fill"])
+    # the two callers that launched unchecked pointers: pieces larger than the header they are assembled under ...
+    small, large = ld.items[4], ld.items[0]
+    hd = G.PlanHeader(small.ntypes, small.rels, list(small.num_nodes))
+    with pytest.raises(RuntimeError, match="plan_assemble: a segment leaves the table"):
+        G.assemble_plan(hd, [large.pieces], dev, [[n] for n in small.num_nodes])
+    # ... and a row range past the plan's rows
+    rp = ops.ReducePlan.from_ptr([0, 5, 1030], dev)
+    rp.ranges[-1] = (5, 1031)
+    with pytest.raises(RuntimeError, match="row_segment: a segment leaves the table"):
+        rp.row_segment()
+    assert rp._row_seg is None
 
 
 def _make(name="HEATNet4", hidden=64, drop=0.0, train=False):

@@ -1,15 +1,15 @@
-// Fill of a padded batch slot (data.BatchSlot, graph.slot_fill): the kernel plan, the readout tables, the labels and the type-major
-// feature table of "the real slides, then empty graphs, then one filler graph" written into the slot's STATIC buffers, so that a training step
-// captured once over those buffers replays over any batch that fits.  ONE launch over a table of segment descriptors, in the format of
-// wsi_plan_assemble (csrc/plan.hip) with more modes: the real slides' parts are offset copies of their stored pieces, the filler's parts are
-// index arithmetic (csrc/slot_math.h), the features a 16-byte streaming copy.  Contract: include/wsi_hgnn.h (wsi_slot_fill).
+// Tables written from pieces: ONE launch over a table of segment descriptors, every segment a run of elements that are an offset copy of a stored
+// piece, a lookup, a fill or index arithmetic.  Two users, one kernel: the kernel plan of a block-diagonal batch (graph.assemble_plan,
+// wsi_plan_assemble: ~90 framework launches per new batch as tensor operations) and the fill of a padded batch slot (data.BatchSlot,
+// graph.slot_fill, wsi_slot_fill), whose filler parts are index arithmetic (csrc/slot_math.h) and whose features are a 16-byte
+// streaming copy.  Contract: include/wsi_hgnn.h (segment descriptor tables).
 #include "common.h"
 #include "slot_math.h"
 
 namespace wsi {
 
-constexpr int SLOT_ROW = 10;              // int64 words per segment descriptor
-constexpr int SLOT_BLOCK = 1024;          // elements per workgroup (modes 5: 16-byte elements)
+constexpr int SEG_ROW = 10;               // int64 words per segment descriptor
+constexpr int SEG_BLOCK = 1024;           // elements per workgroup (modes 5: 16-byte elements)
 
 // desc (device, int64): per segment  [out, in1, in2, tab_off, key, add, stride, n, mode, block_start], then the tables the tab_off's point into.
 //  mode 0  int32 out[i] = add + i * stride + in1[i] + tab[in2[i]]        (in1, in2: int64 arrays or null; tab = desc + tab_off + key)
@@ -20,21 +20,21 @@ constexpr int SLOT_BLOCK = 1024;          // elements per workgroup (modes 5: 16
 //  mode 10 rowptr of the filler's segments      mode 11 src of the filler's edges      mode 13 colptr of the filler's sources
 //  mode 14 out[i] = add + stride * (destination of the filler's i-th edge): the softmax segment of every filler edge
 //  mode 12 CSC entries of the filler's edges: out = csc_eid and in1 = csc_dst, the WHOLE tables (the entry's position is computed)
-__global__ __launch_bounds__(256) void slot_fill_kernel(const int64_t* __restrict__ desc, int nsegs) {
+__global__ __launch_bounds__(256) void segment_table_kernel(const int64_t* __restrict__ desc, int nsegs) {
     const int b = blockIdx.x;
     int lo = 0, hi = nsegs - 1;           // last segment whose block_start <= b
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (desc[(int64_t)mid * SLOT_ROW + 9] <= b) lo = mid; else hi = mid - 1;
+        if (desc[(int64_t)mid * SEG_ROW + 9] <= b) lo = mid; else hi = mid - 1;
     }
-    const int64_t* d = desc + (int64_t)lo * SLOT_ROW;
+    const int64_t* d = desc + (int64_t)lo * SEG_ROW;
     const int64_t n = d[7];
     const int mode = (int)d[8];
-    const int64_t i0 = ((int64_t)b - d[9]) * SLOT_BLOCK;
+    const int64_t i0 = ((int64_t)b - d[9]) * SEG_BLOCK;
     const int64_t* tab = d[3] >= 0 ? desc + d[3] : nullptr;
     const int64_t key = d[4], add = d[5], stride = d[6];
 #pragma unroll
-    for (int r = 0; r < SLOT_BLOCK / 256; ++r) {
+    for (int r = 0; r < SEG_BLOCK / 256; ++r) {
         const int64_t i = i0 + r * 256 + threadIdx.x;          // a wave's 64 lanes: 64 consecutive elements (modes 5: one contiguous KB)
         if (i >= n) break;
         switch (mode) {
@@ -78,14 +78,22 @@ __global__ __launch_bounds__(256) void slot_fill_kernel(const int64_t* __restric
     }
 }
 
+static int launch_segment_table(const char* who, const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
+    if (nsegs < 0 || total_blocks < 0) { set_error("%s: bad argument", who); return WSI_EINVAL; }
+    if (nsegs == 0 || total_blocks == 0) return WSI_OK;
+    if (!desc) { set_error("%s: null pointer", who); return WSI_EINVAL; }
+    hipLaunchKernelGGL(segment_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, desc, (int)nsegs);
+    return check_launch(who);
+}
+
 }  // namespace wsi
 
 using namespace wsi;
 
+extern "C" int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
+    return launch_segment_table("plan_assemble", desc, nsegs, total_blocks, stream);
+}
+
 extern "C" int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
-    if (nsegs < 0 || total_blocks < 0) { set_error("slot_fill: bad argument"); return WSI_EINVAL; }
-    if (nsegs == 0 || total_blocks == 0) return WSI_OK;
-    if (!desc) { set_error("slot_fill: null pointer"); return WSI_EINVAL; }
-    hipLaunchKernelGGL(slot_fill_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, desc, (int)nsegs);
-    return check_launch("slot_fill");
+    return launch_segment_table("slot_fill", desc, nsegs, total_blocks, stream);
 }

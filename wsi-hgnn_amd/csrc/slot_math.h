@@ -1,4 +1,4 @@
-// Closed forms of the FILLER graph of a padded batch slot (graph.filler_graph), shared by the fill kernel (csrc/slot.hip) and by the
+// Closed forms of the FILLER graph of a padded batch slot (graph.filler_graph), shared by the fill kernel (csrc/segment_table.hip) and by the
 // host program that checks them against a sort (tests/slot_math_check.cpp).  Plain integer arithmetic, no device intrinsics.
 //
 // The filler has nf[t] nodes of every node type t and, for every destination type t with ef[t] > 0, ef[t] edges in relation slot 0 of t, whose

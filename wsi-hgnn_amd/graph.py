@@ -22,9 +22,11 @@ plain COO tensors.
 """
 from __future__ import annotations
 
+import array
 import collections
 
 import os
+import struct
 
 import contextlib
 from collections import OrderedDict
@@ -478,6 +480,54 @@ def host_to_device(values, dtype, device) -> torch.Tensor:
     return arena.stage(t, device)
 
 
+class SegmentTable:
+    """Host builder of a segment descriptor table (include/wsi_hgnn.h, "Segment descriptor tables"): rows of ten words
+    ``[out, in1, in2, tab_off, key, add, stride, n, mode, block_start]``, then the lookup tables.  Every segment is checked against the bounds of
+    the table it writes before anything is launched.  ``who`` names the caller in the error messages.  Plain lists: this runs per batch."""
+
+    def __init__(self, who: str):
+        self.who, self.segs, self.tabs, self.names, self.blocks = who, [], [], {}, 0       # blocks: 1024-element blocks of the launch
+
+    def table(self, name: str, words: Sequence[int]) -> int:
+        """Register a lookup table behind the descriptors; the handle (also ``names[name]``) is what ``seg(tab=...)`` takes."""
+        self.names[name] = len(self.tabs)
+        self.tabs += words
+        return self.names[name]
+
+    def seg(self, out: torch.Tensor, off, n, in1=None, in2=None, tab=None, key=0, add=0, stride=0, mode=0, esize=4) -> None:
+        """``n`` elements of ``esize`` bytes from element ``off`` of ``out`` (all numbers Python ints); nothing for ``n == 0``.  ``in1``: a tensor,
+        or a raw pointer (mode 12's second output)."""
+        if n <= 0:
+            return
+        if off < 0 or (off + n) * esize > out.nbytes:
+            raise RuntimeError(f"{self.who}: a segment leaves the table it writes ({off} + {n} elements of {esize} bytes into {out.nbytes} bytes)")
+        if in1 is None or isinstance(in1, int):
+            p1 = in1 or 0
+        else:
+            if mode in (0, 1, 5) and in1.nbytes < n * (8 if mode == 0 else esize):
+                raise RuntimeError(f"{self.who}: a segment reads past its source ({n} elements from {in1.nbytes} bytes)")
+            p1 = in1.data_ptr()
+        self.segs.append([out.data_ptr() + off * esize, p1, 0 if in2 is None else in2.data_ptr(), -1 if tab is None else tab,
+                          key, add, stride, n, mode, self.blocks])
+        self.blocks += (n + 1023) // 1024
+
+    @property
+    def nsegs(self) -> int:
+        return len(self.segs)
+
+    def upload(self, dev) -> torch.Tensor:
+        """The device table (ONE upload), ``tab_off`` counted from the table's start.  The caller keeps it alive until the launch has run."""
+        tab0 = len(self.segs) * 10
+        words: List[int] = []
+        for s_ in self.segs:
+            words += s_
+            if s_[3] >= 0:
+                words[-7] += tab0
+        words += self.tabs
+        # (through array: torch.tensor walks a list of Python ints at twice the cost)
+        return host_to_device(torch.frombuffer(array.array("q", words), dtype=torch.int64), torch.int64, dev)
+
+
 def _count(idx: torch.Tensor, size: int) -> torch.Tensor:
     """``torch.bincount(idx, minlength=size)`` without its device->host sync (bincount reads max(idx) on the host)."""
     out = torch.zeros(size, dtype=torch.int64, device=idx.device)
@@ -544,15 +594,36 @@ def set_plan_options(heavy_degree: Optional[int] = None, heavy_degree_locality: 
         LOCALITY = bool(locality)
 
 
+def _new_plan(hd: PlanHeader, dev) -> GraphPlan:
+    """An empty plan with the fields that come from the header alone."""
+    p = GraphPlan()
+    p.device = dev
+    p.type_off, p.num_nodes, p.rel_slots, p.num_segs, p.rel_rows = hd.type_off, hd.N, hd.R, hd.S, list(hd.rel_rows)
+    return p
+
+
+def _set_readout_ptr(p: GraphPlan, hd: PlanHeader, batch_counts: List[List[int]]) -> None:
+    """``batch_size`` and the readout pointers (first row of every (node type, graph)) of ``batch_counts[type][graph]``."""
+    B = len(batch_counts[0]) if batch_counts else 1
+    p.batch_size = B
+    ptr = [0]
+    for ti in range(len(hd.ntypes)):
+        base, acc = hd.type_off[ti], 0
+        for b in range(B):
+            acc += int(batch_counts[ti][b])
+            ptr.append(base + acc)
+        if acc != hd.counts[ti]:
+            raise ValueError(f"batch_num_nodes of type {hd.ntypes[ti]} does not sum to its node count")
+    p.readout_ptr = host_to_device(ptr, torch.int32, p.device)
+
+
 def finish_plan(hd: PlanHeader, gsrc, gdst, gseg, dev, per_relation_src: bool,
                 batch_counts: List[List[int]], max_in_degree: Optional[int] = None, pos: Optional[torch.Tensor] = None) -> GraphPlan:
     """Device part of the plan from the concatenated global edge arrays (int64, any order): CSR by (dst, relation slot),
     CSC by source row, degree orders, readout pointers.  No device->host synchronisation when the caller knows
     ``max_in_degree`` (the loader does, per stored graph); otherwise it is read back once (one sync per plan)."""
-    p = GraphPlan()
-    p.device = dev
+    p = _new_plan(hd, dev)
     N, S = hd.N, hd.S
-    p.type_off, p.num_nodes, p.rel_slots, p.num_segs, p.rel_rows = hd.type_off, N, hd.R, S, list(hd.rel_rows)
     node_seg = torch.empty(N + 1, dtype=torch.int64, device=dev)
     inv_rd = torch.empty(N, dtype=torch.float32, device=dev)
     for ti in range(len(hd.ntypes)):
@@ -632,15 +703,7 @@ def finish_plan(hd: PlanHeader, gsrc, gdst, gseg, dev, per_relation_src: bool,
         p.order_dst = torch.sort(kd, stable=True).indices.to(torch.int32).contiguous()
         p.order_src = torch.sort(gid[:NS] * big + (E - outdeg), stable=True).indices.to(torch.int32).contiguous() \
             if NS == N else torch.sort(outdeg, descending=True, stable=True).indices.to(torch.int32).contiguous()
-    ptr = [0]
-    for ti in range(len(hd.ntypes)):
-        base, acc = hd.type_off[ti], 0
-        for b in range(B):
-            acc += int(batch_counts[ti][b])
-            ptr.append(base + acc)
-        if acc != hd.counts[ti]:
-            raise ValueError(f"batch_num_nodes of type {hd.ntypes[ti]} does not sum to its node count")
-    p.readout_ptr = host_to_device(ptr, torch.int32, dev)
+    _set_readout_ptr(p, hd, batch_counts)
     return p
 
 
@@ -730,10 +793,8 @@ class PlanPieces:
 
 def plan_frame(hd: PlanHeader, dev, batch_counts: List[List[int]]) -> GraphPlan:
     """The parts of a plan that depend on the node counts only: node_seg, inv_rd, readout pointers."""
-    p = GraphPlan()
-    p.device = dev
+    p = _new_plan(hd, dev)
     N, S = hd.N, hd.S
-    p.type_off, p.num_nodes, p.rel_slots, p.num_segs, p.rel_rows = hd.type_off, N, hd.R, S, list(hd.rel_rows)
     node_seg = torch.empty(N + 1, dtype=torch.int64, device=dev)
     inv_rd = torch.empty(N, dtype=torch.float32, device=dev)
     for ti in range(len(hd.ntypes)):
@@ -744,37 +805,72 @@ def plan_frame(hd: PlanHeader, dev, batch_counts: List[List[int]]) -> GraphPlan:
     node_seg[N:].fill_(S)        # (not `node_seg[N] = S`: a scalar __setitem__ is a synchronising pageable copy)
     p.node_seg = node_seg.to(torch.int32).contiguous()
     p.inv_rd = inv_rd.contiguous()
-    B = len(batch_counts[0]) if batch_counts else 1
-    p.batch_size = B
-    ptr = [0]
-    for ti in range(len(hd.ntypes)):
-        base, acc = hd.type_off[ti], 0
-        for b in range(B):
-            acc += int(batch_counts[ti][b])
-            ptr.append(base + acc)
-        if acc != hd.counts[ti]:
-            raise ValueError(f"batch_num_nodes of type {hd.ntypes[ti]} does not sum to its node count")
-    p.readout_ptr = host_to_device(ptr, torch.int32, dev)
+    _set_readout_ptr(p, hd, batch_counts)
     return p
 
 
-def _plan_frame_host(hd: PlanHeader, dev, batch_counts: List[List[int]]) -> GraphPlan:
-    """plan_frame without its device tables (node_seg, inv_rd: written by the assembly kernel)."""
-    p = GraphPlan()
-    p.device = dev
-    p.type_off, p.num_nodes, p.rel_slots, p.num_segs, p.rel_rows = hd.type_off, hd.N, hd.R, hd.S, list(hd.rel_rows)
-    B = len(batch_counts[0]) if batch_counts else 1
-    p.batch_size = B
-    ptr = [0]
-    for ti in range(len(hd.ntypes)):
-        base, acc = hd.type_off[ti], 0
+def _batch_offsets(hd: PlanHeader, pieces: Sequence[PlanPieces], batch_counts: List[List[int]]):
+    """Where the pieces go in a dense block-diagonal batch: ``pre[b][t]`` nodes of type t in front of slide b, ``node_tab[b*T + t]`` the first
+    global id of (slide, type), ``eoff / coff[(t, b)]`` the first CSR edge / CSC entry of the piece, ``edge_tab[b*T + t]``, the edge count."""
+    T, B = len(hd.ntypes), len(pieces)
+    pre = [[0] * T for _ in range(B + 1)]
+    for b in range(B):
+        for t in range(T):
+            pre[b + 1][t] = pre[b][t] + batch_counts[t][b]
+    node_tab = [hd.type_off[t] + pre[b][t] for b in range(B) for t in range(T)]
+    eoff, coff, acc_e, acc_c = {}, {}, 0, 0
+    for t in range(T):
         for b in range(B):
-            acc += int(batch_counts[ti][b])
-            ptr.append(base + acc)
-        if acc != hd.counts[ti]:
-            raise ValueError(f"batch_num_nodes of type {hd.ntypes[ti]} does not sum to its node count")
-    p.readout_ptr = host_to_device(ptr, torch.int32, dev)
-    return p
+            eoff[(t, b)], coff[(t, b)] = acc_e, acc_c
+            acc_e += pieces[b].ecount[t]
+            acc_c += pieces[b].ccount[t]
+    if acc_e >= 2 ** 31 - 1 or hd.S >= 2 ** 31 - 1:
+        raise ValueError("graph too large for the int32 kernel plan")
+    return pre, node_tab, eoff, coff, [eoff[(t, b)] for b in range(B) for t in range(T)], acc_e
+
+
+def _finish_assembled(p: GraphPlan, pieces: Sequence[PlanPieces]) -> None:
+    """What an assembled plan takes from its pieces' flags: the hub prefix, the locality order (all of the slides or none), the threshold."""
+    p.num_heavy = sum(pc.num_heavy for pc in pieces) if HUB_SPLIT else 0
+    p.locality = all(pc.locality for pc in pieces)
+    if any(pc.locality for pc in pieces) and not p.locality:
+        raise ValueError("a batch mixes locality-ordered and plain graphs: apply graph.apply_locality_order to all of a data set's slides or none")
+    p.heavy_degree = HEAVY_DEGREE_LOCALITY if p.locality else HEAVY_DEGREE
+
+
+def _piece_segments(tb: SegmentTable, out: Dict[str, torch.Tensor], hd: PlanHeader, pc: PlanPieces, t: int, key: int, so: int, row: int, eo: int, co: int):
+    """The plan segments of one (node type, slide): relation-slot segments from ``so``, nodes from ``row``, CSR edges from ``eo``, CSC entries
+    from ``co``; ``key`` = slide * T, the slide's row of the "node" / "edge" lookup tables."""
+    node, edge = tb.names["node"], tb.names["edge"]
+    nc, ne, ncc = pc.counts[t], pc.ecount[t], pc.ccount[t]
+    tb.seg(out["rowptr"], so, nc * hd.R[t], in1=pc.rp[t], add=eo)
+    tb.seg(out["colptr"], row, nc, in1=pc.cp[t], add=co)
+    tb.seg(out["src"], eo, ne, in1=pc.src_l[t], in2=pc.src_t[t], tab=node, key=key)
+    tb.seg(out["sim"], eo, ne, in1=pc.sim[t], mode=1)
+    tb.seg(out["csc_eid"], co, ncc, in1=pc.eid_l[t], in2=pc.ent_t[t], tab=edge, key=key)
+    tb.seg(out["csc_dst"], co, ncc, in1=pc.dst_l[t], in2=pc.ent_t[t], tab=node, key=key)
+
+
+def _order_segments(tb: SegmentTable, out: Dict[str, torch.Tensor], pc: PlanPieces, key: int, ho: int, lo: int, oo: int):
+    """The processing-order segments of one slide: its hubs from ``ho`` and its light destinations from ``lo`` of order_dst, its sources from
+    ``oo`` of order_src.  Returns the three positions behind them."""
+    node = tb.names["node"]
+    nh, nl, no = int(pc.heavy_l.numel()), int(pc.light_l.numel()), int(pc.so_l.numel())
+    tb.seg(out["order_dst"], ho, nh, in1=pc.heavy_l, in2=pc.heavy_t, tab=node, key=key)
+    tb.seg(out["order_dst"], lo, nl, in1=pc.light_l, in2=pc.light_t, tab=node, key=key)
+    tb.seg(out["order_src"], oo, no, in1=pc.so_l, in2=pc.so_t, tab=node, key=key)
+    return ho + nh, lo + nl, oo + no
+
+
+def _frame_segments(tb: SegmentTable, out: Dict[str, torch.Tensor], hd: PlanHeader, E: int) -> None:
+    """node_seg and inv_rd of the header's node counts, and the closing words of rowptr, colptr and node_seg."""
+    for t in range(len(hd.ntypes)):
+        R = hd.R[t]
+        tb.seg(out["node_seg"], hd.type_off[t], hd.counts[t], add=hd.seg_off[t], stride=R)
+        tb.seg(out["inv_rd"], hd.type_off[t], hd.counts[t], add=_float_bits([(1.0 / R) if R > 0 else 0.0])[0], mode=2)
+    tb.seg(out["rowptr"], hd.S, 1, add=E)
+    tb.seg(out["colptr"], hd.N, 1, add=E)
+    tb.seg(out["node_seg"], hd.N, 1, add=hd.S)
 
 
 def assemble_plan(hd: PlanHeader, pieces: Sequence[PlanPieces], dev, batch_counts: List[List[int]]):
@@ -785,87 +881,33 @@ def assemble_plan(hd: PlanHeader, pieces: Sequence[PlanPieces], dev, batch_count
     dev = torch.device(dev)
     if dev.type != "cuda":
         return assemble_plan_torch(hd, pieces, dev, batch_counts)
-    import struct
     from . import _native as N
-    T, B = len(hd.ntypes), len(pieces)
-    p = _plan_frame_host(hd, dev, batch_counts)
+    T = len(hd.ntypes)
+    p = _new_plan(hd, dev)
+    _set_readout_ptr(p, hd, batch_counts)
     Nn, S = hd.N, hd.S
-    pre = [[0] * T for _ in range(B + 1)]
-    for b in range(B):
-        for t in range(T):
-            pre[b + 1][t] = pre[b][t] + batch_counts[t][b]
-    node_tab = [hd.type_off[t] + pre[b][t] for b in range(B) for t in range(T)]                       # [b*T + t]
-    eoff, coff, acc_e, acc_c = {}, {}, 0, 0
-    for t in range(T):
-        for b in range(B):
-            eoff[(t, b)], coff[(t, b)] = acc_e, acc_c
-            acc_e += pieces[b].ecount[t]
-            acc_c += pieces[b].ccount[t]
-    E = acc_e
-    if E >= 2 ** 31 - 1 or S >= 2 ** 31 - 1:
-        raise ValueError("graph too large for the int32 kernel plan")
+    pre, node_tab, eoff, coff, edge_tab, E = _batch_offsets(hd, pieces, batch_counts)
     p.num_edges, p.num_src_rows = E, Nn
-    edge_tab = [eoff[(t, b)] for b in range(B) for t in range(T)]
-    H = sum(pc.num_heavy for pc in pieces)
-    i32 = lambda n: torch.empty(max(int(n), 1), dtype=torch.int32, device=dev)[:int(n)]
-    rowptr, colptr, node_seg = i32(S + 1), i32(Nn + 1), i32(Nn + 1)
-    src, csc_eid, csc_dst = i32(E), i32(E), i32(E)
-    order_dst, order_src = i32(Nn), i32(Nn)
-    sim = torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E]
-    inv_rd = torch.empty(max(Nn, 1), dtype=torch.float32, device=dev)[:Nn]
-    segs: List[List[int]] = []
-
-    def seg(out, off, esize, n, in1=None, in2=None, tab=-1, key=0, add=0, stride=0, mode=0):
-        if n > 0:
-            segs.append([out.data_ptr() + off * esize, 0 if in1 is None else in1.data_ptr(), 0 if in2 is None else in2.data_ptr(),
-                         tab, key, add, stride, int(n), mode, 0])
-
-    NODE, EDGE = 0, B * T              # offsets of the two lookup tables behind the descriptors (filled in below)
-    so = co = 0
+    mk = lambda n, dt=torch.int32: torch.empty(n, dtype=dt, device=dev) if n > 0 else torch.empty(1, dtype=dt, device=dev)[:0]
+    out = {"rowptr": mk(S + 1), "colptr": mk(Nn + 1), "node_seg": mk(Nn + 1), "src": mk(E), "csc_eid": mk(E), "csc_dst": mk(E),
+           "order_dst": mk(Nn), "order_src": mk(Nn), "sim": mk(E, torch.float32), "inv_rd": mk(Nn, torch.float32)}
+    tb = SegmentTable("plan_assemble")
+    tb.table("node", node_tab)
+    tb.table("edge", edge_tab)
     for t in range(T):
-        for b in range(B):
-            pc = pieces[b]
-            ns, nc = pc.counts[t] * hd.R[t], pc.counts[t]
-            seg(rowptr, so, 4, ns, in1=pc.rp[t], add=eoff[(t, b)])
-            seg(colptr, co, 4, nc, in1=pc.cp[t], add=coff[(t, b)])
-            so += ns
-            co += nc
-            ne, ncc = pc.ecount[t], pc.ccount[t]
-            seg(src, eoff[(t, b)], 4, ne, in1=pc.src_l[t], in2=pc.src_t[t], tab=NODE, key=b * T)
-            seg(sim, eoff[(t, b)], 4, ne, in1=pc.sim[t], mode=1)
-            seg(csc_eid, coff[(t, b)], 4, ncc, in1=pc.eid_l[t], in2=pc.ent_t[t], tab=EDGE, key=b * T)
-            seg(csc_dst, coff[(t, b)], 4, ncc, in1=pc.dst_l[t], in2=pc.ent_t[t], tab=NODE, key=b * T)
-    seg(rowptr, S, 4, 1, add=E)
-    seg(colptr, Nn, 4, 1, add=E)
-    ho, lo, oo = 0, H, 0
+        for b, pc in enumerate(pieces):
+            _piece_segments(tb, out, hd, pc, t, b * T, hd.seg_off[t] + pre[b][t] * hd.R[t], node_tab[b * T + t], eoff[(t, b)], coff[(t, b)])
+    pos = (0, sum(pc.num_heavy for pc in pieces), 0)
     for b, pc in enumerate(pieces):                 # processing orders: exact hub list first, then graph-major / heaviest-first inside (graph, type)
-        nh, nl, no = int(pc.heavy_l.numel()), int(pc.light_l.numel()), int(pc.so_l.numel())
-        seg(order_dst, ho, 4, nh, in1=pc.heavy_l, in2=pc.heavy_t, tab=NODE, key=b * T)
-        seg(order_dst, lo, 4, nl, in1=pc.light_l, in2=pc.light_t, tab=NODE, key=b * T)
-        seg(order_src, oo, 4, no, in1=pc.so_l, in2=pc.so_t, tab=NODE, key=b * T)
-        ho, lo, oo = ho + nh, lo + nl, oo + no
-    for t in range(T):
-        seg(node_seg, hd.type_off[t], 4, hd.counts[t], add=hd.seg_off[t], stride=hd.R[t])
-        seg(inv_rd, hd.type_off[t], 4, hd.counts[t], add=struct.unpack("<i", struct.pack("<f", (1.0 / hd.R[t]) if hd.R[t] > 0 else 0.0))[0], mode=2)
-    seg(node_seg, Nn, 4, 1, add=S)
-    blocks = 0
-    tab0 = len(segs) * 10
-    for s_ in segs:
-        if s_[3] >= 0:
-            s_[3] += tab0
-        s_[9] = blocks
-        blocks += (s_[7] + 1023) // 1024
-    desc = host_to_device([w for s_ in segs for w in s_] + node_tab + edge_tab, torch.int64, dev)
-    N.check(N.load().wsi_plan_assemble(N.ptr(desc), len(segs), blocks, N.stream()), "wsi_plan_assemble")
-    p.node_seg, p.inv_rd = node_seg, inv_rd
-    p.rowptr, p.colptr, p.src, p.csc_eid, p.csc_dst = rowptr, colptr, src, csc_eid, csc_dst
-    p.order_dst, p.order_src = order_dst, order_src
+        pos = _order_segments(tb, out, pc, b * T, *pos)
+    _frame_segments(tb, out, hd, E)
+    desc = tb.upload(dev)
+    N.check(N.load().wsi_plan_assemble(N.ptr(desc), tb.nsegs, tb.blocks, N.stream()), "wsi_plan_assemble")
+    sim = out.pop("sim")
+    for k, v in out.items():
+        setattr(p, k, v)
     p._assembly_desc = desc             # (the pieces are owned by the stored graphs; the descriptor table must outlive the launch: held by the plan)
-    p.num_heavy = H if HUB_SPLIT else 0
-    p.locality = all(pc.locality for pc in pieces)
-    if any(pc.locality for pc in pieces) and not p.locality:
-        raise ValueError("a batch mixes locality-ordered and plain graphs: apply graph.apply_locality_order to all of a data set's slides or none")
-    p.heavy_degree = HEAVY_DEGREE_LOCALITY if p.locality else HEAVY_DEGREE
+    _finish_assembled(p, pieces)
     return p, sim
 
 
@@ -874,23 +916,10 @@ def assemble_plan_torch(hd: PlanHeader, pieces: Sequence[PlanPieces], dev, batch
     T, B = len(hd.ntypes), len(pieces)
     p = plan_frame(hd, dev, batch_counts)
     N, S = hd.N, hd.S
-    pre = [[0] * T for _ in range(B + 1)]
-    for b in range(B):
-        for t in range(T):
-            pre[b + 1][t] = pre[b][t] + batch_counts[t][b]
-    node_tab = [hd.type_off[t] + pre[b][t] for b in range(B) for t in range(T)]                       # [b*T + t]
-    eoff, coff, acc_e, acc_c = {}, {}, 0, 0
-    for t in range(T):
-        for b in range(B):
-            eoff[(t, b)], coff[(t, b)] = acc_e, acc_c
-            acc_e += pieces[b].ecount[t]
-            acc_c += pieces[b].ccount[t]
-    E = acc_e
-    if E >= 2 ** 31 - 1 or S >= 2 ** 31 - 1:
-        raise ValueError("graph too large for the int32 kernel plan")
+    _, node_tab, eoff, coff, edge_tab, E = _batch_offsets(hd, pieces, batch_counts)
     p.num_edges, p.num_src_rows = E, N
     order = [(t, b) for t in range(T) for b in range(B)]
-    tabs = host_to_device([node_tab, [eoff[(t, b)] for b in range(B) for t in range(T)]], torch.int64, dev)     # [2, B*T]
+    tabs = host_to_device([node_tab, edge_tab], torch.int64, dev)     # [2, B*T]
     meta = host_to_device([[eoff[k] for k in order], [pieces[b].counts[t] * hd.R[t] for (t, b) in order],
                            [coff[k] for k in order], [pieces[b].counts[t] for (t, b) in order],
                            [b * T for (t, b) in order], [pieces[b].ecount[t] for (t, b) in order],
@@ -920,11 +949,7 @@ def assemble_plan_torch(hd: PlanHeader, pieces: Sequence[PlanPieces], dev, batch
     p.src, p.csc_eid, p.csc_dst = src.to(torch.int32), csc_eid.to(torch.int32), csc_dst.to(torch.int32)
     p.order_dst = torch.cat([heavy, light]).to(torch.int32)
     p.order_src = osrc.to(torch.int32)
-    p.num_heavy = H if HUB_SPLIT else 0
-    p.locality = all(pc.locality for pc in pieces)
-    if any(pc.locality for pc in pieces) and not p.locality:
-        raise ValueError("a batch mixes locality-ordered and plain graphs: apply graph.apply_locality_order to all of a data set's slides or none")
-    p.heavy_degree = HEAVY_DEGREE_LOCALITY if p.locality else HEAVY_DEGREE
+    _finish_assembled(p, pieces)
     return p, sim
 
 
@@ -1092,7 +1117,8 @@ def _piece_edge_seg(pc: PlanPieces, t: int, R: int) -> torch.Tensor:
 
 
 def _float_bits(xs: Sequence[float]) -> List[int]:
-    return torch.tensor(list(xs), dtype=torch.float32).view(torch.int32).tolist()
+    """The int32 bit patterns of the floats (rounded to fp32 to nearest)."""
+    return list(struct.unpack(f"<{len(xs)}i", struct.pack(f"<{len(xs)}f", *xs)))
 
 
 def slot_fill(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: Sequence[PlanPieces], labels: Sequence[int],
@@ -1112,108 +1138,72 @@ def slot_fill(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: Sequence[P
                     bufs[k].copy_(v)
         return out["batch"]
     from . import _native as N
-    sb, words, nsegs, blocks = _slot_descriptors(lay, bufs, pieces, labels, feats, scales)
-    desc = host_to_device(words, torch.int64, dev)
-    N.check(N.load().wsi_slot_fill(N.ptr(desc), nsegs, blocks, N.stream()), "wsi_slot_fill")
+    sb, tb = _slot_descriptors(lay, bufs, pieces, labels, feats, scales)
+    desc = tb.upload(dev)
+    N.check(N.load().wsi_slot_fill(N.ptr(desc), tb.nsegs, tb.blocks, N.stream()), "wsi_slot_fill")
     bufs["_desc"] = desc            # (stream-ordered: the table must outlive the launch; the next fill replaces it behind this one)
     return sb
 
 
 def _slot_descriptors(lay: SlotLayout, bufs, pieces, labels, feats, scales):
-    """The descriptor table of ``slot_fill`` (include/wsi_hgnn.h, wsi_slot_fill): (SlotBatch, words, segments, 1024-element blocks).  Every
-    segment is checked against the bounds of the table it writes before anything is launched."""
+    """The descriptor table of ``slot_fill``: (SlotBatch, SegmentTable)."""
     dev = bufs["rowptr"].device
     sb = SlotBatch(lay, pieces)
     T, hd, B, G = lay.T, lay.hd, sb.B, lay.graphs
     F = lay.in_dim
-    # tables behind the descriptors, in words from the start of the table area
-    tabs, tab_off = [], {}
+    tb = SegmentTable("slot_fill")
     for name, words in (("node", sb.node_tab), ("edge", sb.edge_tab), ("fill", sb.filler_block), ("readout_ptr", sb.readout_ptr),
                         ("labels", [int(y) for y in labels] + [-100] * (G - B)), ("chunk_row", sb.chunk_row), ("chunk_seg", sb.chunk_seg),
                         ("seg_chunk", sb.seg_chunk), ("seg_counts", _float_bits(sb.seg_counts)), ("seg_inv_counts", _float_bits(sb.seg_inv_counts)),
                         ("seg_nonempty", _float_bits(sb.seg_nonempty))):
-        tab_off[name] = len(tabs)
-        tabs += list(words)
-    segs: List[List[int]] = []
-
-    def seg(out, off, n, in1=None, in2=None, tab=None, key=0, add=0, stride=0, mode=0, esize=4):
-        if n > 0:
-            if off < 0 or (int(off) + int(n)) * esize > bufs[out].numel() * bufs[out].element_size():
-                raise RuntimeError(f"slot_fill: a segment of {out} leaves the table ({off} + {n} elements of {esize} bytes)")
-            if in1 is not None and not isinstance(in1, int) and mode in (0, 1, 5) and in1.numel() * in1.element_size() < int(n) * (8 if mode == 0 else esize):
-                raise RuntimeError(f"slot_fill: a segment of {out} reads past its source")
-            p1 = in1 if isinstance(in1, int) else (0 if in1 is None else in1.data_ptr())
-            segs.append([bufs[out].data_ptr() + int(off) * esize, p1, 0 if in2 is None else in2.data_ptr(),
-                         -1 if tab is None else tab_off[tab], int(key), int(add), int(stride), int(n), mode, 0])
-
-    nreal = sum(sb.n)
-    H = sum(pc.num_heavy for pc in pieces)
-    ho, lo, oo = 0, H, 0
+        tb.table(name, words)
+    seg, fill = tb.seg, tb.names["fill"]
+    pos = (0, sum(pc.num_heavy for pc in pieces), 0)
     for b, pc in enumerate(pieces):             # the real nodes in the order of the unpadded batch's plan (graph.assemble_plan) ...
-        nh, nl, no = int(pc.heavy_l.numel()), int(pc.light_l.numel()), int(pc.so_l.numel())
-        seg("order_dst", ho, nh, in1=pc.heavy_l, in2=pc.heavy_t, tab="node", key=b * T)
-        seg("order_dst", lo, nl, in1=pc.light_l, in2=pc.light_t, tab="node", key=b * T)
-        seg("order_src", oo, no, in1=pc.so_l, in2=pc.so_t, tab="node", key=b * T)
-        ho, lo, oo = ho + nh, lo + nl, oo + no
-    pos = nreal
+        pos = _order_segments(tb, bufs, pc, b * T, *pos)
+    pos = sum(sb.n)
     for t in range(T):                          # ... the filler's last
-        seg("order_dst", pos, sb.nf[t], add=sb.fb[t], stride=1)
-        seg("order_src", pos, sb.nf[t], add=sb.fb[t], stride=1)
+        seg(bufs["order_dst"], pos, sb.nf[t], add=sb.fb[t], stride=1)
+        seg(bufs["order_src"], pos, sb.nf[t], add=sb.fb[t], stride=1)
         pos += sb.nf[t]
+    wide = F % 4 == 0 and bufs["feat"].data_ptr() % 16 == 0
     for t in range(T):
         R = hd.R[t]
         for b, pc in enumerate(pieces):
-            row, eo, co = sb.node_tab[b * T + t], sb.eoff[(t, b)], sb.coff[(t, b)]
+            row, eo = sb.node_tab[b * T + t], sb.eoff[(t, b)]
             so = hd.seg_off[t] + sb.pre[b][t] * R
-            nc, ne, ncc = pc.counts[t], pc.ecount[t], pc.ccount[t]
-            seg("rowptr", so, nc * R, in1=pc.rp[t], add=eo)
-            seg("colptr", row, nc, in1=pc.cp[t], add=co)
-            seg("src", eo, ne, in1=pc.src_l[t], in2=pc.src_t[t], tab="node", key=b * T)
-            seg("sim", eo, ne, in1=pc.sim[t], mode=1)
-            seg("edge_seg", eo, ne, in1=_piece_edge_seg(pc, t, R) if ne else None, add=so)
-            seg("csc_eid", co, ncc, in1=pc.eid_l[t], in2=pc.ent_t[t], tab="edge", key=b * T)
-            seg("csc_dst", co, ncc, in1=pc.dst_l[t], in2=pc.ent_t[t], tab="node", key=b * T)
+            nc, ne = pc.counts[t], pc.ecount[t]
+            _piece_segments(tb, bufs, hd, pc, t, b * T, so, row, eo, sb.coff[(t, b)])
+            seg(bufs["edge_seg"], eo, ne, in1=_piece_edge_seg(pc, t, R) if ne else None, add=so)
             x = feats[b][t]
             if nc:
                 if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != (nc, F) or x.device != dev:
                     raise ValueError("slot_fill: features must be contiguous fp32 [nodes, in_dim] tables on the slot's device")
-                wide = F % 4 == 0 and x.data_ptr() % 16 == 0 and bufs["feat"].data_ptr() % 16 == 0
-                if wide:
-                    seg("feat", row * F // 4, nc * F // 4, in1=x, mode=5, esize=16)
+                if wide and x.data_ptr() % 16 == 0:
+                    seg(bufs["feat"], row * F // 4, nc * F // 4, in1=x, mode=5, esize=16)
                 else:
-                    seg("feat", row * F, nc * F, in1=x, mode=1)
+                    seg(bufs["feat"], row * F, nc * F, in1=x, mode=1)
                 if scales is not None:
-                    seg("scales", row, nc, in1=scales[b][t], mode=1)
+                    seg(bufs["scales"], row, nc, in1=scales[b][t], mode=1)
         so = hd.seg_off[t] + sb.n[t] * R
-        seg("rowptr", so, sb.nf[t] * R, tab="fill", key=t, mode=10)
-        seg("colptr", sb.fb[t], sb.nf[t], tab="fill", key=t, mode=13)
-        seg("src", sb.feb[t], sb.ef[t], tab="fill", key=t, mode=11)
-        seg("sim", sb.feb[t], sb.ef[t], add=0, mode=2)
-        seg("edge_seg", sb.feb[t], sb.ef[t], tab="fill", key=t, add=so, stride=R, mode=14)
-        seg("csc_eid", 0, sb.ef[t], in1=bufs["csc_dst"].data_ptr(), tab="fill", key=t, mode=12)
-        if F % 4 == 0 and bufs["feat"].data_ptr() % 16 == 0:
-            seg("feat", sb.fb[t] * F // 4, sb.nf[t] * F // 4, mode=5, esize=16)       # (in1 null: zero rows)
+        seg(bufs["rowptr"], so, sb.nf[t] * R, tab=fill, key=t, mode=10)
+        seg(bufs["colptr"], sb.fb[t], sb.nf[t], tab=fill, key=t, mode=13)
+        seg(bufs["src"], sb.feb[t], sb.ef[t], tab=fill, key=t, mode=11)
+        seg(bufs["sim"], sb.feb[t], sb.ef[t], add=0, mode=2)
+        seg(bufs["edge_seg"], sb.feb[t], sb.ef[t], tab=fill, key=t, add=so, stride=R, mode=14)
+        seg(bufs["csc_eid"], 0, sb.ef[t], in1=bufs["csc_dst"].data_ptr(), tab=fill, key=t, mode=12)
+        if wide:
+            seg(bufs["feat"], sb.fb[t] * F // 4, sb.nf[t] * F // 4, mode=5, esize=16)       # (in1 null: zero rows)
         else:
-            seg("feat", sb.fb[t] * F, sb.nf[t] * F, add=0, mode=2)
-        seg("scales", sb.fb[t], sb.nf[t], add=0, mode=2)                               # the scale of an all-zero row: absmax bits 0
-        seg("node_seg", hd.type_off[t], hd.counts[t], add=hd.seg_off[t], stride=R)
-        seg("inv_rd", hd.type_off[t], hd.counts[t], add=_float_bits([(1.0 / R) if R > 0 else 0.0])[0], mode=2)
-    seg("rowptr", lay.S, 1, add=lay.E)
-    seg("colptr", lay.N, 1, add=lay.E)
-    seg("node_seg", lay.N, 1, add=lay.S)
-    seg("labels", 0, G, tab="labels", mode=4, esize=8)
+            seg(bufs["feat"], sb.fb[t] * F, sb.nf[t] * F, add=0, mode=2)
+        seg(bufs["scales"], sb.fb[t], sb.nf[t], add=0, mode=2)                               # the scale of an all-zero row: absmax bits 0
+    _frame_segments(tb, bufs, hd, lay.E)
+    seg(bufs["labels"], 0, G, tab=tb.names["labels"], mode=4, esize=8)
     for name in ("readout_ptr", "chunk_row", "chunk_seg", "seg_chunk", "seg_counts", "seg_inv_counts", "seg_nonempty"):
-        seg(name, 0, bufs[name].numel(), tab=name, mode=3)
+        seg(bufs[name], 0, bufs[name].numel(), tab=tb.names[name], mode=3)
     for s_, (a, b_) in enumerate(sb.ranges):
-        seg("row_seg", a, b_ - a, add=s_)
-    blocks = 0
-    tab0 = len(segs) * 10
-    for s_ in segs:
-        if s_[3] >= 0:
-            s_[3] += tab0
-        s_[9] = blocks
-        blocks += (s_[7] + 1023) // 1024
-    return sb, [w for s_ in segs for w in s_] + tabs, len(segs), blocks
+        seg(bufs["row_seg"], a, b_ - a, add=s_)
+    return sb, tb
 
 
 def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]],
@@ -1472,11 +1462,8 @@ def slot_fill_augmented(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: 
 def slot_plan(lay: SlotLayout, bufs: Dict[str, torch.Tensor], locality: bool = False) -> GraphPlan:
     """The kernel plan whose tables ARE the slot's static buffers.  ``num_heavy = 0``: every destination takes the light path (correct for any
     degree); a hub prefix of fixed size is not part of a slot."""
-    hd = lay.hd
-    p = GraphPlan()
-    p.device = bufs["rowptr"].device
-    p.type_off, p.num_nodes, p.rel_slots, p.num_segs, p.rel_rows = hd.type_off, hd.N, hd.R, hd.S, list(hd.rel_rows)
-    p.num_edges, p.num_src_rows, p.batch_size = lay.E, hd.N, lay.graphs
+    p = _new_plan(lay.hd, bufs["rowptr"].device)
+    p.num_edges, p.num_src_rows, p.batch_size = lay.E, lay.N, lay.graphs
     for k in ("rowptr", "colptr", "node_seg", "src", "csc_eid", "csc_dst", "order_dst", "order_src", "inv_rd", "readout_ptr"):
         setattr(p, k, bufs[k])
     p.num_heavy, p.locality = 0, bool(locality)

@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _native as N
-from .graph import GraphPlan, host_to_device
+from .graph import GraphPlan, SegmentTable, host_to_device
 
 
 
@@ -1103,15 +1103,12 @@ class ReducePlan:
             if dev.type == "cuda":
                 # one upload + one launch: a run of `rows` copies of the segment number per segment (wsi_plan_assemble, mode 0 with add = s)
                 out = torch.empty(max(self.num_rows, 1), dtype=torch.int32, device=dev)[:self.num_rows]
-                desc, blocks = [], 0
+                tb = SegmentTable("row_segment")
                 for s_, (a, b) in enumerate(self.ranges):
-                    if b > a:
-                        desc += [out.data_ptr() + 4 * (a - self.first_row), 0, 0, -1, 0, s_, 0, b - a, 0, blocks]
-                        blocks += (b - a + 1023) // 1024
-                if desc:
-                    table = host_to_device(desc, torch.int64, dev)
-                    N.check(N.load().wsi_plan_assemble(N.ptr(table), len(desc) // 10, blocks, N.stream()), "wsi_plan_assemble")
-                    self._row_seg_desc = table
+                    tb.seg(out, a - self.first_row, b - a, add=s_)
+                if tb.nsegs:
+                    self._row_seg_desc = tb.upload(dev)
+                    N.check(N.load().wsi_plan_assemble(N.ptr(self._row_seg_desc), tb.nsegs, tb.blocks, N.stream()), "wsi_plan_assemble")
                 self._row_seg = out
             else:
                 reps = torch.tensor([b - a for a, b in self.ranges], dtype=torch.int64)
