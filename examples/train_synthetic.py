@@ -3,7 +3,8 @@
 (trainer/train_gnn.py:19-120), on synthetic WSI-shaped graphs:
 
   graph files (io.save_graph / load_graph)  ->  GraphBatchLoader (replaces GraphDataLoader + g.to(device))  ->
-  HEATNet4 + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate.
+  HEATNet4 + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate
+  (--captured-eval: trainer.CapturedSlotEval, the epoch's metrics kept on the device).
 
 Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation;
                            --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers)
@@ -39,6 +40,9 @@ def main(argv=None):
                     help="train through trainer.CapturedSlotStep over K padded batch slots by slide size (DESIGN 3.15): one captured step per slot, "
                          "replayed over every new batch that fits; needs --optimizer adam, sgd or adadelta (capturable).  With --augment the slots draw the "
                          "augmentation on the device in front of every replay (DESIGN 3.16)")
+    ap.add_argument("--captured-eval", action="store_true",
+                    help="evaluate through trainer.CapturedSlotEval (DESIGN 3.17): one captured forward per slot, the epoch's metrics accumulated on the "
+                         "device and read back once; with --captured-slots the training metrics of the epoch come from the captured step as well")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -85,7 +89,14 @@ def main(argv=None):
     bucket = dist.GradBucket.from_model(gnn) if world > 1 else None         # every parameter the architecture reaches, with used flags
     store = io.CheckpointStore(os.path.join(work, "ckpt"))
 
-    slot_step = None
+    slot_step, slot_eval, train_metrics = None, None, None
+    if args.captured_eval:
+        if world > 1:
+            raise SystemExit("--captured-eval: single process")
+        from wsi_hgnn_amd.metrics import EpochMetrics
+        slot_eval = trainer.CapturedSlotEval(gnn, [data.BatchSlot(eval_loader)])
+        if args.captured_slots:
+            train_metrics = EpochMetrics(2, len(graphs), dev)
     if args.captured_slots:
         if world > 1 or args.optimizer not in ("adam", "sgd", "adadelta"):
             raise SystemExit("--captured-slots: single process and --optimizer adam | sgd | adadelta")
@@ -100,12 +111,14 @@ def main(argv=None):
             part = its[:max(args.batch, (len(its) * (k + 1) + K - 1) // K)]
             caps.append(([top([it.num_nodes[t] for it in part]) + 1 for t in range(len(its[0].num_nodes))], [top([it.pieces.ecount[t] for it in part]) for t in range(len(its[0].num_nodes))], args.batch))
         gnn.train()
-        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c) for c in caps])
+        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c) for c in caps], metrics=train_metrics)
 
     # 3. epochs
     for epoch in range(args.epochs):
         gnn.train()
         tot, n = 0.0, 0
+        if train_metrics is not None:
+            train_metrics.reset()
         if slot_step is not None:
             order = torch.randperm(len(graphs), generator=loader.gen).tolist()
             losses = [slot_step.step(order[i:i + args.batch])[0].clone() for i in range(0, len(order), args.batch)]     # no host sync inside the epoch
@@ -114,9 +127,11 @@ def main(argv=None):
             loss, acc, *_ = trainer.train_one_step(gnn, opt, loss_fn, G, y, dev, bucket=bucket, sync=True)
             tot, n = tot + loss, n + 1
         gnn.eval()
-        metrics = io.evaluate(gnn, eval_loader)
+        metrics = io.evaluate(gnn, eval_loader) if slot_eval is None else slot_eval.evaluate()
         if rank == 0:
             print(f"epoch {epoch}: train loss {tot / max(n, 1):.4f}  eval {metrics}")
+            if train_metrics is not None:                                       # train_gnn.py:104-108, one read-back per epoch
+                print(f"epoch {epoch}: train metrics {train_metrics.compute()}")
             store.save_model(gnn.state_dict(), version=epoch + 1, stats={"epoch": epoch, "loss": tot / max(n, 1), **metrics})
     if rank == 0:
         sd = store.load_model()

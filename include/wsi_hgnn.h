@@ -837,6 +837,44 @@ int wsi_slot_aug_keys(const int64_t* args, void* stream);
 int wsi_slot_aug_scan(const int64_t* args, void* stream);
 int wsi_slot_aug_write(const int64_t* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Epoch metrics kept on the device (wsi_hgnn_amd/metrics.py::EpochMetrics): the reference's per-epoch accuracy / precision / recall / F1 / AUC and
+ * mean cross entropy (trainer/train_gnn.py:73-79,104-108; evaluator/eval_homo_graph.py:61-95; utils.py:37-47) without a read-back per step.
+ * Entry points added to ABI 26.  No allocation, no synchronisation, nothing a hipGraph cannot record; counts are integers and every float sum
+ * has one order, so the buffers hold the same bits run after run.
+ *
+ * The accumulator (caller-owned, zeroed by the caller to reset it):
+ *   state       int32 [WSI_METRICS_STATE_HEAD + C * C], 8-byte aligned: [0] cursor n (rows stored), [1] flag bits (WSI_METRICS_*), [2..3] the fp64
+ *               sum of the stored rows' cross entropies, then the confusion matrix, conf[label * C + prediction]
+ *   probs       fp32 [capacity, C]   row_labels, row_preds  int64 [capacity]
+ *
+ * wsi_metrics_update: ONE launch, one workgroup.  logits [B, C] fp32, labels int64 [B]; C <= 32, B * C <= 65536 (as wsi_cross_entropy).  For every
+ * row in row order: a label of -100 skips the row before its logits are read (a padding graph may carry anything); any other label outside
+ * [0, C) skips it and sets WSI_METRICS_BAD_LABEL; a non-finite logit skips it and sets WSI_METRICS_NONFINITE; a row that would land at or past
+ * `capacity` is dropped and sets WSI_METRICS_OVERFLOW (nothing is written past the capacity).  A counted row writes, at the cursor, its softmax
+ * probabilities (maximum subtracted, precise expf / logf), its label and its prediction (the FIRST maximum of its logits), adds 1 to conf and its
+ * cross entropy to the fp64 sum (a fixed tree per 256 rows, those in order), and advances the cursor.
+ *
+ * wsi_metrics_finalize: two launches over the n stored rows.  pair_partials: scratch, int64 [C * ceil(capacity / 256) * 2].
+ *   result      fp64 [WSI_METRICS_RESULT_HEAD + 4 * C]:
+ *               [0] n  [1] flag bits  [2] accuracy  [3] mean cross entropy  (n = 0: NaN)
+ *               [4..7]   'binary' precision, recall, F1 of class 1 and (TPR + TNR) / 2 of class 1 against the rest from the confusion matrix
+ *                        (what roc_curve gives on hard 0 / 1 predictions, utils.py:42-44)
+ *               [8..11]  'macro' precision, recall, F1, AUC: unweighted class means
+ *               then per class c: precision, recall, F1, one-vs-rest AUC of the stored probabilities' column c
+ *   An empty denominator gives 0 for precision / recall / F1; a class without a positive or without a negative row has the AUC NaN (and the
+ *   macro AUC is then NaN).  AUC_c is the exact Mann-Whitney statistic by pair counting: over the pairs (i: label c, j: another label),
+ *   (2 #(s_ic > s_jc) + #(s_ic == s_jc)) / (2 P N), counted in 64-bit integers, one division in fp64. */
+#define WSI_METRICS_STATE_HEAD   4
+#define WSI_METRICS_RESULT_HEAD  12
+#define WSI_METRICS_BAD_LABEL    1
+#define WSI_METRICS_NONFINITE    2
+#define WSI_METRICS_OVERFLOW     4
+int wsi_metrics_update(const float* logits, const int64_t* labels, int32_t B, int32_t C, int32_t* state, float* probs, int64_t* row_labels,
+                       int64_t* row_preds, int32_t capacity, void* stream);
+int wsi_metrics_finalize(const int32_t* state, const float* probs, const int64_t* row_labels, int32_t C, int32_t capacity,
+                         int64_t* pair_partials, double* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

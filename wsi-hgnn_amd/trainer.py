@@ -160,6 +160,29 @@ class CapturedStep:
         return self.cuda_graph.pool()
 
 
+def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
+    """What a capture over batch slots needs of the model and the slots (``CapturedSlotStep``, ``CapturedSlotEval``): a HEAT trunk with a sum / mean /
+    max readout, slots on the GPU fed by one loader.  Returns (slots as a list, their loader, its device)."""
+    from .data import BatchSlot
+    from .models.heat_net import HEATTrunk
+    from .pooling import GlobalAttentionPooling
+    slots = [slots] if isinstance(slots, BatchSlot) else list(slots)
+    if not slots:
+        raise ValueError(f"{who}: no slot")
+    if not isinstance(gnn, HEATTrunk):
+        raise RuntimeError(f"{who}: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4 only (HGT derives a per-relation-source plan "
+                           f"from the batch's COO on the host for every new batch, which a replay cannot redo); {verb} it eagerly")
+    if isinstance(gnn.pools[0], GlobalAttentionPooling):
+        raise RuntimeError(f"{who}: the attention readout ('att') expands host-side node counts per batch; use a sum / mean / max readout "
+                           f"or {verb} eagerly")
+    loader = slots[0].loader
+    if any(s.loader is not loader for s in slots):
+        raise ValueError(f"{who}: all slots must be fed by one loader")
+    if loader.device.type != "cuda":
+        raise RuntimeError(f"{who}: the slots must live on the GPU")
+    return slots, loader, loader.device
+
+
 class CapturedSlotStep:
     """One captured training step per batch SLOT (``data.BatchSlot``), replayed over NEW slides every step: the regime the reference trains in
     (one or two slides per step, ``trainer/train_gnn.py:48-79``), where the host takes longer to issue the step's launches than the GPU to run them.
@@ -176,27 +199,17 @@ class CapturedSlotStep:
 
     Slots over a loader with a slot-compatible ``transform=`` (``data.slot_augment_spec``) are AUGMENTED: every ``step`` fills its slot with a fresh
     draw taken on the device (no read-back) in front of the replay, a batch no slot fits goes through ``loader._augmented``, and either way the
-    loader's batch counter advances exactly once per step - under one seed the trajectory follows the eager loader's draws."""
+    loader's batch counter advances exactly once per step - under one seed the trajectory follows the eager loader's draws.
 
-    def __init__(self, gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_fcn, slots, warmup: int = 1, warmup_batches=None):
-        from .data import BatchSlot
-        from .models.heat_net import HEATTrunk
-        from .pooling import GlobalAttentionPooling
-        self.slots = [slots] if isinstance(slots, BatchSlot) else list(slots)
-        if not self.slots:
-            raise ValueError("CapturedSlotStep: no slot")
-        if not isinstance(gnn, HEATTrunk):
-            raise RuntimeError(f"CapturedSlotStep: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4 only (HGT derives a per-relation-source plan "
-                               "from the batch's COO on the host for every new batch, which a replay cannot redo); step it eagerly")
-        if isinstance(gnn.pools[0], GlobalAttentionPooling):
-            raise RuntimeError("CapturedSlotStep: the attention readout ('att') expands host-side node counts per batch; use a sum / mean / max readout "
-                               "or step eagerly")
-        self.loader = self.slots[0].loader
-        if any(s.loader is not self.loader for s in self.slots):
-            raise ValueError("CapturedSlotStep: all slots must be fed by one loader")
-        dev = self.loader.device
-        if dev.type != "cuda":
-            raise RuntimeError("CapturedSlotStep: the slots must live on the GPU")
+    ``metrics``: a ``metrics.EpochMetrics`` on the slots' device; the recorded step and the eager one then end with
+    ``metrics.update(logits, labels)`` - the reference's per-epoch training metrics (``train_gnn.py:73-79,104-108``) with no read-back per step
+    (the warm-up steps count too: ``metrics.reset()`` where the epoch starts).  ``None``: the recorded step is exactly what it was."""
+
+    def __init__(self, gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_fcn, slots, warmup: int = 1, warmup_batches=None, metrics=None):
+        self.slots, self.loader, dev = _check_slots("CapturedSlotStep", "step", gnn, slots)
+        if metrics is not None and metrics.device != dev:
+            raise RuntimeError(f"CapturedSlotStep: metrics= must live on the slots' device ({dev})")
+        self.metrics = metrics
         for group in optimizer.param_groups:
             if not group.get("capturable", False):
                 raise RuntimeError("CapturedSlotStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step count has "
@@ -256,6 +269,8 @@ class CapturedSlotStep:
         self.optimizer.step()
         if self.seed_base is not None:
             ops.advance_dropout_seed_base(self.seed_base)
+        if self.metrics is not None:
+            self.metrics.update(pred.detach(), label)
         return loss.detach(), pred.detach()
 
     def slot_for(self, idxs: Sequence[int]):
@@ -286,3 +301,117 @@ class CapturedSlotStep:
         self.replays += 1
         loss, pred = self.outputs[i]
         return loss, pred[:slot.num_real]
+
+
+class CapturedSlotEval:
+    """The forward of an evaluation pass captured once per batch SLOT and replayed over the data set: what the reference does after every epoch,
+    one slide at a time (``trainer/train_gnn.py:110-115``, ``evaluator/eval_homo_graph.py:61-95``) - the same host-bound regime as its training
+    step.  Each slot's graph records ``pred = gnn(slot.graph); metrics.update(pred, slot.labels)`` in eval mode under ``no_grad``; ``evaluate``
+    fills and replays batch after batch and reads the epoch's numbers back ONCE (``metrics.EpochMetrics.compute``).  The filler and the empty
+    graphs of a slot are labelled -100 and are not counted.
+
+    The recorded forward reads the LIVE parameters: under a stream capture every projection packs its own weights (``ops.repack_weights``), the
+    statistics stream is not used, and the eval-mode forward keeps no other table that depends on a parameter - an optimizer step between two
+    ``evaluate`` calls changes the result as it must.  A training capture (``CapturedSlotStep``) lives beside this one on slots and a memory
+    pool of its own.
+
+    Refused: what ``CapturedSlotStep`` refuses (HGT, the ``att`` readout, slots off the GPU or over several loaders), and slots over a loader
+    with ``transform=`` - evaluation sees the stored slides (the reference augments ``type_ == "train"`` only, data.py:116-117).
+    ``metrics=None`` builds an ``EpochMetrics`` for ``len(loader.items)`` rows."""
+
+    def __init__(self, gnn: torch.nn.Module, slots, metrics=None, warmup: int = 1):
+        self.slots, self.loader, dev = _check_slots("CapturedSlotEval", "evaluate", gnn, slots)
+        if self.loader.transform is not None:
+            raise RuntimeError("CapturedSlotEval: the slots' loader has a transform=; evaluation sees the stored slides - build the slots over a "
+                               "loader without one")
+        self.gnn = gnn
+        self.slots = sorted(self.slots, key=lambda s: s.layout.N)                      # smallest first: what run() tries in turn
+        self.replays, self.eager_runs = 0, 0
+        self.graphs, self.outputs = [], []
+        was_training = gnn.training
+        gnn.eval()
+        try:
+            with torch.no_grad():
+                firsts = []
+                for i, slot in enumerate(self.slots):
+                    first = next(([j] for j in sorted(slot.members) if slot.fits([j])), None)
+                    if first is None:
+                        raise ValueError(f"CapturedSlotEval: no slide of the data set fits slot {i}")
+                    firsts.append(first)
+                if metrics is None:
+                    from .metrics import EpochMetrics
+                    slot = self.slots[0].load(firsts[0])
+                    metrics = EpochMetrics(gnn(slot.graph).shape[1], len(self.loader.items), dev)
+                elif metrics.device != dev:
+                    raise RuntimeError(f"CapturedSlotEval: metrics= must live on the slots' device ({dev})")
+                self.metrics = metrics
+                pool = None
+                for slot, first in zip(self.slots, firsts):
+                    slot.load(first)
+                    side = torch.cuda.Stream(device=dev)
+                    side.wait_stream(torch.cuda.current_stream(dev))
+                    with torch.cuda.stream(side):                  # (plans, caches and allocator pools settle before the capture)
+                        for _ in range(max(1, warmup)):
+                            self._eager(slot.graph, slot.labels)
+                    torch.cuda.current_stream(dev).wait_stream(side)
+                    torch.cuda.synchronize(dev)
+                    cg = torch.cuda.CUDAGraph()
+                    try:
+                        with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
+                            out = self._eager(slot.graph, slot.labels)
+                    except Exception as exc:
+                        raise RuntimeError("CapturedSlotEval: the forward could not be captured into a hipGraph; evaluate eagerly (io.evaluate) "
+                                           "instead") from exc
+                    pool = cg.pool()
+                    self.graphs.append(cg)
+                    self.outputs.append(out)
+                metrics.reset()                                    # (the warm-up forwards counted their rows)
+        finally:
+            gnn.train(was_training)
+
+    def _eager(self, graph: HeteroGraph, label: torch.Tensor) -> torch.Tensor:
+        pred = self.gnn(graph)
+        self.metrics.update(pred, label)
+        return pred
+
+    def slot_for(self, idxs: Sequence[int]):
+        """Index of the smallest slot the batch fits, or None."""
+        for i, slot in enumerate(self.slots):
+            if slot.fits(idxs):
+                return i
+        return None
+
+    def run(self, idxs: Sequence[int]) -> torch.Tensor:
+        """The logits ``[len(idxs), C]`` of the loader's slides ``idxs`` (a device tensor; those of a replay are overwritten by the next replay of
+        the same slot), their rows appended to ``metrics``.  A batch no slot fits runs eagerly through the loader's ordinary assembly."""
+        idxs = list(idxs)
+        i = self.slot_for(idxs)
+        if i is None:
+            was_training = self.gnn.training
+            self.gnn.eval()
+            try:
+                with torch.no_grad():
+                    G, labels, ready = self.loader._assemble(idxs, 0)
+                    if ready is not None:
+                        torch.cuda.current_stream(self.loader.device).wait_event(ready)
+                    self.eager_runs += 1
+                    return self._eager(G, labels)
+            finally:
+                self.gnn.train(was_training)
+        slot = self.slots[i]
+        slot.load(idxs)
+        self.graphs[i].replay()
+        self.replays += 1
+        return self.outputs[i][:slot.num_real]
+
+    def batches(self):
+        """The default batches of ``evaluate``: every schema bucket's slides in stored order, ``loader.batch_size`` at a time."""
+        bs = self.loader.batch_size
+        return [ix[k:k + bs] for ix in self.loader.buckets.values() for k in range(0, len(ix), bs)]
+
+    def evaluate(self, batches=None, average: str = "binary"):
+        """``metrics.reset()``, every batch through ``run``, ``metrics.compute(average)``: the keys of ``io.evaluate`` plus ``"n"``.  One read-back."""
+        self.metrics.reset()
+        for idxs in (self.batches() if batches is None else batches):
+            self.run(idxs)
+        return self.metrics.compute(average)
