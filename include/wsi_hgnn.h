@@ -424,6 +424,46 @@ int wsi_segment_weighted_sums(const float* x, int64_t ldx, int32_t D, const floa
                               const int32_t* chunk_row, int32_t num_chunks, const int32_t* seg_chunk, int32_t num_segs,
                               float* partial, float* out, void* stream);
 
+/* Bag softmax pooling (an addition to ABI 26): per segment s and score column c a softmax over the segment's rows, then the weighted sum
+ * of the value rows.  Replaces F.softmax(A, dim=1) + torch.mm(A, H) of baselines/ReMix_DSMIL_ABMIL/model/abmil.py:25-28 and
+ * F.softmax(A / sqrt(128), 0) + torch.mm(A^T, V) of model/dsmil.py:51-52, for many bags at once:
+ *   p[r, c]      = exp(scale * scores[r, c] - lse[seg(r), c])
+ *   out[s, c, :] = sum_{r in s} p[r, c] * values[r, :]            [num_segs, C, D] contiguous
+ *   lse[s, c]    = logsumexp_{r in s}(scale * scores[r, c])       [num_segs, C]
+ * scores [rows, C] with row stride lds, values [rows, D] with row stride ldv; chunk tables as for wsi_segment_reduce_fwd.  An empty segment
+ * gives out = 0 and lse = 0.  1 <= C <= 8 (more: WSI_ENOSYS), any D >= 1; 16-byte row loads when values and ldv are 16-byte aligned, a
+ * scalar path otherwise.  Two stages (an online softmax over the chunk's rows, then the segment's chunks combined in chunk order): values
+ * is read once, no atomics, bit-reproducible.  partial: caller scratch, num_chunks * C * (D + 2) floats.
+ * stats [num_segs, C, 2] (may be NULL): the two terms of lse apart - the segment's maximum of scale * scores and the log of the sum rescaled
+ * by it (0, 0 for an empty segment).  The backward forms p from these: at scores near -1e4 their float32 sum has an ulp of 1e-3. */
+int wsi_bag_softmax_pool_fwd(const float* scores, int64_t lds, int32_t C, float scale,
+                             const float* values, int64_t ldv, int32_t D,
+                             const int32_t* chunk_row, int32_t num_chunks, const int32_t* seg_chunk, int32_t num_segs,
+                             float* partial, float* out, float* lse, float* stats, void* stream);
+
+/* Its gradients, from g_out [num_segs, C, D] and the forward's out and stats (p[r, c] = exp((scale * scores[r, c] - stats[s, c, 0]) - stats[s, c, 1])):
+ *   g_values[r, :] = sum_c p[r, c] * g_out[seg(r), c, :]
+ *   g_scores[r, c] = scale * p[r, c] * (<g_out[s, c], values[r]> - <g_out[s, c], out[s, c]>)
+ * Either gradient pointer may be NULL (that gradient is not computed; out and delta are needed for g_scores only).  values is read once and
+ * g_values written once; no atomics, fixed summation order.  A segment whose g_out rows are zero gets exactly zero gradients.
+ * delta: caller scratch, num_segs * C floats. */
+int wsi_bag_softmax_pool_bwd(const float* g_out, const float* out, const float* scores, int64_t lds, int32_t C, float scale,
+                             const float* stats, const float* values, int64_t ldv, int32_t D,
+                             const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks, int32_t num_segs,
+                             float* delta, float* g_scores, int64_t ldgs, float* g_values, int64_t ldgv, void* stream);
+
+/* DSMIL's score step over many bags (torch.mm(Q, q_max^T), model/dsmil.py:50): scores[r, c] = <x[r, :], t[seg(r), c, :]> with
+ * t [num_segs, C, D] contiguous; one launch whatever the number of bags.  1 <= C <= 8. */
+int wsi_bag_scores_fwd(const float* x, int64_t ldx, int32_t D, const float* t, int32_t C,
+                       const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks,
+                       float* scores, int64_t lds, void* stream);
+
+/* Its row gradient: gx[r, :] = sum_c w[r, c] * t[seg(r), c, :]  (+ sum_c w2[r, c] * t2[seg(r), c, :] when w2 and t2 are given: the
+ * critical-instance gather's share, w2 = its one-hot rows).  The gradient of t is wsi_segment_weighted_sums(x, w). */
+int wsi_bag_scores_bwd(const float* w, int64_t ldw, const float* t, const float* w2, int64_t ldw2, const float* t2,
+                       int32_t C, int32_t D, const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks,
+                       float* gx, int64_t ldgx, void* stream);
+
 /* One Adam step over `count` parameter tensors in ONE launch: the optimizer step of the reference's trainer (torch.optim.Adam(lr, weight_decay),
  * parser.py:33-38; trainer/train_gnn.py:72) with torch's arithmetic, amsgrad = False, maximize = False:
  *   g += weight_decay * p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;

@@ -7,6 +7,7 @@ Import as ``wsi_hgnn_amd`` (alias package at the repo root).  Layout:
   _native.py    ctypes loader of csrc/libwsi_hgnn.so (fails loudly when missing)
   ops.py        torch.autograd.Function wrappers calling the C-ABI
   models/, pooling/   nn.Module mirror of the reference's models/* and pooling/* API
+  mil/          the multiple-instance-learning baselines (ABMIL, DSMIL) over batches of bags: bag softmax pooling in HIP
   metrics.py    per-epoch classification metrics accumulated on the device (one recordable launch per step, one read-back per epoch)
   dist.py       WSI-sharded data parallelism (RCCL gradient all-reduce)
 """

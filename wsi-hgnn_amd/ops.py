@@ -1289,6 +1289,111 @@ def segment_weighted_sums(x: torch.Tensor, w: torch.Tensor, rp: "ReducePlan") ->
 
 
 # ------------------------------------------------------------------------------------------------
+# bag softmax pooling and the DSMIL score step (wsi_bag_softmax_pool_* / wsi_bag_scores_*: the MIL baselines, wsi_hgnn_amd.mil)
+# ------------------------------------------------------------------------------------------------
+def _bag_rows(what: str, rp: ReducePlan, *tensors) -> None:
+    for t in tensors:
+        if t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError(f"{what}: expected 2-D float32 tensors, got {tuple(t.shape)} {t.dtype}")
+        if rp.first_row != 0 or rp.num_rows != t.shape[0]:
+            raise ValueError(f"{what}: the plan covers rows [{rp.first_row}, {rp.first_row + rp.num_rows}) but a tensor has {t.shape[0]} rows")
+
+
+class _BagSoftmaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, values, rp: ReducePlan, scale: float):
+        N.require_cuda(scores, values)
+        _bag_rows("bag_softmax_pool", rp, scores, values)
+        scores, values = scores.contiguous(), values.contiguous()
+        C, D, dev = scores.shape[1], values.shape[1], values.device
+        out = torch.empty((rp.num_segs, C, D), dtype=torch.float32, device=dev)
+        lse = torch.empty((rp.num_segs, C), dtype=torch.float32, device=dev)
+        stats = torch.empty((rp.num_segs, C, 2), dtype=torch.float32, device=dev)
+        partial = torch.empty(max(rp.num_chunks * C * (D + 2), 1), dtype=torch.float32, device=dev)
+        N.check(N.load().wsi_bag_softmax_pool_fwd(N.ptr(scores), C, C, scale, N.ptr(values), D, D, N.ptr(rp.chunk_row), rp.num_chunks,
+                                                  N.ptr(rp.seg_chunk), rp.num_segs, N.ptr(partial), N.ptr(out), N.ptr(lse), N.ptr(stats),
+                                                  N.stream()), "wsi_bag_softmax_pool_fwd")
+        ctx.rp, ctx.scale = rp, scale
+        ctx.save_for_backward(scores, values, out, stats)
+        ctx.mark_non_differentiable(lse, stats)
+        return out, lse, stats
+
+    @staticmethod
+    def backward(ctx, g_out, _g_lse, _g_stats):
+        scores, values, out, stats = ctx.saved_tensors
+        rp = ctx.rp
+        g_out = g_out.contiguous()
+        C, D, dev = scores.shape[1], values.shape[1], values.device
+        g_scores = torch.empty_like(scores) if ctx.needs_input_grad[0] else None
+        g_values = torch.empty_like(values) if ctx.needs_input_grad[1] else None
+        delta = torch.empty(max(rp.num_segs * C, 1), dtype=torch.float32, device=dev) if g_scores is not None else None
+        N.check(N.load().wsi_bag_softmax_pool_bwd(N.ptr(g_out), N.ptr(out), N.ptr(scores), C, C, ctx.scale, N.ptr(stats), N.ptr(values), D, D,
+                                                  N.ptr(rp.chunk_row), N.ptr(rp.chunk_seg), rp.num_chunks, rp.num_segs, N.ptr(delta),
+                                                  N.ptr(g_scores), C, N.ptr(g_values), D, N.stream()), "wsi_bag_softmax_pool_bwd")
+        return g_scores, g_values, None, None
+
+
+def bag_softmax_pool_lse(scores: torch.Tensor, values: torch.Tensor, rp: ReducePlan, scale: float = 1.0):
+    """(out, lse, stats): ``bag_softmax_pool`` together with lse [num_segs, C] = logsumexp over the segment's rows of scale * scores and
+    with stats [num_segs, C, 2] = its two terms apart (the segment's maximum, the log of the sum rescaled by it) - neither differentiable.
+    The backward and ``bag_attention`` form the weights from ``stats``: the float32 sum of the two has an ulp of 1e-3 at scores near -1e4."""
+    return _BagSoftmaxPool.apply(scores, values, rp, float(scale))
+
+
+def bag_softmax_pool(scores: torch.Tensor, values: torch.Tensor, rp: ReducePlan, scale: float = 1.0) -> torch.Tensor:
+    """out[s, c, :] = sum over the rows r of segment s of softmax_r(scale * scores[:, c])[r] * values[r, :];  scores [rows, C] (C <= 8),
+    values [rows, D] -> [num_segs, C, D].  The softmax runs over the rows of each segment (bag) alone; an empty segment gives 0."""
+    return _BagSoftmaxPool.apply(scores, values, rp, float(scale))[0]
+
+
+def bag_attention(scores: torch.Tensor, lse: torch.Tensor, rp: ReducePlan, scale: float = 1.0) -> torch.Tensor:
+    """[rows, C]: the normalised attention exp(scale * scores - lse[segment of the row]) the MIL references return as ``A`` (detached).
+    ``lse``: [num_segs, C], or the ``stats`` [num_segs, C, 2] of ``bag_softmax_pool_lse`` (its two terms, subtracted one after the other)."""
+    N.require_cuda(scores, lse)
+    per_row = lse.detach().index_select(0, rp.row_segment())
+    s = scores.detach() * float(scale)
+    return torch.exp(s - per_row) if lse.dim() == 2 else torch.exp((s - per_row[..., 0]) - per_row[..., 1])
+
+
+class _BagScores(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, onehot, rp: ReducePlan):
+        N.require_cuda(q, onehot)
+        _bag_rows("bag_scores", rp, q, onehot)
+        q, onehot = q.contiguous(), onehot.contiguous()
+        C, D = onehot.shape[1], q.shape[1]
+        q_max = segment_weighted_sums(q, onehot, rp)                     # [S, C, D]: the marked row of every (bag, column); 0 where none is
+        scores = torch.empty((q.shape[0], C), dtype=torch.float32, device=q.device)
+        N.check(N.load().wsi_bag_scores_fwd(N.ptr(q), D, D, N.ptr(q_max), C, N.ptr(rp.chunk_row), N.ptr(rp.chunk_seg), rp.num_chunks,
+                                            N.ptr(scores), C, N.stream()), "wsi_bag_scores_fwd")
+        ctx.rp = rp
+        ctx.save_for_backward(q, onehot, q_max)
+        return scores
+
+    @staticmethod
+    def backward(ctx, g_scores):
+        q, onehot, q_max = ctx.saved_tensors
+        rp = ctx.rp
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g_scores = g_scores.contiguous()
+        C, D = onehot.shape[1], q.shape[1]
+        g_q_max = segment_weighted_sums(q, g_scores, rp)                 # [S, C, D]: sum_r g_scores[r, c] * q[r]
+        g_q = torch.empty_like(q)
+        # a row's own score term, and - where the row is a marked one - the gradient of the q_max it supplied (dense: no scatter-add)
+        N.check(N.load().wsi_bag_scores_bwd(N.ptr(g_scores), C, N.ptr(q_max), N.ptr(onehot), C, N.ptr(g_q_max), C, D, N.ptr(rp.chunk_row),
+                                            N.ptr(rp.chunk_seg), rp.num_chunks, N.ptr(g_q), D, N.stream()), "wsi_bag_scores_bwd")
+        return g_q, None, None
+
+
+def bag_scores(q: torch.Tensor, onehot: torch.Tensor, rp: ReducePlan) -> torch.Tensor:
+    """DSMIL's score step over many bags: scores[r, c] = <q[r], q_max[seg(r), c]> where q_max[s, c] = sum over the rows of bag s of
+    onehot[r, c] * q[r] - the query of the critical instance ``onehot`` [rows, C] marks (an all-zero column: q_max = 0).  The gradient
+    reaches ``q`` through both factors, in a number of launches that does not depend on the number of bags and without atomics."""
+    return _BagScores.apply(q, onehot, rp)
+
+
+# ------------------------------------------------------------------------------------------------
 # segment dot (skip-gate gradient)
 # ------------------------------------------------------------------------------------------------
 def segment_dot_diff(g: torch.Tensor, a: torch.Tensor, b: torch.Tensor, rp: "ReducePlan") -> torch.Tensor:
