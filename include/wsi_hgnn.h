@@ -468,7 +468,9 @@ int wsi_bag_scores_bwd(const float* w, int64_t ldw, const float* t, const float*
  * parser.py:33-38; trainer/train_gnn.py:72) with torch's arithmetic, amsgrad = False, maximize = False:
  *   g += weight_decay * p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
  *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
- * `step` = the 1-based step count AFTER this step (torch increments before use).  p, m, v are updated in place; contiguous fp32 tensors. */
+ * `step` = the 1-based step count AFTER this step (torch increments before use).  p, m, v are updated in place; contiguous fp32 tensors.
+ * It is wsi_optim_step(WSI_OPTIM_ADAM) below with a host count (s0 = m, s1 = v, no `step` word, host_step = step) under the drop-in signature:
+ * the same kernel, 88 non-empty tensors per launch, and like it every tensor is checked before the first launch (WSI_EINVAL leaves nothing stepped). */
 typedef struct wsi_adam_tensor { float* p; const float* g; float* m; float* v; int64_t n; } wsi_adam_tensor_t;
 int wsi_adam_step(const wsi_adam_tensor_t* tensors, int32_t count, double lr, double beta1, double beta2, double eps,
                   double weight_decay, int64_t step, void* stream);      /* (hyper-parameters in double, as torch holds them: 1 - beta2 is taken in double) */

@@ -1197,12 +1197,11 @@ def test_train_one_step_matches_reference_semantics():
 
 def test_adam_step_matches_torch_adam():
     """wsi_hgnn_amd.optim.Adam (one launch over all tensors) against torch.optim.Adam (the reference's optimizer, parser.py:33-38) over 6 steps:
-    tensors of odd sizes (the scalar tail path), one unaligned view, a parameter whose gradient is missing at some steps (its own step count),
-    weight decay on; state_dicts interchange."""
+    tensors of odd sizes (the scalar tail path), a parameter whose gradient is missing at some steps (its own step count), weight decay on;
+    state_dicts interchange.  (A misaligned view: test_optim_gpu.py::test_rule_matches_torch_optim[adam].)"""
     from wsi_hgnn_amd.optim import Adam
     torch.manual_seed(9)
     shapes = [(512, 1024), (513,), (7, 3), (1,), (4096 * 3 + 5,), (64, 64)]
-    base = torch.randn(70, device=_dev())
     ps = [torch.randn(s_, device=_dev()) for s_ in shapes]
     mine = [p.clone().requires_grad_() for p in ps]
     ref = [p.clone().requires_grad_() for p in ps]
@@ -1236,8 +1235,8 @@ def test_adam_step_matches_torch_adam():
 
 
 def test_adam_step_many_tensors_with_empty_ones_and_version_counters():
-    """More than 128 tensors (the kernel's table size; HEATNet4 with 3 node types has 75, the real schema more) with ZERO-ELEMENT tensors among the
-    first 128 - the launch loop used to advance by a full table while the table had skipped the empty ones, stepping the overlap twice (round-3 advisor) -
+    """More than 88 tensors (the kernel's table size; HEATNet4 with 3 node types has 75, the real schema more) with ZERO-ELEMENT tensors among the
+    first 88 - the launch loop used to advance by a full table while the table had skipped the empty ones, stepping the overlap twice (round-3 advisor) -
     against torch.optim.Adam; and the step moves the version counters of p / exp_avg / exp_avg_sq like torch's in-place ops do."""
     from wsi_hgnn_amd.optim import Adam
     torch.manual_seed(4)

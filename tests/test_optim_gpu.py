@@ -1,10 +1,11 @@
-"""The one-launch optimizers (wsi_hgnn_amd.optim.SGD / Adagrad / Adadelta, Adam with its count on the device; csrc/optim.hip::optim_step_kernel)
-against the installed ``torch.optim`` classes on the same device in fp32.
+"""The one-launch optimizers (wsi_hgnn_amd.optim.SGD / Adagrad / Adadelta / Adam, the count on the host or on the device;
+csrc/optim.hip::optim_step_kernel) against the installed ``torch.optim`` classes on the same device in fp32.
 
 Tolerance: the project's own from test_adam_step_matches_torch_adam - after every step ``|x - y|_max <= 2e-6 * max(1, |y|_max)`` on the parameters,
 ``1e-6`` relative (to the tensor's largest magnitude, floored at 1) on the state tensors at the end.  Both sides do the same handful of fp32
 operations per element; they differ by where a product is fused into an add, i.e. by an ulp (6e-8 relative) per operation."""
 import copy
+import ctypes
 import functools
 
 import pytest
@@ -81,6 +82,7 @@ RULES = {
     "adagrad-initial": ("Adagrad", dict(lr=1e-2, lr_decay=5e-3, weight_decay=5e-3, initial_accumulator_value=0.1)),
     "adadelta-lr1": ("Adadelta", dict(lr=1.0, weight_decay=5e-3)),
     "adadelta": ("Adadelta", dict(lr=5e-3, weight_decay=5e-3)),
+    "adam": ("Adam", dict(lr=1e-2, weight_decay=5e-3)),
 }
 
 
@@ -181,6 +183,58 @@ def test_device_step_count_matches_the_host_count(name, kw):
         c = torch.optim.Adam([x.detach().clone().requires_grad_() for x in mine], capturable=True, **kw)
         c.load_state_dict(copy.deepcopy(a.state_dict()))
         assert all(torch.is_tensor(s["step"]) and s["step"].is_cuda for s in c.state.values())
+
+
+def test_adam_entry_point_is_the_shared_path():
+    """lib.wsi_adam_step (the drop-in entry point; this test is its only Python caller) against optim.Adam(capturable=False) on clones: both run
+    the same kernel instance with host-computed factors from the same doubles, so p, exp_avg and exp_avg_sq are EQUAL after every step.  Its own
+    argument checks return WSI_EINVAL and leave every tensor as it was - a bad tensor 99 of 100 included (checked before the first launch)."""
+    from wsi_hgnn_amd import optim as O, _native as N
+    lib = N.load()
+    kw = dict(lr=1e-2, betas=(0.9, 0.999), eps=1e-8, weight_decay=5e-3)
+    ref = _params()
+    b = O.Adam(ref, capturable=False, **kw)
+    mine = _params()
+    ms, vs = [torch.zeros_like(p) for p in mine], [torch.zeros_like(p) for p in mine]
+
+    def call(arr, count, step=1, beta1=kw["betas"][0]):
+        return lib.wsi_adam_step(ctypes.cast(arr, ctypes.c_void_p) if arr is not None else None, count, kw["lr"], beta1, kw["betas"][1],
+                                 kw["eps"], kw["weight_decay"], step, N.stream())
+
+    def table(idx):
+        arr = (N.AdamTensor * len(idx))()
+        for k, i in enumerate(idx):
+            arr[k].p, arr[k].g, arr[k].m, arr[k].v, arr[k].n = mine[i].data_ptr(), mine[i].grad.data_ptr(), ms[i].data_ptr(), vs[i].data_ptr(), mine[i].numel()
+        return arr
+
+    taken = [0] * len(mine)
+    for it in range(3):
+        _set_grads(mine, it)
+        _set_grads(ref, it)
+        by_t = {}
+        for i, p in enumerate(mine):
+            if p.grad is not None:
+                taken[i] += 1
+                by_t.setdefault(taken[i], []).append(i)
+        for t, idx in by_t.items():
+            assert call(table(idx), len(idx), step=t) == N.WSI_OK
+        b.step()
+        for i, (x, y) in enumerate(zip(mine, ref)):
+            assert torch.equal(x, y), (it, i)
+            assert torch.equal(ms[i], b.state[y]["exp_avg"]) and torch.equal(vs[i], b.state[y]["exp_avg_sq"]), (it, i)
+            assert b.state[y]["step"] == taken[i]
+    # refused calls: WSI_EINVAL, nothing written
+    _set_grads(mine, 0)
+    idx = list(range(len(mine)))
+    copies = [[t.detach().clone() for t in ts] for ts in (mine, ms, vs)]
+    hundred = table([k % len(mine) for k in range(100)])       # (the same tensors over and over: more entries than the kernel's table of 88 holds)
+    hundred[99].g, hundred[99].n = None, 5                     # a null gradient on a non-empty tensor, behind a full first table
+    for rc in (call(table(idx), len(idx), step=0), call(table(idx), len(idx), beta1=1.0), call(None, 2), call(hundred, 100)):
+        assert rc == N.WSI_EINVAL
+    torch.cuda.synchronize()
+    for ts, cs in zip((mine, ms, vs), copies):
+        for i, (x, c) in enumerate(zip(ts, cs)):
+            assert torch.equal(x, c), i
 
 
 @pytest.mark.parametrize("which", ["adam", "sgd"])

@@ -30,7 +30,7 @@ m = (models.HGTASAP(ND, ed, 1024, 200, 2, 2, 4, pooled_edges=EDGES) if ASAP else
 G, y = synthetic.hetero_batch(B, 20000, 1024, rank=0, dst_mode=os.environ.get("DST", "uniform"), edges_per_dst=3)
 G = G.to(dev); y = y.to(dev)
 from wsi_hgnn_amd.optim import Adam
-opt = Adam([p for p in m.parameters()], lr=1e-5)        # (the reference's Adam in one launch: wsi_adam_step, as bench.py)
+opt = Adam([p for p in m.parameters()], lr=1e-5)        # (the reference's Adam in one launch: wsi_optim_step, as bench.py)
 lf = torch.nn.CrossEntropyLoss()
 
 def step():

@@ -46,7 +46,7 @@ def summary(path, out=None):
     rows += [(s, e - s, "C", st, f"{n} {b}") for n, s, e, b, st in cur.execute("select name, start, end, size, stream_id from memory_copies")]
     rows.sort()
     main_stream = collections.Counter(r[3] for r in rows if r[2] == "K").most_common(1)[0][0]
-    adam = [i for i, r in enumerate(rows) if "adam_step" in r[4]]
+    adam = [i for i, r in enumerate(rows) if "adam_step" in r[4] or "optim_step_kernel" in r[4]]       # (adam_step: traces older than round 16)
     lines = ["# step: wall us | kernel time on the caller's stream us | H2D feature copies (>= 8 MB): count, busy us, first start, last end (us after the previous optimizer launch)"]
     plain, fed = None, None
     for a, b in zip(adam[:-1], adam[1:]):

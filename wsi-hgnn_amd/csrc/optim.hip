@@ -1,76 +1,9 @@
-// Multi-tensor Adam step for gfx950: ONE launch over all parameters of the model (the optimizer step the reference's trainer takes after
-// loss.backward(): torch.optim.Adam(lr, weight_decay) of parser.py:33-38, trainer/train_gnn.py:72).  Contract: include/wsi_hgnn.h.
+// The optimizer steps for gfx950: ONE launch over all parameters of the model (the step the reference's trainer takes after loss.backward():
+// torch.optim.Adam(lr, weight_decay) of parser.py:33-38, trainer/train_gnn.py:72; Adagrad, Adadelta and SGD are parser.py:15-46's other branches).
+// Contract: include/wsi_hgnn.h.
 //
-// HBM-bound streaming: per element 16 bytes read (p, g, m, v), 12 written; 16-byte lane accesses where the four pointers allow it.  The
-// tensor table travels in the kernel arguments (no upload); a workgroup finds its tensor by a scan of the block prefix (<= 64 entries).
-#include "common.h"
-#include <math.h>
-#include <cmath>
-
-namespace wsi {
-
-constexpr int ADAM_MAX = 128;           // tensors per launch (HEATNet4 with 3 node types has 75)
-constexpr int ADAM_BLOCK_ELEMS = 4096;  // elements per workgroup (256 threads x 4 vectors of 4)
-
-struct AdamTable {
-    float* p[ADAM_MAX];
-    const float* g[ADAM_MAX];
-    float* m[ADAM_MAX];
-    float* v[ADAM_MAX];
-    int32_t block_start[ADAM_MAX + 1];  // prefix of workgroups per tensor
-    int64_t n[ADAM_MAX];
-    int32_t count;
-    float step_size, beta1, beta2, omb1, omb2, eps, weight_decay, bc2_sqrt;   // step_size = lr / (1 - beta1^t), omb = 1 - beta (taken in double), bc2_sqrt = sqrt(1 - beta2^t)
-};
-
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamTable& T) {
-    g = fmaf(T.weight_decay, p, g);                       // torch.optim.Adam: L2 penalty added to the gradient (not AdamW)
-    m = fmaf(T.omb1, g - m, m);                           // exp_avg.lerp_(grad, 1 - beta1)
-    v = fmaf(T.beta2, v, T.omb2 * g * g);                 // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    const float denom = sqrtf(v) / T.bc2_sqrt + T.eps;
-    p -= T.step_size * (m / denom);
-}
-
-__global__ __launch_bounds__(256) void adam_step_kernel(const AdamTable T) {
-    int t = 0;
-    const int b = (int)blockIdx.x;
-    while (t + 1 < T.count && T.block_start[t + 1] <= b) ++t;          // (block-uniform; <= 64 steps)
-    const int64_t base = (int64_t)(b - T.block_start[t]) * ADAM_BLOCK_ELEMS;
-    const int64_t n = T.n[t];
-    float* __restrict__ p = T.p[t];
-    const float* __restrict__ g = T.g[t];
-    float* __restrict__ m = T.m[t];
-    float* __restrict__ v = T.v[t];
-    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-#pragma unroll
-    for (int q = 0; q < ADAM_BLOCK_ELEMS / 1024; ++q) {
-        const int64_t i = base + q * 1024 + (int64_t)threadIdx.x * 4;
-        if (i >= n) break;
-        if (vec && i + 3 < n) {
-            float4 pv = *reinterpret_cast<const float4*>(p + i);
-            const float4 gv = *reinterpret_cast<const float4*>(g + i);
-            float4 mv = *reinterpret_cast<const float4*>(m + i);
-            float4 vv = *reinterpret_cast<const float4*>(v + i);
-            adam_one(pv.x, gv.x, mv.x, vv.x, T); adam_one(pv.y, gv.y, mv.y, vv.y, T);
-            adam_one(pv.z, gv.z, mv.z, vv.z, T); adam_one(pv.w, gv.w, mv.w, vv.w, T);
-            *reinterpret_cast<float4*>(p + i) = pv;
-            *reinterpret_cast<float4*>(m + i) = mv;
-            *reinterpret_cast<float4*>(v + i) = vv;
-        } else {
-            for (int k = 0; k < 4 && i + k < n; ++k) {
-                float pk = p[i + k], mk = m[i + k], vk = v[i + k];
-                adam_one(pk, g[i + k], mk, vk, T);
-                p[i + k] = pk; m[i + k] = mk; v[i + k] = vk;
-            }
-        }
-    }
-}
-
-}  // namespace wsi
-
-// ---------------------------------------------------------------------------------------------------------------------------------------
-// SGD / Adagrad / Adadelta / Adam-with-a-device-count: one kernel template over the rule, same shape as adam_step_kernel above (table in the
-// kernel arguments, 4096 elements per workgroup, block-prefix scan, 16-byte lane accesses where every pointer of the tensor allows it).
+// One kernel template over the rule.  HBM-bound streaming, 16-byte lane accesses where every pointer of the tensor allows it; the tensor table
+// travels in the kernel arguments (no upload); a workgroup of 256 threads takes 4096 elements and finds its tensor by a scan of the block prefix.
 // HBM bytes per element (read + written): SGD 8 + 4, SGD with momentum 12 + 8 (8 + 8 on a tensor's first step), Adagrad 12 + 8,
 // Adadelta 16 + 12, Adam 16 + 12.
 //
@@ -80,9 +13,14 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamTable T) {
 // draws the last one stores old + 1 and swaps the ticket back to 0.  Nobody waits for anybody: a workgroup has CONSUMED its load of the count
 // (it went through LDS and a barrier) before its add issues, so the one store of the new count comes after every load of the old one, and
 // what this launch writes (elements, count, ticket) is read by the next kernel only - no fence.
+#include "common.h"
+#include <math.h>
+#include <cmath>
+
 namespace wsi {
 
-constexpr int OPTIM_MAX = 88;           // tensors per launch: sizeof(OptimTable) <= sizeof(AdamTable) (HEATNet4 with 3 node types has 75)
+constexpr int OPTIM_MAX = 88;             // tensors per launch (HEATNet4 with 3 node types has 75); see the static_assert below
+constexpr int OPTIM_BLOCK_ELEMS = 4096;   // elements per workgroup (256 threads x 4 vectors of 4)
 enum { R_SGD = 0, R_SGD_MOMENTUM, R_ADAGRAD, R_ADADELTA, R_ADAM };      // (kernel instances: SGD without a buffer is one of its own)
 
 struct OptimTable {
@@ -101,7 +39,8 @@ struct OptimTable {
     float f0, f1;                                         // the factors for t = host_step: Adam step_size, bc2_sqrt; Adagrad clr
     int32_t nesterov;
 };
-static_assert(sizeof(OptimTable) <= sizeof(AdamTable), "the table travels in the kernel arguments: no larger than adam_step_kernel's");
+static_assert(sizeof(OptimTable) <= 5680, "the table travels in the kernel arguments: no larger than the largest argument block this library has "
+                                          "launched with (5680 bytes: the 128-tensor table of the Adam kernel this template replaced)");
 
 // the factors of the 1-based count t (double in, float out): the host for host_step, lane 0 of a workgroup for a device count
 template <int RULE>
@@ -135,7 +74,7 @@ __device__ __forceinline__ void optim_one(float& p, float g, float& a, float& b,
         const float d = __fmul_rn(sqrtf(b + T.eps) / sqrtf(a + T.eps), g); // delta = sqrt(acc_delta + eps) / sqrt(square_avg + eps) * grad
         b = fmaf(__fmul_rn(T.omr, d), d, __fmul_rn(T.rho, b));             // acc_delta.mul_(rho).addcmul_(delta, delta, value=1 - rho)
         p = fmaf(-T.lr, d, p);
-    } else {                                                               // adam_one, with step_size = f0 and bc2_sqrt = f1
+    } else {                                                               // Adam: step_size = f0, bc2_sqrt = f1
         a = fmaf(T.omb1, g - a, a);
         b = fmaf(T.beta2, b, T.omb2 * g * g);
         const float denom = sqrtf(b) / f1 + T.eps;
@@ -151,7 +90,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
     const int blk = (int)blockIdx.x;
     while (t + 1 < T.count && T.block_start[t + 1] <= blk) ++t;            // (block-uniform)
     t = __builtin_amdgcn_readfirstlane(t);                                 // (said to the compiler: every table read below stays a scalar load of the kernel arguments)
-    const int64_t base = (int64_t)(blk - T.block_start[t]) * ADAM_BLOCK_ELEMS;
+    const int64_t base = (int64_t)(blk - T.block_start[t]) * OPTIM_BLOCK_ELEMS;
     const int64_t n = T.n[t];
     float* __restrict__ p = T.p[t];
     const float* __restrict__ g = T.g[t];
@@ -178,7 +117,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
     if (NS >= 2) bits |= reinterpret_cast<uintptr_t>(s1);
     const bool vec = (bits & 15) == 0;
 #pragma unroll
-    for (int q = 0; q < ADAM_BLOCK_ELEMS / 1024; ++q) {
+    for (int q = 0; q < OPTIM_BLOCK_ELEMS / 1024; ++q) {
         const int64_t i = base + q * 1024 + (int64_t)threadIdx.x * 4;
         if (i >= n) break;
         if (vec && i + 3 < n) {
@@ -223,34 +162,77 @@ static void optim_launch(const OptimTable& T, unsigned blocks, hipStream_t st) {
 
 using namespace wsi;
 
+// the kernel instance of a rule, and the state tensors it reads (s0, s1)
+static int optim_instance(int32_t rule, const wsi_optim_hyper_t& H) {
+    return rule == WSI_OPTIM_SGD ? (H.momentum != 0.0 ? R_SGD_MOMENTUM : R_SGD) : rule == WSI_OPTIM_ADAGRAD ? R_ADAGRAD : rule == WSI_OPTIM_ADADELTA ? R_ADADELTA : R_ADAM;
+}
+static int optim_states(int inst) { return inst == R_SGD ? 0 : (inst == R_SGD_MOMENTUM || inst == R_ADAGRAD) ? 1 : 2; }
+
+// What both entry points do once every argument is checked: the hyper-parameters into the table, then one launch per OPTIM_MAX non-empty tensors.
+static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t& H, hipStream_t st) {
+    const int inst = optim_instance(rule, H), ns = optim_states(inst);
+    OptimTable T;
+    T.lr_d = H.lr; T.lr_decay_d = H.lr_decay; T.beta1_d = H.beta1; T.beta2_d = H.beta2;
+    // the scalar factors in double, as torch's host code takes them (1 - 0.999f in float is off by 1.3e-5 relative)
+    T.lr = (float)H.lr; T.weight_decay = (float)H.weight_decay; T.momentum = (float)H.momentum; T.omd = (float)(1.0 - H.dampening);
+    T.eps = (float)H.eps; T.rho = (float)H.rho; T.omr = (float)(1.0 - H.rho);
+    T.beta2 = (float)H.beta2; T.omb1 = (float)(1.0 - H.beta1); T.omb2 = (float)(1.0 - H.beta2);
+    T.nesterov = H.nesterov != 0.0;
+    T.f0 = T.f1 = 0.f;
+    if (H.host_step >= 1.0) {
+        if (inst == R_ADAM) optim_factors<R_ADAM>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
+        if (inst == R_ADAGRAD) optim_factors<R_ADAGRAD>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
+    }
+    for (int32_t first = 0; first < count;) {          // (`first` advances by what the table CONSUMED: empty tensors are skipped without taking a slot)
+        T.count = 0;
+        int64_t blocks = 0;
+        int32_t i = first;
+        for (; i < count && T.count < OPTIM_MAX; ++i) {
+            const wsi_optim_tensor_t& a = tensors[i];
+            if (a.n == 0) continue;
+            const int k = T.count++;
+            T.p[k] = a.p; T.g[k] = a.g; T.s0[k] = ns >= 1 ? a.s0 : nullptr; T.s1[k] = ns >= 2 ? a.s1 : nullptr;
+            T.step[k] = a.step; T.ticket[k] = a.ticket; T.n[k] = a.n; T.flags[k] = (uint8_t)(a.flags & WSI_OPTIM_FIRST);
+            T.block_start[k] = (int32_t)blocks;
+            blocks += (a.n + OPTIM_BLOCK_ELEMS - 1) / OPTIM_BLOCK_ELEMS;
+        }
+        T.block_start[T.count] = (int32_t)blocks;
+        if (T.count) {
+            switch (inst) {
+                case R_SGD: optim_launch<R_SGD>(T, (unsigned)blocks, st); break;
+                case R_SGD_MOMENTUM: optim_launch<R_SGD_MOMENTUM>(T, (unsigned)blocks, st); break;
+                case R_ADAGRAD: optim_launch<R_ADAGRAD>(T, (unsigned)blocks, st); break;
+                case R_ADADELTA: optim_launch<R_ADADELTA>(T, (unsigned)blocks, st); break;
+                default: optim_launch<R_ADAM>(T, (unsigned)blocks, st); break;
+            }
+        }
+        first = i;
+    }
+}
+
 extern "C" int wsi_adam_step(const wsi_adam_tensor_t* tensors, int32_t count, double lr, double beta1, double beta2, double eps,
                              double weight_decay, int64_t step, void* stream) {
+    // wsi_optim_step(WSI_OPTIM_ADAM) with a host count; like it, every tensor is checked before the first launch
     if (count < 0 || step <= 0 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) { set_error("adam_step: bad argument"); return WSI_EINVAL; }
     if (count == 0) return WSI_OK;
     if (!tensors) { set_error("adam_step: null tensor table"); return WSI_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    // the scalar factors in double, as torch's host code takes them (1 - 0.999f in float is off by 1.3e-5 relative)
-    const float step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
-    const float bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-    for (int32_t first = 0; first < count;) {          // (`first` advances by what the table CONSUMED: empty tensors are skipped without taking a slot)
-        AdamTable T;
-        T.count = 0; T.step_size = step_size; T.beta1 = (float)beta1; T.beta2 = (float)beta2; T.omb1 = (float)(1.0 - beta1); T.omb2 = (float)(1.0 - beta2);
-        T.eps = (float)eps; T.weight_decay = (float)weight_decay; T.bc2_sqrt = bc2_sqrt;
-        int64_t blocks = 0;
-        int32_t i = first;
-        for (; i < count && T.count < ADAM_MAX; ++i) {
+    int64_t all_blocks = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        const wsi_adam_tensor_t& a = tensors[i];
+        if (a.n < 0 || (a.n > 0 && (!a.p || !a.g || !a.m || !a.v))) { set_error("adam_step: tensor %d: null pointer or negative size", i); return WSI_EINVAL; }
+        all_blocks += a.n / OPTIM_BLOCK_ELEMS + 1;
+        if (all_blocks > INT32_MAX) { set_error("adam_step: too many elements in one call"); return WSI_EINVAL; }
+    }
+    wsi_optim_hyper_t H = {};
+    H.lr = lr; H.weight_decay = weight_decay; H.eps = eps; H.beta1 = beta1; H.beta2 = beta2; H.host_step = (double)step;
+    wsi_optim_tensor_t chunk[OPTIM_MAX];               // the descriptors of one launch, translated (s0 = m, s1 = v, no step word)
+    for (int32_t i = 0; i < count;) {
+        int32_t k = 0;
+        for (; i < count && k < OPTIM_MAX; ++i) {
             const wsi_adam_tensor_t& a = tensors[i];
-            if (a.n < 0 || (a.n > 0 && (!a.p || !a.g || !a.m || !a.v))) { set_error("adam_step: tensor %d: null pointer or negative size", i); return WSI_EINVAL; }
-            if (a.n == 0) continue;
-            const int k = T.count++;
-            T.p[k] = a.p; T.g[k] = a.g; T.m[k] = a.m; T.v[k] = a.v; T.n[k] = a.n;
-            T.block_start[k] = (int32_t)blocks;
-            blocks += (a.n + ADAM_BLOCK_ELEMS - 1) / ADAM_BLOCK_ELEMS;
-            if (blocks > INT32_MAX) { set_error("adam_step: too many elements in one launch"); return WSI_EINVAL; }
+            if (a.n) chunk[k++] = wsi_optim_tensor_t{a.p, a.g, a.m, a.v, nullptr, nullptr, a.n, 0};
         }
-        T.block_start[T.count] = (int32_t)blocks;
-        if (T.count) hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)blocks), dim3(256), 0, st, T);
-        first = i;
+        if (k) optim_launches(WSI_OPTIM_ADAM, chunk, k, H, (hipStream_t)stream);
     }
     return check_launch("adam_step");
 }
@@ -273,14 +255,13 @@ extern "C" int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, i
     if (count == 0) return WSI_OK;
     if (!tensors) { set_error("optim_step: null tensor table"); return WSI_EINVAL; }
     const bool counts = rule == WSI_OPTIM_ADAGRAD || rule == WSI_OPTIM_ADAM;           // the rules that read t
-    const bool momentum = rule == WSI_OPTIM_SGD && H.momentum != 0.0;
-    const int ns = rule == WSI_OPTIM_SGD ? (momentum ? 1 : 0) : rule == WSI_OPTIM_ADAGRAD ? 1 : 2;
+    const int ns = optim_states(optim_instance(rule, H));
     int64_t all_blocks = 0;
     int32_t nonempty = 0;
     for (int32_t i = 0; i < count; ++i) {
         const wsi_optim_tensor_t& a = tensors[i];
         if (a.n < 0) { set_error("optim_step: tensor %d: negative size", i); return WSI_EINVAL; }
-        all_blocks += a.n / ADAM_BLOCK_ELEMS + 1;
+        all_blocks += a.n / OPTIM_BLOCK_ELEMS + 1;
         if (all_blocks > INT32_MAX) { set_error("optim_step: too many elements in one call"); return WSI_EINVAL; }
         if (a.step && !a.ticket) { set_error("optim_step: tensor %d: a step word without a ticket word", i); return WSI_EINVAL; }
         if (a.n == 0) continue;
@@ -289,43 +270,6 @@ extern "C" int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, i
         if (counts && !a.step && !(H.host_step >= 1.0 && std::isfinite(H.host_step))) { set_error("optim_step: tensor %d has no step word and host_step is not a count >= 1", i); return WSI_EINVAL; }
     }
     if (nonempty == 0) return WSI_OK;                  // zero-element tensors only: nothing to launch (and no HIP call)
-    const int inst = rule == WSI_OPTIM_SGD ? (momentum ? R_SGD_MOMENTUM : R_SGD) : rule == WSI_OPTIM_ADAGRAD ? R_ADAGRAD : rule == WSI_OPTIM_ADADELTA ? R_ADADELTA : R_ADAM;
-    hipStream_t st = (hipStream_t)stream;
-    OptimTable T;
-    T.lr_d = H.lr; T.lr_decay_d = H.lr_decay; T.beta1_d = H.beta1; T.beta2_d = H.beta2;
-    T.lr = (float)H.lr; T.weight_decay = (float)H.weight_decay; T.momentum = (float)H.momentum; T.omd = (float)(1.0 - H.dampening);
-    T.eps = (float)H.eps; T.rho = (float)H.rho; T.omr = (float)(1.0 - H.rho);
-    T.beta2 = (float)H.beta2; T.omb1 = (float)(1.0 - H.beta1); T.omb2 = (float)(1.0 - H.beta2);
-    T.nesterov = H.nesterov != 0.0;
-    T.f0 = T.f1 = 0.f;
-    if (counts && H.host_step >= 1.0) {
-        if (inst == R_ADAM) optim_factors<R_ADAM>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
-        else optim_factors<R_ADAGRAD>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
-    }
-    for (int32_t first = 0; first < count;) {          // (`first` advances by what the table CONSUMED: empty tensors are skipped without taking a slot)
-        T.count = 0;
-        int64_t blocks = 0;
-        int32_t i = first;
-        for (; i < count && T.count < OPTIM_MAX; ++i) {
-            const wsi_optim_tensor_t& a = tensors[i];
-            if (a.n == 0) continue;
-            const int k = T.count++;
-            T.p[k] = a.p; T.g[k] = a.g; T.s0[k] = ns >= 1 ? a.s0 : nullptr; T.s1[k] = ns >= 2 ? a.s1 : nullptr;
-            T.step[k] = a.step; T.ticket[k] = a.ticket; T.n[k] = a.n; T.flags[k] = (uint8_t)(a.flags & WSI_OPTIM_FIRST);
-            T.block_start[k] = (int32_t)blocks;
-            blocks += (a.n + ADAM_BLOCK_ELEMS - 1) / ADAM_BLOCK_ELEMS;
-        }
-        T.block_start[T.count] = (int32_t)blocks;
-        if (T.count) {
-            switch (inst) {
-                case R_SGD: optim_launch<R_SGD>(T, (unsigned)blocks, st); break;
-                case R_SGD_MOMENTUM: optim_launch<R_SGD_MOMENTUM>(T, (unsigned)blocks, st); break;
-                case R_ADAGRAD: optim_launch<R_ADAGRAD>(T, (unsigned)blocks, st); break;
-                case R_ADADELTA: optim_launch<R_ADADELTA>(T, (unsigned)blocks, st); break;
-                default: optim_launch<R_ADAM>(T, (unsigned)blocks, st); break;
-            }
-        }
-        first = i;
-    }
+    optim_launches(rule, tensors, count, H, (hipStream_t)stream);
     return check_launch("optim_step");
 }

@@ -1,18 +1,18 @@
 """The optimizer step of the reference's trainer on the GPU in ONE launch.
 
-``parser.parse_optimizer`` (parser.py:33-38) builds ``torch.optim.Adam(model.parameters(), lr, weight_decay)`` and
-``trainer/train_gnn.py:72`` calls ``optimizer.step()`` after ``loss.backward()``.  :class:`Adam` is that optimizer with the same
-arithmetic (L2 penalty added to the gradient, bias-corrected moments, ``amsgrad=False``) and the same ``state_dict`` layout
-(``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter: checkpoints move between the two), stepping every parameter of a group through
-``wsi_adam_step`` (csrc/optim.hip): one kernel, 28 bytes of HBM traffic per element, where torch's fused path takes two launches at half
-the bandwidth on this model's 54 tensors.  GPU only - there is no CPU path.
+``parser.parse_optimizer`` (parser.py:15-46) builds ``torch.optim.Adam(model.parameters(), lr, weight_decay)`` (:33-38), :class:`Adagrad`
+(``lr_decay = weight_decay``, :23), :class:`Adadelta`, and :class:`SGD` for anything else; ``trainer/train_gnn.py:72`` calls ``optimizer.step()``
+after ``loss.backward()``.  The four classes here are those optimizers with torch's arithmetic (Adam: L2 penalty added to the gradient,
+bias-corrected moments, ``amsgrad=False``), torch's constructor arguments and torch's ``state_dict`` layout (``step`` / ``exp_avg`` /
+``exp_avg_sq``; ``momentum_buffer``; ``sum`` / ``step``; ``step`` / ``square_avg`` / ``acc_delta`` - checkpoints move between the two), each
+stepping every parameter of a group through ``wsi_optim_step`` (csrc/optim.hip): one kernel template over the rule, one launch over all tensors -
+for Adam 28 bytes of HBM traffic per element, where torch's fused path takes two launches at half the bandwidth on this model's 54 tensors.
+GPU only - there is no CPU path.
 
-The other three branches of ``parse_optimizer`` (parser.py:15-46) - :class:`Adagrad` (``lr_decay = weight_decay``, :23), :class:`Adadelta` and
-:class:`SGD` for anything else - and ``Adam(..., capturable=True)`` step through ``wsi_optim_step``: one kernel template over the rule, again one
-launch over all tensors, with torch's arithmetic, constructor arguments and ``state_dict`` layout (``momentum_buffer`` / ``step``, ``sum`` /
-``step``, ``square_avg``, ``acc_delta``).  ``capturable=True`` keeps ``state["step"]`` as a 0-dim fp32 device word, torch's capturable layout,
-which the kernel itself advances: that is what ``trainer.CapturedStep`` needs to replay the step from a hipGraph.  SGD and Adadelta never read a
-count, so their groups always carry ``capturable=True``.
+Adam and Adagrad read the step count.  By default ``state["step"]`` is a Python int, as a checkpoint of torch's holds it, and the step's factors
+are taken on the host.  ``capturable=True`` keeps it as a 0-dim fp32 device word, torch's capturable layout, which the kernel itself reads and
+advances: that is what ``trainer.CapturedStep`` needs to replay the step from a hipGraph.  SGD and Adadelta never read a count, so their groups
+always carry ``capturable=True``.
 """
 from __future__ import annotations
 
@@ -52,6 +52,7 @@ class _OneLaunch(torch.optim.Optimizer):
             st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if group["capturable"] else 0
         for k in self.STATE:
             st[k] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        self.__dict__.pop("_wsi_tables", None)                    # (a cached table holds the pointers of the state it was built over)
         return st
 
     def _state_keys(self, group: dict):
@@ -114,7 +115,10 @@ class _OneLaunch(torch.optim.Optimizer):
             st = self.state[p] if keys else {}                  # (SGD without momentum keeps no state, and like torch leaves no empty entry)
             flags = self._ensure_state(p, group, st)
             t = 0
-            if host_counts:                                      # a plain Python number, as Adam's (a state loaded from torch brings a tensor: converted once)
+            # the count is a plain Python number (a state loaded from torch.optim brings a tensor: converted once; torch converts back when it
+            # loads ours).  One host-tensor update per parameter and step, as torch keeps them, was the one thing in this loop that touched the
+            # CPU tensor machinery - and with it, once in ~30 steps, an 80 ms stall of the whole process on a CPU-quota'd box.
+            if host_counts:
                 t = int(st["step"]) + 1
                 st["step"] = t
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
@@ -129,7 +133,8 @@ class _OneLaunch(torch.optim.Optimizer):
             hyper = self.__dict__["_wsi_hyper"] = N.OptimHyper()
         self._hyper(group, hyper)
         for t, items in by_step.items():                        # (one launch when every parameter has been stepped equally often, or counts on the device)
-            # the descriptor table is kept between steps and only the pointers that move are refreshed (gradients; a state a checkpoint replaced)
+            # the descriptor table is kept between steps and only the pointers that move are refreshed: the parameter's and the gradient's.  The
+            # state tensors, step words included, are replaced by _new_state and load_state_dict only, and both drop the table
             key = tuple(id(p) for p, _, _, _ in items)
             cached = tables.get(gi)
             if cached is None or cached[0] != key:
@@ -139,8 +144,10 @@ class _OneLaunch(torch.optim.Optimizer):
                 for a, (p, _, st, _) in zip(arr, items):
                     a.n = p.numel()
                     written.append(p)
-                    written.extend(st[k] for k in self.STATE)
-                    if has_step:                                 # (a step word is only ever replaced by load_state_dict, which drops this table)
+                    for field, k in zip(("s0", "s1"), self.STATE):
+                        setattr(a, field, st[k].data_ptr())
+                        written.append(st[k])
+                    if has_step:
                         if p.device != tick.device:
                             tick = self._tickets(p.device)
                         a.step, a.ticket = st["step"].data_ptr(), tick.data_ptr() + 4 * index[id(p)]
@@ -149,18 +156,14 @@ class _OneLaunch(torch.optim.Optimizer):
                             empty.append(st["step"])
                 cached = tables[gi] = (key, arr, ctypes.cast(arr, ctypes.c_void_p), written, empty)
             _, arr, arr_p, written, empty = cached
-            s0, s1 = (tuple(self.STATE) + (None, None))[:2]
-            for a, (p, g, st, flags) in zip(arr, items):
+            for a, (p, g, _, flags) in zip(arr, items):
                 a.p, a.g, a.flags = p.data_ptr(), g.data_ptr(), flags
-                if s0 is not None:
-                    a.s0 = st[s0].data_ptr()
-                    if s1 is not None:
-                        a.s1 = st[s1].data_ptr()
             for word in empty:
                 word += 1                                        # (no workgroup of the launch covers a zero-element tensor; torch counts its steps too)
             hyper.host_step = float(t)
             N.check(lib.wsi_optim_step(self.RULE, arr_p, len(items), ctypes.addressof(hyper), N.stream()), "wsi_optim_step")
-            # the kernel wrote through raw pointers: move the version counters as torch.optim's in-place ops would (see Adam.step)
+            # the kernel wrote through raw pointers: move the version counters as torch.optim's in-place ops would, so that autograd's "modified
+            # by an inplace operation" check and every version-keyed fact about these tensors (ops._annotate) see the step
             torch.autograd.graph.increment_version(written)
 
     @torch.no_grad()
@@ -199,6 +202,7 @@ class SGD(_OneLaunch):
     def _new_state(self, p, group):
         st = self.state[p]
         st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)      # written, not read, by the first step
+        self.__dict__.pop("_wsi_tables", None)
         return st
 
     def _ensure_state(self, p, group, st):
@@ -266,6 +270,7 @@ class Adadelta(_OneLaunch):
 
 
 class Adam(_OneLaunch):
+    """``torch.optim.Adam`` (parser.py:33-38, the reference's default) in one launch; the count a Python int, or a device word under ``capturable=True``."""
     RULE = N.WSI_OPTIM_ADAM
     STATE = ("exp_avg", "exp_avg_sq")
     READS_COUNT = True
@@ -283,57 +288,3 @@ class Adam(_OneLaunch):
     def _hyper(self, group, h):
         h.lr, h.weight_decay, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
         h.beta1, h.beta2 = float(group["betas"][0]), float(group["betas"][1])
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        lib = N.load()
-        from . import ops
-        ops._background_recover()       # a backward pass that raised never joined its side stream: order this step behind it (no-op otherwise)
-        for gi, group in enumerate(self.param_groups):
-            if group.get("capturable", False):                  # the count on the device: wsi_optim_step (the default path below is as it was)
-                self._step_group(lib, gi, group)
-                continue
-            by_step = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("wsi_hgnn_amd.optim.Adam steps contiguous fp32 parameters on the GPU only (no CPU path)")
-                if p.grad.is_sparse:
-                    raise RuntimeError("wsi_hgnn_amd.optim.Adam does not take sparse gradients")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                # the count is a plain Python number (a state loaded from torch.optim.Adam brings a tensor: converted once; torch converts back
-                # when it loads ours).  54 host-tensor updates per step, as torch keeps them, were the one thing in this loop that touched
-                # the CPU tensor machinery - and with it, once in ~30 steps, an 80 ms stall of the whole process on a CPU-quota'd box.
-                t = int(st["step"]) + 1
-                st["step"] = t
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                by_step.setdefault(t, []).append((p, g, st["exp_avg"], st["exp_avg_sq"]))
-            for t, items in by_step.items():            # (one launch when every parameter has been stepped equally often - the usual case)
-                # the descriptor table is kept between steps and only the gradient pointers are refreshed: p / m / v never move, and a fresh
-                # table of 54 structs per step is allocation churn that brings Python's cyclic collector round sooner (an 80 ms pause)
-                key = tuple(id(p) for p, _, _, _ in items)
-                tables = self.__dict__.setdefault("_wsi_tables", {})          # (on the optimizer, not in param_groups: state_dict() stays plain data)
-                cached = tables.get(gi)
-                if cached is None or cached[0] != key:
-                    arr = (N.AdamTensor * len(items))(*[N.AdamTensor(p.data_ptr(), 0, m.data_ptr(), v.data_ptr(), p.numel()) for p, _, m, v in items])
-                    cached = tables[gi] = (key, arr, ctypes.cast(arr, ctypes.c_void_p))
-                _, arr, arr_p = cached
-                for i, (p, g, m, v) in enumerate(items):
-                    a = arr[i]
-                    a.p, a.g, a.m, a.v = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-                N.check(lib.wsi_adam_step(arr_p, len(items), float(group["lr"]), float(group["betas"][0]),
-                                          float(group["betas"][1]), float(group["eps"]), float(group["weight_decay"]), t, N.stream()), "wsi_adam_step")
-                # the kernel wrote p / m / v through raw pointers: move their version counters as torch.optim.Adam's in-place ops would, so that
-                # autograd's "modified by an inplace operation" check and every version-keyed fact about these tensors (ops._annotate) see the step
-                torch.autograd.graph.increment_version([t_ for p, _, m, v in items for t_ in (p, m, v)])
-        ops.repack_weights()            # the packed fp16 planes of the weights the projections read (ops._PACKED): all of them in one launch per op
-        return loss
