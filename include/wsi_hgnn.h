@@ -464,6 +464,48 @@ int wsi_bag_scores_bwd(const float* w, int64_t ldw, const float* t, const float*
                        int32_t C, int32_t D, const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks,
                        float* gx, int64_t ldgx, void* stream);
 
+/* ReMix's bag reduction (an addition to ABI 26): ONE Lloyd iteration of a k-means over the rows of many bags at once - what faiss does per slide
+ * for baselines/ReMix_DSMIL_ABMIL/reduce.py:18-19 (tools/clustering.py).  x [rows, D] with row stride ldx, the bags one after the other under the
+ * chunk tables of wsi_segment_reduce_fwd (chunk_seg as for wsi_segment_reduce_bwd); centroids [num_segs, K, D] contiguous.  Per row
+ *   xn    = normalize ? x / (|x|_2 + 1e-10) : x                (tools/clustering.py:42-44; a zero row stays zero)
+ *   label = the first minimum over k of sum_c (xn[c] - centroid[k, c])^2
+ * labels [rows] int32; objective [num_segs] = the sum of the winning squared distances; new_centroids [num_segs, K, D] = the mean of xn per label,
+ * or NULL: assign only.  counts [num_segs, K] int32 = rows per label - with new_centroids given, AFTER the split of the empty clusters; they sum
+ * to the bag's rows either way.
+ * Empty clusters (faiss's split with a deterministic donor), for k upwards: the donor is the cluster with the largest current count (the lowest
+ * index on a tie); centroid[k] = donor * (1 + e) on even columns and donor * (1 - e) on odd ones, the donor's centroid the opposite, e = 1 / 1024;
+ * k takes donor_count / 2 of the count, the donor keeps the rest.
+ * A bag with fewer than K rows (an empty one included) is legal: its labels are 0 and its counts, objective and new centroids are 0.
+ * 1 <= K <= 16 (more: WSI_ENOSYS), any D >= 1; 16-byte row loads when x and ldx are 16-byte aligned, a scalar path otherwise; beyond D = 1024 a
+ * slower kernel that re-reads a row from cache.  Two stages (a chunk's rows, then the bag's chunks in chunk order): x is read from memory once,
+ * no atomics, bit-reproducible, and a bag's results do not depend on the other bags of the launch.
+ * partial: caller scratch, num_chunks * K * (D + 2) floats. */
+int wsi_bag_kmeans_step(const float* x, int64_t ldx, int32_t D, const float* centroids, int32_t K, int32_t normalize,
+                        const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks,
+                        const int32_t* seg_chunk, int32_t num_segs, float* partial,
+                        int32_t* labels, int32_t* counts, float* objective, float* new_centroids, void* stream);
+
+/* ReMix's mixing (train_remix_k-fold.py:71-107, mix_aug) over a bank of reduced bags protos [S, K, D] and its shift bank shifts [S, K, V, D]
+ * (NULL: no WSI_REMIX_COV row), an addition to ABI 26.
+ * wsi_remix_nearest: nearest[b, i] = the first minimum over j of |protos[src[b], i] - protos[tgt[b], j]|^2 for the B mixed bags of a step
+ * (np.argmin(cdist(...), axis=1), line 75); 1 <= K <= 16.
+ * wsi_remix_rows: out[o, :] for every output row of every mixed bag in ONE launch, from desc [rows, 8] int32 =
+ *   [op, slot, src_row, partner, replaced, v, bits(lambda), bits(1 - lambda)]:  c = nearest[slot], tgt = protos[partner, c],
+ *   cur = replaced ? tgt : protos.view(S * K, D)[src_row], and
+ *     WSI_REMIX_KEEP         cur                                   (a row of the source bag, replaced or not)
+ *     WSI_REMIX_APPEND       tgt
+ *     WSI_REMIX_INTERPOLATE  (1 - lambda) * cur + lambda * tgt     (two rounded products, one rounded sum)
+ *     WSI_REMIX_COV          cur + lambda * shifts[partner, c, v]
+ *   A descriptor that points outside the bank gives a row of zeros and reads nothing. */
+#define WSI_REMIX_KEEP        0
+#define WSI_REMIX_APPEND      1
+#define WSI_REMIX_INTERPOLATE 2
+#define WSI_REMIX_COV         3
+int wsi_remix_nearest(const float* protos, int32_t S, int32_t K, int32_t D, const int32_t* src, const int32_t* tgt, int32_t B,
+                      int32_t* nearest, void* stream);
+int wsi_remix_rows(const float* protos, const float* shifts, int32_t S, int32_t K, int32_t V, int32_t D,
+                   const int32_t* nearest, int32_t num_slots, const int32_t* desc, int32_t rows, float* out, void* stream);
+
 /* One Adam step over `count` parameter tensors in ONE launch: the optimizer step of the reference's trainer (torch.optim.Adam(lr, weight_decay),
  * parser.py:33-38; trainer/train_gnn.py:72) with torch's arithmetic, amsgrad = False, maximize = False:
  *   g += weight_decay * p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;

@@ -2,7 +2,8 @@
 
 A slide's patch features are a bag of rows with no edges; a batch is the bags laid one after the other plus a bag plan
 (``bag_plan``).  ``abmil`` / ``dsmil`` mirror ``model/abmil.py`` / ``model/dsmil.py``; ``bag_loss`` and ``train_one_step`` mirror the
-objective and the loop body of ``train_tcga_k-fold.py``.  Not built: ReMix, ``dropout_patches``, the k-fold scripts, ``multi_label_roc``.
+objective and the loop body of ``train_tcga_k-fold.py``; ``remix`` is how the reference trains them (``reduce.py``, ``train_remix_k-fold.py``):
+k-means bag reduction and prototype mixing on the device.  Not built: ``dropout_patches``, the k-fold scripts, ``multi_label_roc``.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ from .. import ops
 from . import abmil, dsmil
 from .bags import bag_plan, rows_and_plan
 
-__all__ = ["abmil", "dsmil", "bag_plan", "bag_targets", "bag_loss", "train_one_step"]
+__all__ = ["abmil", "dsmil", "remix", "bag_plan", "bag_targets", "bag_loss", "train_one_step"]
 
 
 def bag_targets(labels, num_classes: int, device=None) -> torch.Tensor:
@@ -65,3 +66,6 @@ def train_one_step(milnet, optimizer, x, bags, labels) -> torch.Tensor:
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+from . import remix  # noqa: E402  (its train_one_step calls the one above)

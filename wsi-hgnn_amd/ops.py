@@ -1394,6 +1394,86 @@ def bag_scores(q: torch.Tensor, onehot: torch.Tensor, rp: ReducePlan) -> torch.T
 
 
 # ------------------------------------------------------------------------------------------------
+# ReMix: the k-means step over many bags and the prototype mixing (wsi_bag_kmeans_step / wsi_remix_*: wsi_hgnn_amd.mil.remix)
+# ------------------------------------------------------------------------------------------------
+KMEANS_MAX_K = 16
+REMIX_OPS = {"keep": N.WSI_REMIX_KEEP, "append": N.WSI_REMIX_APPEND, "interpolate": N.WSI_REMIX_INTERPOLATE, "cov": N.WSI_REMIX_COV}
+
+
+def bag_kmeans_step(x: torch.Tensor, rp: ReducePlan, centroids: torch.Tensor, normalize: bool = True, update: bool = True):
+    """One Lloyd iteration over every bag of the plan (``wsi_bag_kmeans_step``): x [rows, D] fp32 with unit column stride (a row stride is
+    taken as it is), centroids [num_segs, K, D], K <= 16.  Returns (labels [rows] int32, counts [num_segs, K] int32, objective [num_segs],
+    new_centroids [num_segs, K, D] or None with ``update=False``: assign only).  Nothing is read back."""
+    N.require_cuda(x, centroids)
+    if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("bag_kmeans_step: an fp32 [rows, D] table with contiguous rows")
+    if rp.first_row != 0 or rp.num_rows != x.shape[0]:
+        raise ValueError(f"bag_kmeans_step: the plan covers {rp.num_rows} rows, the table has {x.shape[0]}")
+    D = x.shape[1]
+    if centroids.dim() != 3 or centroids.shape[0] != rp.num_segs or centroids.shape[2] != D or centroids.dtype != torch.float32:
+        raise ValueError(f"bag_kmeans_step: centroids [{rp.num_segs}, K, {D}] fp32 expected, got {tuple(centroids.shape)} {centroids.dtype}")
+    centroids = centroids.contiguous()
+    K, dev = centroids.shape[1], x.device
+    labels = torch.empty(max(x.shape[0], 1), dtype=torch.int32, device=dev)[:x.shape[0]]
+    counts = torch.empty((rp.num_segs, K), dtype=torch.int32, device=dev)
+    objective = torch.empty(rp.num_segs, dtype=torch.float32, device=dev)
+    new = torch.empty_like(centroids) if update else None
+    partial = torch.empty(max(rp.num_chunks * K * (D + 2), 1), dtype=torch.float32, device=dev)
+    ldx = x.stride(0) if x.shape[0] > 1 else D
+    with _Timed("bag_kmeans_step"):
+        N.check(N.load().wsi_bag_kmeans_step(N.ptr(x), ldx, D, N.ptr(centroids), K, int(bool(normalize)), N.ptr(rp.chunk_row), N.ptr(rp.chunk_seg),
+                                             rp.num_chunks, N.ptr(rp.seg_chunk), rp.num_segs, N.ptr(partial), N.ptr(labels), N.ptr(counts),
+                                             N.ptr(objective), N.ptr(new), N.stream()), "wsi_bag_kmeans_step")
+    return labels, counts, objective, new
+
+
+def remix_nearest(protos: torch.Tensor, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
+    """[B, K] int32: for every prototype of bag src[b] the closest prototype of bag tgt[b] (first minimum); protos [S, K, D] fp32."""
+    N.require_cuda(protos, src, tgt)
+    protos = protos.contiguous()
+    S, K, D = protos.shape
+    src, tgt = src.to(torch.int32).contiguous(), tgt.to(torch.int32).contiguous()
+    B = int(src.numel())
+    out = torch.empty((B, K), dtype=torch.int32, device=protos.device)
+    N.check(N.load().wsi_remix_nearest(N.ptr(protos), S, K, D, N.ptr(src), N.ptr(tgt), B, N.ptr(out), N.stream()), "wsi_remix_nearest")
+    return out
+
+
+def remix_rows(protos: torch.Tensor, shifts: Optional[torch.Tensor], nearest: torch.Tensor, desc: torch.Tensor) -> torch.Tensor:
+    """[rows, D]: every output row of a step's mixed bags from the descriptor table desc [rows, 8] int32 (``wsi_remix_rows``; the table is
+    built by ``mil.remix.draw_mix``); protos [S, K, D], shifts [S, K, V, D] or None, nearest = ``remix_nearest``'s [B, K]."""
+    N.require_cuda(protos, shifts, nearest, desc)
+    protos = protos.contiguous()
+    S, K, D = protos.shape
+    V = 0
+    if shifts is not None:
+        shifts = shifts.contiguous()
+        if shifts.dim() != 4 or shifts.shape[:2] != (S, K) or shifts.shape[3] != D or shifts.dtype != torch.float32:
+            raise ValueError(f"remix_rows: shifts [{S}, {K}, V, {D}] fp32 expected, got {tuple(shifts.shape)}")
+        V = shifts.shape[2]
+    if desc.dim() != 2 or desc.shape[1] != 8 or desc.dtype != torch.int32:
+        raise ValueError("remix_rows: desc is an int32 [rows, 8] table")
+    desc, nearest = desc.contiguous(), nearest.contiguous()
+    rows = desc.shape[0]
+    out = torch.empty((rows, D), dtype=torch.float32, device=protos.device)
+    N.check(N.load().wsi_remix_rows(N.ptr(protos), N.ptr(shifts), S, K, V, D, N.ptr(nearest), int(nearest.numel()), N.ptr(desc), rows, N.ptr(out),
+                                    N.stream()), "wsi_remix_rows")
+    return out
+
+
+def gemm_tn_fp32(groups: Sequence[dict], device) -> None:
+    """C = A^T B for every group in exact fp32 whatever ``gemm_precision()`` says (the weight-gradient kernel of ``wsi_gemm_grouped``), at most
+    ``WSI_GEMM_MAX_GROUPS`` groups per call.  Group dicts as for ``_gemm``: A [K, M] / lda, B [K, N] / ldb, C [M, N] / ldc."""
+    lib = N.load()
+    groups = [g for g in groups if g["M"] > 0 and g["N"] > 0]
+    for i in range(0, len(groups), N.WSI_GEMM_MAX_GROUPS):
+        arr = _group_array(groups[i:i + N.WSI_GEMM_MAX_GROUPS])
+        ws_bytes = lib.wsi_gemm_workspace_bytes(N.WSI_GEMM_TN, N.WSI_GEMM_FP32, arr, len(arr))
+        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=device)
+        N.check(lib.wsi_gemm_grouped(N.WSI_GEMM_TN, 0, N.WSI_GEMM_FP32, arr, len(arr), N.ptr(ws), ws_bytes, N.stream()), "wsi_gemm_grouped")
+
+
+# ------------------------------------------------------------------------------------------------
 # segment dot (skip-gate gradient)
 # ------------------------------------------------------------------------------------------------
 def segment_dot_diff(g: torch.Tensor, a: torch.Tensor, b: torch.Tensor, rp: "ReducePlan") -> torch.Tensor:
@@ -2674,14 +2754,20 @@ def _segment_rows(counts: Sequence[int], extra) -> Tuple[List[int], int, List[in
 
 def _shuffle_perms(counts: Sequence[int], subs: Sequence[int], dev) -> List[torch.Tensor]:
     """NodeShuffle's permutation of every node type: the 32-bit hash keys of all types in one table ((type << 32) | key), ONE stable sort."""
+    idx, offs = segment_hash_order(counts, subs, dev)
+    return [idx[a:a + c] - a for a, c in zip(offs, counts)]
+
+
+def segment_hash_order(counts: Sequence[int], subs: Sequence[int], dev) -> Tuple[torch.Tensor, List[int]]:
+    """(order, offsets): the elements of consecutive segments (``counts`` each, segment j starting at offsets[j]) in the stable ascending order
+    of their draw ``augment_hash(i, subs[j])`` - order[offsets[j] + r] is the position in the whole table of segment j's r-th element."""
     total = sum(counts)
     words, tiles, offs = _segment_rows(counts, lambda j: (subs[j], 0, 0))
     keys = torch.empty(total, dtype=torch.int64, device=dev)
     if total:
         desc = host_to_device(words, torch.int64, dev)
         N.check(N.load().wsi_augment_keys(N.ptr(desc), len(counts), tiles, N.ptr(keys), N.stream()), "wsi_augment_keys")
-    idx = torch.sort(keys, stable=True).indices
-    return [idx[a:a + c] - a for a, c in zip(offs, counts)]
+    return torch.sort(keys, stable=True).indices, offs
 
 
 def augment_graph(g, stages, seed: int):
