@@ -959,6 +959,37 @@ int wsi_metrics_update(const float* logits, const int64_t* labels, int32_t B, in
 int wsi_metrics_finalize(const int32_t* state, const float* probs, const int64_t* row_labels, int32_t C, int32_t capacity,
                          int64_t* pair_partials, double* result, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GTNMIL (wsi_hgnn_amd/gtn, baselines/GTNMIL/models/GraphTransformer.py): the mincut assignment over a sparse adjacency and the attention of
+ * its 101-token transformer.  Entry points added to ABI 26.  No atomics, no allocation, no synchronisation: identical calls give identical bits.
+ *
+ * wsi_mincut_fwd: packed rows of all graphs, one plan segment per graph (chunk tables as for wsi_segment_reduce_fwd).  (ptr, idx, edge_w) = the
+ *   adjacency as a CSR by row: A[i, idx[e]] += edge_w[e] for e in [ptr[i], ptr[i + 1]) (edge_w NULL = 1; repeated entries add up; a row may be
+ *   empty; nothing is assumed symmetric).  z [n, K] logits with row stride ldz, 1 <= K <= 128 (more: WSI_ENOSYS).  Writes, all dense:
+ *     s [n, K] = softmax(z, -1)      t [n, K] = A s      deg [n]: d_i = sum_e edge_w[e]
+ *     num [num_segs] = sum_{i in g} <s_i, t_i> = trace(s^T A s)       den [num_segs] = sum_{i in g} d_i |s_i|^2 = trace(s^T D s)
+ *   partial: scratch of wsi_mincut_partials(num_chunks) floats.  A segment without rows gets num = den = 0.
+ * wsi_mincut_bwd: g_z [n, K] from g_s [n, K] (row stride ldgs), g_num, g_den [num_segs] (each may be NULL = 0) and the forward's s, t, deg:
+ *     u_i = g_s_i + g_num[g] (t_i + t'_i) + 2 g_den[g] d_i s_i        g_z_i = s_i * (u_i - <s_i, u_i>)
+ *   with t' = A^T s gathered along the CSC side of the same entries (colptr, csc_dst = the row of every entry grouped by its column,
+ *   edge_w_csc = the weights in that order).  K = 1 gives exact zeros. */
+int32_t wsi_mincut_partials(int32_t num_chunks);
+int wsi_mincut_fwd(const float* z, int64_t ldz, int32_t n, int32_t K, const int32_t* ptr, const int32_t* idx, const float* edge_w,
+                   const int32_t* chunk_row, int32_t num_chunks, const int32_t* seg_chunk, int32_t num_segs,
+                   float* s, float* t, float* deg, float* partial, float* num, float* den, void* stream);
+int wsi_mincut_bwd(const float* g_s, int64_t ldgs, const float* g_num, const float* g_den, const float* s, const float* t,
+                   const float* deg, int32_t n, int32_t K, const int32_t* colptr, const int32_t* csc_dst, const float* edge_w_csc,
+                   const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks, float* g_z, void* stream);
+
+/* wsi_seq_attn_fwd: multi-head attention over a short sequence (models/ViT.py:183-215).  qkv [B, n, 3 H d] dense, 16-byte aligned, columns in
+ *   the reference's (qkv h d) order; out [B, n, H d] in (h d) order; lse [B, H, n] = the log-sum-exp of every row of scale * q k^T over the
+ *   keys - all the forward keeps.  1 <= n <= 128 and d in {8, 16}; anything else: WSI_ENOSYS (B = 0 or n = 0: nothing to do).  No dropout.
+ * wsi_seq_attn_bwd: g_qkv [B, n, 3 H d] (same layout, every element written) from g_out [B, n, H d], qkv and lse; the probabilities are
+ *   recomputed.  One workgroup per (b, h) in both. */
+int wsi_seq_attn_fwd(const float* qkv, int32_t B, int32_t n, int32_t H, int32_t d, float scale, float* out, float* lse, void* stream);
+int wsi_seq_attn_bwd(const float* g_out, const float* qkv, const float* lse, int32_t B, int32_t n, int32_t H, int32_t d, float scale,
+                     float* g_qkv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,159 @@
+#!/usr/bin/env python
+"""GTNMIL timing on one GPU (``wsi_hgnn_amd.gtn``), ms per call, medians of interleaved repeats.
+
+Leg 1, one training step (zero_grad, forward, backward, Adam) at 8 slides x 2 000 nodes with 8 neighbours each, where the reference's dense
+form still fits: the native path (``gtn.Classifier``), the same model through tensor operations (``kernels=False``) and a plain-PyTorch
+restatement of the reference's padded forward - dense [B, N, N] adjacency, ``(A x + x) W``, ``s^T A s`` - on the same weights.
+Leg 2, the same step at 8 x 10 000 nodes, native paths only (the dense adjacency alone would be 3.2 GB).
+Leg 3, ``ops.seq_attention`` forward + backward against torch's own attention (the reference's einsum form and
+``F.scaled_dot_product_attention``) at B = 8, n = 101, 8 heads of 8.
+Prints one JSON line (and writes it to --out when given).
+
+    python tools/gtn_bench.py --repeats 7 --inner 5 [--out profiles/r17_gtn.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import torch
+import torch.nn.functional as F
+
+import __graft_entry__
+from mil_bench import _interleaved
+
+FEATS, CLASSES, SLIDES, NEIGHBOURS = 1024, 2, 8, 8
+
+
+def dense_step(model, vit, x, adj, labels):
+    """The reference's forward over padded tensors in plain PyTorch (all slides the same size here: the mask is all ones) with the weights of
+    ``model``; returns the loss."""
+    c = model.conv1
+    y = (adj @ x + x) @ c.weight + c.bias
+    y = F.normalize(y, p=2, dim=2)
+    y = c.bn_layer(y.reshape(-1, y.shape[2])).reshape(y.shape)
+    s = torch.softmax(F.linear(y, model.pool1.weight, model.pool1.bias), -1)
+    out = s.transpose(1, 2) @ y
+    out_adj = s.transpose(1, 2) @ adj @ s
+    num = torch.einsum("bii->b", out_adj)
+    den = torch.einsum("bii->b", s.transpose(1, 2) @ (adj.sum(-1).unsqueeze(-1) * s))
+    mc = torch.mean(-(num / den))
+    ss = s.transpose(1, 2) @ s
+    eye = torch.eye(s.shape[-1], device=s.device)
+    ortho = torch.mean(torch.norm(ss / torch.norm(ss, dim=(-1, -2), keepdim=True) - eye / torch.norm(eye), dim=(-1, -2)))
+    tokens = torch.cat([model.cls_token.repeat(out.shape[0], 1, 1), out], 1)
+    return F.cross_entropy(vit(tokens), labels) + mc + ortho
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--inner", type=int, default=5)
+    ap.add_argument("--small", type=int, default=2000)
+    ap.add_argument("--large", type=int, default=10000)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("gtn_bench.py measures on the GPU; none is visible")
+    __graft_entry__.build()
+    import wsi_hgnn_amd as W
+    from wsi_hgnn_amd import gtn, ops, optim, synthetic
+    from wsi_hgnn_amd.gtn.ViT import torch_attention
+
+    dev = torch.device("cuda:0")
+    torch.manual_seed(611)
+    res = {"workload": "GTNMIL training step and short-sequence attention", "feats": FEATS, "slides": SLIDES, "neighbours": NEIGHBOURS,
+           "repeats": args.repeats, "inner": args.inner, "steps": {}, "attention": {}}
+    labels = (torch.arange(SLIDES, device=dev) % CLASSES).to(torch.int64)
+
+    def models():
+        native = gtn.Classifier(CLASSES).to(dev)
+        tensors = gtn.Classifier(CLASSES, kernels=False).to(dev)
+        tensors.load_state_dict(native.state_dict())
+        return native, tensors
+
+    def stepper(model, batch):
+        opt = optim.Adam(model.parameters(), lr=1e-4)
+        return lambda: gtn.train_one_step(model, batch, labels, opt)
+
+    for name, nodes, with_dense in (("small", args.small, True), ("large", args.large, False)):
+        g = W.batch([synthetic.homogeneous_graph(nodes, FEATS, NEIGHBOURS, seed=611 + i) for i in range(SLIDES)]).to(dev)
+        batch = gtn.as_batch(g)
+        batch.ec, batch.rp                                          # (the plan is built once per batch, outside the timed step)
+        native, tensors = models()
+        legs = {"native_ms": stepper(native, batch), "tensor_ops_ms": stepper(tensors, batch)}
+        row = {"nodes_per_slide": nodes, "entries": int(batch.row.numel())}
+        if with_dense:
+            dense = gtn.Classifier(CLASSES, kernels=False).to(dev)
+            dense.load_state_dict(native.state_dict())
+            x = batch.x.view(SLIDES, nodes, FEATS)
+            adj = torch.zeros(SLIDES, nodes, nodes, device=dev)
+            local = batch.row % nodes, batch.col % nodes
+            adj.index_put_((batch.row // nodes, local[0], local[1]), torch.ones_like(batch.row, dtype=torch.float32), accumulate=True)
+            dopt = optim.Adam(dense.parameters(), lr=1e-4)
+
+            def dense_leg():
+                dense.train()
+                dopt.zero_grad()
+                loss = dense_step(dense, dense.transformer, x, adj, labels)
+                loss.backward()
+                dopt.step()
+                return loss.detach()
+
+            legs["torch_dense_ms"] = dense_leg
+            with torch.no_grad():                                   # the three forms compute one objective (same weights, before any step)
+                native.train(); dense.train()
+                a = float(native(batch, labels)[2]); b = float(tensors.train()(batch, labels)[2]); c = float(dense_step(dense, dense.transformer, x, adj, labels))
+            row["loss_native_tensor_dense"] = [a, b, c]
+            row["dense_adjacency_MB"] = round(adj.numel() * 4 / 1e6, 1)
+        med, spread = _interleaved(legs, args.repeats, args.inner)
+        row.update(med)
+        row["min_max"] = spread
+        row["tensor_ops_over_native"] = round(med["tensor_ops_ms"] / med["native_ms"], 3)
+        if with_dense:
+            row["torch_dense_over_native"] = round(med["torch_dense_ms"] / med["native_ms"], 3)
+        ops.enable_kernel_timing(True)
+        for _ in range(3):
+            legs["native_ms"]()
+        torch.cuda.synchronize()
+        row["native_kernel_ms_per_3_steps"] = ops.kernel_timing_summary()
+        ops.enable_kernel_timing(False)
+        res["steps"][name] = row
+        del g, batch, native, tensors, legs
+        torch.cuda.empty_cache()
+
+    # ---- attention alone, forward + backward
+    B, n, H, d = SLIDES, 101, 8, 8
+    qkv = torch.randn(B, n, 3 * H * d, device=dev, requires_grad=True)
+    g_out = torch.randn(B, n, H * d, device=dev)
+
+    def run(fn):
+        def leg():
+            qkv.grad = None
+            fn(qkv).backward(g_out)
+        return leg
+
+    def sdpa(t):
+        q, k, v = t.reshape(B, n, 3, H, d).permute(2, 0, 3, 1, 4)
+        return F.scaled_dot_product_attention(q, k, v).permute(0, 2, 1, 3).reshape(B, n, H * d)
+
+    legs = {"fused_ms": run(lambda t: ops.seq_attention(t, H)), "torch_einsum_ms": run(lambda t: torch_attention(t, H)), "torch_sdpa_ms": run(sdpa)}
+    med, spread = _interleaved(legs, args.repeats, max(args.inner, 50))
+    med["min_max"] = spread
+    med["shape"] = [B, n, H, d]
+    med["fused_faster_than_torch"] = bool(med["fused_ms"] < min(med["torch_einsum_ms"], med["torch_sdpa_ms"]))
+    with torch.no_grad():
+        med["max_abs_diff_from_einsum"] = float((ops.seq_attention(qkv, H) - torch_attention(qkv, H)).abs().max())
+    res["attention"] = med
+
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -8,6 +8,7 @@ Import as ``wsi_hgnn_amd`` (alias package at the repo root).  Layout:
   ops.py        torch.autograd.Function wrappers calling the C-ABI
   models/, pooling/   nn.Module mirror of the reference's models/* and pooling/* API
   mil/          the multiple-instance-learning baselines (ABMIL, DSMIL) over batches of bags: bag softmax pooling in HIP
+  gtn/          the graph-transformer baseline (GTNMIL) over a packed batch: mincut assignment over a sparse adjacency and short-sequence attention in HIP
   metrics.py    per-epoch classification metrics accumulated on the device (one recordable launch per step, one read-back per epoch)
   dist.py       WSI-sharded data parallelism (RCCL gradient all-reduce)
 """

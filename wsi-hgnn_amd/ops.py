@@ -2992,3 +2992,170 @@ def leave_one_out_batch(g, nids: Sequence[int], ntype: str, tables, check: bool 
                 out._eframes[r][key] = x[out_eid[roff[j]:roff[j] + etot[j]]]
     out._loo_desc = desc                # (the descriptor table must outlive the launches that read it: held by the graph)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# GTNMIL (wsi_hgnn_amd.gtn): the mincut assignment over a sparse adjacency (wsi_mincut_*), the pooled products s^T [x | s] on the grouped
+# GEMMs, and the attention of the short-sequence transformer (wsi_seq_attn_*)
+# ------------------------------------------------------------------------------------------------
+SEQ_ATTN_MAX_N = 128
+SEQ_ATTN_HEAD_DIMS = (8, 16)
+
+
+def _mincut_check(logits: torch.Tensor, ec: "EdgeCSR", rp: ReducePlan) -> None:
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[1] < 1:
+        raise ValueError(f"mincut_assign: logits are an fp32 [rows, K >= 1] table, got {tuple(logits.shape)} {logits.dtype}")
+    if rp.first_row != 0 or rp.num_rows != logits.shape[0] or ec.num_nodes != logits.shape[0]:
+        raise ValueError(f"mincut_assign: {logits.shape[0]} rows of logits, a plan over {rp.num_rows} rows, an adjacency over {ec.num_nodes}")
+
+
+class _MincutAssign(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, ec: "EdgeCSR", rp: ReducePlan):
+        N.require_cuda(logits)
+        _mincut_check(logits, ec, rp)
+        z = logits if (logits.shape[1] == 1 or logits.stride(1) == 1) and logits.stride(0) >= logits.shape[1] else logits.contiguous()
+        n, K = z.shape
+        dev = z.device
+        lib = N.load()
+        s = torch.empty((n, K), dtype=torch.float32, device=dev)
+        t = torch.empty((n, K), dtype=torch.float32, device=dev)
+        deg = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        num = torch.empty(rp.num_segs, dtype=torch.float32, device=dev)
+        den = torch.empty(rp.num_segs, dtype=torch.float32, device=dev)
+        partial = torch.empty(max(lib.wsi_mincut_partials(rp.num_chunks), 1), dtype=torch.float32, device=dev)
+        with _Timed("mincut_fwd"):
+            N.check(lib.wsi_mincut_fwd(N.ptr(z), z.stride(0) if n > 1 else K, n, K, N.ptr(ec.rowptr), N.ptr(ec.src), N.ptr(ec.edge_w),
+                                       N.ptr(rp.chunk_row), rp.num_chunks, N.ptr(rp.seg_chunk), rp.num_segs, N.ptr(s), N.ptr(t), N.ptr(deg),
+                                       N.ptr(partial), N.ptr(num), N.ptr(den), N.stream()), "wsi_mincut_fwd")
+        ctx.ec, ctx.rp, ctx.deg = ec, rp, deg
+        ctx.save_for_backward(s, t)
+        ctx.mark_non_differentiable(t)
+        return s, num, den, t
+
+    @staticmethod
+    def backward(ctx, g_s, g_num, g_den, _g_t):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        s, t = ctx.saved_tensors
+        ec, rp = ctx.ec, ctx.rp
+        n, K = s.shape
+        if g_s is not None and not ((K == 1 or g_s.stride(1) == 1) and g_s.stride(0) >= K):
+            g_s = g_s.contiguous()
+        g_num = g_num.contiguous() if g_num is not None else None
+        g_den = g_den.contiguous() if g_den is not None else None
+        g_z = torch.empty((n, K), dtype=torch.float32, device=s.device)
+        with _Timed("mincut_bwd"):
+            N.check(N.load().wsi_mincut_bwd(N.ptr(g_s), (g_s.stride(0) if n > 1 else K) if g_s is not None else 0, N.ptr(g_num), N.ptr(g_den),
+                                            N.ptr(s), N.ptr(t), N.ptr(ctx.deg), n, K, N.ptr(ec.colptr), N.ptr(ec.csc_dst), N.ptr(ec.edge_w_csc),
+                                            N.ptr(rp.chunk_row), N.ptr(rp.chunk_seg), rp.num_chunks, N.ptr(g_z), N.stream()), "wsi_mincut_bwd")
+        return g_z, None, None
+
+
+def mincut_assign_t(logits: torch.Tensor, ec: "EdgeCSR", rp: ReducePlan):
+    """``mincut_assign`` together with t = A s [rows, K] (not differentiable): what ``gtn.dense_mincut_pool`` forms s^T A s = s^T t from."""
+    return _MincutAssign.apply(logits, ec, rp)
+
+
+def mincut_assign(logits: torch.Tensor, ec: "EdgeCSR", rp: ReducePlan):
+    """(s, num, den) of torch_geometric's dense_mincut_pool over a SPARSE adjacency in the packed layout: ``logits`` [rows, K <= 128] fp32, the
+    rows of all graphs one after the other (``rp``: one segment per graph); ``ec`` = ``EdgeCSR(group=row, other=column, n=rows)``, optionally
+    ``with_weights`` (constants; repeated entries add up, rows may be empty, nothing is assumed symmetric).
+    s = softmax(logits, -1);  num[g] = trace(s^T A s) and den[g] = trace(s^T D s) over the rows of graph g, D = diag(A.sum(-1)).  All three are
+    differentiable in ``logits`` through one backward launch; identical calls give identical bits."""
+    return _MincutAssign.apply(logits, ec, rp)[:3]
+
+
+class _PoolTN(torch.autograd.Function):
+    """out[g] = s_g^T [x_g | s_g] ([K, D + K]) for every graph g of the plan: one grouped TN GEMM in exact fp32; the backward is one grouped NT
+    GEMM (the gradient through the left factor) and one grouped NN GEMM (through the right one)."""
+
+    @staticmethod
+    def forward(ctx, s, x, rp: ReducePlan):
+        N.require_cuda(s, x)
+        s = s.contiguous()
+        xs = torch.cat([x, s], 1)
+        K, W, dev = s.shape[1], xs.shape[1], s.device
+        out = torch.zeros((rp.num_segs, K, W), dtype=torch.float32, device=dev) if rp.has_empty() else \
+            torch.empty((rp.num_segs, K, W), dtype=torch.float32, device=dev)
+        gemm_tn_fp32([dict(A=N.ptr(s, a * K * 4), lda=K, B=N.ptr(xs, a * W * 4), ldb=W, C=N.ptr(out, g * K * W * 4), ldc=W, M=K, N=W, K=b - a)
+                      for g, (a, b) in enumerate(rp.ranges) if b > a], dev)
+        ctx.rp, ctx.D = rp, x.shape[1]
+        ctx.save_for_backward(s, xs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        s, xs = ctx.saved_tensors
+        rp, D = ctx.rp, ctx.D
+        g_out = g_out.contiguous()
+        K, W, dev = s.shape[1], xs.shape[1], s.device
+        live = [(g, a, b) for g, (a, b) in enumerate(rp.ranges) if b > a]
+        # through the right factor: g_xs_g = s_g g_out_g   ([n_g, K] x [K, W])
+        g_xs = torch.empty_like(xs)
+        _gemm(N.WSI_GEMM_NN, 0, [dict(A=N.ptr(s, a * K * 4), lda=K, B=N.ptr(g_out, g * K * W * 4), ldb=W, C=N.ptr(g_xs, a * W * 4), ldc=W,
+                                      M=b - a, N=W, K=K) for g, a, b in live], dev)
+        # through the left factor: g_s_g = xs_g g_out_g^T   ([n_g, W] x [K, W]^T)
+        g_s = torch.empty_like(s)
+        _gemm(N.WSI_GEMM_NT, 0, [dict(A=N.ptr(xs, a * W * 4), lda=W, B=N.ptr(g_out, g * K * W * 4), ldb=W, C=N.ptr(g_s, a * K * 4), ldc=K,
+                                      M=b - a, N=K, K=W) for g, a, b in live], dev)
+        g_s = g_s + g_xs[:, D:]
+        return g_s, (g_xs[:, :D] if ctx.needs_input_grad[1] else None), None
+
+
+def mincut_pool_products(s: torch.Tensor, x: torch.Tensor, rp: ReducePlan):
+    """(s^T x [G, K, D], s^T s [G, K, K]) per graph of the plan from ONE grouped TN GEMM over [x | s] in exact fp32 (``gemm_tn_fp32``)."""
+    if rp.first_row != 0 or rp.num_rows != s.shape[0] or x.shape[0] != s.shape[0]:
+        raise ValueError(f"mincut_pool_products: a plan over {rp.num_rows} rows, s has {s.shape[0]}, x has {x.shape[0]}")
+    out = _PoolTN.apply(s, x, rp)
+    return out[:, :, :x.shape[1]], out[:, :, x.shape[1]:]
+
+
+def seq_attention_supported(n: int, head_dim: int) -> bool:
+    """The range the compiled kernels cover (anything else: ``wsi_seq_attn_*`` answer WSI_ENOSYS and the caller uses tensor operations)."""
+    return 1 <= int(n) <= SEQ_ATTN_MAX_N and int(head_dim) in SEQ_ATTN_HEAD_DIMS
+
+
+class _SeqAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads: int):
+        N.require_cuda(qkv)
+        if qkv.dim() != 3 or qkv.dtype != torch.float32 or heads < 1 or qkv.shape[2] % (3 * heads):
+            raise ValueError(f"seq_attention: qkv is an fp32 [B, n, 3 * heads * d] tensor, got {tuple(qkv.shape)} {qkv.dtype} with {heads} heads")
+        qkv = qkv.contiguous()
+        B, n, W = qkv.shape
+        d = W // (3 * heads)
+        out = torch.empty((B, n, heads * d), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((B, heads, n), dtype=torch.float32, device=qkv.device)
+        with _Timed("seq_attn_fwd"):
+            N.check(N.load().wsi_seq_attn_fwd(N.ptr(qkv), B, n, heads, d, float(d) ** -0.5, N.ptr(out), N.ptr(lse), N.stream()), "wsi_seq_attn_fwd")
+        ctx.heads = heads
+        ctx.save_for_backward(qkv, lse)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, g_out, _g_lse):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        qkv, lse = ctx.saved_tensors
+        B, n, W = qkv.shape
+        d = W // (3 * ctx.heads)
+        g_out = g_out.contiguous()
+        g_qkv = torch.empty_like(qkv)
+        with _Timed("seq_attn_bwd"):
+            N.check(N.load().wsi_seq_attn_bwd(N.ptr(g_out), N.ptr(qkv), N.ptr(lse), B, n, ctx.heads, d, float(d) ** -0.5, N.ptr(g_qkv), N.stream()),
+                    "wsi_seq_attn_bwd")
+        return g_qkv, None
+
+
+def seq_attention_lse(qkv: torch.Tensor, heads: int):
+    """(out, lse): ``seq_attention`` with the saved row log-sum-exp [B, heads, n] (not differentiable)."""
+    return _SeqAttention.apply(qkv, int(heads))
+
+
+def seq_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """softmax(q k^T / sqrt(d)) v per head over a short sequence: ``qkv`` [B, n, 3 * heads * d] in the (qkv h d) column order of the
+    reference's ``rearrange`` (models/ViT.py:186) -> [B, n, heads * d] in (h d) order.  1 <= n <= 128, d in {8, 16}; anything else raises
+    (``seq_attention_supported`` tells beforehand).  No dropout: the reference runs attn_drop_rate = 0."""
+    return _SeqAttention.apply(qkv, int(heads))[0]
