@@ -990,6 +990,40 @@ int wsi_seq_attn_fwd(const float* qkv, int32_t B, int32_t n, int32_t H, int32_t 
 int wsi_seq_attn_bwd(const float* g_out, const float* qkv, const float* lse, int32_t B, int32_t n, int32_t H, int32_t d, float scale,
                      float* g_qkv, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GraphCAM of GTNMIL (wsi_hgnn_amd/gtn/graphcam.py): the relevance-propagation rules of baselines/GTNMIL/models/layers.py at alpha = 1, for G
+ * slides and C classes per launch.  Entry points added to ABI 26.  fp32; no atomics, no allocation, no synchronisation: identical calls give
+ * identical bits.  Every tensor is dense and 16-byte aligned (else WSI_EINVAL).  Forward tensors are [G, n, width], relevances [G, C, n, width].
+ *   sd(a, b) = layers.safe_divide: 0 where b == 0, else a / (b + 1e-9f), the denominator 1e-9f where that sum is exactly 0.
+ *   x+ = max(x, 0), x- = min(x, 0).
+ *
+ * wsi_lrp_linear: Linear.relprop.  X [G, n, in], W [out, in], R [G, C, n, out] -> out_rel [G, C, n, in]:
+ *     Z = X+ W+^T + X- W-^T  (once per token, shared by the classes; the bias plays no part)     S = sd(R, Z)
+ *     out_rel = X+ * (S W+) + X- * (S W-)
+ *   in a multiple of 4, 4 <= in <= 256, 1 <= out <= 256; anything else: WSI_ENOSYS.  W+ and W- are taken from one copy of W staged in LDS.
+ *
+ * wsi_lrp_residual: Clone.relprop of a tensor's two uses, then Add.relprop of the residual below it.  X, A, B [G, n, E]; r1, r2 [G, C, n, E].
+ *     R = X * (sd(r1, X) + sd(r2, X))            (r2 NULL: R = r1, X is not read and may be NULL)
+ *     S = sd(R, A + B);  a = A S;  b = B S;  a *= sd(sd(|Sa|, |Sa| + |Sb|) * SR, Sa);  b *= sd(sd(|Sb|, |Sa| + |Sb|) * SR, Sb)
+ *   with Sa, Sb, SR the sums of a, b, R over the [n, E] tensor of one (slide, class): one workgroup per (slide, class), a fixed order.
+ *   E a multiple of 4 (else WSI_ENOSYS), n * E < 2^31.
+ *
+ * wsi_lrp_attention: Attention.relprop between its two Linear rules, and the block's layer map.  qkv [G, n, 3 H d] and lse [G, H, n] as
+ *   wsi_seq_attn_fwd leaves them (the probabilities are recomputed as in wsi_seq_attn_bwd), R [G, C, n, H d] the relevance of the attention
+ *   output, g_out [G, C, n, H d] the gradient of the class score with respect to it, or NULL.  Per head, with P = the probabilities:
+ *     S2 = sd(R, P v);  cam_attn = P * (S2 v^T) / 2;  cam_v = v * (P^T S2) / 2
+ *     S1 = sd(cam_attn, q k^T)  (q k^T unscaled);  cam_q = q * (S1 k) / 2;  cam_k = k * (S1^T q) / 2
+ *     cam_qkv [G, C, n, 3 H d] in the (qkv h d) column order, every element written
+ *     M [G, C, n, n] = (1 / H) sum_h max(d attn * cam_attn, 0),  d attn = g_out v^T     (g_out NULL: max(cam_attn, 0), the rollout map)
+ *   One workgroup per (slide, class, head).  With H > 1 every head writes its term to partial [G * C * H * n * n] floats and a second launch
+ *   adds the heads in order; H = 1 writes M directly and partial may be NULL.  1 <= n <= 128 and d in {8, 16}; anything else: WSI_ENOSYS. */
+int wsi_lrp_linear(const float* X, const float* W, const float* R, int32_t G, int32_t C, int32_t n, int32_t fan_in, int32_t fan_out,
+                   float* out_rel, void* stream);
+int wsi_lrp_residual(const float* X, const float* r1, const float* r2, const float* A, const float* B, int32_t G, int32_t C, int32_t n,
+                     int32_t E, float* out_a, float* out_b, void* stream);
+int wsi_lrp_attention(const float* qkv, const float* lse, const float* R, const float* g_out, int32_t G, int32_t C, int32_t n, int32_t H,
+                      int32_t d, float scale, float* partial, float* cam_qkv, float* M, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """``Classifier`` of the GTNMIL baseline (``baselines/GTNMIL/models/GraphTransformer.py:18-103``) over the packed batch: one GCNBlock, a linear
 cluster assignment, mincut pooling to ``node_cluster_num`` tokens, a class token in front and the transformer; the objective is the cross
-entropy plus the two pooling regularisers.  ``graphcam_flag`` and ``is_print`` are not mirrored."""
+entropy plus the two pooling regularisers.  The reference's ``graphcam_flag`` branch is ``gtn.graphcam.class_maps`` (with
+``save_reference_files`` for the files it writes); ``is_print`` is not mirrored."""
 from __future__ import annotations
 
 import torch

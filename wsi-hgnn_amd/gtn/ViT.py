@@ -1,6 +1,7 @@
 """The transformer of the GTNMIL baseline (``baselines/GTNMIL/models/ViT.py``): pre-norm blocks over the class token and the pooled
 cluster tokens, the class token read at index 0.  Same constructor and ``state_dict`` keys as the reference, so its checkpoints load with
-``strict=True``.  ``relprop`` / GraphCAM and the attention hooks are not mirrored."""
+``strict=True``.  The reference's stateful ``relprop`` and its attention hooks are not mirrored: ``forward_saving`` returns what relevance
+propagation reads and ``gtn.graphcam`` applies the rules to it."""
 from __future__ import annotations
 
 import torch
@@ -18,6 +19,14 @@ def _linear(x, layer: nn.Linear, kernels: bool):
     if not kernels:
         return F.linear(x, layer.weight, layer.bias)
     return ops.linear(x.reshape(-1, x.shape[-1]), layer.weight, layer.bias).reshape(*x.shape[:-1], layer.weight.shape[0])
+
+
+def _linear_const(x, layer: nn.Linear, kernels: bool):
+    """``_linear`` with the layer's parameters as constants (``forward_saving``: a gradient taken through it forms no weight gradient)."""
+    w, b = layer.weight.detach(), None if layer.bias is None else layer.bias.detach()
+    if not kernels:
+        return F.linear(x, w, b)
+    return ops.linear(x.reshape(-1, x.shape[-1]), w, b).reshape(*x.shape[:-1], w.shape[0])
 
 
 def torch_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
@@ -69,6 +78,19 @@ class Attention(nn.Module):
             out = torch_attention(qkv, self.num_heads)
         return self.proj_drop(_linear(out, self.proj, self.kernels))
 
+    def forward_saving(self, x, kernels: bool):
+        """``forward`` in eval mode keeping (qkv, lse [B, h, n] - the row log-sum-exp of scale q k^T -, attn_concat, proj_out)."""
+        qkv = _linear_const(x, self.qkv, kernels)
+        B, n, W = qkv.shape
+        d = W // (3 * self.num_heads)
+        if kernels and ops.seq_attention_supported(n, d):
+            out, lse = ops.seq_attention_lse(qkv, self.num_heads)
+        else:
+            q, k, _ = qkv.detach().reshape(B, n, 3, self.num_heads, d).permute(2, 0, 3, 1, 4)
+            lse = torch.logsumexp(torch.einsum("bhid,bhjd->bhij", q, k) * d ** -0.5, -1)
+            out = torch_attention(qkv, self.num_heads)
+        return qkv, lse, out, _linear_const(out, self.proj, kernels)
+
 
 class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., kernels=True, fused_attention=None):
@@ -82,6 +104,17 @@ class Block(nn.Module):
     def forward(self, x):
         x = x + self.attn(self.norm1(x))
         return x + self.mlp(self.norm2(x))
+
+    def forward_saving(self, x, kernels: bool):
+        """(block output, what relevance propagation reads of this block)."""
+        s = {"x_in": x, "norm1_out": self.norm1(x)}
+        s["qkv"], s["lse"], s["attn_concat"], s["proj_out"] = self.attn.forward_saving(s["norm1_out"], kernels)
+        x = s["x_mid"] = x + s["proj_out"]
+        s["norm2_out"] = self.norm2(x)
+        h = _linear_const(s["norm2_out"], self.mlp.fc1, kernels)
+        s["gelu_out"] = ops.gelu(h) if kernels else F.gelu(h)
+        s["mlp_out"] = _linear_const(s["gelu_out"], self.mlp.fc2, kernels)
+        return x + s["mlp_out"], s
 
 
 class VisionTransformer(nn.Module):
@@ -107,3 +140,18 @@ class VisionTransformer(nn.Module):
             x = blk(x)
         x = self.norm(x)[:, 0]
         return self.head(x) if isinstance(self.head, Mlp) else _linear(x, self.head, self.kernels)
+
+    def forward_saving(self, x, kernels=None):
+        """``forward`` without dropout (eval mode) that also returns what relevance propagation reads: (logits, per block a dict of x_in,
+        norm1_out, qkv, lse, attn_concat, proj_out, x_mid, norm2_out, gelu_out, mlp_out, and the final normed token 0 [B, embed_dim]).
+        Nothing is kept on the module; ``kernels`` = None follows the model.  The Linear parameters enter as constants: a gradient with respect
+        to an activation is taken without forming weight gradients."""
+        if isinstance(self.head, Mlp):
+            raise NotImplementedError("gtn.VisionTransformer.forward_saving: mlp_head=True is not built (the reference's Classifier uses the single Linear head)")
+        kernels = self.kernels if kernels is None else bool(kernels)
+        saved = []
+        for blk in self.blocks:
+            x, s = blk.forward_saving(x, kernels)
+            saved.append(s)
+        x0 = self.norm(x)[:, 0]
+        return _linear_const(x0, self.head, kernels), saved, x0

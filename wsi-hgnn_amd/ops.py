@@ -3159,3 +3159,97 @@ def seq_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     reference's ``rearrange`` (models/ViT.py:186) -> [B, n, heads * d] in (h d) order.  1 <= n <= 128, d in {8, 16}; anything else raises
     (``seq_attention_supported`` tells beforehand).  No dropout: the reference runs attn_drop_rate = 0."""
     return _SeqAttention.apply(qkv, int(heads))[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# GraphCAM of GTNMIL (wsi_hgnn_amd.gtn.graphcam): the relevance-propagation rules of models/layers.py at alpha = 1 (wsi_lrp_*), batched over
+# slides and classes.  Not differentiable; every wrapper raises on a shape the kernels do not cover (the ``*_supported`` functions tell
+# beforehand and the caller then runs the tensor-operation form).
+# ------------------------------------------------------------------------------------------------
+LRP_MAX_WIDTH = 256
+
+
+def lrp_linear_supported(fan_in: int, fan_out: int) -> bool:
+    return 4 <= int(fan_in) <= LRP_MAX_WIDTH and int(fan_in) % 4 == 0 and 1 <= int(fan_out) <= LRP_MAX_WIDTH
+
+
+def lrp_residual_supported(width: int) -> bool:
+    return int(width) >= 4 and int(width) % 4 == 0
+
+
+def _lrp_rel(t: torch.Tensor, like: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dim() != 4 or t.dtype != torch.float32 or t.shape[0] != like.shape[0] or t.shape[2] != like.shape[1]:
+        raise ValueError(f"{what}: relevance is fp32 [G, C, n, width] over tensors [G, n, width], got {tuple(t.shape)} over {tuple(like.shape)}")
+    return t.contiguous()
+
+
+def lrp_linear(X: torch.Tensor, W: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
+    """The Linear rule at alpha = 1 for all classes: X [G, n, in], W [out, in], R [G, C, n, out] -> [G, C, n, in] =
+    X+ * (S W+) + X- * (S W-) with S = sd(R, X+ W+^T + X- W-^T); the bias plays no part.  in a multiple of 4, in and out <= 256."""
+    N.require_cuda(X, W, R)
+    if X.dim() != 3 or X.dtype != torch.float32 or W.dim() != 2 or W.dtype != torch.float32 or W.shape[1] != X.shape[2]:
+        raise ValueError(f"lrp_linear: X fp32 [G, n, in], W fp32 [out, in], got {tuple(X.shape)} and {tuple(W.shape)}")
+    R = _lrp_rel(R, X, "lrp_linear")
+    if R.shape[3] != W.shape[0]:
+        raise ValueError(f"lrp_linear: R has {R.shape[3]} columns, W {W.shape[0]} rows")
+    X, W = X.contiguous(), W.contiguous()
+    G, n, fin = X.shape
+    C = R.shape[1]
+    out = torch.empty((G, C, n, fin), dtype=torch.float32, device=X.device)
+    with _Timed("lrp_linear"):
+        N.check(N.load().wsi_lrp_linear(N.ptr(X), N.ptr(W), N.ptr(R), G, C, n, fin, W.shape[0], N.ptr(out), N.stream()), "wsi_lrp_linear")
+    return out
+
+
+def lrp_residual(X: Optional[torch.Tensor], r1: torch.Tensor, r2: Optional[torch.Tensor], A: torch.Tensor, B: torch.Tensor):
+    """(a, b) = add(A, B, R) with R = clone(X, r1, r2) = X * (sd(r1, X) + sd(r2, X)), or R = r1 when r2 is None (X is then not read): the Clone
+    rule of a tensor's two uses followed by the Add rule of the residual below it, in one launch.  X, A, B [G, n, E]; r1, r2 [G, C, n, E]; the
+    Add rule's three sums run over the [n, E] tensor of every (slide, class), in a fixed order.  E a multiple of 4."""
+    N.require_cuda(r1, r2, A, B)
+    if A.dim() != 3 or A.dtype != torch.float32 or B.shape != A.shape or B.dtype != torch.float32:
+        raise ValueError(f"lrp_residual: A and B fp32 [G, n, E], got {tuple(A.shape)} and {tuple(B.shape)}")
+    r1 = _lrp_rel(r1, A, "lrp_residual")
+    if r1.shape[3] != A.shape[2]:
+        raise ValueError(f"lrp_residual: relevance of width {r1.shape[3]} over tensors of width {A.shape[2]}")
+    if r2 is not None:
+        r2 = _lrp_rel(r2, A, "lrp_residual")
+        if r2.shape != r1.shape or X is None or X.shape != A.shape or X.dtype != torch.float32:
+            raise ValueError("lrp_residual: r2 has r1's shape, and X the shape of A")
+        N.require_cuda(X)
+        X = X.contiguous()
+    A, B = A.contiguous(), B.contiguous()
+    G, n, E = A.shape
+    a, b = torch.empty_like(r1), torch.empty_like(r1)
+    with _Timed("lrp_residual"):
+        N.check(N.load().wsi_lrp_residual(N.ptr(X) if r2 is not None else None, N.ptr(r1), N.ptr(r2), N.ptr(A), N.ptr(B), G, r1.shape[1], n, E,
+                                          N.ptr(a), N.ptr(b), N.stream()), "wsi_lrp_residual")
+    return a, b
+
+
+def lrp_attention(qkv: torch.Tensor, lse: torch.Tensor, R: torch.Tensor, g_out: Optional[torch.Tensor], heads: int):
+    """The attention rule of ViT.Attention.relprop and the block's layer map: qkv [G, n, 3 H d] and lse [G, H, n] as ``seq_attention_lse``
+    leaves them, R [G, C, n, H d] (the relevance of the attention output), g_out [G, C, n, H d] (d / d attention output of the class
+    score; None: the rollout map) -> (cam_qkv [G, C, n, 3 H d], M [G, C, n, n] = mean_h max(d attn * cam_attn, 0) with d attn = g_out v^T).
+    1 <= n <= 128, d in {8, 16}."""
+    N.require_cuda(qkv, lse, R, g_out)
+    heads = int(heads)
+    if qkv.dim() != 3 or qkv.dtype != torch.float32 or heads < 1 or qkv.shape[2] % (3 * heads):
+        raise ValueError(f"lrp_attention: qkv is an fp32 [G, n, 3 * heads * d] tensor, got {tuple(qkv.shape)} {qkv.dtype} with {heads} heads")
+    G, n, W = qkv.shape
+    d = W // (3 * heads)
+    R = _lrp_rel(R, qkv, "lrp_attention")
+    C = R.shape[1]
+    if R.shape[3] != heads * d or lse.shape != (G, heads, n) or lse.dtype != torch.float32:
+        raise ValueError(f"lrp_attention: R [G, C, n, {heads * d}] and lse fp32 [G, {heads}, n], got {tuple(R.shape)} and {tuple(lse.shape)}")
+    if g_out is not None:
+        g_out = _lrp_rel(g_out, qkv, "lrp_attention")
+        if g_out.shape != R.shape:
+            raise ValueError("lrp_attention: g_out has R's shape")
+    qkv, lse = qkv.contiguous(), lse.contiguous()
+    cam = torch.empty((G, C, n, W), dtype=torch.float32, device=qkv.device)
+    M = torch.empty((G, C, n, n), dtype=torch.float32, device=qkv.device)
+    partial = torch.empty(G * C * heads * n * n if heads > 1 else 1, dtype=torch.float32, device=qkv.device)
+    with _Timed("lrp_attention"):
+        N.check(N.load().wsi_lrp_attention(N.ptr(qkv), N.ptr(lse), N.ptr(R), N.ptr(g_out), G, C, n, heads, d, float(d) ** -0.5, N.ptr(partial),
+                                           N.ptr(cam), N.ptr(M), N.stream()), "wsi_lrp_attention")
+    return cam, M
