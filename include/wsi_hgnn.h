@@ -1024,6 +1024,42 @@ int wsi_lrp_residual(const float* X, const float* r1, const float* r2, const flo
 int wsi_lrp_attention(const float* qkv, const float* lse, const float* R, const float* g_out, int32_t G, int32_t C, int32_t n, int32_t H,
                       int32_t d, float scale, float* partial, float* cam_qkv, float* M, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * H2MIL (wsi_hgnn_amd/h2mil, baselines/H2MIL/code): RAConv's two-level attention and IHPool's cluster assignment.  Entry points added to
+ * ABI 26.  No atomics, no allocation, no synchronisation, every sum in one fixed order: identical calls give identical bits.
+ *
+ * Edge layout of both wsi_ra_attn_*: rowptr[n+1] / src[E] = CSR by destination with the SOURCE'S TYPE as the secondary key (a destination's
+ * groups (v, t) are contiguous runs; edge id = CSR position), colptr[n+1] / csc_eid[E] / csc_dst[E] = CSC by source over the same edge ids.
+ * node_type[n] int32 in {0, 1, 2} (anything else is clamped into that range).  ft [n, C] fp32, 1 <= C <= 4096;
+ * sc [n, 4] dense = el | er | pl | pr, the four per-node scalars of RAConv.py:96-97,121-122 (pl, pr through the folded t_lin_l).
+ *
+ * wsi_ra_attn_fwd: with t(e) = node_type[src[e]], s_e = leaky_relu(el[u_e] + er[v], negative_slope):
+ *     a_e = softmax of s over the edges of group (v, t);   q_vt = leaky_relu(mean_{e in (v,t)} pl[u_e] + pr[v], negative_slope);
+ *     beta_vt = softmax of q over the groups PRESENT at v;  out[v] = sum_e beta_{v,t(e)} a_e ft[u_e] + bias  (bias optional; a node without
+ *     in-edges: out = bias).  Both softmaxes subtract the maximum and add no epsilon.
+ *     stat [n, 3, 4] <- per (node, type): max_e s_e (+inf for an absent group) | log sum_e exp(s_e - max) | the group's edge count | beta.
+ * wsi_ra_attn_bwd: from g_out and the forward's sc / stat: g_ft [n, C] <- the AGGREGATION term only, sum_e beta a_e g_out[v_e]  (the terms
+ *     through sc are the caller's: sc is a projection of the same input);  g_sc [n, 4] <- the gradients of el | er | pl | pr;
+ *     g_bias [C] (optional) <- the column sums of g_out.  Scratch, all caller-owned: edge_ws [E] floats, group_ws [3 n] floats,
+ *     bias_ws [WSI_RA_BIAS_PARTS * C] floats (read only when g_bias is given).
+ *
+ * wsi_ihpool_assign (IHPool.py:138-142, 185-189 at dis = 'ou'): xyf [num_nodes, 3] dense = x | y | fitness.  The members of all segments,
+ *     grouped by segment: member_node[m] (row of xyf), member_seg[m] (non-decreasing, in [0, num_segs)); the seeds of segment s are
+ *     seed_node[seed_ptr[s] .. seed_ptr[s + 1]) (rows of xyf).  assign[i] <- the position within its segment's seed list of the seed nearest
+ *     to member i in |xy_s - xy_n|_2 + |f_s - f_n|; equal distances go to the lowest position; a member that is itself a seed gets its own
+ *     position; -1 for a member whose segment has no seed.  A segment may be empty.  Indices outside their tables are ignored, never followed. */
+#define WSI_RA_BIAS_PARTS 64
+int wsi_ra_attn_fwd(const float* ft, int64_t ldf, const float* sc, const int32_t* node_type, int32_t n, int32_t C,
+                    const int32_t* rowptr, const int32_t* src, float negative_slope, const float* bias,
+                    float* out, int64_t ldo, float* stat, void* stream);
+int wsi_ra_attn_bwd(const float* ft, int64_t ldf, const float* sc, const int32_t* node_type, const float* stat,
+                    const float* g_out, int64_t ldg, int32_t n, int32_t E, int32_t C,
+                    const int32_t* rowptr, const int32_t* src, const int32_t* colptr, const int32_t* csc_eid,
+                    const int32_t* csc_dst, float negative_slope, float* edge_ws, float* group_ws, float* bias_ws,
+                    float* g_ft, int64_t ldgf, float* g_sc, float* g_bias, void* stream);
+int wsi_ihpool_assign(const float* xyf, int32_t num_nodes, const int32_t* member_node, const int32_t* member_seg, int32_t num_members,
+                      const int32_t* seed_ptr, const int32_t* seed_node, int32_t num_segs, int32_t num_seeds, int32_t* assign, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ Import as ``wsi_hgnn_amd`` (alias package at the repo root).  Layout:
   models/, pooling/   nn.Module mirror of the reference's models/* and pooling/* API
   mil/          the multiple-instance-learning baselines (ABMIL, DSMIL) over batches of bags: bag softmax pooling in HIP
   gtn/          the graph-transformer baseline (GTNMIL) over a packed batch: mincut assignment over a sparse adjacency and short-sequence attention in HIP
+  h2mil/        the hierarchical baseline (H2MIL) over packed slide trees: RAConv's two-level attention and IHPool's cluster assignment in HIP
   metrics.py    per-epoch classification metrics accumulated on the device (one recordable launch per step, one read-back per epoch)
   dist.py       WSI-sharded data parallelism (RCCL gradient all-reduce)
 """

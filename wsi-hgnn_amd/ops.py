@@ -3253,3 +3253,117 @@ def lrp_attention(qkv: torch.Tensor, lse: torch.Tensor, R: torch.Tensor, g_out: 
         N.check(N.load().wsi_lrp_attention(N.ptr(qkv), N.ptr(lse), N.ptr(R), N.ptr(g_out), G, C, n, heads, d, float(d) ** -0.5, N.ptr(partial),
                                            N.ptr(cam), N.ptr(M), N.stream()), "wsi_lrp_attention")
     return cam, M
+
+
+# ------------------------------------------------------------------------------------------------
+# H2MIL (wsi_hgnn_amd/h2mil): RAConv's two-level attention (csrc/ra_attn.hip) and IHPool's cluster assignment (csrc/ihpool.hip)
+# ------------------------------------------------------------------------------------------------
+RA_NODE_TYPES = 3
+
+
+def edge_csr_by_source_type(src: torch.Tensor, dst: torch.Tensor, node_type: torch.Tensor, n: int) -> EdgeCSR:
+    """The edge layout of ``ra_attention``: an ``EdgeCSR`` grouped by destination whose rows are ordered by the SOURCE'S type (two stable
+    sorts, on the edges' own device), so that the groups (destination, source type) of a destination are contiguous runs.  ``perm`` maps a CSR
+    position to the original edge; ``node_type`` (int32) is kept on the plan."""
+    if src.dim() != 1 or src.shape != dst.shape or node_type.dim() != 1 or node_type.shape[0] != int(n):
+        raise ValueError(f"edge_csr_by_source_type: src and dst are 1-D tensors of one length and node_type is [{int(n)}], got "
+                         f"{tuple(src.shape)}, {tuple(dst.shape)}, {tuple(node_type.shape)}")
+    src, dst = src.to(torch.int64), dst.to(torch.int64)
+    first = torch.sort(node_type.to(torch.int64)[src], stable=True).indices if src.numel() else src
+    ec = EdgeCSR(dst[first], src[first], n)
+    ec.perm = first[ec.perm] if src.numel() else first
+    ec.node_type = node_type.to(torch.int32).contiguous()
+    ec.by_source_type = True
+    return ec
+
+
+def _ra_check(ft, sc, bias, ec, node_type) -> None:
+    if not getattr(ec, "by_source_type", False):
+        raise ValueError("ra_attention: the edge plan must come from ops.edge_csr_by_source_type (rows ordered by the source's type)")
+    n = ec.num_nodes
+    if ft.dim() != 2 or ft.shape[0] != n or not 1 <= ft.shape[1] <= 4096 or ft.dtype != torch.float32:
+        raise ValueError(f"ra_attention: ft is an fp32 [{n}, 1 <= C <= 4096] tensor, got {tuple(ft.shape)} {ft.dtype}")
+    if sc.shape != (n, 4) or sc.dtype != torch.float32:
+        raise ValueError(f"ra_attention: sc is an fp32 [{n}, 4] tensor (el | er | pl | pr), got {tuple(sc.shape)} {sc.dtype}")
+    if bias is not None and (bias.shape != (ft.shape[1],) or bias.dtype != torch.float32):
+        raise ValueError(f"ra_attention: bias is an fp32 [{ft.shape[1]}] tensor or None, got {tuple(bias.shape)} {bias.dtype}")
+    if node_type.shape != (n,) or node_type.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"ra_attention: node_type is an integer [{n}] tensor, got {tuple(node_type.shape)} {node_type.dtype}")
+
+
+class _RaAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ft, sc, bias, ec, node_type, slope: float):
+        N.require_cuda(ft, sc, bias, node_type, ec.rowptr)
+        n, C = ft.shape
+        if not (ft.stride(1) == 1 and ft.stride(0) >= C) and n > 1:
+            ft = ft.contiguous()
+        ldf = ft.stride(0) if n > 1 else C
+        sc = sc.detach().contiguous()
+        b = bias.detach().contiguous() if bias is not None else None
+        out = torch.empty((n, C), dtype=torch.float32, device=ft.device)
+        stat = torch.empty((n, RA_NODE_TYPES, 4), dtype=torch.float32, device=ft.device)
+        with _Timed("ra_attn_fwd"):
+            N.check(N.load().wsi_ra_attn_fwd(N.ptr(ft), ldf, N.ptr(sc), N.ptr(node_type), n, C, N.ptr(ec.rowptr), N.ptr(ec.src), float(slope),
+                                             N.ptr(b), N.ptr(out), C, N.ptr(stat), N.stream()), "wsi_ra_attn_fwd")
+        ctx.ec, ctx.slope, ctx.has_bias, ctx.ldf = ec, float(slope), bias is not None, ldf
+        ctx.save_for_backward(ft, sc, stat, node_type)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        ft, sc, stat, node_type = ctx.saved_tensors
+        ec = ctx.ec
+        n, C = ft.shape
+        E = ec.num_edges
+        g_out = g_out.contiguous()
+        dev = ft.device
+        edge_ws = torch.empty(max(E, 1), dtype=torch.float32, device=dev)
+        group_ws = torch.empty(max(RA_NODE_TYPES * n, 1), dtype=torch.float32, device=dev)
+        bias_ws = torch.empty(N.WSI_RA_BIAS_PARTS * C, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        g_ft = torch.empty((n, C), dtype=torch.float32, device=dev)
+        g_sc = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        g_b = torch.empty(C, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        with _Timed("ra_attn_bwd"):
+            N.check(N.load().wsi_ra_attn_bwd(N.ptr(ft), ctx.ldf, N.ptr(sc), N.ptr(node_type), N.ptr(stat), N.ptr(g_out), C, n, E, C,
+                                             N.ptr(ec.rowptr), N.ptr(ec.src), N.ptr(ec.colptr), N.ptr(ec.csc_eid), N.ptr(ec.csc_dst), ctx.slope,
+                                             N.ptr(edge_ws), N.ptr(group_ws), N.ptr(bias_ws), N.ptr(g_ft), C, N.ptr(g_sc), N.ptr(g_b), N.stream()),
+                    "wsi_ra_attn_bwd")
+        return g_ft, g_sc, g_b, None, None, None
+
+
+def ra_attention(ft: torch.Tensor, sc: torch.Tensor, bias: Optional[torch.Tensor], ec: EdgeCSR, node_type: torch.Tensor,
+                 negative_slope: float = 0.2) -> torch.Tensor:
+    """RAConv after its projection (``baselines/H2MIL/code/RAConv.py`` at heads = 1): ``ft`` [n, C] fp32 (unit column stride; a row stride
+    is taken as it is), ``sc`` [n, 4] = el | er | pl | pr, ``bias`` [C] or None, ``ec`` from ``edge_csr_by_source_type``, ``node_type`` [n]
+    in {0, 1, 2}.  With the group of an edge u -> v being (v, node_type[u]):
+
+        a_e = softmax over the group of leaky_relu(el[u] + er[v]);   q_vt = leaky_relu(mean over the group of pl[u] + pr[v])
+        beta_vt = softmax of q over the groups present at v;           out[v] = sum_e beta a_e ft[u] + bias
+
+    One autograd function: the gradient of ``ft`` is the aggregation term alone (``sc`` carries the rest), and ``sc`` and ``bias`` receive
+    theirs.  Identical calls give identical bits."""
+    _ra_check(ft, sc, bias, ec, node_type)
+    nt = node_type if node_type.dtype == torch.int32 and node_type.is_contiguous() else node_type.to(torch.int32).contiguous()
+    return _RaAttention.apply(ft, sc, bias, ec, nt, float(negative_slope))
+
+
+def ihpool_assign(xyf: torch.Tensor, member_node: torch.Tensor, member_seg: torch.Tensor, seed_ptr: torch.Tensor, seed_node: torch.Tensor) -> torch.Tensor:
+    """``wsi_ihpool_assign``: ``xyf`` [nodes, 3] fp32 = x | y | fitness; the members of all segments grouped by segment (``member_node`` rows of
+    xyf, ``member_seg`` non-decreasing), the seeds of segment s = ``seed_node[seed_ptr[s]:seed_ptr[s + 1]]`` (all int32).  Returns for every
+    member the position, within its segment's seeds, of the nearest one in |xy_s - xy_n|_2 + |f_s - f_n| (int32; ties to the lowest
+    position, a seed to itself, -1 without seeds).  One launch, no read-back."""
+    if xyf.dim() != 2 or xyf.shape[1] != 3 or xyf.dtype != torch.float32:
+        raise ValueError(f"ihpool_assign: xyf is an fp32 [nodes, 3] tensor, got {tuple(xyf.shape)} {xyf.dtype}")
+    if member_node.dim() != 1 or member_node.shape != member_seg.shape or seed_ptr.dim() != 1 or seed_ptr.numel() < 1 or seed_node.dim() != 1:
+        raise ValueError("ihpool_assign: member_node and member_seg are 1-D tensors of one length, seed_ptr is [segments + 1], seed_node 1-D")
+    if any(t.dtype != torch.int32 for t in (member_node, member_seg, seed_ptr, seed_node)):
+        raise ValueError("ihpool_assign: member_node, member_seg, seed_ptr and seed_node are int32")
+    N.require_cuda(xyf, member_node, member_seg, seed_ptr, seed_node)
+    xyf, member_node, member_seg, seed_ptr, seed_node = (t.contiguous() for t in (xyf, member_node, member_seg, seed_ptr, seed_node))
+    m = member_node.shape[0]
+    out = torch.empty(max(m, 1), dtype=torch.int32, device=xyf.device)[:m]
+    with _Timed("ihpool_assign"):
+        N.check(N.load().wsi_ihpool_assign(N.ptr(xyf), xyf.shape[0], N.ptr(member_node), N.ptr(member_seg), m, N.ptr(seed_ptr), N.ptr(seed_node),
+                                           seed_ptr.numel() - 1, seed_node.numel(), N.ptr(out), N.stream()), "wsi_ihpool_assign")
+    return out
