@@ -1060,6 +1060,58 @@ int wsi_ra_attn_bwd(const float* ft, int64_t ldf, const float* sc, const int32_t
 int wsi_ihpool_assign(const float* xyf, int32_t num_nodes, const int32_t* member_node, const int32_t* member_seg, int32_t num_members,
                       const int32_t* seed_ptr, const int32_t* seed_node, int32_t num_segs, int32_t num_seeds, int32_t* assign, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Slide graphs from patch grids (wsi_hgnn_amd/construct.py: grid_adjacency, slide_trees).  Entry points added to ABI 26.  Exact look-ups in many
+ * small integer point sets: coords [P, 2] int32, all sets of a call packed, set s = the points [set_ptr[s], set_ptr[s + 1]), 1 <= S <= 8192.
+ * A valid coordinate is 0 <= c < 2^24; the key of a point is (set << 50) | ((x + 1) << 25) | (y + 1), so the probes at -1 and 2^24 are
+ * representable and match nothing.  capacity: a power of two >= 2 P (else WSI_EINVAL).  Every probe loop runs at most `capacity` steps.
+ * Look-ups that miss and indices outside their tables are ignored, never followed.  Identical calls give identical outputs, whatever slot a
+ * key happened to land in.
+ *
+ * wsi_grid_index: one open-addressing table (keys int64 [capacity], rows int32 [capacity]) over (set, x, y) -> point, by a 64-bit
+ *   compare-and-swap on the key; the winner writes the row.  set_max int32 [S, 2] <- the per-set maxima of x and y (integer atomic max; -1 for
+ *   an empty set).  flags int32 [2] <- 0, then flags[0] |= WSI_GRID_BAD_COORD (a coordinate outside [0, 2^24); the point is not stored) |
+ *   WSI_GRID_REPEATED (a (set, x, y) given twice) | WSI_GRID_TABLE_FULL (no free slot within `capacity` steps).  It resets all three tables.
+ * wsi_grid_count: counts int32 <- the items every node will emit, laid out so that ONE prefix sum over it gives the write offsets.
+ * wsi_grid_write: probes again and writes at offsets_incl[i] - counts[i], offsets_incl int64 = the INCLUSIVE prefix sum of counts.  No atomics.
+ *
+ * mode WSI_GRID_ADJACENCY (GTNMIL, baselines/GTNMIL/feature_extractor/build_graphs.py:78-96): one set per slide, nodes in the caller's order
+ *   (the reference: file order).  counts [P].  The entries of node i are (out_a = i, out_b = j) for every j != i of the same set with
+ *   |x_i - x_j| <= 1 and |y_i - y_j| <= 1; rows ascend and the columns of a row ascend (the order of adj.nonzero()).  i and j are point
+ *   numbers, i.e. global rows of the packed batch.  n1, cover, parent, set_max, node_type, node_tree, x_y_index are not read (NULL).
+ *
+ * mode WSI_GRID_TREE (H2MIL, baselines/H2MIL/code/github_pretreat.py:94-329): B slides, S = 2 B; the points are the level-1 nodes of all
+ *   slides (n1 of them; set b = slide b; (i, j) of a 5x patch name a-b-c-d-i-j) and then the level-2 nodes of all slides (set B + b; a 10x
+ *   patch name x-y); cover [n1, 4] = (a, b, c, d) of every level-1 node.  Node rows per slide: the root, its level-1 nodes, its level-2 nodes,
+ *   each in the given order; every row below is global.  counts [2 n1 + n2] in [slide][section][node] order, the slide's edges being
+ *     section A (:106-133), per level-1 node r: r -> root, root -> r, then for the children (a,c), (b,c), (a,d), (b,d) - each one that exists
+ *       among the slide's level-2 coordinates - r -> child, child -> r.  The four slots are independent: a == b or c == d emits a child twice.
+ *     section B (:142-170), per level-1 node, for the offsets (0,+1), (0,-1), (+1,0), (-1,0), (+1,+1), (-1,+1), (+1,-1), (-1,-1) in this
+ *       order: self -> neighbour where the neighbour exists.       section C (:173-202): the same over the level-2 nodes.
+ *   out_a / out_b = source / destination row.  wsi_grid_count also leaves parent int32 [n2]: for every level-2 node the row of the LAST level-1
+ *   node in order that covers it (:228-254; an integer atomic max), -1 if none.  wsi_grid_write also writes, for all N = B + P rows,
+ *     node_type int64 [N]: 0 / 1 / 2      node_tree int64 [N]: -1 for a root, the root's row for a level-1 node, parent for a level-2 node
+ *       (an uncovered one: -2, and flags[1] <- WSI_GRID_UNCOVERED by a plain store)
+ *     x_y_index fp64 [N, 2] (:257-315): (0, 0) for a root, else (x / max_x, y / max_y) with the maxima over the node's slide and level: one
+ *       IEEE double division per value (a maximum of 0 gives inf / nan).
+ *   A slide without level-1 nodes gets no root row written: the caller refuses empty levels.
+ * The output buffers hold the largest possible count: 8 P entries (adjacency), 18 n1 + 8 n2 edges (tree). */
+#define WSI_GRID_ADJACENCY   0
+#define WSI_GRID_TREE        1
+#define WSI_GRID_BAD_COORD   1
+#define WSI_GRID_REPEATED    2
+#define WSI_GRID_TABLE_FULL  4
+#define WSI_GRID_UNCOVERED   8
+int wsi_grid_index(const int32_t* coords, int32_t num_points, const int32_t* set_ptr, int32_t num_sets, int64_t* keys, int32_t* rows,
+                   int32_t capacity, int32_t* set_max, int32_t* flags, void* stream);
+int wsi_grid_count(int32_t mode, const int32_t* coords, int32_t num_points, const int32_t* set_ptr, int32_t num_sets, int32_t n1,
+                   const int32_t* cover, const int64_t* keys, const int32_t* rows, int32_t capacity, int32_t* counts, int32_t* parent,
+                   void* stream);
+int wsi_grid_write(int32_t mode, const int32_t* coords, int32_t num_points, const int32_t* set_ptr, int32_t num_sets, int32_t n1,
+                   const int32_t* cover, const int64_t* keys, const int32_t* rows, int32_t capacity, const int32_t* counts,
+                   const int64_t* offsets_incl, const int32_t* parent, const int32_t* set_max, int64_t* out_a, int64_t* out_b,
+                   int64_t* node_type, int64_t* node_tree, double* x_y_index, int32_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ restatement of the reference's padded forward - dense [B, N, N] adjacency, ``(A 
 Leg 2, the same step at 8 x 10 000 nodes, native paths only (the dense adjacency alone would be 3.2 GB).
 Leg 3, ``ops.seq_attention`` forward + backward against torch's own attention (the reference's einsum form and
 ``F.scaled_dot_product_attention``) at B = 8, n = 101, 8 heads of 8.
-Prints one JSON line (and writes it to --out when given).
+``--from-grid`` draws the slides as filled discs on a patch grid and builds the batch with ``gtn.from_grid`` instead (the committed profile
+used the default).  Prints one JSON line (and writes it to --out when given).
 
     python tools/gtn_bench.py --repeats 7 --inner 5 [--out profiles/r17_gtn.json]
 """
@@ -53,6 +54,8 @@ def main():
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--small", type=int, default=2000)
     ap.add_argument("--large", type=int, default=10000)
+    ap.add_argument("--from-grid", action="store_true", help="draw the slides as filled discs on a patch grid and build the batch with "
+                    "gtn.from_grid (the reference's 8-neighbour adjacency, made on the device) instead of random graphs")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -65,7 +68,8 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(611)
     res = {"workload": "GTNMIL training step and short-sequence attention", "feats": FEATS, "slides": SLIDES, "neighbours": NEIGHBOURS,
-           "repeats": args.repeats, "inner": args.inner, "steps": {}, "attention": {}}
+           "repeats": args.repeats, "inner": args.inner, "inputs": "gtn.from_grid over filled discs" if args.from_grid else "synthetic.homogeneous_graph",
+           "steps": {}, "attention": {}}
     labels = (torch.arange(SLIDES, device=dev) % CLASSES).to(torch.int64)
 
     def models():
@@ -79,8 +83,13 @@ def main():
         return lambda: gtn.train_one_step(model, batch, labels, opt)
 
     for name, nodes, with_dense in (("small", args.small, True), ("large", args.large, False)):
-        g = W.batch([synthetic.homogeneous_graph(nodes, FEATS, NEIGHBOURS, seed=611 + i) for i in range(SLIDES)]).to(dev)
-        batch = gtn.as_batch(g)
+        if args.from_grid:
+            from grid_graph_bench import disc
+            coords = torch.cat([disc(nodes, 611 + i) for i in range(SLIDES)]).to(dev)
+            g = batch = gtn.from_grid(torch.randn(SLIDES * nodes, FEATS, device=dev), coords, sizes=[nodes] * SLIDES)
+        else:
+            g = W.batch([synthetic.homogeneous_graph(nodes, FEATS, NEIGHBOURS, seed=611 + i) for i in range(SLIDES)]).to(dev)
+            batch = gtn.as_batch(g)
         batch.ec, batch.rp                                          # (the plan is built once per batch, outside the timed step)
         native, tensors = models()
         legs = {"native_ms": stepper(native, batch), "tensor_ops_ms": stepper(tensors, batch)}

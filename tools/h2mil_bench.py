@@ -7,7 +7,8 @@ slides at two sizes: three levels, 8 same-level neighbours plus parent / child e
 Leg 2, ``ops.ra_attention`` forward + backward alone against its tensor-operation form (``h2mil.ra_attention_tensor``) on the larger batch's
 graph at the model's width.
 The reference itself cannot be timed: it needs torch_geometric, torch_scatter and torch_sparse, which are not installed; nothing is estimated.
-Prints one JSON line (and writes it to --out when given).
+``--from-grid`` draws the slides as patch grids and builds the batch with ``h2mil.from_grid`` instead (1 + 5 n1 nodes per slide; the committed
+profile used the default).  Prints one JSON line (and writes it to --out when given).
 
     python tools/h2mil_bench.py --repeats 7 --inner 3 [--out profiles/r19_h2mil.json]
 """
@@ -53,6 +54,8 @@ def main():
     ap.add_argument("--inner", type=int, default=3)
     ap.add_argument("--small", type=int, default=100, help="level-1 nodes per slide of the smaller batch")
     ap.add_argument("--large", type=int, default=500, help="level-1 nodes per slide of the larger batch")
+    ap.add_argument("--from-grid", action="store_true", help="draw the slides as patch grids (a disc of level-1 cells, four level-2 cells under each: "
+                    "1 + 5 n1 nodes per slide) and build the batch with h2mil.from_grid (the reference's tree, made on the device)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -64,7 +67,7 @@ def main():
     torch.manual_seed(611)
     res = {"workload": "H2MIL training step and RAConv attention", "feats": FEATS, "out_classes": HIDDEN, "slides": SLIDES, "neighbours": NEIGHBOURS,
            "children": CHILDREN, "pool_ratios": list(RATIOS), "optimizer": "Adam(lr=5e-5, weight_decay=5e-4)", "repeats": args.repeats,
-           "inner": args.inner, "reference": "not measured: torch_geometric, torch_scatter and torch_sparse are not installed", "steps": {}}
+           "inner": args.inner, "inputs": "h2mil.from_grid over patch grids" if args.from_grid else "synthetic_slide", "reference": "not measured: torch_geometric, torch_scatter and torch_sparse are not installed", "steps": {}}
     labels = (torch.arange(SLIDES, device=dev) % CLASSES).to(torch.int64)
 
     def stepper(model, batch):
@@ -73,7 +76,13 @@ def main():
 
     batch = None
     for name, n1 in (("small", args.small), ("large", args.large)):
-        batch = h2mil.from_slides([synthetic_slide(n1, 611 + i) for i in range(SLIDES)]).to(dev)
+        if args.from_grid:
+            from grid_graph_bench import tree_tables
+            tables = [tree_tables(n1, 611 + i) for i in range(SLIDES)]
+            batch = h2mil.from_grid([{"x": torch.randn(1 + 5 * n1, FEATS, device=dev), "coords1": t[0].to(dev), "cover": t[1].to(dev), "coords2": t[2].to(dev)}
+                                     for t in tables], dtype=torch.float32)
+        else:
+            batch = h2mil.from_slides([synthetic_slide(n1, 611 + i) for i in range(SLIDES)]).to(dev)
         batch.ec, batch.rp                                          # (the plans are built once per batch, outside the timed step)
         native = h2mil.H2MIL(FEATS, 0, HIDDEN, CLASSES, pool1_ratio=RATIOS[0], pool2_ratio=RATIOS[1], kernels=True).to(dev)
         tensors = h2mil.H2MIL(FEATS, 0, HIDDEN, CLASSES, pool1_ratio=RATIOS[0], pool2_ratio=RATIOS[1], kernels=False).to(dev)

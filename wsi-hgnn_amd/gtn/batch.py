@@ -114,3 +114,45 @@ def as_batch(batch) -> GraphBatch:
                                                        [int(c) for c in batch.batch_num_nodes().tolist()])
         return hit
     raise TypeError(f"gtn: expected a HeteroGraph batch or a gtn.GraphBatch, got {type(batch).__name__}")
+
+
+def read_coords(path: str) -> torch.Tensor:
+    """The reference's ``c_idx.txt`` (build_graphs.py:72-76: one ``x<TAB>y`` line per patch, in file order) as an int64 [n, 2] tensor."""
+    rows = []
+    with open(path, "r") as f:
+        for number, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            fields = line.rstrip("\n").split("\t")
+            try:
+                if len(fields) != 2:
+                    raise ValueError
+                rows.append((int(fields[0]), int(fields[1])))
+            except ValueError:
+                raise ValueError(f"read_coords: {path}:{number}: expected two integers separated by a tab, got {line.rstrip()!r}") from None
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 2)
+
+
+def from_grid(feats, coords, sizes: Optional[Sequence[int]] = None, kernels: Optional[bool] = None) -> GraphBatch:
+    """A packed batch from patch features and grid coordinates, with the reference's adjacency (build_graphs.py:78-96: 1 where two patches of a
+    slide are at most one grid step apart in x and in y) built on the device by ``construct.grid_adjacency`` - no dense matrix, no host loop.
+    ``feats`` / ``coords``: lists of per-slide [n, F] / [n, 2] tensors, or packed tensors [N, F] / [N, 2] with ``sizes``.  The entries come in the
+    order ``from_dense`` gives for the reference's dense matrix; ``weight`` is None (every entry is 1)."""
+    from ..construct import grid_adjacency
+    if isinstance(feats, torch.Tensor) != isinstance(coords, torch.Tensor):
+        raise ValueError("from_grid: feats and coords are both lists of per-slide tensors or both packed tensors")
+    if isinstance(feats, torch.Tensor):
+        if sizes is None:
+            raise ValueError("from_grid: packed tensors need the slides' sizes")
+    else:
+        if sizes is not None or len(feats) != len(coords) or not len(feats):
+            raise ValueError("from_grid: one coordinate tensor per feature tensor, at least one slide, and no sizes with lists")
+        if any(f.dim() != 2 or c.dim() != 2 or f.shape[0] != c.shape[0] for f, c in zip(feats, coords)):
+            raise ValueError("from_grid: every slide gives feats [n, F] and coords [n, 2] with one n")
+        sizes = [f.shape[0] for f in feats]
+        feats, coords = torch.cat(list(feats), 0), torch.cat(list(coords), 0)
+    if feats.dim() != 2 or feats.shape[0] != coords.shape[0]:
+        raise ValueError("from_grid: one coordinate pair per feature row")
+    coords = coords.to(feats.device)
+    row, col = grid_adjacency(coords, sizes, kernels=kernels)
+    return GraphBatch(feats, row, col, None, sizes)

@@ -133,3 +133,52 @@ def from_slides(slides: Sequence, dtype: Optional[torch.dtype] = None) -> TreeBa
     if dtype is not None:
         x, xy = x.to(dtype), xy.to(dtype)
     return TreeBatch(x, torch.cat(types), torch.cat(trees), xy, torch.cat(edges, 1), sizes, n1s, n2s)
+
+
+def tables_from_names(names: Sequence[str]):
+    """The host-side name parser of one slide (github_pretreat.py:64-76).  ``names``: the patch names of the slide in file order, with or without
+    an extension - ``-1`` the thumbnail (the root), ``a-b-c-d-i-j`` a 5x patch, ``x-y`` a 10x patch.  Returns ``(coords1 [n1, 2], cover [n1, 4],
+    coords2 [n2, 2], perm [1 + n1 + n2])``, int64: the integer tables ``from_grid`` takes, in the reference's order (the root, the 6-field names
+    in file order, the 2-field names in file order), and the permutation to apply to the feature rows (``x[perm]``).  ``ValueError``: no root or
+    more than one, a name of any other shape."""
+    root, l1, l2 = [], [], []
+    for pos, name in enumerate(names):
+        stem = str(name).split(".")[0]
+        if stem == "-1":
+            root.append(pos)
+            continue
+        fields = stem.split("-")
+        try:
+            values = [int(v) for v in fields]
+            if len(values) not in (2, 6) or any(v < 0 for v in values) or any(not v.isdigit() for v in fields):
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"tables_from_names: {name!r} is neither '-1', a 5x name a-b-c-d-i-j nor a 10x name x-y") from None
+        (l1 if len(values) == 6 else l2).append((pos, values))
+    if len(root) != 1:
+        raise ValueError(f"tables_from_names: a slide has exactly one root '-1', got {len(root)}")
+    t = lambda rows, width: torch.tensor(rows, dtype=torch.int64).reshape(-1, width)
+    return (t([v[4:] for _, v in l1], 2), t([v[:4] for _, v in l1], 4), t([v for _, v in l2], 2),
+            torch.tensor(root + [p for p, _ in l1] + [p for p, _ in l2], dtype=torch.int64))
+
+
+def from_grid(slides: Sequence, dtype: Optional[torch.dtype] = None, kernels: Optional[bool] = None) -> TreeBatch:
+    """A packed batch from patch features and grid tables, the trees built on the device by ``construct.slide_trees`` in one pass for all
+    slides.  Every slide (a dict or an object) gives ``x`` [1 + n1 + n2, F] (the root's row, the level-1 rows, the level-2 rows), ``coords1``
+    [n1, 2], ``cover`` [n1, 4] and ``coords2`` [n2, 2] as ``tables_from_names`` returns them.  Equal, field by field, to ``from_slides`` of the
+    tensors the reference's github_pretreat.py makes for the same slides.  ``x_y_index`` is float64 unless ``dtype`` is given (which also
+    converts ``x``)."""
+    from ..construct import slide_trees
+    if not slides:
+        raise ValueError("from_grid: no slide")
+    xs, c1, cv, c2 = ([_get(s, k) for s in slides] for k in ("x", "coords1", "cover", "coords2"))
+    for i, (x, a, c, b) in enumerate(zip(xs, c1, cv, c2)):
+        if x.dim() != 2 or a.dim() != 2 or b.dim() != 2 or c.dim() != 2 or c.shape[0] != a.shape[0] or x.shape[0] != 1 + a.shape[0] + b.shape[0]:
+            raise ValueError(f"from_grid: slide {i}: x [1 + n1 + n2, F], coords1 [n1, 2], cover [n1, 4], coords2 [n2, 2]")
+    n1, n2 = [a.shape[0] for a in c1], [b.shape[0] for b in c2]
+    x = torch.cat(xs, 0)
+    dev = x.device
+    edge_index, node_type, node_tree, xy = slide_trees(torch.cat(c1, 0).to(dev), torch.cat(cv, 0).to(dev), torch.cat(c2, 0).to(dev), n1, n2, kernels=kernels)
+    if dtype is not None:
+        x, xy = x.to(dtype), xy.to(dtype)
+    return TreeBatch(x, node_type, node_tree, xy, edge_index, [1 + a + b for a, b in zip(n1, n2)], n1, n2)

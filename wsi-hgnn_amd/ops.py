@@ -3367,3 +3367,130 @@ def ihpool_assign(xyf: torch.Tensor, member_node: torch.Tensor, member_seg: torc
         N.check(N.load().wsi_ihpool_assign(N.ptr(xyf), xyf.shape[0], N.ptr(member_node), N.ptr(member_seg), m, N.ptr(seed_ptr), N.ptr(seed_node),
                                            seed_ptr.numel() - 1, seed_node.numel(), N.ptr(out), N.stream()), "wsi_ihpool_assign")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Slide graphs from patch grids (csrc/grid_graph.hip; the host layer is construct.grid_adjacency / construct.slide_trees)
+# ------------------------------------------------------------------------------------------------
+GRID_COORD_LIMIT = 1 << 24
+GRID_MAX_SETS = 1 << 13
+GRID_MODES = {"adjacency": N.WSI_GRID_ADJACENCY, "tree": N.WSI_GRID_TREE}
+GRID_FLAGS = ((N.WSI_GRID_BAD_COORD, "a coordinate outside 0 <= c < 2^24"),
+              (N.WSI_GRID_REPEATED, "a coordinate pair repeated within one slide and level"),
+              (N.WSI_GRID_TABLE_FULL, "the look-up table is full"),
+              (N.WSI_GRID_UNCOVERED, "a level-2 node that no level-1 node covers"))
+
+
+def grid_capacity(num_points: int) -> int:
+    """The smallest power of two >= 2 x ``num_points`` (at least 2): the table size ``wsi_grid_index`` asks for."""
+    return 1 << max(1, (2 * int(num_points) - 1).bit_length())
+
+
+class GridIndex:
+    """What ``grid_index`` leaves on the device: the table (``keys`` int64 / ``rows`` int32 [capacity]), ``set_max`` int32 [S, 2], ``flags``
+    int32 [2], and the tables it was built from."""
+
+    def __init__(self, coords, set_ptr, keys, rows, set_max, flags):
+        self.coords, self.set_ptr, self.keys, self.rows, self.set_max, self.flags = coords, set_ptr, keys, rows, set_max, flags
+
+    @property
+    def num_points(self) -> int:
+        return self.coords.shape[0]
+
+    @property
+    def num_sets(self) -> int:
+        return self.set_ptr.shape[0] - 1
+
+    @property
+    def capacity(self) -> int:
+        return self.keys.shape[0]
+
+
+def _grid_tables(what: str, coords: torch.Tensor, set_ptr: torch.Tensor) -> None:
+    if coords.dim() != 2 or coords.shape[1] != 2 or coords.dtype != torch.int32:
+        raise ValueError(f"{what}: coords is an int32 [P, 2] tensor, got {tuple(coords.shape)} {coords.dtype}")
+    if set_ptr.dim() != 1 or set_ptr.dtype != torch.int32 or not 2 <= set_ptr.shape[0] <= GRID_MAX_SETS + 1:
+        raise ValueError(f"{what}: set_ptr is an int32 [S + 1] tensor with 1 <= S <= {GRID_MAX_SETS}")
+    N.require_cuda(coords, set_ptr)
+
+
+def grid_index(coords: torch.Tensor, set_ptr: torch.Tensor) -> GridIndex:
+    """``wsi_grid_index``: one open-addressing table over (set, x, y) -> point for the packed point sets ``coords`` [P, 2] int32 / ``set_ptr``
+    [S + 1] int32 (non-decreasing from 0 to P: the caller's), the per-set coordinate maxima and the flag words.  No read-back."""
+    _grid_tables("grid_index", coords, set_ptr)
+    coords, set_ptr = coords.contiguous(), set_ptr.contiguous()
+    P, S, dev = coords.shape[0], set_ptr.shape[0] - 1, coords.device
+    cap = grid_capacity(P)
+    keys = torch.empty(cap, dtype=torch.int64, device=dev)
+    rows = torch.empty(cap, dtype=torch.int32, device=dev)
+    set_max = torch.empty((S, 2), dtype=torch.int32, device=dev)
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    with _Timed("grid_index"):
+        N.check(N.load().wsi_grid_index(N.ptr(coords), P, N.ptr(set_ptr), S, N.ptr(keys), N.ptr(rows), cap, N.ptr(set_max), N.ptr(flags), N.stream()),
+                "wsi_grid_index")
+    return GridIndex(coords, set_ptr, keys, rows, set_max, flags)
+
+
+def _grid_tree_args(what: str, index: GridIndex, mode: str, n1: int, cover: Optional[torch.Tensor]):
+    if mode not in GRID_MODES:
+        raise ValueError(f"{what}: mode is 'adjacency' or 'tree', got {mode!r}")
+    if mode == "adjacency":
+        return 0, None
+    n1 = int(n1)
+    if index.num_sets % 2 or not 0 <= n1 <= index.num_points:
+        raise ValueError(f"{what}: a tree call has the sets [level 1 of every slide | level 2 of every slide] and 0 <= n1 <= P")
+    if cover is None or cover.dtype != torch.int32 or tuple(cover.shape) != (n1, 4):
+        raise ValueError(f"{what}: cover is an int32 [n1, 4] tensor")
+    N.require_cuda(cover)
+    return n1, cover.contiguous()
+
+
+def grid_count(index: GridIndex, mode: str, n1: int = 0, cover: Optional[torch.Tensor] = None):
+    """``wsi_grid_count``: ``counts`` int32, the items every node will emit - [P] entries for ``mode='adjacency'``, [2 n1 + n2] edges in
+    [slide][section][node] order for ``mode='tree'`` - and, for a tree, ``parent`` int32 [n2] (else None).  No read-back."""
+    n1, cover = _grid_tree_args("grid_count", index, mode, n1, cover)
+    P, dev = index.num_points, index.coords.device
+    counts = torch.empty(P + n1, dtype=torch.int32, device=dev)
+    parent = torch.empty(P - n1, dtype=torch.int32, device=dev) if mode == "tree" else None
+    with _Timed("grid_count"):
+        N.check(N.load().wsi_grid_count(GRID_MODES[mode], N.ptr(index.coords), P, N.ptr(index.set_ptr), index.num_sets, n1, N.ptr(cover),
+                                        N.ptr(index.keys), N.ptr(index.rows), index.capacity, N.ptr(counts), N.ptr(parent), N.stream()),
+                "wsi_grid_count")
+    return counts, parent
+
+
+def grid_write(index: GridIndex, mode: str, counts: torch.Tensor, offsets_incl: torch.Tensor, n1: int = 0, cover: Optional[torch.Tensor] = None,
+               parent: Optional[torch.Tensor] = None):
+    """``wsi_grid_write``: the items at ``offsets_incl - counts`` (``offsets_incl`` int64 = ``cumsum(counts)``), in buffers of the largest
+    possible size - the caller cuts them at the total.  ``mode='adjacency'``: ``(row, col)`` int64 [8 P].  ``mode='tree'``: ``(edge_index``
+    int64 [2, 18 n1 + 8 n2], ``node_type`` int64 [N], ``node_tree`` int64 [N], ``x_y_index`` fp64 [N, 2]) over the N = B + P rows of the
+    batch, ``index.flags[1]`` raised for an uncovered level-2 node.  No atomics, no read-back."""
+    n1, cover = _grid_tree_args("grid_write", index, mode, n1, cover)
+    P, dev = index.num_points, index.coords.device
+    if counts.dtype != torch.int32 or offsets_incl.dtype != torch.int64 or counts.shape != (P + n1,) or offsets_incl.shape != counts.shape:
+        raise ValueError("grid_write: counts int32 and offsets_incl int64, one entry per counted node")
+    N.require_cuda(counts, offsets_incl)
+    counts, offsets_incl = counts.contiguous(), offsets_incl.contiguous()
+    lib, st = N.load(), N.stream()
+    if mode == "adjacency":
+        row = torch.empty(8 * P, dtype=torch.int64, device=dev)
+        col = torch.empty(8 * P, dtype=torch.int64, device=dev)
+        with _Timed("grid_write"):
+            N.check(lib.wsi_grid_write(GRID_MODES[mode], N.ptr(index.coords), P, N.ptr(index.set_ptr), index.num_sets, 0, None, N.ptr(index.keys),
+                                       N.ptr(index.rows), index.capacity, N.ptr(counts), N.ptr(offsets_incl), None, None, N.ptr(row), N.ptr(col),
+                                       None, None, None, None, st), "wsi_grid_write")
+        return row, col
+    if parent is None or parent.dtype != torch.int32 or parent.shape != (P - n1,):
+        raise ValueError("grid_write: parent is the int32 [n2] tensor grid_count returned")
+    N.require_cuda(parent)
+    rows = index.num_sets // 2 + P
+    edges = torch.empty((2, 18 * n1 + 8 * (P - n1)), dtype=torch.int64, device=dev)
+    node_type = torch.empty(rows, dtype=torch.int64, device=dev)
+    node_tree = torch.empty(rows, dtype=torch.int64, device=dev)
+    xy = torch.empty((rows, 2), dtype=torch.float64, device=dev)
+    with _Timed("grid_write"):
+        N.check(lib.wsi_grid_write(GRID_MODES[mode], N.ptr(index.coords), P, N.ptr(index.set_ptr), index.num_sets, n1, N.ptr(cover), N.ptr(index.keys),
+                                   N.ptr(index.rows), index.capacity, N.ptr(counts), N.ptr(offsets_incl), N.ptr(parent.contiguous()),
+                                   N.ptr(index.set_max), N.ptr(edges), N.ptr(edges, edges.shape[1] * 8), N.ptr(node_type), N.ptr(node_tree),
+                                   N.ptr(xy), N.ptr(index.flags), st), "wsi_grid_write")
+    return edges, node_type, node_tree, xy
