@@ -400,3 +400,162 @@ def test_new_entry_points_refuse_cpu_tensors_and_bad_arguments():
     assert lib.wsi_ihpool_assign(None, 3, None, None, 2, None, None, 1, 1, None, None) == EINVAL and "null pointer" in err()
     assert lib.wsi_ihpool_assign(None, 3, None, None, 0, None, None, 1, 1, None, None) == 0
     assert N.WSI_RA_BIAS_PARTS == 64
+
+
+# ------------------------------------------------------------------------------------------------ the ra_attention dispatch sweep
+# What tests/test_h2mil_kernels_gpu.py runs on the GPU is decided and checked here, without one: which kernel instantiation every width
+# reaches, what the sweep graph contains, and that every case leaves the kernels room (tests/h2mil_cases.py: ra_case).
+def ra_cfg(C, vec4_ok=True):
+    """csrc/ra_attn.hip's ra_cfg and RA_DISPATCH's code, restated: (VEC * 100000 + G * 100 + NK, the chunks per lane the width needs)."""
+    vec = 4 if vec4_ok and C % 4 == 0 else 1
+    chunks = C // vec
+    G = next(g for g in (4, 8, 16, 32, 64) if g == 64 or g >= chunks)
+    need = -(-chunks // G)
+    NK = next(k for k in (1, 2, 4, 8, 16, 32, 64, 128) if k >= need)
+    return vec * 100000 + G * 100 + NK, need
+
+
+def ra_code(C, vec4_ok=True):
+    return ra_cfg(C, vec4_ok)[0]
+
+
+def _ra_dispatch_codes():
+    import re
+    with open(os.path.join(ROOT, "wsi-hgnn_amd", "csrc", "ra_attn.hip")) as f:
+        text = f.read()
+    table = text[text.index("#define RA_DISPATCH"):text.index("static int ra_check_shape")]
+    return sorted(int(c) for c in re.findall(r"case (\d+):", table))
+
+
+def test_ra_sweep_reaches_every_dispatch_code():
+    codes = _ra_dispatch_codes()
+    assert len(codes) == len(set(codes)) == 20
+    before = {ra_code(Cw) for Cw in C.RA_WIDTHS_BEFORE}
+    assert before == {100401, 400401, 400801, 406401, 406402}
+    assert all(Cw % 4 == 0 for Cw in C.RA_SWEEP_VEC4) and all(Cw % 4 for Cw in C.RA_SWEEP_VEC1) and len(set(C.RA_SWEEP)) == len(C.RA_SWEEP) == 22
+    reached = {}
+    for Cw in C.RA_SWEEP:
+        reached.setdefault(ra_code(Cw), []).append(Cw)
+    assert sorted(set(reached) | before) == codes, f"not reached: {sorted(set(codes) - set(reached) - before)}"
+    assert sorted(reached) == codes                                                # the sweep alone reaches them too
+    # no width repeats another's kernel, but for the partly filled and the full last chunk of the widest code of each family
+    twice = {code: ws for code, ws in reached.items() if len(ws) > 1}
+    assert twice == {406416: [2052, 4096], 106464: [2050, 4095]}
+    assert ra_cfg(2052) == (406416, 9) and ra_cfg(4096) == (406416, 16) and ra_cfg(2050) == (106464, 33) and ra_cfg(4095) == (106464, 64)
+    # no width on a boundary of the rule: but for the full width 4096, the last lane of a group has less to do than the first
+    for Cw in C.RA_SWEEP:
+        code = ra_code(Cw)
+        vec, G, NK = code // 100000, code // 100 % 1000, code % 100
+        assert (Cw // vec < G * NK) == (Cw != 4096), Cw
+    # an idle chunk index (k with VEC * G * k >= C for every lane) exists at every NK >= 4
+    for NK in (4, 8, 16, 32, 64):
+        assert any(ra_cfg(Cw)[0] % 100 == NK and ra_cfg(Cw)[1] < NK for Cw in C.RA_SWEEP), NK
+    # the scalar fallback at multiples of 4: its codes exist and differ from the vector family's
+    for Cw in C.RA_FALLBACK_WIDTHS:
+        assert Cw % 4 == 0 and Cw in C.RA_SWEEP and ra_code(Cw, False) in codes and ra_code(Cw, False) // 100000 == 1 and ra_code(Cw) // 100000 == 4
+    assert [ra_code(Cw, False) for Cw in C.RA_FALLBACK_WIDTHS] == [100801, 106401, 106404, 106416]
+    # what the other cases are there for: one width per group size at peaked scores, one width per family at the other slopes
+    assert {ra_code(Cw) // 100 % 1000 for Cw in C.RA_ONE_HOT_WIDTHS} == {4, 8, 16, 32, 64} and {2052, 2050} <= set(C.RA_ONE_HOT_WIDTHS)
+    for slope in (0.05, 0.0):
+        assert sorted(ra_code(Cw) // 100000 for Cw, s in C.RA_SLOPE_CASES if s == slope) == [1, 4]
+    assert all(Cw in C.RA_SWEEP for Cw in C.RA_ONE_HOT_WIDTHS + C.RA_DEGENERATE_WIDTHS + tuple(Cw for Cw, _ in C.RA_SLOPE_CASES))
+
+
+def test_ra_sweep_graph_has_what_it_promises():
+    from wsi_hgnn_amd import ops
+    n, nt, ei = C.ra_graph("sweep")
+    ec = ops.edge_csr_by_source_type(ei[0], ei[1], nt, n)
+    indeg, outdeg = C.ra_sweep_facts(n, nt, ei, ec.rowptr, ec.colptr)
+    print(f"sweep graph: E = {ei.shape[1]}, hub out-degrees {[int(outdeg[h]) for h, _ in C.RA_HUBS]}, sinks {int((outdeg == 0).sum())}, "
+          f"largest in-degree {int(indeg.max())}")
+    # the stride loops over a source's edges make a second trip: 16 lanes in pass C, up to 64 in pass A
+    assert int(outdeg[10]) > 16 and int(outdeg[11]) > 64 and int(outdeg[12]) > 3 * 64
+    old_n, old_nt, old_ei = C.ra_kernel_graph()
+    assert int(torch.bincount(old_ei[0], minlength=old_n).max()) <= 16                         # why the old graph could not reach them
+    deg = C.ra_degenerate_graphs()
+    assert deg["one-node"][0] == 1 and deg["one-node"][2].shape == (2, 0)
+    n5, nt5, ei5 = deg["ring-of-three"]
+    assert n5 == 5 and ei5.t().tolist() == [[0, 1], [1, 2], [2, 0]] and n5 < 64
+
+
+@pytest.mark.parametrize("name,Cw,scale,slope", C.ra_gpu_cases(), ids=[f"{g}-{w}-x{int(s)}-{sl}" for g, w, s, sl in C.ra_gpu_cases()])
+def test_ra_cases_leave_the_kernels_their_margin(name, Cw, scale, slope):
+    """Every case of the GPU tests, on the seed ``ra_case`` settles on (the first of 20 that meets both conditions): the fp32 CPU run of the
+    restatement is within a quarter of the tolerance of float64 under every norm the GPU tests use, and no leaky_relu argument is nearer
+    to zero than 1e-5 x the score scale."""
+    n, nt, ei = C.ra_graph(name)
+    case = C.ra_case((n, nt, ei), Cw, scale, slope)
+    worst = max(case["e32"].items(), key=lambda kv: kv[1])
+    print(f"{name} C={Cw} x{scale} slope {slope}: seed {case['seed']}, kink distance {case['kink']:.3e}, largest fp32 figure {worst[1]:.3e} ({worst[0]})")
+    assert case["kink"] >= C.RA_KINK * scale
+    assert C.ra_kink_distance(case["inputs"][1], ei, nt) == case["kink"]
+    assert max(case["e32"].values()) <= C.RA_TOL / 4, case["e32"]
+    names = set(case["e32"])
+    assert {"out", "g_ft", "g_sc", "g_bias"} <= names
+    if name == "sweep":
+        assert {f"out[{r}]" for r in C.RA_OUT_ROWS} | {f"g_ft[{r}]" for r in C.RA_GFT_ROWS} | {"g_el", "g_er", "g_pl", "g_pr"} <= names
+    else:
+        assert not case["ref"][2].any()                          # every softmax has one term: the score gradients are exactly zero
+
+
+def test_a_plan_without_edges_still_passes_addresses():
+    """An empty tensor has no address and wsi_ra_attn_fwd / _bwd refuse NULL: ``ops.ra_attention`` on a graph without edges (the one-node
+    case of the GPU tests; it answered 'null pointer' before) hands over one unread element per edge array, and the plan's own otherwise."""
+    from wsi_hgnn_amd import ops
+    n, nt, ei = C.ra_graph("one-node")
+    ec = ops.edge_csr_by_source_type(ei[0], ei[1], nt, n)
+    assert ec.num_edges == 0 and ec.rowptr.tolist() == [0, 0] and ec.colptr.tolist() == [0, 0]
+    assert all(t.numel() == 1 and t.dtype == torch.int32 for t in ops._ra_edges(ec))
+    n, nt, ei = C.ra_graph("ring-of-three")
+    ec = ops.edge_csr_by_source_type(ei[0], ei[1], nt, n)
+    src, eid, dst = ops._ra_edges(ec)
+    assert src is ec.src and eid is ec.csc_eid and dst is ec.csc_dst
+
+
+def test_ra_stat_restatement_agrees_with_the_attention_restatement():
+    """``ra_stat_ref`` (the loops) against ``ra_attention_ref`` (the dense form): out rebuilt from stat's max, log-sum and beta."""
+    n, nt, ei = C.ra_graph("sweep")
+    ft, sc, bias, _ = C.ra_inputs(n, 7)
+    stat = C.ra_stat_ref(sc, ei, nt)
+    u, v = ei[0], ei[1]
+    s = torch.nn.functional.leaky_relu(sc.double()[u, 0] + sc.double()[v, 1], 0.2)
+    a = torch.exp(s - stat[v, nt[u], 0] - stat[v, nt[u], 1]) * stat[v, nt[u], 3]
+    out = torch.zeros(n, 7, dtype=torch.float64).index_add(0, v, a[:, None] * ft.double()[u]) + bias.double()
+    _close(out, C.ra_attention_ref(ft.double(), sc.double(), bias.double(), ei, nt), "out from stat")
+    present = stat[:, :, 2] > 0
+    assert torch.equal(stat[:, :, 2].sum(1).long(), torch.bincount(v, minlength=n))
+    assert bool((stat[~present] == torch.tensor([math.inf, 0.0, 0.0, 0.0], dtype=torch.float64)).all())
+
+
+def test_assign_cases_outside_the_tables_and_over_three_tiles():
+    case, _ = C.find_case(C.assign_outside_case, lambda c: c[6])
+    buf, member_node, member_seg, seed_ptr, seed_node, want, _ = case
+    T, lead = C.ASSIGN_TABLE, C.ASSIGN_LEAD
+    assert buf.shape == (C.ASSIGN_ROWS, 3) and seed_ptr.tolist() == [0, 5, 6, 71, 74]
+    for t in (member_node, seed_node):                           # every index, followed or not, stays inside the buffer
+        assert int(t.min()) >= -lead and int(t.max()) < C.ASSIGN_ROWS - lead
+    out_seed = ((seed_node < 0) | (seed_node >= T)).nonzero().view(-1).tolist()
+    assert out_seed == [1, 3, 5, 6 + 64] and int(seed_node[1]) < 0 and int(seed_node[3]) >= T
+    out_member = (member_node < 0) | (member_node >= T)
+    assert int(out_member.sum()) == 3 and bool((member_seg[out_member] == 3).all())
+    assert bool((want[out_member] == -1).all()) and bool((want[member_seg == 1] == -1).all()) and bool((want[member_seg >= 4] == -1).all())
+    assert int((member_seg >= 4).sum()) == 10 and bool((member_seg[1:] >= member_seg[:-1]).all())
+    assert int((member_seg < 0).sum()) == 4 and bool((want[member_seg < 0] == -1).all())
+    rest = ~out_member & (member_seg != 1) & (member_seg >= 0) & (member_seg < 4)
+    assert bool((want[rest] >= 0).all())
+    for s, bad in ((0, (1, 3)), (2, (64,))):                     # an outside seed is never chosen; its neighbours keep their positions
+        got = set(want[member_seg == s].tolist())
+        assert not got & set(bad) and max(got) > max(bad) - (s == 2) * 64
+    # every lure is in place: following an outside index would have changed the answer
+    for p in out_seed:
+        seg = int((seed_ptr[1:] > p).nonzero()[0])
+        mem = member_node[(member_seg == seg) & ~out_member].long()
+        assert bool((buf[lead + mem] == buf[lead + int(seed_node[p])]).all(1).any())
+    for i in out_member.nonzero().view(-1).tolist():
+        assert torch.equal(buf[lead + int(member_node[i])], buf[lead + int(seed_node[seed_ptr[3]])])
+    tiles, _ = C.find_case(C.assign_tiles_case, lambda c: float(C.assign_ref(*c)[1].min()))
+    assert tiles[3].diff().tolist() == [128, 129]
+    got = C.assign_ref(*tiles)[0]
+    for s, k in enumerate((128, 129)):
+        mine = got[tiles[2] == s]
+        assert int(mine.min()) >= 0 and int(mine.max()) == k - 1 and int((mine >= 64).sum()) > 0       # the later tiles are chosen from

@@ -3291,6 +3291,15 @@ def _ra_check(ft, sc, bias, ec, node_type) -> None:
         raise ValueError(f"ra_attention: node_type is an integer [{n}] tensor, got {tuple(node_type.shape)} {node_type.dtype}")
 
 
+def _ra_edges(ec):
+    """The plan's per-edge arrays as the C ABI takes them: an empty tensor has no address and the entry points refuse NULL, so a graph
+    without edges passes one unread element each."""
+    if ec.num_edges:
+        return ec.src, ec.csc_eid, ec.csc_dst
+    one = torch.zeros(1, dtype=torch.int32, device=ec.rowptr.device)
+    return one, one, one
+
+
 class _RaAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ft, sc, bias, ec, node_type, slope: float):
@@ -3304,7 +3313,7 @@ class _RaAttention(torch.autograd.Function):
         out = torch.empty((n, C), dtype=torch.float32, device=ft.device)
         stat = torch.empty((n, RA_NODE_TYPES, 4), dtype=torch.float32, device=ft.device)
         with _Timed("ra_attn_fwd"):
-            N.check(N.load().wsi_ra_attn_fwd(N.ptr(ft), ldf, N.ptr(sc), N.ptr(node_type), n, C, N.ptr(ec.rowptr), N.ptr(ec.src), float(slope),
+            N.check(N.load().wsi_ra_attn_fwd(N.ptr(ft), ldf, N.ptr(sc), N.ptr(node_type), n, C, N.ptr(ec.rowptr), N.ptr(_ra_edges(ec)[0]), float(slope),
                                              N.ptr(b), N.ptr(out), C, N.ptr(stat), N.stream()), "wsi_ra_attn_fwd")
         ctx.ec, ctx.slope, ctx.has_bias, ctx.ldf = ec, float(slope), bias is not None, ldf
         ctx.save_for_backward(ft, sc, stat, node_type)
@@ -3324,9 +3333,10 @@ class _RaAttention(torch.autograd.Function):
         g_ft = torch.empty((n, C), dtype=torch.float32, device=dev)
         g_sc = torch.empty((n, 4), dtype=torch.float32, device=dev)
         g_b = torch.empty(C, dtype=torch.float32, device=dev) if ctx.has_bias else None
+        src, csc_eid, csc_dst = _ra_edges(ec)
         with _Timed("ra_attn_bwd"):
             N.check(N.load().wsi_ra_attn_bwd(N.ptr(ft), ctx.ldf, N.ptr(sc), N.ptr(node_type), N.ptr(stat), N.ptr(g_out), C, n, E, C,
-                                             N.ptr(ec.rowptr), N.ptr(ec.src), N.ptr(ec.colptr), N.ptr(ec.csc_eid), N.ptr(ec.csc_dst), ctx.slope,
+                                             N.ptr(ec.rowptr), N.ptr(src), N.ptr(ec.colptr), N.ptr(csc_eid), N.ptr(csc_dst), ctx.slope,
                                              N.ptr(edge_ws), N.ptr(group_ws), N.ptr(bias_ws), N.ptr(g_ft), C, N.ptr(g_sc), N.ptr(g_b), N.stream()),
                     "wsi_ra_attn_bwd")
         return g_ft, g_sc, g_b, None, None, None
