@@ -506,6 +506,30 @@ int wsi_remix_nearest(const float* protos, int32_t S, int32_t K, int32_t D, cons
 int wsi_remix_rows(const float* protos, const float* shifts, int32_t S, int32_t K, int32_t V, int32_t D,
                    const int32_t* nearest, int32_t num_slots, const int32_t* desc, int32_t rows, float* out, void* stream);
 
+/* Patch dropout of many bags and the fill of a padded bag slot (an addition to ABI 26; mil.dropout_patches, mil.BagSlot).
+ * The reference's dropout_patches (baselines/ReMix_DSMIL_ABMIL/train_tcga_k-fold.py:90-96) keeps k = int(n * (1 - p)) rows of a bag of n drawn
+ * without replacement and appends m = int(n * p) of the kept rows again; the host computes k and m (mil.patch_counts).  The draw is the
+ * project's own, from a 32-bit draw word d per bag, in uint32 arithmetic with fmix32 = MurmurHash3's finaliser and mask = 2^key_bits - 1:
+ *   s1 = fmix32(d), s2 = fmix32(d ^ 0x85EBCA6B), key1(i) = fmix32(i * 0x9E3779B1 + s1) & mask, key2(i) = fmix32(i * 0x9E3779B1 + s2) & mask
+ *   kept rows: the k rows i of [0, n) with the smallest (key1(i), i), in ascending i;  pad rows: the m kept rows with the smallest (key2(i), i),
+ *   in ascending i.  A tie on a key goes to the lower row.  1 <= key_bits <= 32 (the package passes 32; fewer bits make ties common).
+ * bag_desc (device): 8 int64 words per bag [src, stride, n, k, m, dst_row, draw, 0] - src = the bag's first source row (fp32, unit column
+ * stride, `stride` floats from row to row), dst_row = its first row in the output.  Bags are listed by ascending dst_row, without gaps:
+ * dst_row of the next bag = dst_row + k + m.
+ * wsi_bag_dropout_select: sel[dst_row + j] = the source row (0-based within its bag) of output row j of every bag, j < k + m; one workgroup per
+ * bag, one launch, no allocation, no read-back, the same result run after run, and a bag's rows do not depend on the other bags.  Nothing is
+ * written at or beyond sel_rows; k > n and m > k are clamped. */
+int wsi_bag_dropout_select(const int64_t* bag_desc, int32_t num_bags, int32_t key_bits, int32_t* sel, int64_t sel_rows, void* stream);
+
+/* wsi_bag_slot_fill: rows[r, :feats] (row stride ld) for EVERY r < num_rows in one launch: the source row sel[r] of the bag that owns r (sel
+ * NULL: the bag's rows in order, k = n and m = 0), zeros for a row no bag owns or a source row outside [0, n).  16-byte accesses when rows, ld,
+ * feats and the bag's src / stride allow, a scalar path otherwise (per bag).  row_seg (may be NULL): row_seg[r] = the owning bag, filler_seg
+ * for the rest.  small_words int32 words are copied from small_src to small_dst (both device; 0: none): the host-built small tables of a slot,
+ * which travel behind the descriptors in the same upload. */
+int wsi_bag_slot_fill(const int64_t* bag_desc, int32_t num_bags, const int32_t* sel, float* rows, int64_t ld, int32_t feats,
+                      int64_t num_rows, int32_t* row_seg, int32_t filler_seg,
+                      const int32_t* small_src, int32_t* small_dst, int32_t small_words, void* stream);
+
 /* One Adam step over `count` parameter tensors in ONE launch: the optimizer step of the reference's trainer (torch.optim.Adam(lr, weight_decay),
  * parser.py:33-38; trainer/train_gnn.py:72) with torch's arithmetic, amsgrad = False, maximize = False:
  *   g += weight_decay * p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;

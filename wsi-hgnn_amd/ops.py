@@ -12,6 +12,7 @@ torch calls of models/HEATNet4.py the ops stand in for):
 """
 from __future__ import annotations
 
+import array
 import ctypes
 import contextlib
 from typing import List, Optional, Sequence, Tuple
@@ -1391,6 +1392,51 @@ def bag_scores(q: torch.Tensor, onehot: torch.Tensor, rp: ReducePlan) -> torch.T
     onehot[r, c] * q[r] - the query of the critical instance ``onehot`` [rows, C] marks (an all-zero column: q_max = 0).  The gradient
     reaches ``q`` through both factors, in a number of launches that does not depend on the number of bags and without atomics."""
     return _BagScores.apply(q, onehot, rp)
+
+
+# ------------------------------------------------------------------------------------------------
+# patch dropout of many bags and the fill of a padded bag slot (wsi_bag_dropout_select / wsi_bag_slot_fill: mil.dropout_patches, mil.BagSlot)
+# ------------------------------------------------------------------------------------------------
+BAG_DESC_WORDS = 8
+
+
+def bag_descriptors(sources: Sequence[torch.Tensor], counts: Sequence[Tuple[int, int]], draws: Sequence[int], feats: int) -> Tuple[List[int], int]:
+    """The descriptor words of wsi_bag_dropout_select / wsi_bag_slot_fill (eight per bag: [src, stride, n, k, m, dst_row, draw, 0]) for the
+    bags ``sources`` ([n_i, feats] fp32 device tensors with unit column stride; a row stride of their own is fine) laid one after the other,
+    ``counts[i] = (k_i, m_i)``; returns (words, total rows).  Everything is checked here: the kernels trust the table."""
+    words: List[int] = []
+    row = 0
+    for t, (k, m), d in zip(sources, counts, draws):
+        if t.dim() != 2 or t.dtype != torch.float32 or t.shape[1] != feats or (t.shape[0] > 0 and feats > 1 and t.stride(1) != 1):
+            raise ValueError(f"bag rows: expected [n, {feats}] float32 with unit column stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+        n = t.shape[0]
+        if not (0 <= k <= n and 0 <= m <= k):
+            raise ValueError(f"bag rows: cannot keep {k} and repeat {m} of {n} rows")
+        if n >= 1 << 31:
+            raise ValueError("bag rows: a bag of 2^31 rows or more")
+        words += [t.data_ptr(), t.stride(0) if n > 1 else feats, n, k, m, row, int(d) & 0xffffffff, 0]
+        row += k + m
+    return words, row
+
+
+def bag_dropout_rows(sources: Sequence[torch.Tensor], counts: Sequence[Tuple[int, int]], draws: Sequence[int], key_bits: int = 32):
+    """(rows [sum(k + m), feats], sel int32 [sum(k + m)]): the bags ``sources`` after the patch dropout of the draw contract in
+    include/wsi_hgnn.h - per bag the k kept rows, then the m repeated ones; ``sel`` = the source row (within its bag) of every output row.
+    One upload and two launches whatever the number of bags; no read-back."""
+    N.require_cuda(*sources)
+    if not sources:
+        raise ValueError("bag_dropout_rows: no bag")
+    feats, dev = sources[0].shape[1], sources[0].device
+    words, total = bag_descriptors(sources, counts, draws, feats)
+    rows = torch.empty((total, feats), dtype=torch.float32, device=dev)
+    sel = torch.empty(total, dtype=torch.int32, device=dev)
+    if total:
+        desc = host_to_device(torch.frombuffer(array.array("q", words), dtype=torch.int64), torch.int64, dev)
+        lib = N.load()
+        N.check(lib.wsi_bag_dropout_select(N.ptr(desc), len(sources), int(key_bits), N.ptr(sel), total, N.stream()), "wsi_bag_dropout_select")
+        N.check(lib.wsi_bag_slot_fill(N.ptr(desc), len(sources), N.ptr(sel), N.ptr(rows), feats, feats, total, None, 0, None, None, 0,
+                                      N.stream()), "wsi_bag_slot_fill")
+    return rows, sel
 
 
 # ------------------------------------------------------------------------------------------------
