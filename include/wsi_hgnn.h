@@ -1136,6 +1136,43 @@ int wsi_grid_write(int32_t mode, const int32_t* coords, int32_t num_points, cons
                    const int64_t* offsets_incl, const int32_t* parent, const int32_t* set_max, int64_t* out_a, int64_t* out_b,
                    int64_t* node_type, int64_t* node_tree, double* x_y_index, int32_t* flags, void* stream);
 
+/* The fill of a padded GTNMIL graph slot (an addition to ABI 26; gtn.GraphSlot).  A slot is `cells` cells of `cell_rows` rows;
+ * slide i of a batch lies at the head of cell i, every other row is dead.  slide_desc (device): 16 int64 words per slide
+ *   [x, x_stride, rowptr, src, edge_w, colptr, csc_dst, edge_w_csc, rows, entries, dst_entry, label, 0, 0, 0, 0]
+ * x = the slide's fp32 rows (unit column stride, x_stride floats from row to row); rowptr / colptr int32 [rows + 1] and src / csc_dst int32
+ * [entries] = the slide's LOCAL ops.EdgeCSR tables; edge_w / edge_w_csc fp32 [entries] or 0 (every weight 1); dst_entry = the slide's first
+ * entry in the slot = the sum of the entries of the slides before it.  rows <= cell_rows, total_entries = the sum of all entries <= entry_cap.
+ * Written, in two launches whatever the batch (no atomics, no read-back, no allocation, the same bits run after run):
+ *   x [cells * cell_rows, feats] (contiguous): the slides' rows, zero in dead rows;  live [rows] 1 / 0;  cell_live [cells] 1 / 0;
+ *   labels int64 [cells]: the descriptor's label, -100 in unused cells;  scalars[0] = inv_cells, scalars[1] = live_rows (passed by the host);
+ *   rowptr / colptr int32 [cells * cell_rows + 1]: local value + dst_entry in a live row, the running entry offset in a dead one (an empty
+ *     range), total_entries at the end;  src / csc_dst [e] = local value + the cell's first row, edge_w / edge_w_csc [e] the weight or 1.0, for
+ *     e < total_entries: nothing at or behind total_entries is written, and nothing that walks rowptr / colptr ever reads there. */
+int wsi_graph_slot_fill(const int64_t* slide_desc, int32_t num_slides, int32_t cells, int32_t cell_rows, int32_t feats,
+                        int64_t entry_cap, int64_t total_entries, float inv_cells, float live_rows,
+                        float* x, float* live, float* cell_live, float* scalars, int64_t* labels,
+                        int32_t* rowptr, int32_t* src, float* edge_w, int32_t* colptr, int32_t* csc_dst, float* edge_w_csc, void* stream);
+
+/* BatchNorm1d over the LIVE rows of a padded table (an addition to ABI 26; ops.masked_batch_norm).  x [rows, C] fp32 (row stride
+ * ldx), live [rows] fp32 0 / 1, live_rows = ONE device word holding the number of live rows n as fp32 (n >= 2 in training; the host checks).
+ * wsi_masked_bn_fwd, training != 0: per column the mean and the biased variance over the live rows - centred (Welford per lane, Chan merges of
+ *   (count, mean, M2) across waves, chunks and lanes in one fixed order; never E[x^2] - mean^2) - then stats [2, C] = (mean, 1 / sqrt(var + eps)),
+ *   running_mean = (1 - momentum) running_mean + momentum mean and running_var likewise with the unbiased variance M2 / (n - 1) (either may be
+ *   NULL: not tracked), and y = (x - mean) rstd gamma + beta in live rows, 0 in dead rows (gamma / beta NULL: 1 / 0).
+ *   training == 0: stats = (running_mean, 1 / sqrt(running_var + eps)), the same y; live_rows and partial are not read.
+ *   partial: 3 * wsi_masked_bn_chunks(rows) * C floats of workspace.
+ * wsi_masked_bn_bwd: dbeta = sum over live rows of g, dgamma = sum of g xhat (xhat = (x - mean) rstd from the saved stats), and
+ *   dx = gamma rstd (g - dbeta / n - xhat dgamma / n) in live rows (training == 0: gamma rstd g), 0 in dead rows.
+ *   partial: 2 * wsi_masked_bn_chunks(rows) * C floats.
+ * No atomics: chunk partials are finished by a second small launch; identical calls give identical bits. */
+int32_t wsi_masked_bn_chunks(int32_t rows);
+int wsi_masked_bn_fwd(const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live, const float* live_rows,
+                      const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t training,
+                      float momentum, float eps, float* partial, float* stats, float* y, int64_t ldy, void* stream);
+int wsi_masked_bn_bwd(const float* gy, int64_t ldg, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live,
+                      const float* live_rows, const float* gamma, const float* stats, int32_t training, float* partial,
+                      float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

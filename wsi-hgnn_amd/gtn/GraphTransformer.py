@@ -44,7 +44,11 @@ class Classifier(nn.Module):
 
     def forward(self, batch, labels):
         """``batch``: a homogeneous ``HeteroGraph`` batch (features in ``ndata['feat']``) or a ``gtn.GraphBatch`` (``gtn.from_dense`` makes one
-        from the reference's ``node_feat, adjs, masks``).  Returns the reference's (pred, labels, loss, softmax(out))."""
+        from the reference's ``node_feat, adjs, masks``), or a ``gtn.GraphSlot`` - then ``labels=None`` takes the slot's (-100 in unused
+        cells, which the cross entropy ignores) and every output has one row per cell.  Returns the reference's (pred, labels, loss,
+        softmax(out))."""
+        if labels is None:
+            labels = as_batch(batch).labels
         out, mc1, o1 = self.logits(batch)
         loss = (ops.cross_entropy(out, labels) if self.kernels else F.cross_entropy(out, labels)) + mc1 + o1
         pred = out.detach().max(1)[1]

@@ -100,7 +100,7 @@ def from_dense(node_feat: torch.Tensor, adj: torch.Tensor, mask: torch.Tensor) -
 def as_batch(batch) -> GraphBatch:
     """A ``GraphBatch`` as it is; a homogeneous ``HeteroGraph`` batch with its features in ``ndata['feat']``: an edge u -> v is the entry
     A[v, u] = 1 (the destination aggregates its sources).  The conversion is kept on the graph."""
-    if isinstance(batch, GraphBatch):
+    if isinstance(batch, GraphBatch) or getattr(batch, "is_slot", False):       # (a gtn.GraphSlot passes through: the model reads its masks)
         return batch
     if isinstance(batch, HeteroGraph):
         if not batch.is_homogeneous:

@@ -58,7 +58,11 @@ class GCNBlock(nn.Module):
                 y = y + self.bias
         if self.normalize_embedding:
             y = F.normalize(y, p=2, dim=-1)
-        if self.bn:
+        if self.bn and getattr(adj, "is_slot", False):
+            bn = self.bn_layer               # a padded slot: the statistics of the live rows only, dead rows stay 0 and get no gradient
+            y = ops.masked_batch_norm(y, adj.live, adj.live_rows, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.momentum,
+                                      bn.eps, num_batches_tracked=bn.num_batches_tracked, kernels=self.kernels)
+        elif self.bn:
             y = self.bn_layer(y)             # the packed rows ARE the rows the reference gathers in front of its bn_layer (gcn.py:361-375)
         if self.dropout > 0.001:
             y = self.dropout_layer(y)
@@ -79,13 +83,20 @@ def dense_mincut_pool(x, logits, plan: GraphBatch, return_adj=False, kernels=Tru
 
     Returns (out [G, K, D], out_adj [G, K, K] or None, mincut_loss, ortho_loss).  The traces come from ``ops.mincut_assign`` (no [K, K] matrix
     is formed for them), out and ss from one grouped GEMM; ``out_adj`` - which the model discards - is s^T t from the saved t = A s, without a
-    gradient.  A slide without entries has trace(s^T D s) = 0 and gives the reference's 0 / 0 = NaN."""
+    gradient.  A slide without entries has trace(s^T D s) = 0 and gives the reference's 0 / 0 = NaN.
+
+    On a ``gtn.GraphSlot`` every cell is a graph of ``cell_rows`` rows: s is zeroed in dead rows (which have no entries, so num and den are
+    those of the live rows already), and both losses are means over the cells that hold a slide, with denominators an unused cell cannot make
+    0 - neither its value nor its gradient is NaN; a real slide without entries still gives NaN."""
     G, K = plan.num_graphs, logits.shape[1]
+    slot = getattr(plan, "is_slot", False)
     if kernels:
         s, num, den, t = ops.mincut_assign_t(logits, plan.ec, plan.rp)
-        out, ss = ops.mincut_pool_products(s, x, plan.rp)
+        out, ss = ops.mincut_pool_products(s * plan.live.view(-1, 1) if slot else s, x, plan.rp)
     else:
         s = torch.softmax(logits, -1)
+        if slot:
+            s = s * plan.live.to(s.dtype).view(-1, 1)
         t = _aggregate(s, plan)
         seg = plan.segment()
         deg = torch.zeros(s.shape[0], dtype=s.dtype, device=s.device).index_add_(
@@ -98,9 +109,15 @@ def dense_mincut_pool(x, logits, plan: GraphBatch, return_adj=False, kernels=Tru
             off.append(off[-1] + c)
         out = torch.stack([s[a:b].t() @ x[a:b] for a, b in zip(off[:-1], off[1:])])
         ss = torch.stack([s[a:b].t() @ s[a:b] for a, b in zip(off[:-1], off[1:])])
-    mincut_loss = torch.mean(-(num / den))
     eye = torch.eye(K, dtype=ss.dtype, device=ss.device)
-    ortho_loss = torch.mean(torch.norm(ss / torch.norm(ss, dim=(-1, -2), keepdim=True) - eye / torch.norm(eye), dim=(-1, -2)))
+    if slot:
+        used, inv = plan.cell_live.to(ss.dtype), plan.inv_cells.to(ss.dtype).reshape(())
+        mincut_loss = (used * -(num / (den + (1 - used)))).sum() * inv
+        ss = ss + (1 - used).view(-1, 1, 1) * eye
+        ortho_loss = (used * torch.norm(ss / torch.norm(ss, dim=(-1, -2), keepdim=True) - eye / torch.norm(eye), dim=(-1, -2))).sum() * inv
+    else:
+        mincut_loss = torch.mean(-(num / den))
+        ortho_loss = torch.mean(torch.norm(ss / torch.norm(ss, dim=(-1, -2), keepdim=True) - eye / torch.norm(eye), dim=(-1, -2)))
     out_adj = None
     if return_adj:
         with torch.no_grad():

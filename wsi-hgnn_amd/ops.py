@@ -3157,6 +3157,93 @@ def mincut_pool_products(s: torch.Tensor, x: torch.Tensor, rp: ReducePlan):
     return out[:, :, :x.shape[1]], out[:, :, x.shape[1]:]
 
 
+# ------------------------------------------------------------------------------------------------
+# BatchNorm1d over the live rows of a padded table (wsi_masked_bn_fwd / _bwd: gtn.GCNBlock on a gtn.GraphSlot)
+# ------------------------------------------------------------------------------------------------
+class _MaskedBatchNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, live, live_rows, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float):
+        N.require_cuda(y, live, live_rows, weight, bias, running_mean, running_var)
+        x = y if y.dtype == torch.float32 and (y.shape[1] == 1 or y.stride(1) == 1) and y.stride(0) >= y.shape[1] else y.to(torch.float32).contiguous()
+        rows, C = x.shape
+        dev, lib = x.device, N.load()
+        w = None if weight is None else weight.detach().contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        out = torch.empty((rows, C), dtype=torch.float32, device=dev)
+        stats = torch.empty((2, C), dtype=torch.float32, device=dev)
+        partial = torch.empty(max(3 * lib.wsi_masked_bn_chunks(rows) * C, 1), dtype=torch.float32, device=dev) if training else None
+        N.check(lib.wsi_masked_bn_fwd(N.ptr(x), x.stride(0) if rows > 1 else C, rows, C, N.ptr(live), N.ptr(live_rows), N.ptr(w), N.ptr(b),
+                                      N.ptr(running_mean), N.ptr(running_var), 1 if training else 0, float(momentum), float(eps), N.ptr(partial),
+                                      N.ptr(stats), N.ptr(out), C, N.stream()), "wsi_masked_bn_fwd")
+        ctx.training, ctx.has_w, ctx.has_b = training, weight is not None, bias is not None
+        ctx.save_for_backward(x, live, live_rows, w, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, live, live_rows, w, stats = ctx.saved_tensors
+        rows, C = x.shape
+        dev, lib = x.device, N.load()
+        g = g if (C == 1 or g.stride(1) == 1) and g.stride(0) >= C else g.contiguous()
+        dx = torch.empty((rows, C), dtype=torch.float32, device=dev)
+        dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+        partial = torch.empty(max(2 * lib.wsi_masked_bn_chunks(rows) * C, 1), dtype=torch.float32, device=dev)
+        N.check(lib.wsi_masked_bn_bwd(N.ptr(g), g.stride(0) if rows > 1 else C, N.ptr(x), x.stride(0) if rows > 1 else C, rows, C, N.ptr(live),
+                                      N.ptr(live_rows), N.ptr(w), N.ptr(stats), 1 if ctx.training else 0, N.ptr(partial), N.ptr(dgamma),
+                                      N.ptr(dbeta), N.ptr(dx), C, N.stream()), "wsi_masked_bn_bwd")
+        return dx, None, None, (dgamma if ctx.has_w else None), (dbeta if ctx.has_b else None), None, None, None, None, None
+
+
+def masked_batch_norm_tensor(y, live, live_rows, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float):
+    """``masked_batch_norm`` with tensor operations, in y's dtype on y's device: what the kernels are held against (and the CPU path)."""
+    m = live.to(y.dtype).view(-1, 1)
+    if training:
+        n = live_rows.to(y.dtype).reshape(())
+        mean = (y * m).sum(0) / n
+        d = (y - mean) * m
+        var = (d * d).sum(0) / n
+        if running_mean is not None:
+            with torch.no_grad():
+                running_mean.mul_(1 - momentum).add_(momentum * mean.detach().to(running_mean.dtype))
+                running_var.mul_(1 - momentum).add_(momentum * (var.detach() * (n / (n - 1))).to(running_var.dtype))
+    else:
+        mean, var = running_mean.to(y.dtype), running_var.to(y.dtype)
+        d = (y - mean) * m
+    out = d / torch.sqrt(var + eps)
+    if weight is not None:
+        out = out * weight
+    if bias is not None:
+        out = out + bias
+    return out * m
+
+
+def masked_batch_norm(y: torch.Tensor, live: torch.Tensor, live_rows: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                      running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], training: bool, momentum: Optional[float] = 0.1,
+                      eps: float = 1e-5, num_batches_tracked: Optional[torch.Tensor] = None, kernels: Optional[bool] = None) -> torch.Tensor:
+    """``torch.nn.functional.batch_norm`` of the rows of ``y`` [rows, C] with ``live`` [rows] = 1 - and 0 in the others, which enter no
+    statistic and receive no gradient.  ``live_rows``: a one-element tensor on y's device holding the number of live rows (at least 2 in
+    training - the caller checks: the device cannot raise); no host value of the batch enters, so the call can be recorded.  In training the
+    running statistics are updated in place as torch updates them (unbiased variance) and ``num_batches_tracked`` (if given) is incremented;
+    in eval mode the running statistics normalise.  ``momentum=None`` (torch's cumulative average) is refused: it needs a host count.
+    On the GPU two small launches and one streaming pass each way (``wsi_masked_bn_fwd`` / ``_bwd``; identical calls give identical bits);
+    ``kernels=False`` or a CPU tensor: ``masked_batch_norm_tensor``."""
+    if momentum is None:
+        raise ValueError("masked_batch_norm: momentum=None (a cumulative moving average) needs a host count of the batches; pass a number")
+    if y.dim() != 2 or live.shape != y.shape[:1] or live_rows.numel() != 1:
+        raise ValueError(f"masked_batch_norm: y [rows, C], live [rows] and a one-element live_rows; got {tuple(y.shape)}, {tuple(live.shape)}, {tuple(live_rows.shape)}")
+    if (running_mean is None) != (running_var is None) or (not training and running_mean is None):
+        raise ValueError("masked_batch_norm: running_mean and running_var come together, and eval mode needs them")
+    if training and num_batches_tracked is not None:
+        num_batches_tracked.add_(1)
+    use = y.is_cuda if kernels is None else bool(kernels)
+    if not use:
+        return masked_batch_norm_tensor(y, live, live_rows, weight, bias, running_mean, running_var, training, momentum, eps)
+    if live.dtype != torch.float32 or live_rows.dtype != torch.float32:
+        raise ValueError("masked_batch_norm: live and live_rows are fp32 tensors")
+    return _MaskedBatchNorm.apply(y, live.contiguous(), live_rows, weight, bias, running_mean, running_var, bool(training), float(momentum), float(eps))
+
+
 def seq_attention_supported(n: int, head_dim: int) -> bool:
     """The range the compiled kernels cover (anything else: ``wsi_seq_attn_*`` answer WSI_ENOSYS and the caller uses tensor operations)."""
     return 1 <= int(n) <= SEQ_ATTN_MAX_N and int(head_dim) in SEQ_ATTN_HEAD_DIMS
