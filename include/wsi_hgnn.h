@@ -984,6 +984,56 @@ int wsi_metrics_finalize(const int32_t* state, const float* probs, const int64_t
                          int64_t* pair_partials, double* result, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Epoch metrics of the multi-label MIL baselines kept on the device (wsi_hgnn_amd/mil/metrics.py::BagEpochMetrics): what the
+ * reference's test() computes after every epoch (baselines/ReMix_DSMIL_ABMIL/train_tcga_k-fold.py:98-180, train_remix_k-fold.py:160-232) -
+ * sigmoid scores, the ROC-optimal threshold per class (multi_label_roc / optimal_thresh), the hard predictions under it and their counts -
+ * without a read-back per bag.  Entry points added to ABI 26.  No allocation, no synchronisation, nothing a hipGraph cannot record, no float
+ * atomics; every count is an integer and every float sum has one order: identical calls give identical bits.
+ *
+ * The accumulator (caller-owned, `state` zeroed by the caller to reset it):
+ *   state        int32 [WSI_BAG_METRICS_STATE_HEAD], 8-byte aligned: [0] cursor n (rows stored), [1] flag bits (WSI_BAG_METRICS_*), [2..3] the
+ *                fp64 sum of the stored rows' losses
+ *   scores       fp32 [capacity, C]: sigmoid(bag_pred)      row_targets  fp32 [capacity, C]
+ * Limits: 1 <= C <= WSI_BAG_METRICS_MAX_CLASSES, 0 <= capacity <= WSI_BAG_METRICS_MAX_ROWS (one workgroup sorts a class's rows in LDS),
+ * S * C <= 65536.
+ *
+ * wsi_bag_metrics_update: ONE launch, one workgroup.  bag_pred [S, C] fp32 logits, max_pred [S, C] fp32 logits or NULL (ABMIL), targets
+ * [S, C] fp32, weights [S] fp32.  For every segment s in order: weights[s] <= 0 (or NaN) skips it before anything else of it is read (the
+ * padding of a mil.BagSlot may carry anything); a non-finite logit (of either prediction) skips it and sets WSI_BAG_METRICS_NONFINITE; a target
+ * other than 0 or 1 skips it and sets WSI_BAG_METRICS_BAD_TARGET; a row that would land at or past `capacity` is dropped and sets
+ * WSI_BAG_METRICS_OVERFLOW (nothing is written past the capacity).  A counted row writes, at the cursor, 1 / (1 + expf(-x)) of its bag_pred
+ * row and its target row, advances the cursor and adds its loss to the fp64 sum (a fixed tree per 256 segments, those in order): the mean over
+ * the C classes of max(x, 0) - x t + log1p(exp(-|x|)) in fp64 - BCEWithLogits - of bag_pred, or 0.5 x that + 0.5 x that of max_pred.
+ *
+ * wsi_bag_metrics_finalize: two launches over the n stored rows (n read from state[0] on the device).
+ *   result       int64 [WSI_BAG_METRICS_RESULT_HEAD + 8 * C + K * K], K = C > 1 ? C : 2; the fp64 fields are stored as their bits:
+ *                [0] n  [1] flag bits (those of state, and WSI_BAG_METRICS_ONE_LABEL)  [2] fp64 loss sum  [3] rows whose hard prediction row
+ *                equals their target row
+ *                per class c at HEAD + 8 c: [0] fp64 threshold  [1] tp  [2] fp at it  [3] P  [4] N  [5] gt  [6] eq  [7] fp64 AUC
+ *                then conf[true * K + predicted] of the decoded labels
+ *   (a) one workgroup per class c sorts (score bits, label bit) descending in LDS - scores lie in [0, 1], so their bit patterns order them as
+ *   integers - and takes one ROC point per distinct score, at the last row of its tie group: tps = positives so far, fps = rows so far - tps.
+ *   With more than two points it keeps the first, the last and every interior point where the second difference of fps or of tps over its two
+ *   neighbours is non-zero (sklearn's drop_intermediate), prepends the point (0, 0) with the threshold +inf, and takes the FIRST minimum of
+ *   fps / N - tps / P (fp64, this form; N, P = the last fps, tps) in that order: the threshold is that point's score widened to fp64, tp / fp
+ *   its counts.  gt / eq = the pairs (positive i, negative j) with s_i > s_j / s_i == s_j; AUC = (2 gt + eq) / (2 P N), one fp64 division of
+ *   integers.  A class with P = 0 or N = 0 (n = 0 included) has threshold and AUC NaN, tp = fp = gt = eq = 0 and sets WSI_BAG_METRICS_ONE_LABEL.
+ *   (b) one workgroup walks the rows: prediction[c] = score[c] >= threshold[c] (in fp64); counts the rows equal to their target row and the
+ *   confusion matrix of the decoded labels - C > 1: the first c with a 1, 0 for an all-zero row (argmax); C = 1: the value itself. */
+#define WSI_BAG_METRICS_STATE_HEAD   4
+#define WSI_BAG_METRICS_RESULT_HEAD  4
+#define WSI_BAG_METRICS_MAX_ROWS     4096
+#define WSI_BAG_METRICS_MAX_CLASSES  32
+#define WSI_BAG_METRICS_BAD_TARGET   1
+#define WSI_BAG_METRICS_NONFINITE    2
+#define WSI_BAG_METRICS_OVERFLOW     4
+#define WSI_BAG_METRICS_ONE_LABEL    8
+int wsi_bag_metrics_update(const float* bag_pred, const float* max_pred, const float* targets, const float* weights, int32_t S, int32_t C,
+                           int32_t* state, float* scores, float* row_targets, int32_t capacity, void* stream);
+int wsi_bag_metrics_finalize(const int32_t* state, const float* scores, const float* row_targets, int32_t C, int32_t capacity,
+                             int64_t* result, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * GTNMIL (wsi_hgnn_amd/gtn, baselines/GTNMIL/models/GraphTransformer.py): the mincut assignment over a sparse adjacency and the attention of
  * its 101-token transformer.  Entry points added to ABI 26.  No atomics, no allocation, no synchronisation: identical calls give identical bits.
  *

@@ -5,7 +5,9 @@ A slide's patch features are a bag of rows with no edges; a batch is the bags la
 objective and the loop body of ``train_tcga_k-fold.py``; ``remix`` is how the reference trains them (``reduce.py``, ``train_remix_k-fold.py``):
 k-means bag reduction and prototype mixing on the device.  ``slots`` holds the reference's ``dropout_patches`` drawn on the device
 (``dropout_patches``, ``patch_counts``), batches of bags in padded slots of fixed shape (``BagSlot``) and a captured training step replayed over
-them (``CapturedBagStep``): the one-bag-per-step regime the reference trains in.  Not built: the k-fold scripts, ``multi_label_roc``.
+them (``CapturedBagStep``): the one-bag-per-step regime the reference trains in.  ``metrics`` is the reference's ``test()``: the epoch's sigmoid
+scores, ROC-optimal thresholds (``multi_label_roc``) and result-table scores kept on the device (``BagEpochMetrics``), eager (``evaluate``) or as
+one captured forward per slot (``CapturedBagEval``).  Not built: the k-fold scripts.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ from . import abmil, dsmil
 from .bags import bag_plan, rows_and_plan
 
 __all__ = ["abmil", "dsmil", "remix", "bag_plan", "bag_targets", "bag_loss", "train_one_step", "patch_counts", "dropout_patches",
-           "dropout_patches_tensor", "BagSlot", "CapturedBagStep", "slot_step"]
+           "dropout_patches_tensor", "BagSlot", "CapturedBagStep", "slot_step", "BagEpochMetrics", "CapturedBagEval", "evaluate"]
 
 
 def bag_targets(labels, num_classes: int, device=None) -> torch.Tensor:
@@ -80,3 +82,4 @@ def train_one_step(milnet, optimizer, x, bags, labels) -> torch.Tensor:
 
 from . import remix  # noqa: E402  (its train_one_step calls the one above)
 from .slots import BagSlot, CapturedBagStep, dropout_patches, dropout_patches_tensor, patch_counts, slot_step  # noqa: E402
+from .metrics import BagEpochMetrics, CapturedBagEval, evaluate  # noqa: E402

@@ -10,7 +10,8 @@ Every operation has a tensor formulation that runs on any device (``kmeans_step_
 
 Two rules differ from faiss, whose generator cannot be replayed: the initial centroids are the K normalised rows that come first in the
 stable order of ``ops.augment_hash(n, ops.augment_subseed(seed, 0, bag))``, and an empty cluster is split off the cluster with the largest
-current count (lowest index on a tie) instead of a drawn one.  Not built: PCA, PIC, the k-fold scripts, ``multi_label_roc``."""
+current count (lowest index on a tie) instead of a drawn one.  Not built: PCA, PIC, the k-fold scripts
+(evaluation and ``multi_label_roc``: ``mil.metrics``)."""
 from __future__ import annotations
 
 import os
