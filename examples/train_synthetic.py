@@ -3,7 +3,7 @@
 (trainer/train_gnn.py:19-120), on synthetic WSI-shaped graphs:
 
   graph files (io.save_graph / load_graph)  ->  GraphBatchLoader (replaces GraphDataLoader + g.to(device))  ->
-  HEATNet4 + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate
+  HEATNet4 (or --model HGT) + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate
   (--captured-eval: trainer.CapturedSlotEval, the epoch's metrics kept on the device).
 
 Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation;
@@ -30,6 +30,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--dropout", type=float, default=0.2)
+    ap.add_argument("--model", choices=("HEATNet4", "HGT"), default="HEATNet4",
+                    help="HGT: the heterogeneous baseline (its layers' own dropout 0.2; --dropout is HEATNet4's).  With --captured-slots / "
+                         "--captured-eval its slots carry the per-relation-source plan, re-derived on the device behind every fill (DESIGN 3.27)")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--augment", action="store_true",
                     help="train on augmented graphs as the reference does (data.py:16-23: DropNode, DropEdge, NodeShuffle, FeatMask at p = 0.5)")
@@ -80,7 +83,12 @@ def main(argv=None):
     # 2. model / optimizer / loss exactly as parser.py builds them (Adam lr 1e-5 wd 5e-3; CrossEntropyLoss)
     nd = {"0": 0, "1": 1, "2": 2}
     torch.manual_seed(611)
-    gnn = models.HEATNet4(args.in_dim, args.hidden, 2, 2, 4, nd, args.dropout, "mean").to(dev)
+    hgt = args.model == "HGT"
+    if hgt:
+        edge_dict = {r: i for i, r in enumerate(graphs[0].canonical_etypes)}
+        gnn = models.HGT(nd, edge_dict, args.in_dim, args.hidden, 2, 2, 4, use_norm=True, graph_pooling_type="mean").to(dev)
+    else:
+        gnn = models.HEATNet4(args.in_dim, args.hidden, 2, 2, 4, nd, args.dropout, "mean").to(dev)
     if args.optimizer is None:
         opt = torch.optim.Adam(gnn.parameters(), lr=1e-5, weight_decay=5e-3)
     else:
@@ -94,7 +102,7 @@ def main(argv=None):
         if world > 1:
             raise SystemExit("--captured-eval: single process")
         from wsi_hgnn_amd.metrics import EpochMetrics
-        slot_eval = trainer.CapturedSlotEval(gnn, [data.BatchSlot(eval_loader)])
+        slot_eval = trainer.CapturedSlotEval(gnn, [data.BatchSlot(eval_loader, per_relation_src=hgt)])
         if args.captured_slots:
             train_metrics = EpochMetrics(2, len(graphs), dev)
     if args.captured_slots:
@@ -111,7 +119,7 @@ def main(argv=None):
             part = its[:max(args.batch, (len(its) * (k + 1) + K - 1) // K)]
             caps.append(([top([it.num_nodes[t] for it in part]) + 1 for t in range(len(its[0].num_nodes))], [top([it.pieces.ecount[t] for it in part]) for t in range(len(its[0].num_nodes))], args.batch))
         gnn.train()
-        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c) for c in caps], metrics=train_metrics)
+        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c, per_relation_src=hgt) for c in caps], metrics=train_metrics)
 
     # 3. epochs
     for epoch in range(args.epochs):

@@ -1223,6 +1223,30 @@ int wsi_masked_bn_bwd(const float* gy, int64_t ldg, const float* x, int64_t ldx,
                       const float* live_rows, const float* gamma, const float* stats, int32_t training, float* partial,
                       float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream);
 
+/* The per-relation-source plan derived from a base plan (an addition to ABI 26; graph.plan_by_relation): the plan HGT's
+ * attention runs on, whose source rows are numbered per (relation, source node): row(r, u) = rel_lo[r] + (u - type_off[source type of r]).
+ * Inputs, all int32 and all of the base plan: src [E] (global source of every CSR edge), colptr [N + 1] / csc_eid [E] / csc_dst [E] (CSC by
+ * global source), edge_seg [E] (the softmax segment of every CSR edge, < num_segs), and `header`, header_words = 5 T + 5 NR + 8 words on
+ * the device (T = num_types, NR = num_rels; the host knows them and passes them, the table is never read back):
+ *   [T, NR, NS, N]  type_off[T+1]  seg_off[T+1]  R[T]  slot_ptr[T+1]  slot_rel[NR]  rel_lo[NR]  rel_src[NR]  rel_k[NR]  srel_ptr[T+1]  srel[NR]
+ * R[t] = relations into node type t, slot_rel[slot_ptr[t] + j] = the relation of slot j of type t (segment = seg_off[t] + local node * R[t]
+ * + j), rel_lo[r] = first row of relation r, rel_src[r] = its source type, srel[srel_ptr[s] .. srel_ptr[s+1]) = the relations leaving type s,
+ * rel_k[r] = r's position in that list.  max_src_rels = the longest such list; above WSI_PLAN_REL_MAX_RELS the call returns WSI_EINVAL.
+ * Written (int32, caller-owned): src_rel [E]; colptr_rel [NS + 1], NS = num_src_rows; csc_eid_rel [E]; csc_dst_rel [E] - a row's entries in
+ * the order the source's base CSC lists them (a stable partition by relation), which is what a stable sort of the CSR edges by row gives.
+ * scratch: wsi_plan_by_relation_scratch_words(NS) int32 words (entry counts and scan partials; smaller: WSI_ENOMEM).
+ * Five launches on `stream`, a wave per source node (a source of any out-degree is a strided loop of 64 lanes): no atomics, no floats, no
+ * allocation, no synchronisation, no read-back; identical calls give identical bits.  num_edges == 0 (the arrays may then be NULL) writes
+ * colptr_rel = 0 and nothing else. */
+#define WSI_PLAN_REL_MAX_RELS 32
+#define WSI_PLAN_REL_TILE     1024   /* counts per workgroup of the prefix sum */
+int64_t wsi_plan_by_relation_scratch_words(int32_t num_src_rows);
+int wsi_plan_by_relation(const int32_t* src, const int32_t* colptr, const int32_t* csc_eid, const int32_t* csc_dst,
+                         const int32_t* edge_seg, int32_t num_nodes, int32_t num_edges, int32_t num_segs,
+                         const int32_t* header, int32_t header_words, int32_t num_types, int32_t num_rels, int32_t num_src_rows,
+                         int32_t max_src_rels, int32_t* src_rel, int32_t* colptr_rel, int32_t* csc_eid_rel, int32_t* csc_dst_rel,
+                         int32_t* scratch, int64_t scratch_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

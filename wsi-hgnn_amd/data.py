@@ -389,9 +389,15 @@ class BatchSlot:
     fills it with ``[transform(slide_b, draws[b]).., empty graphs.., filler]`` - on the GPU the draw is taken on the device and the tables are
     written from device-side counts (``graph.slot_fill_augmented``: no read-back), on the CPU through the tensor formulation.  Capacities are
     those of the unaugmented batch (augmentation only removes), ``fits`` uses the stored counts plus one rule (see ``fits``), the host mirrors of
-    the counts fail loudly on a GPU slot and ``counts()`` is the explicit read-back."""
+    the counts fail loudly on a GPU slot and ``counts()`` is the explicit read-back.
 
-    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0):
+    ``per_relation_src=True``: the slot also owns HGT's plan - ``src``, ``colptr``, ``csc_eid``, ``csc_dst`` and a source order over
+    one row per (relation, source node), shapes again functions of the capacities - installed as ``slot.graph.plan(per_relation_src=True)`` and
+    re-derived on the device from the tables every ``load`` / ``load_augmented`` has just written (``graph.derive_rel_tables``: one C call behind
+    the fill, no host arithmetic).  ``rel_sorted``: order those rows by out-degree, as ``graph.finish_plan`` does, instead of leaving them in
+    row order - measured 2 % slower per replayed step (tools/hgt_slot_bench.py), so off.  The default allocates nothing and changes nothing."""
+
+    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0, per_relation_src: bool = False):
         if not loader.resident:
             raise RuntimeError("BatchSlot needs a device-resident data set (GraphBatchLoader(..., resident=True)): the fill copies the slides' features "
                                "device to device; a pinned-host loader stays on its own double-buffered path")
@@ -448,6 +454,21 @@ class BatchSlot:
             self.readout_plan = None
         self.graph, self.labels = G, self.bufs["labels"]
         self.num_real, self.batch, self.idxs, self.draws = 0, None, None, None
+        # HGT's plan (source rows per (relation, source node)): four tables and a source order of the slot's own, derived on the
+        # device from the tables every fill has just written; installed as the slot graph's cached per-relation plan
+        self.per_relation_src, self.rel, self.rel_sorted = bool(per_relation_src), None, False
+        if self.per_relation_src:
+            hd.relation_table()
+            if hd.max_src_rels > _graph_mod.PLAN_REL_MAX_RELS:
+                raise ValueError(f"BatchSlot(per_relation_src=True): {hd.max_src_rels} relations leave one node type, the derivation supports "
+                                 f"{_graph_mod.PLAN_REL_MAX_RELS}")
+            self.rel = _graph_mod.plan_rel_buffers(hd, lay.E, self.device)
+            G.__dict__["_plan_rel"] = _graph_mod.rel_plan_over(hd, plan, self.rel)
+
+    def _derive(self) -> None:
+        """The per-relation tables of the batch just filled in, on the current stream behind the fill (one C call and the source order)."""
+        if self.rel is not None:
+            _graph_mod.derive_rel_tables(self.layout.hd, self.graph._plan, self.rel, sort_sources=self.rel_sorted)
 
     def _counts(self, idxs):
         its = [self.loader.items[i] for i in idxs]
@@ -516,6 +537,7 @@ class BatchSlot:
             from . import ops
             ops.refresh_constant_cols(self.bufs["feat"])      # scaled GEMM modes: the features' cached column statistics describe the previous batch
         self.num_real, self.batch, self.idxs = sb.B, sb, idxs
+        self._derive()
         return self
 
     def load_augmented(self, idxs: Sequence[int], draws: Sequence[int]) -> "BatchSlot":
@@ -574,6 +596,7 @@ class BatchSlot:
         for r in rels:
             G._eframes[r].clear()
         self.num_real, self.idxs, self.draws = len(idxs), idxs, draws
+        self._derive()
         return self
 
     def counts(self):

@@ -412,11 +412,24 @@ class HeteroGraph:
         if per_relation_src:
             cache = self.__dict__.setdefault("_plan_rel", None)
             if cache is None:
-                self.__dict__["_plan_rel"] = cache = _build_plan(self, per_relation_src=True)
+                self.__dict__["_plan_rel"] = cache = self._derived_rel_plan() or _build_plan(self, per_relation_src=True)
             return cache
         if self._plan is None:
             self._plan = _build_plan(self)
         return self._plan
+
+    def _derived_rel_plan(self) -> Optional[GraphPlan]:
+        """The per-relation-source plan of a GPU graph that was built from an assembled plan and holds no COO (loader batches, slot graphs),
+        derived on the device from that plan (``plan_by_relation``) instead of rebuilding and sorting the COO; None where that does not apply
+        (graphs made from COO, CPU graphs, more relations per source type than the kernel counts, per-relation rows that coincide with the
+        nodes - ``finish_plan`` orders those sources by another rule)."""
+        if not DERIVE_REL_PLAN or self._edges_store is not None or self._plan is None or self._plan.device.type != "cuda":
+            return None
+        hd = PlanHeader(self.ntypes, self.canonical_etypes, [self.num_nodes(t) for t in self.ntypes])
+        hd.relation_table()
+        if hd.max_src_rels > PLAN_REL_MAX_RELS or hd.rel_rows_total == hd.N or not hd.ntypes:
+            return None
+        return plan_by_relation(hd, self._plan)
 
 
 class _PinnedArena:
@@ -564,6 +577,23 @@ class PlanHeader:
             off += ns
         self.rel_rows_total = off
 
+    def relation_table(self) -> List[int]:
+        """The int32 header table of ``wsi_plan_by_relation`` (include/wsi_hgnn.h): what maps an edge's softmax segment to its relation and a
+        (relation, source node) to its row of the per-relation tables.  Also sets ``max_src_rels``: the most relations leaving one node type."""
+        T, NR = len(self.ntypes), len(self.rels)
+        slots: List[List[int]] = [[] for _ in range(T)]
+        srel: List[List[int]] = [[] for _ in range(T)]
+        rel_src, rel_k = [], []
+        for ri, (s, e, d) in enumerate(self.rels):
+            slots[self.tindex[d]].append(ri)
+            rel_src.append(self.tindex[s])
+            rel_k.append(len(srel[self.tindex[s]]))
+            srel[self.tindex[s]].append(ri)
+        ptr = lambda lists: [sum(len(x) for x in lists[:i]) for i in range(T + 1)]
+        self.max_src_rels = max((len(x) for x in srel), default=0)
+        return ([T, NR, self.rel_rows_total, self.N] + self.type_off + self.seg_off + self.R + ptr(slots) + [r for x in slots for r in x]
+                + [lo for lo, _ in self.rel_rows] + rel_src + rel_k + ptr(srel) + [r for x in srel for r in x])
+
 
 # In-degree above which a node goes to the cooperative hub kernels (passed to the kernels with every call: ops._attn_flags).
 # Attention ms per step by threshold 32 / 64 / 96 / 128 / 192: synthetic hub batch 2.50 / 2.44 / 2.44 / 2.44 / 2.49; kNN study graphs
@@ -578,6 +608,9 @@ HEAVY_DEGREE_LOCALITY = 128
 # variable): HUB_SPLIT = False never routes a node to the hub kernels; LOCALITY = False ignores the slides' '_pos' (heaviest-first orders).
 HUB_SPLIT = True
 LOCALITY = True
+# False: ``HeteroGraph.plan(per_relation_src=True)`` always rebuilds from the COO (``_build_plan``), never derives from the assembled plan
+# (``plan_by_relation``): the A/B switch of tools/hgt_slot_bench.py.
+DERIVE_REL_PLAN = True
 
 
 def set_plan_options(heavy_degree: Optional[int] = None, heavy_degree_locality: Optional[int] = None, hub_split: Optional[bool] = None,
@@ -1470,6 +1503,139 @@ def slot_plan(lay: SlotLayout, bufs: Dict[str, torch.Tensor], locality: bool = F
     p.heavy_degree = HEAVY_DEGREE_LOCALITY if locality else HEAVY_DEGREE
     p.__dict__["_edge_seg"] = bufs["edge_seg"]       # (ops._edge_segments: derived from rowptr once per plan - here refreshed by every fill)
     return p
+
+
+# ------------------------------------------------------------------ the per-relation-source plan, derived from the base plan
+PLAN_REL_MAX_RELS = 32      # WSI_PLAN_REL_MAX_RELS: relations leaving one node type the kernel keeps running counts for
+
+
+def _plan_edge_seg(plan: GraphPlan) -> torch.Tensor:
+    """int32 [E]: the softmax segment of every CSR edge (``ops._edge_segments``: expanded from ``rowptr`` once per plan; a slot's buffer)."""
+    es = plan.__dict__.get("_edge_seg")
+    if es is None:
+        counts = (plan.rowptr[1:] - plan.rowptr[:-1]).to(torch.int64)
+        es = torch.repeat_interleave(torch.arange(plan.num_segs, dtype=torch.int32, device=counts.device), counts, output_size=plan.num_edges)
+        plan.__dict__["_edge_seg"] = es
+    return es
+
+
+def plan_rel_buffers(hd: PlanHeader, num_edges: int, device) -> Dict[str, torch.Tensor]:
+    """Caller-owned tables of ``plan_by_relation(out=...)`` - shapes are functions of the header's node counts and the edge count alone - with
+    the header table uploaded (once) and the kernel's scratch."""
+    dev = torch.device(device)
+    mk = lambda n: torch.empty(max(int(n), 1), dtype=torch.int32, device=dev)[:int(n)]
+    NS, E = hd.rel_rows_total, int(num_edges)
+    words = hd.relation_table()
+    out = {"src": mk(E), "colptr": mk(NS + 1), "csc_eid": mk(E), "csc_dst": mk(E), "order_src": mk(NS),
+           "header": host_to_device(words, torch.int32, dev), "scratch": mk(NS + (NS + 1023) // 1024 + 1)}
+    return out
+
+
+def _rel_plan_frame(hd: PlanHeader, base: GraphPlan) -> GraphPlan:
+    """The derived plan with everything it SHARES with the base plan: the destination side, the readout, the flags."""
+    if base.num_src_rows != base.num_nodes or base.num_nodes != hd.N or base.num_segs != hd.S:
+        raise ValueError("plan_by_relation: the base plan must be the ordinary plan (source rows = nodes) of the header's node counts")
+    p = _new_plan(hd, base.device)
+    p.num_edges, p.num_src_rows, p.batch_size = base.num_edges, hd.rel_rows_total, base.batch_size
+    for k in ("rowptr", "node_seg", "inv_rd", "order_dst", "readout_ptr", "perm"):
+        setattr(p, k, getattr(base, k))
+    p.num_heavy, p.heavy_degree, p.locality = base.num_heavy, base.heavy_degree, base.locality
+    p.__dict__["_edge_seg"] = _plan_edge_seg(base)
+    return p
+
+
+def plan_by_relation_torch(hd: PlanHeader, base: GraphPlan, out: Optional[Dict[str, torch.Tensor]] = None) -> GraphPlan:
+    """``plan_by_relation`` as tensor operations: the CPU path and the kernel's oracle.  The relation of an edge follows from its softmax
+    segment, its row from the relation and the source; the CSC by row is a STABLE sort of the base CSC entries by their row - a source's base
+    entries are in CSR order, so this is the order a stable sort of the CSR edges by row gives (``finish_plan``)."""
+    p = _rel_plan_frame(hd, base)
+    dev, E, NS, T = base.device, base.num_edges, hd.rel_rows_total, len(hd.ntypes)
+    i64 = lambda xs: torch.tensor(xs, dtype=torch.int64, device=dev)
+    if E:
+        seg = _plan_edge_seg(base).long()
+        seg_off, R = i64(hd.seg_off), i64(hd.R)
+        t = torch.bucketize(seg, seg_off[1:], right=True).clamp_(max=T - 1)          # destination type (types without segments are skipped)
+        slot_ptr = i64([sum(hd.R[:i]) for i in range(T)])
+        slot_rel = [0] * len(hd.rels)
+        for ri, (s, e, d) in enumerate(hd.rels):
+            slot_rel[sum(hd.R[:hd.tindex[d]]) + hd.slot_of_rel[ri]] = ri
+        rel = i64(slot_rel)[slot_ptr[t] + (seg - seg_off[t]) % R[t].clamp(min=1)]
+        rel_lo = i64([lo for lo, _ in hd.rel_rows])
+        rel_first = i64([hd.type_off[hd.tindex[s]] for s, _, _ in hd.rels])
+        src = rel_lo[rel] + base.src.long() - rel_first[rel]
+        row = src[base.csc_eid.long()]                                               # per base CSC entry
+        order = torch.sort(row, stable=True).indices
+        csc_eid, csc_dst = base.csc_eid[order], base.csc_dst[order]
+        colptr = torch.zeros(NS + 1, dtype=torch.int64, device=dev)
+        colptr[1:] = torch.cumsum(_count(row, NS), 0)
+    else:
+        src = csc_eid = csc_dst = torch.empty(0, dtype=torch.int32, device=dev)
+        colptr = torch.zeros(NS + 1, dtype=torch.int64, device=dev)
+    outdeg = colptr[1:] - colptr[:-1]
+    tabs = {"src": src, "colptr": colptr, "csc_eid": csc_eid, "csc_dst": csc_dst,
+            "order_src": torch.sort(outdeg, descending=True, stable=True).indices}
+    for k, v in tabs.items():
+        v = v.to(torch.int32).contiguous()
+        if out is not None:
+            out[k].copy_(v)
+            v = out[k]
+        setattr(p, k, v)
+    return p
+
+
+def plan_by_relation(hd: PlanHeader, base: GraphPlan, out: Optional[Dict[str, torch.Tensor]] = None) -> GraphPlan:
+    """The per-relation-source plan (``HeteroGraph.plan(per_relation_src=True)``: HGT's) DERIVED from the ordinary plan ``base`` of the same
+    graph: it shares the base plan's destination side (``rowptr``, ``node_seg``, ``inv_rd``, ``order_dst``, the hub prefix, the readout
+    pointers, the edges' softmax segments) and owns ``src``, ``colptr``, ``csc_eid``, ``csc_dst``, ``order_src`` over
+    ``hd.rel_rows_total`` source rows.  On the GPU one C call (``wsi_plan_by_relation``: five launches on the current stream, no sort of the
+    edges, no read-back) and a stable descending sort of the rows' out-degrees for ``order_src`` (``finish_plan``'s rule for per-relation
+    rows); every table equals ``_build_plan(g, per_relation_src=True)``'s.  ``out``: ``plan_rel_buffers`` the tables are written INTO (a
+    slot's static buffers; the returned plan's tables are those tensors).  CPU plans: ``plan_by_relation_torch``."""
+    if base.device.type != "cuda":
+        return plan_by_relation_torch(hd, base, out)
+    if out is None:
+        out = plan_rel_buffers(hd, base.num_edges, base.device)
+    p = rel_plan_over(hd, base, out)
+    derive_rel_tables(hd, base, out)
+    return p
+
+
+def rel_plan_over(hd: PlanHeader, base: GraphPlan, out: Dict[str, torch.Tensor]) -> GraphPlan:
+    """The derived plan OBJECT whose own tables are ``out``'s (``plan_rel_buffers``), nothing launched: ``derive_rel_tables`` fills them -
+    once for an ordinary plan, after every fill for a slot."""
+    p = _rel_plan_frame(hd, base)
+    if out["src"].numel() != base.num_edges or out["colptr"].numel() != hd.rel_rows_total + 1:
+        raise ValueError("plan_by_relation: out= was made for other node or edge counts")
+    for k in ("src", "colptr", "csc_eid", "csc_dst", "order_src"):
+        setattr(p, k, out[k])
+    p._rel_tables = out             # (header table and scratch are stream-ordered inputs of the launches: held by the plan)
+    return p
+
+
+def derive_rel_tables(hd: PlanHeader, base: GraphPlan, out: Dict[str, torch.Tensor], sort_sources: bool = True) -> None:
+    """Fill ``out`` from the base plan's CURRENT tables on the current stream: ``wsi_plan_by_relation`` (five launches), then ``order_src`` -
+    the rows by out-degree, heaviest first, ties in row order (a stable sort on the device of ``colptr``'s differences: ``finish_plan``'s
+    rule), or with ``sort_sources=False`` the rows in their own order.  No host arithmetic, no read-back."""
+    if base.device.type != "cuda":
+        plan_by_relation_torch(hd, base, out)
+        if not sort_sources:
+            out["order_src"].copy_(torch.arange(hd.rel_rows_total, dtype=torch.int32))
+        return
+    from . import _native as N
+    if getattr(hd, "max_src_rels", None) is None:
+        hd.relation_table()
+    if hd.max_src_rels > PLAN_REL_MAX_RELS:
+        raise RuntimeError(f"plan_by_relation: {hd.max_src_rels} relations leave one node type, the kernel supports {PLAN_REL_MAX_RELS}")
+    N.check(N.load().wsi_plan_by_relation(N.ptr(base.src), N.ptr(base.colptr), N.ptr(base.csc_eid), N.ptr(base.csc_dst),
+                                          N.ptr(_plan_edge_seg(base)), hd.N, base.num_edges, hd.S, N.ptr(out["header"]), out["header"].numel(),
+                                          len(hd.ntypes), len(hd.rels), hd.rel_rows_total, hd.max_src_rels, N.ptr(out["src"]),
+                                          N.ptr(out["colptr"]), N.ptr(out["csc_eid"]), N.ptr(out["csc_dst"]), N.ptr(out["scratch"]),
+                                          out["scratch"].numel(), N.stream()), "wsi_plan_by_relation")
+    colptr, NS = out["colptr"], hd.rel_rows_total
+    if NS and sort_sources:
+        out["order_src"].copy_(torch.sort(colptr[1:] - colptr[:-1], descending=True, stable=True).indices)
+    elif NS:
+        torch.arange(NS, dtype=torch.int32, device=colptr.device, out=out["order_src"])
 
 
 def _build_plan(g: HeteroGraph, per_relation_src: bool = False) -> GraphPlan:

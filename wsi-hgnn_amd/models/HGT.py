@@ -151,6 +151,16 @@ class HGTLayer(nn.Module):
         nn.init.xavier_uniform_(self.relation_att)
         nn.init.xavier_uniform_(self.relation_msg)
 
+    def _dropout_mask(self, h: torch.Tensor) -> torch.Tensor:
+        """The train-mode keep mask over ``h``'s shape, scaled by 1 / (1 - p).  Under an active dropout seed base (``ops.dropout_seed_base``: a
+        captured step) the draw is counter-based - ``ops.CounterDropout`` of (p, a host seed, the DEVICE word), applied to a table of ones by
+        ``wsi_dropout_apply`` - so a replay draws new masks as the word advances; otherwise torch's generator draws it, as before."""
+        keep = 1.0 - self.drop.p
+        base = ops.current_dropout_seed_base(h.device)
+        if base is not None and keep > 0.0:
+            return ops.dropout_apply(torch.ones_like(h), ops.CounterDropout(self.drop.p, ops.next_dropout_seed(), base))
+        return torch.empty_like(h).bernoulli_(keep).mul_(1.0 / keep) if keep > 0.0 else torch.zeros_like(h)
+
     def forward_cat(self, hctx, gctx: HgtContext, h: torch.Tensor) -> torch.Tensor:
         D = self.out_dim
         if self.in_dim != self.out_dim:
@@ -193,8 +203,7 @@ class HGTLayer(nn.Module):
         ab = [self.a_linears[n].bias for n in gctx.a_nids]
         mask = None
         if self.training and self.drop.p > 0.0:                                                # :121 nn.Dropout: keep mask / (1 - p), applied in the
-            keep = 1.0 - self.drop.p                                                           # projection's epilogue (as the HEAT layer does)
-            mask = torch.empty_like(h).bernoulli_(keep).mul_(1.0 / keep) if keep > 0.0 else torch.zeros_like(h)
+            mask = self._dropout_mask(h)                                                       # projection's epilogue (as the HEAT layer does)
         z = ops.gated_linear(t, h, self.skip, gctx.a_rows, gctx.a_nids, gctx.a_rplan, gctx.a_seg, aw, ab, drop_mask=mask)   # :121-122
         if not self.use_norm:
             return z

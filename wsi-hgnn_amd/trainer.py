@@ -161,17 +161,25 @@ class CapturedStep:
 
 
 def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
-    """What a capture over batch slots needs of the model and the slots (``CapturedSlotStep``, ``CapturedSlotEval``): a HEAT trunk with a sum / mean /
-    max readout, slots on the GPU fed by one loader.  Returns (slots as a list, their loader, its device)."""
+    """What a capture over batch slots needs of the model and the slots (``CapturedSlotStep``, ``CapturedSlotEval``): a HEAT trunk, or HGT over
+    slots that carry the per-relation-source plan, with a sum / mean / max readout; slots on the GPU fed by one loader.  Returns (slots as a
+    list, their loader, its device)."""
     from .data import BatchSlot
     from .models.heat_net import HEATTrunk
     from .pooling import GlobalAttentionPooling
     slots = [slots] if isinstance(slots, BatchSlot) else list(slots)
     if not slots:
         raise ValueError(f"{who}: no slot")
-    if not isinstance(gnn, HEATTrunk):
-        raise RuntimeError(f"{who}: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4 only (HGT derives a per-relation-source plan "
-                           f"from the batch's COO on the host for every new batch, which a replay cannot redo); {verb} it eagerly")
+    from .models.HGT import HGT
+    if type(gnn) is HGT:
+        # HGT's attention runs on the per-relation-source plan, which a slot re-derives on the device behind every fill (DESIGN 3.27) - when it
+        # was built with the tables for it
+        if not all(getattr(s, "per_relation_src", False) for s in slots):
+            raise RuntimeError(f"{who}: HGT needs slots that carry the per-relation-source plan - build every slot with "
+                               f"BatchSlot(loader, capacity, per_relation_src=True) - or {verb} it eagerly")
+    elif not isinstance(gnn, HEATTrunk):
+        raise RuntimeError(f"{who}: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4, and HGT over slots built with "
+                           f"per_relation_src=True (HGT + ASAP and HeteroRGCN rebuild host-side structure per batch); {verb} it eagerly")
     if isinstance(gnn.pools[0], GlobalAttentionPooling):
         raise RuntimeError(f"{who}: the attention readout ('att') expands host-side node counts per batch; use a sum / mean / max readout "
                            f"or {verb} eagerly")
@@ -193,9 +201,9 @@ class CapturedSlotStep:
     ``step(idxs)`` takes the smallest slot (fewest node rows) that fits.  A batch no slot fits runs eagerly through the loader's ordinary
     assembly.  The captures share one memory pool.  As with ``CapturedStep`` the ``warmup`` steps before each capture ARE optimisation steps -
     here on ``warmup_batches[i]`` for slot i (default: the slot's first fitting batch of one slide) - the optimizer must be capturable, and
-    train-mode dropout must be the HEAT layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4 with a sum / mean /
-    max readout: HGT builds its per-relation-source plan from the batch's COO on the host, and the attention readout reads host-side node
-    counts - both are refused.
+    train-mode dropout must be the HEAT / HGT layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4, and HGT over
+    slots built with ``per_relation_src=True`` (the slot re-derives HGT's plan on the device behind every fill), with a sum / mean /
+    max readout: the attention readout reads host-side node counts, HGT + ASAP and HeteroRGCN rebuild host-side structure - those are refused.
 
     Slots over a loader with a slot-compatible ``transform=`` (``data.slot_augment_spec``) are AUGMENTED: every ``step`` fills its slot with a fresh
     draw taken on the device (no read-back) in front of the replay, a batch no slot fits goes through ``loader._augmented``, and either way the
@@ -217,8 +225,10 @@ class CapturedSlotStep:
         self.seed_base = None
         if gnn.training and any(isinstance(mod, torch.nn.Dropout) and mod.p > 0.0 for mod in gnn.modules()):
             from .models.heat_layer import HEATLayer
+            from .models.HGT import HGTLayer
             owners = [m_ for m_ in gnn.modules() if any(isinstance(c, torch.nn.Dropout) and c.p > 0.0 for c in m_.children())]
-            if not all(isinstance(m_, HEATLayer) and getattr(m_, "counter_dropout", False) for m_ in owners):
+            # (an HGTLayer draws counter-based whenever a seed base is active, which it is throughout this class's steps)
+            if not all(type(m_) is HGTLayer or (isinstance(m_, HEATLayer) and getattr(m_, "counter_dropout", False)) for m_ in owners):
                 raise RuntimeError("CapturedSlotStep: the model draws dropout masks outside the HEAT layers' counter-based draw (train mode, p > 0); their "
                                    "generator state is a host value a capture would freeze - every replay would drop the same entries.  Step such a "
                                    "model eagerly")
@@ -315,7 +325,7 @@ class CapturedSlotEval:
     ``evaluate`` calls changes the result as it must.  A training capture (``CapturedSlotStep``) lives beside this one on slots and a memory
     pool of its own.
 
-    Refused: what ``CapturedSlotStep`` refuses (HGT, the ``att`` readout, slots off the GPU or over several loaders), and slots over a loader
+    Refused: what ``CapturedSlotStep`` refuses (HGT on slots without the per-relation plan, the ``att`` readout, slots off the GPU or over several loaders), and slots over a loader
     with ``transform=`` - evaluation sees the stored slides (the reference augments ``type_ == "train"`` only, data.py:116-117).
     ``metrics=None`` builds an ``EpochMetrics`` for ``len(loader.items)`` rows."""
 
