@@ -3,7 +3,7 @@
 A GTNMIL step on a packed batch is bound by the host: some 45 small GEMM launches through ctypes, an ``ops.EdgeCSR`` (two sorts, two cumsums)
 per batch, per-slide row ranges baked into the grouped GEMMs.  ``GraphSlot`` holds a batch in static device tables of ONE shape - ``cells``
 cells of ``cell_rows`` rows, slide i at the head of cell i, every other row dead - so that ``CapturedGraphStep`` records the step once per slot
-(``torch.cuda.CUDAGraph``) and replays it over new slides: per step one descriptor upload, the two fill launches (``csrc/graph_slot.hip``), one
+(a hipGraph, ``capture.py``) and replays it over new slides: per step one descriptor upload, the two fill launches (``csrc/graph_slot.hip``), one
 replay.  ``SlideSet`` keeps the data set resident with every slide's LOCAL CSR / CSC tables built once; the block-diagonal adjacency of a
 batch is those tables one after the other, rebased by the fill.
 """
@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import _native as N
-from .. import ops
+from .. import capture, ops
 from .batch import GraphBatch
 
 _DESC = 16              # int64 words per slide descriptor (include/wsi_hgnn.h, wsi_graph_slot_fill)
@@ -226,25 +226,16 @@ def slot_step(model, optimizer, slot: GraphSlot, params=None):
     """One training step on the batch a slot holds - the body of ``gtn.train_one_step`` with the slot's device-side labels and masks, gradients
     from ``torch.autograd.grad``: nothing in it is a host value of the batch, so it can be recorded.  Returns (loss, softmax [cells, n_class]),
     detached."""
-    if params is None:
-        params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
     model.train()
-    optimizer.zero_grad(set_to_none=True)
-    _, _, loss, probs = model(slot, None)
-    grads = torch.autograd.grad(loss, params, allow_unused=True)
-    for p, g in zip(params, grads):
-        p.grad = g
-    optimizer.step()
-    return loss.detach(), probs.detach()
+    return capture.grad_step(optimizer, capture.trainable_params(optimizer) if params is None else params, lambda: model(slot, None)[2:])
 
 
 class CapturedGraphStep:
-    """One captured GTNMIL training step per ``GraphSlot``, replayed over new slides every step.  It follows ``mil.CapturedBagStep``: the
-    ``warmup`` eager steps on a side stream before each capture ARE optimisation steps (on ``warmup_batches[i] = (slides, idxs, labels)`` for
-    slot i; None: on what the caller has loaded into the slot), gradients come from ``torch.autograd.grad``, the captures share one memory
-    pool, the optimizer must be capturable and a ``torch.nn.Dropout`` with p > 0 in train mode is refused (its generator state is a host value
-    a capture would freeze).  Under a capture the projections keep their weight gradients on the capturing stream and the statistics stream is
-    not used (``ops`` checks the capture itself), as for the other captured steps; no queue setting is touched.
+    """One captured GTNMIL training step per ``GraphSlot``, replayed over new slides every step.  Protocol: ``capture.py``; EVERY slot takes
+    its ``warmup`` (1) optimisation steps (on ``warmup_batches[i] = (slides, idxs, labels)`` for slot i; None: on what the caller has loaded
+    into the slot) before the first capture, and a ``torch.nn.Dropout`` with p > 0 in train mode is refused.  Under a capture the
+    projections keep their weight gradients on the capturing stream and the statistics stream is not used (``ops`` checks the capture
+    itself), as for the other captured steps; no queue setting is touched.
 
     ``step(slides, idxs, labels)`` loads the smallest slot (fewest rows) that fits and replays; a batch no slot fits runs eagerly through
     ``gtn.train_one_step`` on ``slides.batch(idxs)`` and is counted in ``eager_steps``.  ``recapture()`` records the graphs again without
@@ -262,61 +253,33 @@ class CapturedGraphStep:
             raise RuntimeError("CapturedGraphStep: the slots must live on one GPU")
         if len({(s.feats, s.cells) for s in slots}) != 1:
             raise ValueError("CapturedGraphStep: the slots must agree on feats and cells")
-        for group in optimizer.param_groups:
-            if not group.get("capturable", False):
-                raise RuntimeError("CapturedGraphStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step "
-                                   "count has to live on the device, a host count would be frozen into the graph")
+        capture.require_capturable("CapturedGraphStep", optimizer)
         model.train()
-        if any(isinstance(mod, torch.nn.Dropout) and mod.p > 0.0 for mod in model.modules()):
-            raise RuntimeError("CapturedGraphStep: the model holds a torch.nn.Dropout with p > 0 in train mode; its generator state is a host value "
-                               "a capture would freeze - every replay would drop the same entries.  Step such a model eagerly")
+        capture.counter_dropout_only("CapturedGraphStep", model)
         self.model, self.optimizer = model, optimizer
-        order = sorted(range(len(slots)), key=lambda i: slots[i].num_rows)                     # smallest first: what step() tries in turn
-        self.slots = [slots[i] for i in order]
-        if warmup_batches is not None:
-            warmup_batches = [warmup_batches[i] for i in order]
-        optimizer.zero_grad(set_to_none=True)
-        self.params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
+        self.slots, warmup_batches = capture.smallest_first(slots, lambda s: s.num_rows, warmup_batches)
+        self.params = capture.trainable_params(optimizer)
         self.steps_taken, self.replays, self.eager_steps = 0, 0, 0
         for i, slot in enumerate(self.slots):
-            if warmup_batches is not None:
-                slot.load(*warmup_batches[i])
-            elif slot.num_real == 0:
-                raise ValueError(f"CapturedGraphStep: slot {i} holds no batch to warm up on - load one, or pass warmup_batches")
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):                      # (caches and allocator pools settle before the capture; these ARE steps)
-                for _ in range(max(1, warmup)):
-                    slot_step(self.model, self.optimizer, slot, self.params)
-                    self.steps_taken += 1
-            torch.cuda.current_stream(dev).wait_stream(side)
+            capture.load_warm_up_batch("CapturedGraphStep", i, slot, warmup_batches)
+            capture.warm_up(dev, warmup, lambda: slot_step(self.model, self.optimizer, slot, self.params))
+            self.steps_taken += max(1, warmup)
         self.graphs, self.outputs = [], []
         self.recapture()
 
     def recapture(self) -> None:
         """Record every slot's graph again (no step is taken): after a change of a host-side hyper-parameter such as ``lr``."""
-        dev = self.slots[0].device
         self.graphs, self.outputs = [], []
-        torch.cuda.synchronize(dev)
-        pool = None
+        torch.cuda.synchronize(self.slots[0].device)
         for slot in self.slots:
-            cg = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
-                    out = slot_step(self.model, self.optimizer, slot, self.params)
-            except Exception as exc:
-                raise RuntimeError("CapturedGraphStep: the step could not be captured into a hipGraph (is a tensor of an earlier eager step's "
-                                   "autograd graph - a previous loss or softmax - still alive in the caller?); run the step eagerly instead") from exc
-            pool = cg.pool()
+            cg, out = capture.record("CapturedGraphStep", lambda: slot_step(self.model, self.optimizer, slot, self.params),
+                                     self.graphs[-1].pool() if self.graphs else None, capture.step_failure("softmax"))
             self.graphs.append(cg)
             self.outputs.append(out)
 
     def slot_for(self, sizes: Sequence[int], entries: Sequence[int]):
         """Index of the smallest slot the batch fits, or None."""
-        for i, slot in enumerate(self.slots):
-            if slot.fits(sizes, entries):
-                return i
-        return None
+        return capture.first_fit(self.slots, sizes, entries)
 
     def step(self, slides: SlideSet, idxs: Sequence[int], labels):
         """One optimisation step on the slides ``idxs`` of ``slides`` with host labels ``labels``.  Returns ``(loss, softmax[:len(idxs)])`` as

@@ -22,6 +22,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 
+from .capture import eval_mode
 from .graph import HeteroGraph
 
 FORMAT = "wsi-hgnn-graph-v1"
@@ -296,14 +297,11 @@ def classification_metrics(outputs: torch.Tensor, targets: torch.Tensor, average
 def evaluate(gnn: torch.nn.Module, loader, average: str = "binary") -> Dict[str, float]:
     """evaluator/eval_homo_graph.py:61-95 (per-graph ``test_one_step`` loop) as batched inference over a
     ``GraphBatchLoader``: accuracy, precision, recall, F1, AUC and mean cross-entropy."""
-    was_training = gnn.training
-    gnn.eval()
     outs, ys = [], []
-    with torch.no_grad():
+    with eval_mode(gnn):
         for G, y in loader:
             outs.append(gnn(G))
             ys.append(y)
-    gnn.train(was_training)
     out = torch.cat(outs)
     y = torch.cat(ys)
     loss = torch.nn.functional.cross_entropy(out, y).item()

@@ -19,10 +19,9 @@ import numpy as np
 import torch
 
 from .. import _native as N
-from .. import ops
-from . import abmil, dsmil
+from .. import capture, ops
 from .bags import bag_plan
-from .slots import BagSlot
+from .slots import check_bag_slots
 
 HEAD = N.WSI_BAG_METRICS_RESULT_HEAD
 MAX_ROWS, MAX_CLASSES = N.WSI_BAG_METRICS_MAX_ROWS, N.WSI_BAG_METRICS_MAX_CLASSES
@@ -299,25 +298,20 @@ def evaluate(milnet, bags: Sequence[torch.Tensor], labels, metrics: Optional[Bag
     if len(labels) != len(bags) or not bags:
         raise ValueError(f"evaluate: {len(bags)} bags but {len(labels)} labels")
     dev = bags[0].device
-    was_training = milnet.training
-    milnet.eval()
-    try:
-        with torch.no_grad():
-            for lo in range(0, len(bags), max(1, int(batch_size))):
-                part = bags[lo:lo + batch_size]
-                sizes = [int(t.shape[0]) for t in part]
-                rows = torch.cat([t.to(torch.float32) for t in part])
-                plan = bag_plan(sizes, dev)
-                if metrics is None:                                # (the number of classes: from a forward of the first batch)
-                    probe = split_outputs(milnet(rows, plan))[0]
-                    metrics = BagEpochMetrics(probe.reshape(len(part), -1).shape[1], len(bags), dev)
-                if lo == 0:
-                    metrics.reset()
-                targets = bag_targets(labels[lo:lo + batch_size], metrics.num_classes, dev).contiguous()
-                weights = torch.tensor([1.0 if n > 0 else 0.0 for n in sizes], dtype=torch.float32, device=dev) if 0 in sizes else None
-                forward_update(milnet, rows, plan, targets, weights, metrics)
-    finally:
-        milnet.train(was_training)
+    with capture.eval_mode(milnet):
+        for lo in range(0, len(bags), max(1, int(batch_size))):
+            part = bags[lo:lo + batch_size]
+            sizes = [int(t.shape[0]) for t in part]
+            rows = torch.cat([t.to(torch.float32) for t in part])
+            plan = bag_plan(sizes, dev)
+            if metrics is None:                                    # (the number of classes: from a forward of the first batch)
+                probe = split_outputs(milnet(rows, plan))[0]
+                metrics = BagEpochMetrics(probe.reshape(len(part), -1).shape[1], len(bags), dev)
+            if lo == 0:
+                metrics.reset()
+            targets = bag_targets(labels[lo:lo + batch_size], metrics.num_classes, dev).contiguous()
+            weights = torch.tensor([1.0 if n > 0 else 0.0 for n in sizes], dtype=torch.float32, device=dev) if 0 in sizes else None
+            forward_update(milnet, rows, plan, targets, weights, metrics)
     return metrics.compute()
 
 
@@ -325,9 +319,8 @@ class CapturedBagEval:
     """The forward of an evaluation pass captured once per ``BagSlot`` and replayed over the evaluation set: what the reference does after every
     epoch of every fold, one bag at a time with one read-back per bag.  Each slot's graph records, in eval mode under ``no_grad``, the forward
     over the slot's tables ending in ``metrics.update(outputs, slot.targets, slot.weights)``; the filler, the unused and the empty bags of a
-    slot have weight 0 and are not counted.  It follows ``trainer.CapturedSlotEval`` and ``CapturedBagStep``: the captures share one memory
-    pool, ``run`` loads the smallest slot that fits and replays, a batch no slot fits runs the same forward and the same ``update`` eagerly on
-    the unpadded bags (``eager_batches``).
+    slot have weight 0 and are not counted.  Protocol: ``capture.py``, slot by slot (warm up, then capture, then the next slot); a batch no
+    slot fits runs the same forward and the same ``update`` eagerly on the unpadded bags (``eager_batches``).
 
     The recorded forward reads the LIVE parameters - ``ops.linear`` packs nothing ahead of time - so an optimizer step (a ``CapturedBagStep``
     on slots of its own beside this one) between two epochs changes the result as it must.  Refused: slots with ``dropout_patch > 0`` (the
@@ -335,14 +328,7 @@ class CapturedBagEval:
     mode makes it the identity.  ``metrics=None`` builds a ``BagEpochMetrics`` of the supported capacity."""
 
     def __init__(self, milnet: torch.nn.Module, slots, metrics: Optional[BagEpochMetrics] = None, warmup: int = 1, warmup_batches=None):
-        slots = [slots] if isinstance(slots, BagSlot) else list(slots)
-        if not slots:
-            raise ValueError("CapturedBagEval: no slot")
-        if not isinstance(milnet, (dsmil.MILNet, abmil.BClassifier)):
-            raise RuntimeError(f"CapturedBagEval: {type(milnet).__name__} is not supported - abmil.BClassifier / BClassifier_ or dsmil.MILNet")
-        dev = slots[0].device
-        if dev.type != "cuda" or any(s.device != dev for s in slots):
-            raise RuntimeError("CapturedBagEval: the slots must live on one GPU")
+        slots, dev = check_bag_slots("CapturedBagEval", milnet, slots)
         if len({(s.feats, s.num_classes) for s in slots}) != 1:
             raise ValueError("CapturedBagEval: the slots must agree on feats and num_classes")
         if any(s.dropout_patch > 0 for s in slots):
@@ -353,52 +339,24 @@ class CapturedBagEval:
         elif metrics.device != dev or metrics.num_classes != slots[0].num_classes:
             raise RuntimeError(f"CapturedBagEval: metrics= must live on the slots' device ({dev}) and count their {slots[0].num_classes} classes")
         self.milnet, self.metrics = milnet, metrics
-        order = sorted(range(len(slots)), key=lambda i: slots[i].row_cap)                      # smallest first: what run() tries in turn
-        self.slots = [slots[i] for i in order]
-        if warmup_batches is not None:
-            warmup_batches = [warmup_batches[i] for i in order]
+        self.slots, warmup_batches = capture.smallest_first(slots, lambda s: s.row_cap, warmup_batches)
         self.replays, self.eager_batches = 0, 0
         self.graphs, self.outputs = [], []
-        was_training = milnet.training
-        milnet.eval()
-        try:
-            with torch.no_grad():
-                pool = None
-                for i, slot in enumerate(self.slots):
-                    if warmup_batches is not None:
-                        slot.load(*warmup_batches[i])
-                    elif slot.num_real == 0:
-                        raise ValueError(f"CapturedBagEval: slot {i} holds no batch to warm up on - load one, or pass warmup_batches")
-                    side = torch.cuda.Stream(device=dev)
-                    side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(side):                  # (plans, caches and allocator pools settle before the capture)
-                        for _ in range(max(1, warmup)):
-                            self._forward(slot)
-                    torch.cuda.current_stream(dev).wait_stream(side)
-                    torch.cuda.synchronize(dev)
-                    cg = torch.cuda.CUDAGraph()
-                    try:
-                        with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
-                            out = self._forward(slot)
-                    except Exception as exc:
-                        raise RuntimeError("CapturedBagEval: the forward could not be captured into a hipGraph; evaluate eagerly "
-                                           "(mil.evaluate) instead") from exc
-                    pool = cg.pool()
-                    self.graphs.append(cg)
-                    self.outputs.append(out)
-                metrics.reset()                                    # (the warm-up forwards counted their rows)
-        finally:
-            milnet.train(was_training)
-
-    def _forward(self, slot: BagSlot) -> torch.Tensor:
-        return forward_update(self.milnet, slot.rows, slot.plan, slot.targets, slot.weights, self.metrics)
+        with capture.eval_mode(milnet):
+            for i, slot in enumerate(self.slots):
+                capture.load_warm_up_batch("CapturedBagEval", i, slot, warmup_batches)
+                body = lambda: forward_update(self.milnet, slot.rows, slot.plan, slot.targets, slot.weights, self.metrics)
+                capture.warm_up(dev, warmup, body)
+                torch.cuda.synchronize(dev)
+                cg, out = capture.record("CapturedBagEval", body, self.graphs[-1].pool() if self.graphs else None,
+                                         "the forward could not be captured into a hipGraph; evaluate eagerly (mil.evaluate) instead")
+                self.graphs.append(cg)
+                self.outputs.append(out)
+            metrics.reset()                                        # (the warm-up forwards counted their rows)
 
     def slot_for(self, sizes: Sequence[int]):
         """Index of the smallest slot the batch fits, or None."""
-        for i, slot in enumerate(self.slots):
-            if slot.fits(sizes):
-                return i
-        return None
+        return capture.first_fit(self.slots, sizes)
 
     def run(self, bags: Sequence[torch.Tensor], labels) -> torch.Tensor:
         """The bag predictions ``[len(bags), C]`` of the bags ``bags`` (device tensors [n_i, feats]) with host labels ``labels`` (a device
@@ -408,19 +366,14 @@ class CapturedBagEval:
         i = self.slot_for(sizes)
         if i is None:
             from . import bag_targets
-            was_training = self.milnet.training
-            self.milnet.eval()
-            try:
-                with torch.no_grad():
-                    dev = self.slots[0].device
-                    rows = torch.cat([t.to(torch.float32) for t in bags])
-                    labels = [float(v) for v in (labels.tolist() if isinstance(labels, torch.Tensor) else labels)]
-                    targets = bag_targets(labels, self.metrics.num_classes, dev).contiguous()
-                    weights = torch.tensor([1.0 if n > 0 else 0.0 for n in sizes], dtype=torch.float32, device=dev)
-                    self.eager_batches += 1
-                    return forward_update(self.milnet, rows, bag_plan(sizes, dev), targets, weights, self.metrics)
-            finally:
-                self.milnet.train(was_training)
+            with capture.eval_mode(self.milnet):
+                dev = self.slots[0].device
+                rows = torch.cat([t.to(torch.float32) for t in bags])
+                labels = [float(v) for v in (labels.tolist() if isinstance(labels, torch.Tensor) else labels)]
+                targets = bag_targets(labels, self.metrics.num_classes, dev).contiguous()
+                weights = torch.tensor([1.0 if n > 0 else 0.0 for n in sizes], dtype=torch.float32, device=dev)
+                self.eager_batches += 1
+                return forward_update(self.milnet, rows, bag_plan(sizes, dev), targets, weights, self.metrics)
         slot = self.slots[i]
         slot.load(bags, labels)
         self.graphs[i].replay()
@@ -430,11 +383,8 @@ class CapturedBagEval:
     def run_epoch(self, batches) -> dict:
         """``metrics.reset()``, every ``(bags, labels)`` of ``batches`` through ``run``, ``metrics.compute()``: one read-back.  The model's
         training flag is what it was on return."""
-        was_training = self.milnet.training
-        try:
+        with capture.eval_mode(self.milnet):
             self.metrics.reset()
             for bags, labels in batches:
                 self.run(bags, labels)
             return self.metrics.compute()
-        finally:
-            self.milnet.train(was_training)

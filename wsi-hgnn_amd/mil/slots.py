@@ -3,7 +3,7 @@
 The reference trains ABMIL / DSMIL on ONE bag per step (``train_tcga_k-fold.py:54-88``), optionally after ``dropout_patches`` (lines 90-96); at
 that size a step is a few dozen small launches and the host takes longer to issue them than the GPU to run them.  ``BagSlot`` holds a batch of
 bags in static device tables of one shape - the real bags, empty bags up to ``bag_cap``, and a filler bag of zero rows that takes what is left -
-so that ``CapturedBagStep`` records the step once per slot (``torch.cuda.CUDAGraph``) and replays it over new bags: per step one descriptor
+so that ``CapturedBagStep`` records the step once per slot (a hipGraph, ``capture.py``) and replays it over new bags: per step one descriptor
 upload, the fill kernels, one replay.  The patch dropout is drawn inside the fill (``csrc/bag_slot.hip``); the draw contract is in
 ``include/wsi_hgnn.h`` and ``dropout_patches_tensor`` restates it with tensor operations.
 """
@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .. import _native as N
-from .. import ops
+from .. import capture, ops
 from . import abmil, dsmil
 from .bags import bag_plan
 
@@ -288,32 +288,40 @@ class BagSlot:
             self.small.copy_(torch.tensor(small, dtype=torch.int32))
 
 
+def check_bag_slots(who: str, milnet, slots):
+    """What a capture over bag slots needs (``CapturedBagStep``, ``CapturedBagEval``): ABMIL or DSMIL, slots on one GPU.  Returns (slots as a
+    list, their device)."""
+    slots = [slots] if isinstance(slots, BagSlot) else list(slots)
+    if not slots:
+        raise ValueError(f"{who}: no slot")
+    if not isinstance(milnet, (dsmil.MILNet, abmil.BClassifier)):
+        raise RuntimeError(f"{who}: {type(milnet).__name__} is not supported - abmil.BClassifier / BClassifier_ or dsmil.MILNet")
+    dev = slots[0].device
+    if dev.type != "cuda" or any(s.device != dev for s in slots):
+        raise RuntimeError(f"{who}: the slots must live on one GPU")
+    return slots, dev
+
+
 def slot_step(milnet, optimizer, slot: BagSlot, params=None):
     """One training step on the batch a slot holds - the body of ``train_one_step`` with the slot's device-side targets and weights, gradients
     from ``torch.autograd.grad``: nothing in it is a host value of the batch, so it can be recorded.  Returns (loss, predictions
     [bag_cap + 1, C]), detached."""
-    if params is None:
-        params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
     from . import bag_loss
-    optimizer.zero_grad(set_to_none=True)
-    outputs = milnet(slot.rows, slot.plan)
-    pred = outputs[1] if isinstance(outputs, (tuple, list)) else outputs
-    model = "dsmil" if isinstance(milnet, dsmil.MILNet) else "abmil"
-    loss = bag_loss(outputs, None, pred.shape[-1], model, slot.plan, weights=slot.weights, targets=slot.targets)
-    grads = torch.autograd.grad(loss, params, allow_unused=True)
-    for p, g in zip(params, grads):
-        p.grad = g
-    optimizer.step()
-    return loss.detach(), pred.detach()
+
+    def compute():
+        outputs = milnet(slot.rows, slot.plan)
+        pred = outputs[1] if isinstance(outputs, (tuple, list)) else outputs
+        model = "dsmil" if isinstance(milnet, dsmil.MILNet) else "abmil"
+        return bag_loss(outputs, None, pred.shape[-1], model, slot.plan, weights=slot.weights, targets=slot.targets), pred
+    return capture.grad_step(optimizer, capture.trainable_params(optimizer) if params is None else params, compute)
 
 
 class CapturedBagStep:
     """One captured ABMIL / DSMIL training step per ``BagSlot``, replayed over new bags every step: the regime the reference trains in (one bag
     per step, ``train_tcga_k-fold.py:54-88``; ReMix's reduced bags), where the host takes longer to issue the step's launches than the GPU to
-    run them.  It follows ``trainer.CapturedSlotStep``: the ``warmup`` eager steps on a side stream before each capture ARE optimisation steps
-    (on ``warmup_batches[i] = (bags, labels)`` for slot i; None: on what the caller has loaded into the slot), gradients come from
-    ``torch.autograd.grad``, the captures share one memory pool, the optimizer must be capturable and a ``torch.nn.Dropout`` with p > 0 in
-    train mode is refused (its generator state is a host value a capture would freeze).
+    run them.  Protocol: ``capture.py``; EVERY slot takes its ``warmup`` (1) optimisation steps (on ``warmup_batches[i] = (bags, labels)`` for
+    slot i; None: on what the caller has loaded into the slot) before the first capture, and a ``torch.nn.Dropout`` with p > 0 in train mode
+    is refused: these models draw no counter-based dropout.
 
     ``step(bags, labels)`` loads the smallest slot (fewest rows) that fits and replays; a batch no slot fits runs eagerly through
     ``mil.train_one_step`` - after ``mil.dropout_patches`` if the slots drop - and is counted in ``eager_steps``.  ``recapture()`` records the
@@ -327,71 +335,36 @@ class CapturedBagStep:
     """
 
     def __init__(self, milnet: torch.nn.Module, optimizer: torch.optim.Optimizer, slots, warmup: int = 1, warmup_batches=None):
-        slots = [slots] if isinstance(slots, BagSlot) else list(slots)
-        if not slots:
-            raise ValueError("CapturedBagStep: no slot")
-        if not isinstance(milnet, (dsmil.MILNet, abmil.BClassifier)):
-            raise RuntimeError(f"CapturedBagStep: {type(milnet).__name__} is not supported - abmil.BClassifier / BClassifier_ or dsmil.MILNet")
-        dev = slots[0].device
-        if dev.type != "cuda" or any(s.device != dev for s in slots):
-            raise RuntimeError("CapturedBagStep: the slots must live on one GPU")
+        slots, dev = check_bag_slots("CapturedBagStep", milnet, slots)
         if len({(s.feats, s.num_classes, s.dropout_patch) for s in slots}) != 1:
             raise ValueError("CapturedBagStep: the slots must agree on feats, num_classes and dropout_patch")
-        for group in optimizer.param_groups:
-            if not group.get("capturable", False):
-                raise RuntimeError("CapturedBagStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step count "
-                                   "has to live on the device, a host count would be frozen into the graph")
+        capture.require_capturable("CapturedBagStep", optimizer)
         milnet.train()
-        if any(isinstance(mod, torch.nn.Dropout) and mod.p > 0.0 for mod in milnet.modules()):
-            raise RuntimeError("CapturedBagStep: the model holds a torch.nn.Dropout with p > 0 in train mode; its generator state is a host value a "
-                               "capture would freeze - every replay would drop the same entries.  Step such a model eagerly")
+        capture.counter_dropout_only("CapturedBagStep", milnet)
         self.milnet, self.optimizer = milnet, optimizer
-        order = sorted(range(len(slots)), key=lambda i: slots[i].row_cap)                      # smallest first: what step() tries in turn
-        self.slots = [slots[i] for i in order]
-        if warmup_batches is not None:
-            warmup_batches = [warmup_batches[i] for i in order]
-        optimizer.zero_grad(set_to_none=True)
-        self.params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
+        self.slots, warmup_batches = capture.smallest_first(slots, lambda s: s.row_cap, warmup_batches)
+        self.params = capture.trainable_params(optimizer)
         self.steps_taken, self.replays, self.eager_steps = 0, 0, 0
         for i, slot in enumerate(self.slots):
-            if warmup_batches is not None:
-                slot.load(*warmup_batches[i])
-            elif slot.num_real == 0:
-                raise ValueError(f"CapturedBagStep: slot {i} holds no batch to warm up on - load one, or pass warmup_batches")
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):                      # (caches and allocator pools settle before the capture; these ARE steps)
-                for _ in range(max(1, warmup)):
-                    slot_step(self.milnet, self.optimizer, slot, self.params)
-                    self.steps_taken += 1
-            torch.cuda.current_stream(dev).wait_stream(side)
+            capture.load_warm_up_batch("CapturedBagStep", i, slot, warmup_batches)
+            capture.warm_up(dev, warmup, lambda: slot_step(self.milnet, self.optimizer, slot, self.params))
+            self.steps_taken += max(1, warmup)
         self.graphs, self.outputs = [], []
         self.recapture()
 
     def recapture(self) -> None:
         """Record every slot's graph again (no step is taken): after a change of a host-side hyper-parameter such as ``lr``."""
-        dev = self.slots[0].device
         self.graphs, self.outputs = [], []
-        torch.cuda.synchronize(dev)
-        pool = None
+        torch.cuda.synchronize(self.slots[0].device)
         for slot in self.slots:
-            cg = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
-                    out = slot_step(self.milnet, self.optimizer, slot, self.params)
-            except Exception as exc:
-                raise RuntimeError("CapturedBagStep: the step could not be captured into a hipGraph (is a tensor of an earlier eager step's autograd "
-                                   "graph - a previous loss or prediction - still alive in the caller?); run the step eagerly instead") from exc
-            pool = cg.pool()
+            cg, out = capture.record("CapturedBagStep", lambda: slot_step(self.milnet, self.optimizer, slot, self.params),
+                                     self.graphs[-1].pool() if self.graphs else None, capture.step_failure("prediction"))
             self.graphs.append(cg)
             self.outputs.append(out)
 
     def slot_for(self, sizes: Sequence[int]):
         """Index of the smallest slot the batch fits, or None."""
-        for i, slot in enumerate(self.slots):
-            if slot.fits(sizes):
-                return i
-        return None
+        return capture.first_fit(self.slots, sizes)
 
     def step(self, bags: Sequence[torch.Tensor], labels):
         """One optimisation step on the bags ``bags`` (device tensors [n_i, feats]) with host labels ``labels``.  Returns ``(loss,

@@ -17,6 +17,7 @@ from typing import Optional, Sequence, Union
 import torch
 import torch.nn.functional as F
 
+from . import capture
 from .dist import GradBucket
 from .graph import HeteroGraph, batch as batch_graphs
 
@@ -72,6 +73,17 @@ def train_one_step(gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_
             prob.detach().cpu().numpy(), label.detach().cpu().numpy())
 
 
+def _seeded_step(optimizer, params, seed_base, compute):
+    """``capture.grad_step`` with every dropout draw of forward and backward taken under the device word ``seed_base`` (None: no dropout),
+    which the step then advances - part of the recorded step: the next replay draws other masks."""
+    from . import ops
+    with ops.dropout_seed_base(seed_base):
+        out = capture.grad_step(optimizer, params, compute)
+    if seed_base is not None:
+        ops.advance_dropout_seed_base(seed_base)
+    return out
+
+
 class CapturedStep:
     """One training step (forward + loss + backward + optimizer) on a RESIDENT batch, captured once into a hipGraph and replayed.
 
@@ -80,11 +92,12 @@ class CapturedStep:
     ``tools/graph_capture_probe.py``).  Everything the step launches goes to the capturing stream - the library keeps no stream or state of its
     own, never allocates or synchronises (``include/wsi_hgnn.h``), and the hub kernels' side stream forks from and joins that stream with events -
     so the whole step records as one graph.  What the capture bakes in: the graph's kernel plan and every shape, i.e. one ``CapturedStep`` per
-    resident batch (captures may share a memory ``pool``); the optimizer must keep its step count on the device
+    resident batch (captures may share a memory ``pool``).  Protocol: ``capture.py`` - a capturable optimizer
     (``wsi_hgnn_amd.optim.Adam(..., capturable=True)``: the whole optimizer step is then ONE node of the graph; ``optim.SGD`` and
-    ``optim.Adadelta`` read no count and are taken as they are; ``torch.optim``'s capturable optimizers work too).  A model stepped eagerly
-    before is fine - as long as the caller holds no tensor of those steps' autograd graphs any more (a previous loss, logits).  At the benchmark's size the step is GPU-bound and replay changes nothing
-    (6.87 vs 6.93 ms).
+    ``optim.Adadelta`` read no count and are taken as they are; ``torch.optim``'s capturable optimizers work too), train-mode dropout only as
+    the HEAT layers' counter-based draw, ``warmup`` (3) eager steps that ARE optimisation steps.  A model stepped eagerly before is fine - as
+    long as the caller holds no tensor of those steps' autograd graphs any more (a previous loss, logits).  At the benchmark's size the step
+    is GPU-bound and replay changes nothing (6.87 vs 6.93 ms).
 
     >>> step = CapturedStep(model, wsi_hgnn_amd.optim.Adam(model.parameters(), lr=1e-4, capturable=True), torch.nn.CrossEntropyLoss(), G, labels)
     >>> for _ in range(epochs): loss = step()          # a device tensor, overwritten by the next replay
@@ -92,63 +105,21 @@ class CapturedStep:
 
     def __init__(self, gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_fcn, graph: HeteroGraph, label: torch.Tensor,
                  warmup: int = 3, pool=None):
+        from .models.heat_layer import HEATLayer
         if not label.is_cuda:
             raise RuntimeError("CapturedStep: the batch and its labels must be resident on the GPU")
-        for group in optimizer.param_groups:
-            if not group.get("capturable", False):
-                raise RuntimeError("CapturedStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step count has to "
-                                   "live on the device, a host count would be frozen into the graph")
-        # Train-mode dropout: the HEAT layers draw their masks as a function of (host seed + a DEVICE word, row, column) - ops.CounterDropout.  The
-        # capture freezes the host seeds; the recorded step itself advances the word, so every replay drops other entries (forward and backward of a
-        # replay the same ones).  Any other dropout (a module that draws a mask tensor from a host-seeded generator state) cannot be replayed.
-        self.seed_base = None
-        if gnn.training and any(isinstance(mod, torch.nn.Dropout) and mod.p > 0.0 for mod in gnn.modules()):
-            from .models.heat_layer import HEATLayer
-            owners = [m_ for m_ in gnn.modules() if any(isinstance(c, torch.nn.Dropout) and c.p > 0.0 for c in m_.children())]
-            if not all(isinstance(m_, HEATLayer) and getattr(m_, "counter_dropout", False) for m_ in owners):
-                raise RuntimeError("CapturedStep: the model draws dropout masks outside the HEAT layers' counter-based draw (train mode, p > 0); their "
-                                   "generator state is a host value a capture would freeze - every replay would drop the same entries.  Step such a "
-                                   "model eagerly")
-            self.seed_base = torch.empty((), dtype=torch.int64).random_(-(1 << 31), 1 << 31).to(torch.int32).reshape(1).to(label.device)
+        capture.require_capturable("CapturedStep", optimizer)
+        self.seed_base = capture.new_seed_word(label.device) if capture.counter_dropout_only("CapturedStep", gnn, (HEATLayer,)) else None
         self.gnn, self.optimizer, self.loss_fcn, self.graph, self.label = gnn, optimizer, loss_fcn, graph, label
-        # A model that has been stepped before keeps its AccumulateGrad nodes bound to the stream of that step for as long as ANYTHING keeps
-        # its last autograd graph alive; such a node makes the capture synchronise with the default stream, which is invalid and, on this
-        # ROCm, a segfault in capture_end rather than an error.  What this class can release it does: the gradients (the path itself keeps no
-        # registry: what producers know about a tensor travels on the tensor, ops._annotate).  What it cannot: tensors of an earlier step the
-        # CALLER still holds (a previous loss or logits) - drop them before building a CapturedStep (PyTorch's general rule for captures).
-        optimizer.zero_grad(set_to_none=True)
-        self.params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
-        side = torch.cuda.Stream(device=label.device)
-        side.wait_stream(torch.cuda.current_stream(label.device))
-        with torch.cuda.stream(side):                      # (plans, caches and allocator pools settle before the capture; these ARE steps)
-            for _ in range(max(1, warmup)):
-                self._eager()
-        torch.cuda.current_stream(label.device).wait_stream(side)
+        self.params = capture.trainable_params(optimizer)
+        self.cuda_graph = None
+        capture.warm_up(label.device, warmup, self._eager)
         torch.cuda.synchronize(label.device)
-        self.cuda_graph = torch.cuda.CUDAGraph()
-        try:
-            # thread_local: only what THIS thread does during the capture can invalidate it (another thread's allocation or sync must not), and an
-            # illegal call here surfaces as a Python error at that call instead of a broken capture found at capture_end
-            with torch.cuda.graph(self.cuda_graph, pool=pool, capture_error_mode="thread_local"):
-                self.loss = self._eager()
-        except Exception as exc:
-            self.cuda_graph = None
-            raise RuntimeError("CapturedStep: the step could not be captured into a hipGraph (is a tensor of an earlier eager step's autograd "
-                               "graph - a previous loss or logits - still alive in the caller?); run the step eagerly instead") from exc
+        self.cuda_graph, self.loss = capture.record("CapturedStep", self._eager, pool, capture.step_failure("logits"))
         self.steps_taken = max(1, warmup)                  # (the capture records the step without executing it)
 
     def _eager(self) -> torch.Tensor:
-        from . import ops
-        self.optimizer.zero_grad(set_to_none=True)
-        with ops.dropout_seed_base(self.seed_base):
-            loss = self.loss_fcn(self.gnn(self.graph), self.label)
-            grads = torch.autograd.grad(loss, self.params, allow_unused=True)   # (same gradients as loss.backward(); parameters the loss does not reach: None)
-        for p, g in zip(self.params, grads):
-            p.grad = g
-        self.optimizer.step()
-        if self.seed_base is not None:
-            ops.advance_dropout_seed_base(self.seed_base)                       # part of the recorded step: the next replay draws other masks
-        return loss.detach()
+        return _seeded_step(self.optimizer, self.params, self.seed_base, lambda: self.loss_fcn(self.gnn(self.graph), self.label))
 
     def __call__(self) -> torch.Tensor:
         self.cuda_graph.replay()
@@ -191,6 +162,14 @@ def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
     return slots, loader, loader.device
 
 
+def _first_slide(who: str, i: int, slot):
+    """The default warm-up batch of slot ``i``: the first slide of the data set that fits it alone."""
+    first = next(([j] for j in sorted(slot.members) if slot.fits([j])), None)
+    if first is None:
+        raise ValueError(f"{who}: no slide of the data set fits slot {i}")
+    return first
+
+
 class CapturedSlotStep:
     """One captured training step per batch SLOT (``data.BatchSlot``), replayed over NEW slides every step: the regime the reference trains in
     (one or two slides per step, ``trainer/train_gnn.py:48-79``), where the host takes longer to issue the step's launches than the GPU to run them.
@@ -199,9 +178,9 @@ class CapturedSlotStep:
 
     ``slots``: one ``BatchSlot`` or several of different capacity over the same loader (small slides then do not pay for the largest);
     ``step(idxs)`` takes the smallest slot (fewest node rows) that fits.  A batch no slot fits runs eagerly through the loader's ordinary
-    assembly.  The captures share one memory pool.  As with ``CapturedStep`` the ``warmup`` steps before each capture ARE optimisation steps -
-    here on ``warmup_batches[i]`` for slot i (default: the slot's first fitting batch of one slide) - the optimizer must be capturable, and
-    train-mode dropout must be the HEAT / HGT layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4, and HGT over
+    assembly.  Protocol: ``capture.py``; slot by slot the ``warmup`` (1) optimisation steps run on ``warmup_batches[i]`` (default: the slot's
+    first fitting batch of one slide) and the slot is captured before the next one warms up; train-mode dropout may be the HEAT and the HGT
+    layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4, and HGT over
     slots built with ``per_relation_src=True`` (the slot re-derives HGT's plan on the device behind every fill), with a sum / mean /
     max readout: the attention readout reads host-side node counts, HGT + ASAP and HeteroRGCN rebuild host-side structure - those are refused.
 
@@ -218,77 +197,38 @@ class CapturedSlotStep:
         if metrics is not None and metrics.device != dev:
             raise RuntimeError(f"CapturedSlotStep: metrics= must live on the slots' device ({dev})")
         self.metrics = metrics
-        for group in optimizer.param_groups:
-            if not group.get("capturable", False):
-                raise RuntimeError("CapturedSlotStep: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): its step count has "
-                                   "to live on the device, a host count would be frozen into the graph")
-        self.seed_base = None
-        if gnn.training and any(isinstance(mod, torch.nn.Dropout) and mod.p > 0.0 for mod in gnn.modules()):
-            from .models.heat_layer import HEATLayer
-            from .models.HGT import HGTLayer
-            owners = [m_ for m_ in gnn.modules() if any(isinstance(c, torch.nn.Dropout) and c.p > 0.0 for c in m_.children())]
-            # (an HGTLayer draws counter-based whenever a seed base is active, which it is throughout this class's steps)
-            if not all(type(m_) is HGTLayer or (isinstance(m_, HEATLayer) and getattr(m_, "counter_dropout", False)) for m_ in owners):
-                raise RuntimeError("CapturedSlotStep: the model draws dropout masks outside the HEAT layers' counter-based draw (train mode, p > 0); their "
-                                   "generator state is a host value a capture would freeze - every replay would drop the same entries.  Step such a "
-                                   "model eagerly")
-            self.seed_base = torch.empty((), dtype=torch.int64).random_(-(1 << 31), 1 << 31).to(torch.int32).reshape(1).to(dev)
+        from .models.heat_layer import HEATLayer
+        from .models.HGT import HGTLayer
+        capture.require_capturable("CapturedSlotStep", optimizer)
+        # (an HGTLayer draws counter-based whenever a seed base is active, which it is throughout this class's steps)
+        self.seed_base = capture.new_seed_word(dev) if capture.counter_dropout_only("CapturedSlotStep", gnn, (HEATLayer, HGTLayer)) else None
         self.gnn, self.optimizer, self.loss_fcn = gnn, optimizer, loss_fcn
-        order = sorted(range(len(self.slots)), key=lambda i: self.slots[i].layout.N)          # smallest first: what step() tries in turn
-        self.slots = [self.slots[i] for i in order]
-        if warmup_batches is not None:
-            warmup_batches = [list(warmup_batches[i]) for i in order]
-        optimizer.zero_grad(set_to_none=True)
-        self.params = [p for group in optimizer.param_groups for p in group["params"] if p.requires_grad]
+        self.slots, warmup_batches = capture.smallest_first(self.slots, lambda s: s.layout.N, warmup_batches)
+        self.params = capture.trainable_params(optimizer)
         self.steps_taken, self.replays, self.eager_steps = 0, 0, 0
         self.graphs, self.outputs = [], []
-        pool = None
         for i, slot in enumerate(self.slots):
-            first = warmup_batches[i] if warmup_batches is not None else next(([j] for j in sorted(slot.members) if slot.fits([j])), None)
-            if first is None:
-                raise ValueError(f"CapturedSlotStep: no slide of the data set fits slot {i}")
-            slot.load(first)
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):                      # (plans, caches and allocator pools settle before the capture; these ARE steps)
-                for _ in range(max(1, warmup)):
-                    self._eager(slot.graph, slot.labels)
-                    self.steps_taken += 1
-            torch.cuda.current_stream(dev).wait_stream(side)
+            slot.load(list(warmup_batches[i]) if warmup_batches is not None else _first_slide("CapturedSlotStep", i, slot))
+            body = lambda: self._eager(slot.graph, slot.labels)
+            capture.warm_up(dev, warmup, body)
+            self.steps_taken += max(1, warmup)
             torch.cuda.synchronize(dev)
-            cg = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
-                    out = self._eager(slot.graph, slot.labels)
-            except Exception as exc:
-                raise RuntimeError("CapturedSlotStep: the step could not be captured into a hipGraph (is a tensor of an earlier eager step's autograd "
-                                   "graph - a previous loss or logits - still alive in the caller?); run the step eagerly instead") from exc
-            pool = cg.pool()
+            cg, out = capture.record("CapturedSlotStep", body, self.graphs[-1].pool() if self.graphs else None, capture.step_failure("logits"))
             self.graphs.append(cg)
             self.outputs.append(out)
 
     def _eager(self, graph: HeteroGraph, label: torch.Tensor):
-        from . import ops
-        self.optimizer.zero_grad(set_to_none=True)
-        with ops.dropout_seed_base(self.seed_base):
+        def compute():
             pred = self.gnn(graph)
-            loss = self.loss_fcn(pred, label)
-            grads = torch.autograd.grad(loss, self.params, allow_unused=True)
-        for p, g in zip(self.params, grads):
-            p.grad = g
-        self.optimizer.step()
-        if self.seed_base is not None:
-            ops.advance_dropout_seed_base(self.seed_base)
+            return self.loss_fcn(pred, label), pred
+        loss, pred = _seeded_step(self.optimizer, self.params, self.seed_base, compute)
         if self.metrics is not None:
-            self.metrics.update(pred.detach(), label)
-        return loss.detach(), pred.detach()
+            self.metrics.update(pred, label)
+        return loss, pred
 
     def slot_for(self, idxs: Sequence[int]):
         """Index of the smallest slot the batch fits, or None."""
-        for i, slot in enumerate(self.slots):
-            if slot.fits(idxs):
-                return i
-        return None
+        return capture.first_fit(self.slots, idxs)
 
     def step(self, idxs: Sequence[int]):
         """One optimisation step on the loader's slides ``idxs``.  Returns ``(loss, logits[:len(idxs)])`` as device tensors; those of a replayed
@@ -318,7 +258,7 @@ class CapturedSlotEval:
     one slide at a time (``trainer/train_gnn.py:110-115``, ``evaluator/eval_homo_graph.py:61-95``) - the same host-bound regime as its training
     step.  Each slot's graph records ``pred = gnn(slot.graph); metrics.update(pred, slot.labels)`` in eval mode under ``no_grad``; ``evaluate``
     fills and replays batch after batch and reads the epoch's numbers back ONCE (``metrics.EpochMetrics.compute``).  The filler and the empty
-    graphs of a slot are labelled -100 and are not counted.
+    graphs of a slot are labelled -100 and are not counted.  Protocol: ``capture.py``, slot by slot as ``CapturedSlotStep``.
 
     The recorded forward reads the LIVE parameters: under a stream capture every projection packs its own weights (``ops.repack_weights``), the
     statistics stream is not used, and the eval-mode forward keeps no other table that depends on a parameter - an optimizer step between two
@@ -338,46 +278,25 @@ class CapturedSlotEval:
         self.slots = sorted(self.slots, key=lambda s: s.layout.N)                      # smallest first: what run() tries in turn
         self.replays, self.eager_runs = 0, 0
         self.graphs, self.outputs = [], []
-        was_training = gnn.training
-        gnn.eval()
-        try:
-            with torch.no_grad():
-                firsts = []
-                for i, slot in enumerate(self.slots):
-                    first = next(([j] for j in sorted(slot.members) if slot.fits([j])), None)
-                    if first is None:
-                        raise ValueError(f"CapturedSlotEval: no slide of the data set fits slot {i}")
-                    firsts.append(first)
-                if metrics is None:
-                    from .metrics import EpochMetrics
-                    slot = self.slots[0].load(firsts[0])
-                    metrics = EpochMetrics(gnn(slot.graph).shape[1], len(self.loader.items), dev)
-                elif metrics.device != dev:
-                    raise RuntimeError(f"CapturedSlotEval: metrics= must live on the slots' device ({dev})")
-                self.metrics = metrics
-                pool = None
-                for slot, first in zip(self.slots, firsts):
-                    slot.load(first)
-                    side = torch.cuda.Stream(device=dev)
-                    side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(side):                  # (plans, caches and allocator pools settle before the capture)
-                        for _ in range(max(1, warmup)):
-                            self._eager(slot.graph, slot.labels)
-                    torch.cuda.current_stream(dev).wait_stream(side)
-                    torch.cuda.synchronize(dev)
-                    cg = torch.cuda.CUDAGraph()
-                    try:
-                        with torch.cuda.graph(cg, pool=pool, capture_error_mode="thread_local"):
-                            out = self._eager(slot.graph, slot.labels)
-                    except Exception as exc:
-                        raise RuntimeError("CapturedSlotEval: the forward could not be captured into a hipGraph; evaluate eagerly (io.evaluate) "
-                                           "instead") from exc
-                    pool = cg.pool()
-                    self.graphs.append(cg)
-                    self.outputs.append(out)
-                metrics.reset()                                    # (the warm-up forwards counted their rows)
-        finally:
-            gnn.train(was_training)
+        with capture.eval_mode(gnn):
+            firsts = [_first_slide("CapturedSlotEval", i, slot) for i, slot in enumerate(self.slots)]
+            if metrics is None:
+                from .metrics import EpochMetrics
+                slot = self.slots[0].load(firsts[0])
+                metrics = EpochMetrics(gnn(slot.graph).shape[1], len(self.loader.items), dev)
+            elif metrics.device != dev:
+                raise RuntimeError(f"CapturedSlotEval: metrics= must live on the slots' device ({dev})")
+            self.metrics = metrics
+            for slot, first in zip(self.slots, firsts):
+                slot.load(first)
+                body = lambda: self._eager(slot.graph, slot.labels)
+                capture.warm_up(dev, warmup, body)
+                torch.cuda.synchronize(dev)
+                cg, out = capture.record("CapturedSlotEval", body, self.graphs[-1].pool() if self.graphs else None,
+                                         "the forward could not be captured into a hipGraph; evaluate eagerly (io.evaluate) instead")
+                self.graphs.append(cg)
+                self.outputs.append(out)
+            metrics.reset()                                        # (the warm-up forwards counted their rows)
 
     def _eager(self, graph: HeteroGraph, label: torch.Tensor) -> torch.Tensor:
         pred = self.gnn(graph)
@@ -386,10 +305,7 @@ class CapturedSlotEval:
 
     def slot_for(self, idxs: Sequence[int]):
         """Index of the smallest slot the batch fits, or None."""
-        for i, slot in enumerate(self.slots):
-            if slot.fits(idxs):
-                return i
-        return None
+        return capture.first_fit(self.slots, idxs)
 
     def run(self, idxs: Sequence[int]) -> torch.Tensor:
         """The logits ``[len(idxs), C]`` of the loader's slides ``idxs`` (a device tensor; those of a replay are overwritten by the next replay of
@@ -397,17 +313,12 @@ class CapturedSlotEval:
         idxs = list(idxs)
         i = self.slot_for(idxs)
         if i is None:
-            was_training = self.gnn.training
-            self.gnn.eval()
-            try:
-                with torch.no_grad():
-                    G, labels, ready = self.loader._assemble(idxs, 0)
-                    if ready is not None:
-                        torch.cuda.current_stream(self.loader.device).wait_event(ready)
-                    self.eager_runs += 1
-                    return self._eager(G, labels)
-            finally:
-                self.gnn.train(was_training)
+            with capture.eval_mode(self.gnn):
+                G, labels, ready = self.loader._assemble(idxs, 0)
+                if ready is not None:
+                    torch.cuda.current_stream(self.loader.device).wait_event(ready)
+                self.eager_runs += 1
+                return self._eager(G, labels)
         slot = self.slots[i]
         slot.load(idxs)
         self.graphs[i].replay()
