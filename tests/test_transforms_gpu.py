@@ -77,6 +77,24 @@ def test_each_transform_alone_equals_the_cpu_result(which, p, width):
     _same(t(g.to(_dev()), draw=SEED, index=2), t(g, draw=SEED, index=2))
 
 
+def test_tile_scan_carries_across_rounds_of_256_tiles():
+    """The one-workgroup scan of the tile sums (csrc/segment_table.hip: tile_scan_kernel, shared by the augmentation, the leave-one-out batches,
+    the augmented slot fill and the per-relation plan) walks the tiles 256 at a time and carries the total from round to round.  A node type of
+    256 * 1024 + 1500 nodes is 258 tiles of 1024: the second round starts from the carry, and the type's kept count is a difference of two
+    prefixes that lie in different rounds."""
+    from wsi_hgnn_amd import transforms as TR
+    from wsi_hgnn_amd.graph import HeteroGraph
+    n, m = 256 * 1024 + 1500, 4000
+    gen = torch.Generator().manual_seed(258)
+    g = HeteroGraph.from_coo(OrderedDict([("0", n)]), OrderedDict([(("0", "a", "0"), (torch.randint(0, n, (m,), generator=gen), torch.randint(0, n, (m,), generator=gen)))]),
+                             feat={"0": torch.rand(n, 4, generator=gen) + 0.5}, sim={("0", "a", "0"): torch.rand(m, generator=gen) - 0.5})
+    g.nodes["0"].data["tag"] = torch.arange(n)
+    t = TR.DropNode(0.5)
+    cpu = t(g, draw=SEED, index=2)
+    assert 0 < cpu.num_nodes("0") < n and cpu.nodes["0"].data["tag"][-1] >= 256 * 1024     # nodes of the second round survive: their places need the carry
+    _same(t(g.to(_dev()), draw=SEED, index=2), cpu)
+
+
 ORDERS = [("drop_node", "drop_edge", "node_shuffle", "feat_mask"),        # the reference's pipeline: DropEdge by rank, shuffle of the survivors
           ("node_shuffle", "drop_edge", "feat_mask", "drop_node"),        # DropEdge by original position, shuffle in front of the compaction
           ("drop_node", "node_shuffle"), ("drop_edge", "drop_node"), ("feat_mask", "node_shuffle")]

@@ -13,25 +13,13 @@ namespace wsi {
 constexpr int AS_BLOCK = 256;
 constexpr int AS_WAVES = AS_BLOCK / 64;
 
-__device__ __forceinline__ int as_row(int n) {
-    int w = (int)blockIdx.x * AS_WAVES + (int)(threadIdx.x >> 6);
-    w = __builtin_amdgcn_readfirstlane(w);
-    return w < n ? w : -1;
-}
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x = fmaxf(x, __shfl_xor(x, m));
-    return x;
-}
-
 // out[w,c] = max over the segment of x[idx[e],c]; arg[w,c] = CSR position e of the FIRST maximum; empty segment: 0 / -1
 // (torch_scatter's scatter(..., reduce='max') leaves 0 where nothing was scattered).
 template <int NV>
 __global__ __launch_bounds__(AS_BLOCK) void gather_max_fwd_kernel(const float* __restrict__ x, int64_t ldx, int n, int D,
                                                                   const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
                                                                   float* __restrict__ out, int64_t ldo, int32_t* __restrict__ arg) {
-    const int w = as_row(n);
+    const int w = row_of_wave<AS_WAVES>(n);
     if (w < 0) return;
     const int lane = threadIdx.x & 63;
     float best[NV];
@@ -66,7 +54,7 @@ __global__ __launch_bounds__(AS_BLOCK) void gather_max_bwd_kernel(const float* _
                                                                   int n_src, int D, const int32_t* __restrict__ colptr,
                                                                   const int32_t* __restrict__ csc_eid, const int32_t* __restrict__ csc_dst,
                                                                   float* __restrict__ gx, int64_t ldgx) {
-    const int u = as_row(n_src);
+    const int u = row_of_wave<AS_WAVES>(n_src);
     if (u < 0) return;
     const int lane = threadIdx.x & 63;
     float acc[NV];
@@ -88,8 +76,6 @@ __global__ __launch_bounds__(AS_BLOCK) void gather_max_bwd_kernel(const float* _
     }
 }
 
-__device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
-
 // score[e] = exp(s_e - max) / (sum exp + 1e-16), s_e = leaky_relu(a[w] + b[idx[e]])  (torch_geometric.utils.softmax);
 // out[w,:] = sum_e score[e] * x[idx[e],:]
 template <int NV>
@@ -97,16 +83,16 @@ __global__ __launch_bounds__(AS_BLOCK) void asap_attend_fwd_kernel(const float* 
                                                                    const float* __restrict__ x, int64_t ldx, int n, int D,
                                                                    const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx, float slope,
                                                                    float* __restrict__ score, float* __restrict__ out, int64_t ldo) {
-    const int w = as_row(n);
+    const int w = row_of_wave<AS_WAVES>(n);
     if (w < 0) return;
     const int lane = threadIdx.x & 63;
     const int e0 = ptr[w], e1 = ptr[w + 1];
     const float aw = a[w];
     float m = -INFINITY;
-    for (int e = e0 + lane; e < e1; e += 64) m = fmaxf(m, leaky(aw + b[idx[e]], slope));
+    for (int e = e0 + lane; e < e1; e += 64) m = fmaxf(m, leaky_relu(aw + b[idx[e]], slope));
     m = wave_max(m);
     float l = 0.f;
-    for (int e = e0 + lane; e < e1; e += 64) l += expf(leaky(aw + b[idx[e]], slope) - m);
+    for (int e = e0 + lane; e < e1; e += 64) l += expf(leaky_relu(aw + b[idx[e]], slope) - m);
     l = wave_sum(l);
     const float inv = 1.f / (l + 1e-16f);
     float acc[NV];
@@ -114,7 +100,7 @@ __global__ __launch_bounds__(AS_BLOCK) void asap_attend_fwd_kernel(const float* 
     for (int i = 0; i < NV; ++i) acc[i] = 0.f;
     for (int e = e0; e < e1; ++e) {
         const int u = idx[e];
-        const float p = expf(leaky(aw + b[u], slope) - m) * inv;
+        const float p = expf(leaky_relu(aw + b[u], slope) - m) * inv;
         if (lane == 0) score[e] = p;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -137,7 +123,7 @@ __global__ __launch_bounds__(AS_BLOCK) void asap_attend_bwd_dst_kernel(const flo
                                                                        const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx, float slope,
                                                                        const float* __restrict__ score, const float* __restrict__ g_out, int64_t ldg,
                                                                        float* __restrict__ gpre, float* __restrict__ g_a) {
-    const int w = as_row(n);
+    const int w = row_of_wave<AS_WAVES>(n);
     if (w < 0) return;
     const int lane = threadIdx.x & 63;
     const int e0 = ptr[w], e1 = ptr[w + 1];
@@ -174,7 +160,7 @@ __global__ __launch_bounds__(AS_BLOCK) void asap_attend_bwd_src_kernel(const flo
                                                                        const int32_t* __restrict__ csc_dst, const float* __restrict__ score,
                                                                        const float* __restrict__ gpre, float* __restrict__ gx, int64_t ldgx,
                                                                        float* __restrict__ g_b) {
-    const int u = as_row(n_src);
+    const int u = row_of_wave<AS_WAVES>(n_src);
     if (u < 0) return;
     const int lane = threadIdx.x & 63;
     float acc[NV];

@@ -1,74 +1,13 @@
 // Train-time graph augmentation on the device (wsi_hgnn_amd/transforms.py; the reference: data.py:16-23 - DropNode, DropEdge, NodeShuffle, FeatMask
 // through dgl.transforms).  Contract and draw rule: include/wsi_hgnn.h (wsi_augment_*).  Every decision is a hash of (sub-seed, element index), so
-// flags are RECOMPUTED wherever they are needed instead of stored; output positions come from two-level exclusive scans (tile sums -> one block
-// scans the tile sums -> tiles scatter), never from atomics: the compacted order is the input order, run after run.
-#include "gemm_common.h"
+// flags are RECOMPUTED wherever they are needed instead of stored; output positions come from the two-level scans of common.h (never atomics).
+#include "common.h"
 
 namespace wsi {
 
 constexpr int AUG_TILE = 1024;            // elements per workgroup: 4 rounds of 256 lanes
 constexpr int AUG_NROW = 6;               // int64 words per node-segment descriptor: n, off, first_tile, seed, thr, -
 constexpr int AUG_EROW = 14;              // ... per edge segment: n, off, first_tile, u, v, sim, src_off, dst_off, seed, thr, mode, n_src, n_dst, -
-
-__device__ __forceinline__ uint32_t aug_hash(uint32_t i, uint32_t sub) { return drop_fmix32(i * 0x9E3779B1u + sub); }
-__device__ __forceinline__ bool aug_drawn(uint32_t i, uint32_t sub, uint32_t thr) { return (aug_hash(i, sub) & 0xffffu) < thr; }
-
-// last segment whose first tile is <= b (segments without elements own no tile and are never found)
-__device__ __forceinline__ int aug_find_seg(const int64_t* __restrict__ desc, int row, int nseg, int b) {
-    int lo = 0, hi = nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[(int64_t)mid * row + 2] <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// exclusive prefix of a 0/1 flag over the 256 lanes of the workgroup (ballot + popcount per wave, the 4 wave totals through LDS); `total` = their sum.
-// Two barriers; `lds` holds 4 ints and may be reused by the next call (the second barrier guards it).
-__device__ __forceinline__ int block_flag_scan(bool flag, int* lds, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(flag);
-    const int excl = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) lds[w] = __popcll(b);
-    __syncthreads();
-    const int t0 = lds[0], t1 = lds[1], t2 = lds[2], t3 = lds[3];
-    __syncthreads();
-    total = t0 + t1 + t2 + t3;
-    return excl + (w > 0 ? t0 : 0) + (w > 1 ? t1 : 0) + (w > 2 ? t2 : 0);
-}
-
-// ---------------------------------------------------------------- scan of the tile sums (one workgroup, any number of tiles)
-// tile_sum[0 .. ntiles) -> exclusive prefix in place, tile_sum[ntiles] = total; counts[s] = elements kept in segment s.
-__global__ __launch_bounds__(256) void aug_scan_tiles_kernel(int32_t* __restrict__ tile_sum, int ntiles, const int64_t* __restrict__ desc, int row, int nseg,
-                                                             int32_t* __restrict__ counts) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < ntiles; base += 256) {
-        const int i = base + threadIdx.x;
-        const int v = i < ntiles ? tile_sum[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        const int t0 = wsum[0], t1 = wsum[1], t2 = wsum[2], t3 = wsum[3];
-        __syncthreads();
-        const int before = (w > 0 ? t0 : 0) + (w > 1 ? t1 : 0) + (w > 2 ? t2 : 0);
-        if (i < ntiles) tile_sum[i] = carry + before + x - v;
-        carry += t0 + t1 + t2 + t3;
-    }
-    if (threadIdx.x == 0) tile_sum[ntiles] = carry;
-    __syncthreads();                      // the prefix is read back below by other lanes of this workgroup
-    for (int s = threadIdx.x; s < nseg; s += 256) {
-        const int a = (int)desc[(int64_t)s * row + 2];
-        const int b = s + 1 < nseg ? (int)desc[(int64_t)(s + 1) * row + 2] : ntiles;
-        counts[s] = tile_sum[b] - tile_sum[a];
-    }
-}
 
 // ---------------------------------------------------------------- nodes
 // pass 0: tile_sum[tile] = kept nodes of the tile;  pass 1 (after the scan): new_id / kept
@@ -77,7 +16,7 @@ __global__ __launch_bounds__(256) void aug_nodes_kernel(const int64_t* __restric
                                                         int32_t* __restrict__ new_id, int64_t* __restrict__ kept) {
     __shared__ int lds[4];
     const int b = blockIdx.x;
-    const int64_t* d = desc + (int64_t)aug_find_seg(desc, AUG_NROW, nseg, b) * AUG_NROW;
+    const int64_t* d = desc + (int64_t)find_row(desc, AUG_NROW, 2, nseg, b) * AUG_NROW;
     const int64_t n = d[0], off = d[1];
     const int ft = (int)d[2];
     const uint32_t seed = (uint32_t)d[3], thr = (uint32_t)d[4];
@@ -85,7 +24,7 @@ __global__ __launch_bounds__(256) void aug_nodes_kernel(const int64_t* __restric
     int run = PASS == 1 ? tile_sum[b] - tile_sum[ft] : 0;      // position inside the type's compacted range
     for (int r = 0; r < AUG_TILE / 256; ++r) {
         const int64_t i = i0 + r * 256 + threadIdx.x;
-        const bool keep = i < n && !aug_drawn((uint32_t)i, seed, thr);
+        const bool keep = i < n && !drawn((uint32_t)i, seed, thr);
         int total;
         const int excl = block_flag_scan(keep, lds, total);
         if (PASS == 1 && i < n) {
@@ -107,7 +46,7 @@ __device__ __forceinline__ bool aug_edge_flag1(const int64_t* d, const int32_t* 
         f = new_id[d[6] + u] >= 0 && new_id[d[7] + v] >= 0;
         if (f) { u = new_id[d[6] + u]; v = new_id[d[7] + v]; }
     }
-    if (d[10] == 0) f = f && !aug_drawn((uint32_t)i, (uint32_t)d[8], (uint32_t)d[9]);
+    if (d[10] == 0) f = f && !drawn((uint32_t)i, (uint32_t)d[8], (uint32_t)d[9]);
     return f;
 }
 
@@ -120,7 +59,7 @@ __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restric
                                                         int64_t* __restrict__ out_eid) {
     __shared__ int lds[4];
     const int b = blockIdx.x;
-    const int64_t* d = desc + (int64_t)aug_find_seg(desc, AUG_EROW, nseg, b) * AUG_EROW;
+    const int64_t* d = desc + (int64_t)find_row(desc, AUG_EROW, 2, nseg, b) * AUG_EROW;
     const int64_t n = d[0], off = d[1];
     const int ft = (int)d[2];
     const uint32_t seed = (uint32_t)d[8], thr = (uint32_t)d[9];
@@ -137,7 +76,7 @@ __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restric
         bool f;
         if (PASS == 2) {
             const int rk = i < n ? rank1[off + i] : -1;
-            f = rk >= 0 && !(by_rank && aug_drawn((uint32_t)rk, seed, thr));
+            f = rk >= 0 && !(by_rank && drawn((uint32_t)rk, seed, thr));
         } else {
             f = i < n && aug_edge_flag1(d, new_id, i, u, v);
         }
@@ -146,7 +85,7 @@ __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restric
         if (PASS == 1) {
             const int rk = f ? run + excl : -1;
             if (i < n) rank1[off + i] = rk;
-            const bool f2 = f && !(by_rank && aug_drawn((uint32_t)rk, seed, thr));
+            const bool f2 = f && !(by_rank && drawn((uint32_t)rk, seed, thr));
             cnt2 += __popcll(__ballot(f2));       // per wave; summed over the 4 waves below
         }
         if (PASS == 2 && f) {
@@ -170,14 +109,14 @@ __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restric
 // ---------------------------------------------------------------- NodeShuffle keys: (segment << 32) | hash, one stable sort orders every type at once
 __global__ __launch_bounds__(256) void aug_keys_kernel(const int64_t* __restrict__ desc, int nseg, int64_t* __restrict__ keys) {
     const int b = blockIdx.x;
-    const int s = aug_find_seg(desc, AUG_NROW, nseg, b);
+    const int s = find_row(desc, AUG_NROW, 2, nseg, b);
     const int64_t* d = desc + (int64_t)s * AUG_NROW;
     const int64_t n = d[0], off = d[1];
     const int64_t i0 = (int64_t)(b - (int)d[2]) * AUG_TILE;
 #pragma unroll
     for (int r = 0; r < AUG_TILE / 256; ++r) {
         const int64_t i = i0 + r * 256 + threadIdx.x;
-        if (i < n) keys[off + i] = ((int64_t)s << 32) | (int64_t)aug_hash((uint32_t)i, (uint32_t)d[3]);
+        if (i < n) keys[off + i] = ((int64_t)s << 32) | (int64_t)index_hash((uint32_t)i, (uint32_t)d[3]);
     }
 }
 
@@ -189,7 +128,7 @@ __device__ __forceinline__ uint32_t aug_col_bits(int c, int F, uint32_t seed, ui
     uint32_t m = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        if (c + j < F && aug_drawn((uint32_t)(c + j), seed, thr)) m |= 1u << j;
+        if (c + j < F && drawn((uint32_t)(c + j), seed, thr)) m |= 1u << j;
     return m;
 }
 
@@ -235,7 +174,7 @@ __global__ __launch_bounds__(256) void aug_gather_kernel(const float* __restrict
             const float* __restrict__ xr = x + (ok ? r : 0) * ldx;
             float* __restrict__ orow = out + i * ldo;
             for (int c = lane; c < F; c += 64)
-                orow[c] = (ok && !(thr && aug_drawn((uint32_t)c, seed, thr))) ? xr[c] : 0.f;
+                orow[c] = (ok && !(thr && drawn((uint32_t)c, seed, thr))) ? xr[c] : 0.f;
         }
     }
 }
@@ -251,7 +190,7 @@ extern "C" int wsi_augment_nodes(const int64_t* desc, int32_t nseg, int32_t ntil
     if (!desc || !tile_sum || !counts || (ntiles > 0 && (!new_id || !kept))) { set_error("augment_nodes: null pointer"); return WSI_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     if (ntiles > 0) hipLaunchKernelGGL(aug_nodes_kernel<0>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, tile_sum, new_id, kept);
-    hipLaunchKernelGGL(aug_scan_tiles_kernel, dim3(1), dim3(256), 0, s, tile_sum, (int)ntiles, desc, AUG_NROW, (int)nseg, counts);
+    launch_tile_scan(tile_sum, (int)ntiles, desc, AUG_NROW, 2, (int)nseg, counts, s);
     if (ntiles > 0) hipLaunchKernelGGL(aug_nodes_kernel<1>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, tile_sum, new_id, kept);
     return check_launch("augment_nodes");
 }
@@ -267,9 +206,9 @@ extern "C" int wsi_augment_edges(const int64_t* desc, int32_t nseg, int32_t ntil
     hipStream_t s = (hipStream_t)stream;
     int32_t* sum2 = tile_sum + ntiles + 1;
     if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<0>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid);
-    hipLaunchKernelGGL(aug_scan_tiles_kernel, dim3(1), dim3(256), 0, s, tile_sum, (int)ntiles, desc, AUG_EROW, (int)nseg, counts);
+    launch_tile_scan(tile_sum, (int)ntiles, desc, AUG_EROW, 2, (int)nseg, counts, s);
     if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<1>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid);
-    hipLaunchKernelGGL(aug_scan_tiles_kernel, dim3(1), dim3(256), 0, s, sum2, (int)ntiles, desc, AUG_EROW, (int)nseg, counts);
+    launch_tile_scan(sum2, (int)ntiles, desc, AUG_EROW, 2, (int)nseg, counts, s);
     if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<2>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid);
     return check_launch("augment_edges");
 }

@@ -21,31 +21,6 @@ constexpr int BAG_THREADS = 256;
 constexpr int BAG_TILE = 128;     // rows whose weights a workgroup holds in LDS at a time (two per lane of the wave that forms them)
 constexpr int BAG_ROWS = 4;       // rows a wave of the backward carries through D together: one read of g_out[s] serves four rows
 
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-    return x;
-}
-
-// four consecutive floats at p (columns col .. col + 3 of a D-wide row); beyond D: 0
-__device__ __forceinline__ void load4(float (&v)[4], const float* __restrict__ p, int col, int D, bool vec) {
-    if (vec && col + 3 < D) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (col + i < D) ? p[i] : 0.f;
-    }
-}
-
-__device__ __forceinline__ void store4(float* __restrict__ p, const float (&v)[4], int col, int D, bool vec) {
-    if (vec && col + 3 < D) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (col + i < D) p[i] = v[i];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 template <int C>
 __global__ __launch_bounds__(BAG_THREADS) void bag_pool_stage1(const float* __restrict__ scores, int64_t lds, float scale,
@@ -114,7 +89,7 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_pool_stage1(const float* __re
 #pragma unroll 4
             for (int row = wave; row < nr; row += 4) {
                 float v[4];
-                load4(v, values + (int64_t)(t0 + row) * ldv + col, col, D, vec);
+                load4_tail(v, values + (int64_t)(t0 + row) * ldv + col, col, D, vec);
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const float w = sp[row][c];
@@ -233,7 +208,7 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_pool_bwd_rows(const float* __
             float v[BAG_ROWS][4], gv[BAG_ROWS][4];
 #pragma unroll
             for (int j = 0; j < BAG_ROWS; ++j) {
-                if (rb + j < r1) load4(v[j], values + (int64_t)(rb + j) * ldv + col, col, D, vec_v);
+                if (rb + j < r1) load4_tail(v[j], values + (int64_t)(rb + j) * ldv + col, col, D, vec_v);
                 else { v[j][0] = v[j][1] = v[j][2] = v[j][3] = 0.f; }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) gv[j][i] = 0.f;
@@ -241,7 +216,7 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_pool_bwd_rows(const float* __
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 float g[4];
-                load4(g, gs + (int64_t)c * D + col, col, D, vec_g);
+                load4_tail(g, gs + (int64_t)c * D + col, col, D, vec_g);
 #pragma unroll
                 for (int j = 0; j < BAG_ROWS; ++j) {
 #pragma unroll
@@ -254,7 +229,7 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_pool_bwd_rows(const float* __
             if (want_gv) {
 #pragma unroll
                 for (int j = 0; j < BAG_ROWS; ++j)
-                    if (rb + j < r1) store4(g_values + (int64_t)(rb + j) * ldgv + col, gv[j], col, D, vec_gv);
+                    if (rb + j < r1) store4_tail(g_values + (int64_t)(rb + j) * ldgv + col, gv[j], col, D, vec_gv);
             }
         }
         if (want_gs) {                          // (uniform)
@@ -291,11 +266,11 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_scores_fwd_rows(const float* 
         for (int c = 0; c < C; ++c) dot[c] = 0.f;
         for (int col = lane * 4; col < D; col += 256) {
             float v[4];
-            load4(v, x + (int64_t)r * ldx + col, col, D, vec_x);
+            load4_tail(v, x + (int64_t)r * ldx + col, col, D, vec_x);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 float g[4];
-                load4(g, ts + (int64_t)c * D + col, col, D, vec_t);
+                load4_tail(g, ts + (int64_t)c * D + col, col, D, vec_t);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) dot[c] = fmaf(g[i], v[i], dot[c]);
             }
@@ -335,7 +310,7 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_scores_bwd_rows(const float* 
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 float g[4];
-                load4(g, t + tb + (int64_t)c * D + col, col, D, vec_t);
+                load4_tail(g, t + tb + (int64_t)c * D + col, col, D, vec_t);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) a[i] = fmaf(wr[c], g[i], a[i]);
             }
@@ -343,17 +318,15 @@ __global__ __launch_bounds__(BAG_THREADS) void bag_scores_bwd_rows(const float* 
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     float g[4];
-                    load4(g, t2 + tb + (int64_t)c * D + col, col, D, vec_t);
+                    load4_tail(g, t2 + tb + (int64_t)c * D + col, col, D, vec_t);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) a[i] = fmaf(wr2[c], g[i], a[i]);
                 }
             }
-            store4(gx + (int64_t)r * ldgx + col, a, col, D, vec_gx);
+            store4_tail(gx + (int64_t)r * ldgx + col, a, col, D, vec_gx);
         }
     }
 }
-
-static inline bool bag_vec_ok(const void* p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0); }
 
 static inline int bag_check_c(const char* what, int32_t C) {
     if (C > 8) { set_error("%s: %d score columns (at most 8 are compiled)", what, (int)C); return WSI_ENOSYS; }
@@ -391,7 +364,7 @@ extern "C" int wsi_bag_softmax_pool_fwd(const float* scores, int64_t lds, int32_
     float* pl = pm + (int64_t)num_chunks * C;
     const dim3 g1(num_chunks, (D + 255) / 256), g2(num_segs, (C * D + BAG_S2_COLS - 1) / BAG_S2_COLS);
     if (num_chunks) {
-        BAG_DISPATCH_C(C, bag_pool_stage1, g1, dim3(BAG_THREADS), 0, st, scores, lds, scale, values, ldv, D, bag_vec_ok(values, ldv),
+        BAG_DISPATCH_C(C, bag_pool_stage1, g1, dim3(BAG_THREADS), 0, st, scores, lds, scale, values, ldv, D, vec_ok(values, ldv),
                        chunk_row, partial, pm, pl);
     }
     hipLaunchKernelGGL(bag_pool_stage2, g2, dim3(BAG_THREADS), 0, st, (const float*)partial, (const float*)pm, (const float*)pl, C, D,
@@ -415,9 +388,9 @@ extern "C" int wsi_bag_softmax_pool_bwd(const float* g_out, const float* out, co
     if (g_scores) hipLaunchKernelGGL(bag_pool_delta, dim3(num_segs * C), dim3(BAG_THREADS), 0, st, g_out, out, D, delta);
     // few chunks (one bag of 10 000 rows: 79) would leave most of the chip idle: up to 8 workgroups share a chunk's rows, towards ~2048 in all
     const int share = num_chunks >= 2048 ? 1 : (2048 / num_chunks > 8 ? 8 : 2048 / num_chunks);
-    BAG_DISPATCH_C(C, bag_pool_bwd_rows, dim3(num_chunks, share), dim3(BAG_THREADS), 0, st, g_out, bag_vec_ok(g_out, D), scores, lds, scale, stats,
-                   (const float*)delta, values, ldv, D, bag_vec_ok(values, ldv), chunk_row, chunk_seg, g_scores, ldgs, g_values, ldgv,
-                   bag_vec_ok(g_values, ldgv));
+    BAG_DISPATCH_C(C, bag_pool_bwd_rows, dim3(num_chunks, share), dim3(BAG_THREADS), 0, st, g_out, vec_ok(g_out, D), scores, lds, scale, stats,
+                   (const float*)delta, values, ldv, D, vec_ok(values, ldv), chunk_row, chunk_seg, g_scores, ldgs, g_values, ldgv,
+                   vec_ok(g_values, ldgv));
     return check_launch("bag_softmax_pool_bwd");
 }
 
@@ -429,7 +402,7 @@ extern "C" int wsi_bag_scores_fwd(const float* x, int64_t ldx, int32_t D, const 
     if (num_chunks == 0) return WSI_OK;
     if (!x || !t || !chunk_row || !chunk_seg || !scores) { set_error("bag_scores_fwd: null pointer"); return WSI_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
-    BAG_DISPATCH_C(C, bag_scores_fwd_rows, dim3(num_chunks), dim3(BAG_THREADS), 0, st, x, ldx, D, bag_vec_ok(x, ldx), t, bag_vec_ok(t, D),
+    BAG_DISPATCH_C(C, bag_scores_fwd_rows, dim3(num_chunks), dim3(BAG_THREADS), 0, st, x, ldx, D, vec_ok(x, ldx), t, vec_ok(t, D),
                    chunk_row, chunk_seg, scores, lds);
     return check_launch("bag_scores_fwd");
 }
@@ -443,6 +416,6 @@ extern "C" int wsi_bag_scores_bwd(const float* w, int64_t ldw, const float* t, c
     if (!w || !t || !chunk_row || !chunk_seg || !gx || ((w2 != nullptr) != (t2 != nullptr))) { set_error("bag_scores_bwd: null pointer"); return WSI_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     BAG_DISPATCH_C(C, bag_scores_bwd_rows, dim3(num_chunks), dim3(BAG_THREADS), 0, st, w, ldw, t, w2, ldw2, t2, D,
-                   bag_vec_ok(t, D) && (!t2 || bag_vec_ok(t2, D)), chunk_row, chunk_seg, gx, ldgx, bag_vec_ok(gx, ldgx));
+                   vec_ok(t, D) && (!t2 || vec_ok(t2, D)), chunk_row, chunk_seg, gx, ldgx, vec_ok(gx, ldgx));
     return check_launch("bag_scores_bwd");
 }

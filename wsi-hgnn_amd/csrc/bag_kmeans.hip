@@ -28,24 +28,6 @@ constexpr int KM_S2_COLS = 64;
 constexpr float KM_NORM_EPS = 1e-10f;       // tools/clustering.py:44
 constexpr float KM_SPLIT_EPS = 1.f / 1024.f;
 
-__device__ __forceinline__ void km_load4(float (&v)[4], const float* __restrict__ p, int col, int D, bool vec) {
-    if (vec && col + 3 < D) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (col + i < D) ? p[i] : 0.f;
-    }
-}
-
-__device__ __forceinline__ void km_store4(float* __restrict__ p, const float (&v)[4], int col, int D, bool vec) {
-    if (vec && col + 3 < D) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) if (col + i < D) p[i] = v[i];
-    }
-}
-
 // rows of the bag of chunk `ch`
 __device__ __forceinline__ int km_bag_rows(const int32_t* __restrict__ chunk_row, const int32_t* __restrict__ seg_chunk, int s) {
     return chunk_row[seg_chunk[s + 1]] - chunk_row[seg_chunk[s]];
@@ -100,7 +82,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_stage1(const float* __restr
 #pragma unroll
             for (int g = 0; g < NJ; ++g) {
                 const int col = g * 256 + lane * 4;
-                if (row < r1 && col < D) km_load4(v[j][g], x + (int64_t)row * ldx + col, col, D, vec_x);
+                if (row < r1 && col < D) load4_tail(v[j][g], x + (int64_t)row * ldx + col, col, D, vec_x);
                 else { v[j][g][0] = v[j][g][1] = v[j][g][2] = v[j][g][3] = 0.f; }
             }
         }
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_stage1(const float* __restr
     if (update && own && pcol < D) {
 #pragma unroll
         for (int k = 0; k < KP; ++k)
-            if (k < K) km_store4(partial + ((int64_t)ch * K + k) * D + pcol, acc[k], pcol, D, vec_p);
+            if (k < K) store4_tail(partial + ((int64_t)ch * K + k) * D + pcol, acc[k], pcol, D, vec_p);
     }
     if (lane == 0) sobj[wave] = obj;
     __syncthreads();
@@ -247,7 +229,7 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_stage1_wide(const float* __
                 float ss = 0.f;
                 for (int col = lane * 4; col < D; col += 256) {
                     float v[4];
-                    km_load4(v, xr + col, col, D, vec_x);
+                    load4_tail(v, xr + col, col, D, vec_x);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) ss = fmaf(v[i], v[i], ss);
                 }
@@ -259,8 +241,8 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_stage1_wide(const float* __
                 float d = 0.f;
                 for (int col = lane * 4; col < D; col += 256) {
                     float v[4], c[4];
-                    km_load4(v, xr + col, col, D, vec_x);
-                    km_load4(c, cen + (int64_t)k * D + col, col, D, vec_c);
+                    load4_tail(v, xr + col, col, D, vec_x);
+                    load4_tail(c, cen + (int64_t)k * D + col, col, D, vec_c);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const float e = v[i] * inv - c[i];
@@ -388,8 +370,8 @@ __global__ __launch_bounds__(KM_THREADS) void remix_nearest_kernel(const float* 
         float d = 0.f;
         for (int col = lane * 4; col < D; col += 256) {
             float a[4], c[4];
-            km_load4(a, sp + (int64_t)i * D + col, col, D, vec);
-            km_load4(c, tp + (int64_t)j * D + col, col, D, vec);
+            load4_tail(a, sp + (int64_t)i * D + col, col, D, vec);
+            load4_tail(c, tp + (int64_t)j * D + col, col, D, vec);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float e = a[q] - c[q];
@@ -445,15 +427,13 @@ __global__ __launch_bounds__(KM_THREADS) void remix_rows_kernel(const float* __r
     }
 }
 
-static inline bool km_vec_ok(const void* p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0); }
-
 }  // namespace wsi
 
 using namespace wsi;
 
-#define KM_LAUNCH(KP, NJ) hipLaunchKernelGGL((kmeans_stage1<KP, NJ>), dim3(num_chunks), dim3(KM_THREADS), 0, st, x, ldx, D, km_vec_ok(x, ldx),  \
+#define KM_LAUNCH(KP, NJ) hipLaunchKernelGGL((kmeans_stage1<KP, NJ>), dim3(num_chunks), dim3(KM_THREADS), 0, st, x, ldx, D, vec_ok(x, ldx),  \
                                              centroids, K, normalize != 0, update, chunk_row, chunk_seg, seg_chunk, labels, partial,              \
-                                             km_vec_ok(partial, D), pcount, pobj)
+                                             vec_ok(partial, D), pcount, pobj)
 #define KM_DISPATCH_NJ(KP)                                                                                \
     if (D <= 256) KM_LAUNCH(KP, 1); else if (D <= 512) KM_LAUNCH(KP, 2); else KM_LAUNCH(KP, 4)
 
@@ -473,8 +453,8 @@ extern "C" int wsi_bag_kmeans_step(const float* x, int64_t ldx, int32_t D, const
     float* pobj = partial + (int64_t)num_chunks * K * (D + 1);
     if (num_chunks) {
         if (D > 1024) {
-            hipLaunchKernelGGL(kmeans_stage1_wide, dim3(num_chunks), dim3(KM_THREADS), 0, st, x, ldx, D, km_vec_ok(x, ldx), centroids,
-                               km_vec_ok(centroids, D), K, normalize != 0, update, chunk_row, chunk_seg, seg_chunk, labels, partial, pcount, pobj);
+            hipLaunchKernelGGL(kmeans_stage1_wide, dim3(num_chunks), dim3(KM_THREADS), 0, st, x, ldx, D, vec_ok(x, ldx), centroids,
+                               vec_ok(centroids, D), K, normalize != 0, update, chunk_row, chunk_seg, seg_chunk, labels, partial, pcount, pobj);
         } else if (K <= 2) { KM_DISPATCH_NJ(2); }
         else if (K <= 4) { KM_DISPATCH_NJ(4); }
         else if (K <= 8) { KM_DISPATCH_NJ(8); }
@@ -491,7 +471,7 @@ extern "C" int wsi_remix_nearest(const float* protos, int32_t S, int32_t K, int3
     if (K > KM_MAX_K) { set_error("remix_nearest: %d prototypes per bag (at most %d are compiled)", (int)K, KM_MAX_K); return WSI_ENOSYS; }
     if (B == 0) return WSI_OK;
     if (!protos || !src || !tgt || !nearest) { set_error("remix_nearest: null pointer"); return WSI_EINVAL; }
-    hipLaunchKernelGGL(remix_nearest_kernel, dim3(B), dim3(KM_THREADS), 0, (hipStream_t)stream, protos, S, K, D, km_vec_ok(protos, D), src, tgt,
+    hipLaunchKernelGGL(remix_nearest_kernel, dim3(B), dim3(KM_THREADS), 0, (hipStream_t)stream, protos, S, K, D, vec_ok(protos, D), src, tgt,
                        nearest);
     return check_launch("remix_nearest");
 }

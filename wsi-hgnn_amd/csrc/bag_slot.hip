@@ -11,7 +11,6 @@
 //               row itself), then a streaming copy - 16-byte lane accesses when both sides allow, a scalar path otherwise.  Rows no bag owns
 //               (the filler of a slot) are zeroed.  The same launch writes the row -> segment table and copies the host-built small tables.
 #include "common.h"
-#include "gemm_common.h"
 
 namespace wsi {
 
@@ -21,9 +20,10 @@ constexpr int BS_SEL_WAVES = BS_SEL_THREADS / 64;
 constexpr int BS_ROW_THREADS = 256;
 constexpr int BS_ROWS = 16;             // destination rows per workgroup of the row kernel (4 per wave)
 
-__device__ __forceinline__ uint32_t bs_key(uint32_t i, uint32_t s, uint32_t mask) { return drop_fmix32(i * 0x9E3779B1u + s) & mask; }
+__device__ __forceinline__ uint32_t bs_key(uint32_t i, uint32_t s, uint32_t mask) { return index_hash(i, s) & mask; }
 
 // inclusive scan of v over the workgroup's threads in thread order; total = the sum over all of them.  (Two barriers: wsum is reused.)
+// Not common.h's block_scan_inclusive: this one serves 1024 threads (16 wave totals) and has its first barrier BEFORE the totals are written.
 __device__ __forceinline__ uint32_t bs_block_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll

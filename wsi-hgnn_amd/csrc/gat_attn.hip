@@ -20,7 +20,7 @@
 //   A     g_ft[u] = sum a~_e s_e g_rst[w];  g_a keeps the RAW dot r[e,h] = g_rst[w]_h . ft[u]_h
 //   B     d loss / d a~ = s_e r[e,h];  g_scale[e] = sum_h a~_{e,h} r[e,h]  (the lane that owns edge e adds its heads in order)
 // The unscaled instantiations contain none of it.
-#include "gemm_common.h"
+#include "common.h"
 #include <math.h>
 
 namespace wsi {
@@ -33,19 +33,7 @@ constexpr int GA_B_LANES = 16;             // group size of the scalar pass B
 
 enum { GA_ACT_NONE = 0, GA_ACT_RELU = 1, GA_ACT_LEAKY = 2 };
 
-template <int G>
-__device__ __forceinline__ float group_max(float x) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x = fmaxf(x, __shfl_xor(x, m));
-    return x;
-}
-
-__device__ __forceinline__ float ga_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
-
-template <int VEC>
-__device__ __forceinline__ void ga_load(float (&r)[VEC], const float* __restrict__ p) { load_vec<VEC>(r, p); }
-
-// head of every chunk of this lane (0 for chunks past the row: their loads and stores are skipped, their shuffles still run)
+// head of every chunk of this lane (0 for chunks past the row: their loads and stores are skipped, their group reductions still run)
 template <int G, int VEC, int NK>
 __device__ __forceinline__ void chunk_heads(int gl, int F, int D, int (&hk)[NK], bool (&ok)[NK]) {
 #pragma unroll
@@ -89,9 +77,9 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_scores_kernel(const float* __res
         if (ok[k]) {
             const int c = VEC * (gl + G * k);
             float x[VEC], al[VEC], ar[VEC];
-            ga_load<VEC>(x, ft + (int64_t)row * ldf + c);
-            ga_load<VEC>(al, attn_l + c);
-            ga_load<VEC>(ar, attn_r + c);
+            load_vec<VEC>(x, ft + (int64_t)row * ldf + c);
+            load_vec<VEC>(al, attn_l + c);
+            load_vec<VEC>(ar, attn_r + c);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) { pl[k] = fmaf(x[j], al[j], pl[k]); pr[k] = fmaf(x[j], ar[j], pr[k]); }
         }
@@ -117,7 +105,7 @@ __device__ __forceinline__ float softmax_lse(const float* __restrict__ eler, con
         const float erv = eler[(int64_t)v * 2 * H + H + h];
         float m = -INFINITY, l = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
-            const float s = ga_lrelu(eler[(int64_t)src[e] * 2 * H + h] + erv, slope);
+            const float s = leaky_relu(eler[(int64_t)src[e] * 2 * H + h] + erv, slope);
             if (s > m) { l = l * expf(m - s) + 1.f; m = s; }
             else l += expf(s - m);
         }
@@ -140,7 +128,7 @@ __device__ __forceinline__ float edge_factor(const GatDrop& dr, uint32_t seed, i
 }
 
 __device__ __forceinline__ float act_fwd(float z, int act, float act_slope) {
-    return act == GA_ACT_RELU ? fmaxf(z, 0.f) : act == GA_ACT_LEAKY ? ga_lrelu(z, act_slope) : z;
+    return act == GA_ACT_RELU ? fmaxf(z, 0.f) : act == GA_ACT_LEAKY ? leaky_relu(z, act_slope) : z;
 }
 
 template <int G, int VEC, int NK, bool SCALED>
@@ -172,7 +160,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
         const int u = src[e];
         float a = 0.f;
         if (gl < H) {
-            a = expf((ga_lrelu(eler[(int64_t)u * 2 * H + gl] + my_er, slope) - my_m) - my_ls) * edge_factor(dr, seed, e, gl, H);
+            a = expf((leaky_relu(eler[(int64_t)u * 2 * H + gl] + my_er, slope) - my_m) - my_ls) * edge_factor(dr, seed, e, gl, H);
             if constexpr (SCALED) a *= escale[e];
         }
         const float* __restrict__ row = ft + (int64_t)u * ldf;
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
             const float ak = __shfl(a, gbase + hk[k]);
             if (ok[k]) {
                 float x[VEC];
-                ga_load<VEC>(x, row + VEC * (gl + G * k));
+                load_vec<VEC>(x, row + VEC * (gl + G * k));
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) acc[k][j] = fmaf(ak, x[j], acc[k][j]);
             }
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
         if (ok[k]) {
             const int c = VEC * (gl + G * k);
             float b[VEC];
-            if (bias) ga_load<VEC>(b, bias + c);
+            if (bias) load_vec<VEC>(b, bias + c);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) acc[k][j] = act_fwd(acc[k][j] + (bias ? b[j] : 0.f), act, act_slope);
             store_vec<VEC>(out + (int64_t)v * ldo + c, acc[k]);
@@ -223,10 +211,10 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_act_bwd_kernel(const float* __re
             const int c = VEC * (gl + G * k);
             if (c < F) {
                 float g[VEC];
-                ga_load<VEC>(g, g_out + (int64_t)r * ldg + c);
+                load_vec<VEC>(g, g_out + (int64_t)r * ldg + c);
                 if (act != GA_ACT_NONE) {
                     float o[VEC];
-                    ga_load<VEC>(o, out + (int64_t)r * ldo + c);
+                    load_vec<VEC>(o, out + (int64_t)r * ldo + c);
 #pragma unroll
                     for (int j = 0; j < VEC; ++j) g[j] = o[j] > 0.f ? g[j] : (act == GA_ACT_RELU ? 0.f : g[j] * act_slope);
                     store_vec<VEC>(g_rst + (int64_t)r * F + c, g);
@@ -266,7 +254,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
     for (int k = 0; k < NK; ++k) {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { fu[k][j] = 0.f; acc[k][j] = 0.f; }
-        if (ok[k]) ga_load<VEC>(fu[k], ft + (int64_t)u * ldf + VEC * (gl + G * k));
+        if (ok[k]) load_vec<VEC>(fu[k], ft + (int64_t)u * ldf + VEC * (gl + G * k));
     }
     const float my_el = gl < H ? eler[(int64_t)u * 2 * H + gl] : 0.f;
     const int j0 = colptr[u], j1 = colptr[u + 1];
@@ -274,7 +262,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
         const int e = csc_eid[jj], w = csc_dst[jj];
         float a = 0.f;
         if (gl < H) {
-            a = expf((ga_lrelu(my_el + eler[(int64_t)w * 2 * H + H + gl], slope) - lse[(int64_t)w * 2 * H + gl]) - lse[(int64_t)w * 2 * H + H + gl]) *
+            a = expf((leaky_relu(my_el + eler[(int64_t)w * 2 * H + H + gl], slope) - lse[(int64_t)w * 2 * H + gl]) - lse[(int64_t)w * 2 * H + H + gl]) *
                 edge_factor(dr, seed, e, gl, H);
             if constexpr (SCALED) a *= escale[e];
         }
@@ -286,7 +274,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
             p[k] = 0.f;
             if (ok[k]) {
                 float g[VEC];
-                ga_load<VEC>(g, row + VEC * (gl + G * k));
+                load_vec<VEC>(g, row + VEC * (gl + G * k));
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) { acc[k][j] = fmaf(ak, g[j], acc[k][j]); p[k] = fmaf(g[j], fu[k][j], p[k]); }
             }
@@ -316,7 +304,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __re
         const float erv = eler[(int64_t)v * 2 * H + H + h], M = lse[(int64_t)v * 2 * H + h], LS = lse[(int64_t)v * 2 * H + H + h];
         float d = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
-            const float a = expf((ga_lrelu(eler[(int64_t)src[e] * 2 * H + h] + erv, slope) - M) - LS);
+            const float a = expf((leaky_relu(eler[(int64_t)src[e] * 2 * H + h] + erv, slope) - M) - LS);
             // t = d loss / d a: g_a times the factors of a~, rounded ONCE and kept in g_a for the second sweep.  delta and g_pre then see the
             // same number: a destination with one in-edge (a = 1, delta = t) gets a score gradient of exactly zero, as a softmax of one term
             // has (g_a * f - delta contracted into one fma would leave the rounding of the product there)
@@ -335,7 +323,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __re
         float gr = 0.f;
         for (int e = e0 + gl; e < e1; e += G) {
             const float pre = eler[(int64_t)src[e] * 2 * H + h] + erv;
-            const float a = expf((ga_lrelu(pre, slope) - M) - LS);
+            const float a = expf((leaky_relu(pre, slope) - M) - LS);
             const float gp = a * (g_a[(int64_t)e * H + h] - delta) * (pre > 0.f ? 1.f : slope);
             g_a[(int64_t)e * H + h] = gp;
             gr += gp;
@@ -366,8 +354,8 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_attn_kernel(const float* __r
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { al[k][j] = ar[k][j] = pl[k][j] = pr[k][j] = 0.f; }
         if (ok[k]) {
-            ga_load<VEC>(al[k], attn_l + VEC * (gl + G * k));
-            ga_load<VEC>(ar[k], attn_r + VEC * (gl + G * k));
+            load_vec<VEC>(al[k], attn_l + VEC * (gl + G * k));
+            load_vec<VEC>(ar[k], attn_r + VEC * (gl + G * k));
         }
     }
     for (int u = gid; u < n; u += groups) {
@@ -386,8 +374,8 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_attn_kernel(const float* __r
             if (ok[k]) {
                 const int c = VEC * (gl + G * k);
                 float x[VEC], g[VEC];
-                ga_load<VEC>(x, ft + (int64_t)u * ldf + c);
-                ga_load<VEC>(g, g_ft + (int64_t)u * ldgf + c);
+                load_vec<VEC>(x, ft + (int64_t)u * ldf + c);
+                load_vec<VEC>(g, g_ft + (int64_t)u * ldgf + c);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
                     g[j] = fmaf(lk, al[k][j], fmaf(rk, ar[k][j], g[j]));
@@ -437,10 +425,10 @@ __global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __rest
 #pragma unroll
         for (int j = 0; j < VEC; ++j) gw[k][j] = 0.f;
         if (c < D) {
-            ga_load<VEC>(gw[k], g + (int64_t)w * ldg + c);
+            load_vec<VEC>(gw[k], g + (int64_t)w * ldg + c);
             if (relu_ref) {
                 float y[VEC];
-                ga_load<VEC>(y, relu_ref + (int64_t)w * ldref + c);
+                load_vec<VEC>(y, relu_ref + (int64_t)w * ldref + c);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) gw[k][j] = y[j] > 0.f ? gw[k][j] : 0.f;
             }
@@ -457,7 +445,7 @@ __global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __rest
             const int c = VEC * (gl + G * k);
             if (c < D) {
                 float v[VEC];
-                ga_load<VEC>(v, row + c);
+                load_vec<VEC>(v, row + c);
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) p = fmaf(gw[k][j], v[j], p);
             }
@@ -471,8 +459,6 @@ __global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __rest
 struct GaCfg {
     int G, VEC, NK;
 };
-
-static bool aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
 
 // VEC = 4 when every row and pointer allows 16-byte accesses and a chunk stays inside one head; G = the smallest power of two
 // (>= 4, >= H, <= 64) that covers the row's chunks, NK the power of two of chunks per lane that covers the rest

@@ -1,5 +1,5 @@
 // Shared definitions of the grouped GEMM kernels (exact-fp32 MFMA in gemm_f32.hip, split-bf16 emulation in
-// gemm_emu16.hip): tile shape, by-value descriptor tables, XCD-aware tile remap.
+// gemm_emu16.hip): tile shape, by-value descriptor tables.  (The XCD-aware tile remap and the dropout hash: common.h.)
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -51,36 +51,6 @@ struct GemmParams {
     int32_t ablate_guarded; // measurement build: force the element-wise epilogue (WSI_F16G_EPI=g)
 #endif
 };
-
-__device__ __forceinline__ int xcd_remap(int b, int n) {
-    const int q = n >> 3, r = n & 7;
-    const int xcd = b & 7, idx = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-
-// ---- counter-based dropout (WSI_EPI_DROPOUT; the contract is in include/wsi_hgnn.h): one 32-bit hash decides a pair of columns
-__host__ __device__ __forceinline__ uint32_t drop_fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-__host__ __device__ __forceinline__ uint32_t drop_pair_hash(uint32_t row, uint32_t pair, uint32_t pairs_per_row, uint32_t seed) {
-    return drop_fmix32((row * pairs_per_row + pair) * 0x9E3779B1u + seed);
-}
-// factor (scale or 0) of element (row, col) of the masked tensor
-__device__ __forceinline__ float drop_factor1(uint32_t row, uint32_t col, uint32_t pairs, uint32_t seed, uint32_t thr, float scale) {
-    const uint32_t h = drop_pair_hash(row, col >> 1, pairs, seed);
-    return (((col & 1u) ? (h >> 16) : (h & 0xffffu)) >= thr) ? scale : 0.f;
-}
-// the four factors of columns col .. col + 3 of one row (col % 4 == 0): two hashes
-__device__ __forceinline__ float4 drop_factor4(uint32_t row, uint32_t col, uint32_t pairs, uint32_t seed, uint32_t thr, float scale) {
-    const uint32_t h0 = drop_pair_hash(row, col >> 1, pairs, seed), h1 = drop_pair_hash(row, (col >> 1) + 1, pairs, seed);
-    return make_float4((h0 & 0xffffu) >= thr ? scale : 0.f, (h0 >> 16) >= thr ? scale : 0.f, (h1 & 0xffffu) >= thr ? scale : 0.f, (h1 >> 16) >= thr ? scale : 0.f);
-}
-// the draw of this launch: the group's seed + the device word, read ONCE per epilogue into `wsi_drop_seed` (WSI_DROP_SEED), which the two macros use
-#define WSI_DROP_SEED(G, epi) const uint32_t wsi_drop_seed = (((epi) & WSI_EPI_DROPOUT) && (G).drop_seed_base) ? (G).drop_seed + *(G).drop_seed_base : (G).drop_seed
-#define WSI_DROP4(G, row_in_group, col_in_group) drop_factor4((uint32_t)((G).drop_row0 + (row_in_group)), (uint32_t)((G).drop_col0 + (col_in_group)), (G).drop_pairs, wsi_drop_seed, (G).drop_thr, (G).drop_scale)
-#define WSI_DROP1(G, row_in_group, col_in_group) drop_factor1((uint32_t)((G).drop_row0 + (row_in_group)), (uint32_t)((G).drop_col0 + (col_in_group)), (G).drop_pairs, wsi_drop_seed, (G).drop_thr, (G).drop_scale)
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 

@@ -72,15 +72,6 @@ template <> struct Emu<1> {
     static __device__ __forceinline__ f32x16 mfma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
-__device__ __forceinline__ float4 load4_guarded_b(const float* __restrict__ p, int i0, int n) {
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i0 + 0 < n) r.x = p[0];
-    if (i0 + 1 < n) r.y = p[1];
-    if (i0 + 2 < n) r.z = p[2];
-    if (i0 + 3 < n) r.w = p[3];
-    return r;
-}
-
 // ---- epilogue (same contract as gemm_f32.hip); fsm = >= 32 KB of LDS no longer read by anyone
 template <bool SPLITK>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& P, const GroupDesc& G, float* __restrict__ ws, float* fsm,
@@ -279,7 +270,7 @@ struct StageLoader {
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int o = o0 + rr + 64 * q;
-                r[q] = (o < o_end && k < k_end) ? load4_guarded_b(base + (int64_t)o * ld + k, k, k_end) : make_float4(0.f, 0.f, 0.f, 0.f);
+                r[q] = (o < o_end && k < k_end) ? load4_guarded(base + (int64_t)o * ld + k, k, k_end) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         } else {
             const int kr = nk_kp(tid), mg = nk_mg(tid);
@@ -287,7 +278,7 @@ struct StageLoader {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int k = k0 + 2 * kr + h;
-                r[h] = (k < k_end && o < o_end) ? load4_guarded_b(base + (int64_t)k * ld + o, o, o_end) : make_float4(0.f, 0.f, 0.f, 0.f);
+                r[h] = (k < k_end && o < o_end) ? load4_guarded(base + (int64_t)k * ld + o, o, o_end) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
     }
@@ -538,8 +529,6 @@ __global__ __launch_bounds__(256) void absmax_rows_kernel(const AbsmaxParams P) 
     // (fmaxf drops NaNs: a NaN element keeps its row's finite scale and propagates through the split as NaN)
     if (lane == 0) J.out[row] = b;
 }
-
-static inline bool vec_ok16(const void* p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0); }
 
 // ------------------------------------------------------------------------------------------------
 // fp16x3, NT / NN: the small operand (the weights) pre-packed in MFMA fragment order.
@@ -1297,7 +1286,7 @@ static void prepare_fp16x3(int op, GemmParams& P, float* ws, int64_t e_first, hi
                 next += (G.M + 3) & ~3;
                 if (G.K > 0) {
                     AbsmaxJob& J = R.j[R.njobs++];
-                    J.X = G.A; J.ld = G.lda; J.out = reinterpret_cast<uint32_t*>(ws) + off; J.vec = vec_ok16(G.A, G.lda) ? 1 : 0;
+                    J.X = G.A; J.ld = G.lda; J.out = reinterpret_cast<uint32_t*>(ws) + off; J.vec = vec_ok(G.A, G.lda) ? 1 : 0;
                     J.rows = G.M; J.cols = G.K; J.block_start = R.total_blocks;
                     R.total_blocks += (G.M + 3) / 4;
                 }
@@ -1322,7 +1311,7 @@ static void prepare_fp16x3(int op, GemmParams& P, float* ws, int64_t e_first, hi
             J.B[0] = G.B; J.B[1] = B1; J.B[2] = B2; J.ld = G.ldb; J.bits = reinterpret_cast<uint32_t*>(ws) + off;
             J.out = reinterpret_cast<uint16_t*>(ws + pnext);
             J.N = G.N; J.K = G.K; J.bchunk = G.bchunk; J.kc = b_kc ? 1 : 0; J.KB = (G.K + 15) >> 4; J.rows = (G.N + 127) & ~127;
-            J.vec = (vec_ok16(G.B, G.ldb) && (!B1 || vec_ok16(B1, G.ldb)) && (!B2 || vec_ok16(B2, G.ldb))) ? 1 : 0;
+            J.vec = (vec_ok(G.B, G.ldb) && (!B1 || vec_ok(B1, G.ldb)) && (!B2 || vec_ok(B2, G.ldb))) ? 1 : 0;
             J.block_start = K.total_blocks;
             K.total_blocks += J.rows / PR;
             pnext += (int64_t)J.rows * J.KB * 16;
@@ -1352,7 +1341,7 @@ int launch_pack_b(int op, const wsi_gemm_group_t* groups, int32_t ngroups, hipSt
         J.bits = reinterpret_cast<uint32_t*>(s.b_packed);
         J.out = reinterpret_cast<uint16_t*>(J.bits + ((s.N + 3) & ~3));
         J.N = s.N; J.K = s.K; J.bchunk = s.b_chunk; J.kc = b_kc ? 1 : 0; J.KB = (s.K + 15) >> 4; J.rows = (s.N + 127) & ~127;
-        J.vec = (vec_ok16(s.B, s.ldb) && (!B1 || vec_ok16(B1, s.ldb)) && (!B2 || vec_ok16(B2, s.ldb))) ? 1 : 0;
+        J.vec = (vec_ok(s.B, s.ldb) && (!B1 || vec_ok(B1, s.ldb)) && (!B2 || vec_ok(B2, s.ldb))) ? 1 : 0;
         J.block_start = K.total_blocks;
         K.total_blocks += J.rows / PR;
     }
@@ -1404,7 +1393,7 @@ extern "C" int wsi_row_absmax(const float* x, int64_t ld, int32_t rows, int32_t 
     wsi::AbsmaxParams R;
     R.njobs = 1; R.total_blocks = (rows + 3) / 4;
     R.j[0].X = x; R.j[0].ld = ld; R.j[0].out = out; R.j[0].rows = rows; R.j[0].cols = cols; R.j[0].block_start = 0;
-    R.j[0].vec = wsi::vec_ok16(x, ld) ? 1 : 0;
+    R.j[0].vec = wsi::vec_ok(x, ld) ? 1 : 0;
     hipLaunchKernelGGL(wsi::absmax_rows_kernel, dim3(R.total_blocks), dim3(256), 0, (hipStream_t)stream, R);
     return wsi::check_launch("row_absmax");
 }

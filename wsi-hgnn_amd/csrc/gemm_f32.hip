@@ -28,16 +28,6 @@
 
 namespace wsi {
 
-// 4 consecutive floats starting at p (logical index i0 of a dimension of extent n); zero beyond n. Scalar, any alignment.
-__device__ __forceinline__ float4 load4_guarded(const float* __restrict__ p, int i0, int n) {
-    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i0 + 0 < n) r.x = p[0];
-    if (i0 + 1 < n) r.y = p[1];
-    if (i0 + 2 < n) r.z = p[2];
-    if (i0 + 3 < n) r.w = p[3];
-    return r;
-}
-
 // Operand tile loader. "Outer" = the M (for A) or N (for B) dimension of the tile (128 wide),
 // "k" = the reduction dimension (32 deep).  KCONTIG: element (o,k) at base[o*ld + k]; else base[k*ld + o].
 //   load_fast   : unguarded 16-byte loads.  Requires a full k-tile (k0+BK <= k_end) and 16-byte alignment;
@@ -635,10 +625,6 @@ static bool launch_skinny(int32_t op, int32_t epilogue, const wsi_gemm_group_t* 
         else hipLaunchKernelGGL((gemm_skinny_kernel<WSI_GEMM_NN, 32>), gw, b, 0, st, P);
     }
     return true;
-}
-
-static inline bool vec_ok(const void* p, int64_t ld) {
-    return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0);
 }
 
 // TN split planning shared by workspace query and launch: one chunk length (multiple of BK) for all

@@ -449,7 +449,6 @@ __global__ __launch_bounds__(256) void colstat_final_kernel(const ColParams P) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline bool tn_vec_ok(const void* p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0); }
 
 // the tile form: 256 x 128 with two accumulator sets; measurement builds: WSI_TN16_CFG=256 selects 256 x 256 with one
 static int tn16_tile_n() {
@@ -546,7 +545,7 @@ int launch_gemm_tn16(int32_t epilogue, const wsi_gemm_group_t* groups, int32_t n
         d.tiles_n = pl.tiles_n[i]; d.tiles_mn = pl.tiles_m[i] * pl.tiles_n[i]; d.kchunk = pl.kchunk[i];
         d.tile_start = tiles;
         tiles += d.tiles_mn * pl.splits[i];
-        d.flags = (tn_vec_ok(s.A, s.lda) ? 1 : 0) | (tn_vec_ok(s.B, s.ldb) ? 2 : 0);
+        d.flags = (vec_ok(s.A, s.lda) ? 1 : 0) | (vec_ok(s.B, s.ldb) ? 2 : 0);
         d.ws_off = f;
         ReduceDesc& r = RP.g[RP.ngroups++];
         r.ws = ws + f; r.C = s.C; r.gate = s.gate; r.ldc = s.ldc; r.M = s.M; r.N = s.N; r.pad = 0; r.splits = pl.splits[i]; r.start = red_total;
@@ -583,7 +582,7 @@ int launch_gemm_tn16(int32_t epilogue, const wsi_gemm_group_t* groups, int32_t n
             J.part = wu + cursor; cursor += (int64_t)J.chunks * J.cols_pad;
             J.psum = nullptr;
             if (sum_out) { J.psum = reinterpret_cast<float*>(wu + cursor); cursor += (int64_t)J.chunks * J.cols_pad; }
-            J.vec = tn_vec_ok(X, ld) ? 1 : 0;
+            J.vec = vec_ok(X, ld) ? 1 : 0;
             J.block_start = pblocks; pblocks += J.chunks * J.col_blocks;
         }
         J.fblock_start = fblocks; fblocks += (cols + CF_COLS - 1) / CF_COLS;
@@ -630,7 +629,7 @@ extern "C" int wsi_col_stats(const float* x, int64_t ld, int32_t rows, int32_t c
     ColJob& J = CP.j[0];
     J.X = x; J.ld = ld; J.rows = rows; J.cols = cols; J.cols_pad = (int32_t)pad4(cols); J.col_blocks = (cols + 255) / 256;
     J.out = nullptr; J.sum_out = nullptr; J.gate = nullptr; J.own = 1; J.part_ld = part_ld; J.chunks = (rows + T_CH - 1) / T_CH;
-    J.part = part_max; J.psum = part_sum; J.vec = tn_vec_ok(x, ld) ? 1 : 0;
+    J.part = part_max; J.psum = part_sum; J.vec = vec_ok(x, ld) ? 1 : 0;
     J.block_start = 0; J.fblock_start = 0;
     hipLaunchKernelGGL(colstat_partial_kernel, dim3(J.chunks * J.col_blocks), dim3(256), 0, (hipStream_t)stream, CP);
     return check_launch("col_stats");
@@ -653,7 +652,7 @@ extern "C" int wsi_col_absmax(const float* x, int64_t ld, int32_t rows, int32_t 
     ColJob& J = CP.j[0];
     J.X = x; J.ld = ld; J.rows = rows; J.cols = cols; J.cols_pad = (int32_t)pad4(cols); J.col_blocks = (cols + 255) / 256;
     J.out = out; J.sum_out = nullptr; J.gate = nullptr; J.own = 1; J.part_ld = J.cols_pad; J.chunks = (rows + T_CH - 1) / T_CH;
-    J.part = reinterpret_cast<uint32_t*>(workspace); J.psum = nullptr; J.vec = tn_vec_ok(x, ld) ? 1 : 0;
+    J.part = reinterpret_cast<uint32_t*>(workspace); J.psum = nullptr; J.vec = vec_ok(x, ld) ? 1 : 0;
     J.block_start = 0; J.fblock_start = 0;
     hipStream_t st = (hipStream_t)stream;
     if (J.chunks > 0) hipLaunchKernelGGL(colstat_partial_kernel, dim3(J.chunks * J.col_blocks), dim3(256), 0, st, CP);

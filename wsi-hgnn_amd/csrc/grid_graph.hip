@@ -63,12 +63,6 @@ __device__ __forceinline__ int gg_set_of(const int32_t* __restrict__ set_ptr, in
     return lo;
 }
 
-__device__ __forceinline__ int gg_wave_max(int v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v = max(v, __shfl_xor(v, d));
-    return v;
-}
-
 // The maxima go through one atomic per wave and coordinate where the whole wave lies in one set (all but the waves on a set boundary): ten
 // thousand atomics on one address serialise in L2 and took 1.8 ms at 80 000 points; 64 times fewer take microseconds.
 __global__ __launch_bounds__(GG_BLOCK) void grid_index_kernel(const int32_t* __restrict__ coords, int P, const int32_t* __restrict__ set_ptr, int S,
@@ -80,9 +74,9 @@ __global__ __launch_bounds__(GG_BLOCK) void grid_index_kernel(const int32_t* __r
     const bool ok = in && gg_valid(x) && gg_valid(y);
     if (in && !ok) atomicOr(flags, WSI_GRID_BAD_COORD);
     const int s = in ? gg_set_of(set_ptr, S, p) : -1;
-    const int s_hi = gg_wave_max(s), s_lo = -gg_wave_max(in ? -s : -0x7fffffff);
+    const int s_hi = wave_max(s), s_lo = -wave_max(in ? -s : -0x7fffffff);
     if (s_lo == s_hi) {
-        const int mx = gg_wave_max(ok ? x : -1), my = gg_wave_max(ok ? y : -1);
+        const int mx = wave_max(ok ? x : -1), my = wave_max(ok ? y : -1);
         if ((threadIdx.x & 63) == 0 && mx >= 0) {                 // lane 0 holds the wave's lowest point: it is `in` whenever any lane is
             atomicMax(set_max + 2 * s_hi, mx);
             atomicMax(set_max + 2 * s_hi + 1, my);

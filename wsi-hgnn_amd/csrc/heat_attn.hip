@@ -49,13 +49,6 @@ struct AttnGraph {
                            // readout: the gathers of pass 3 then hit a table that stays in the L2); null = row w
 };
 
-// same bijective remap as the GEMMs' tile order (gemm_common.h)
-__device__ __forceinline__ int attn_xcd_remap(int b, int n) {
-    const int q = n >> 3, r = n & 7;
-    const int xcd = b & 7, idx = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
 constexpr int kHeavyDegree = 32;
 constexpr int kHeavyUnroll = 4;
 
@@ -94,7 +87,7 @@ constexpr int kWavesPerBlock = kBlock / 64;
 template <bool COOP = false>
 __device__ __forceinline__ int wave_uniform_node(const AttnGraph& g, int& lane) {
     lane = threadIdx.x & 63;
-    const int blk = (g.xcd && !COOP) ? attn_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int blk = (g.xcd && !COOP) ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
     int wave = COOP ? blk : blk * kWavesPerBlock + (int)(threadIdx.x >> 6);
     wave = __builtin_amdgcn_readfirstlane(wave);
     if (wave >= g.num_nodes) return -1;
@@ -547,7 +540,7 @@ __global__ __launch_bounds__(kBlock) void heat_attn_bwd_p3_kernel(
     const int32_t* __restrict__ gt_row, AttnPool pool) {
     constexpr int H = 64 / LPH;
     const int lane = threadIdx.x & 63;
-    const int blk = xcd ? attn_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int blk = xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
     int wave = blk * kWavesPerBlock + (int)(threadIdx.x >> 6);
     wave = __builtin_amdgcn_readfirstlane(wave);
     if (wave >= num_nodes) return;
@@ -675,7 +668,7 @@ __global__ __launch_bounds__(kBlock) void heat_attn_bwd_srcA_kernel(
     float* __restrict__ gv, int64_t ldgv, uint32_t* __restrict__ absmax) {
     constexpr int H = 64 / LPH;
     const int lane = threadIdx.x & 63;
-    const int blk = xcd ? attn_xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int blk = xcd ? xcd_remap((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
     int wave = blk * kWavesPerBlock + (int)(threadIdx.x >> 6);
     wave = __builtin_amdgcn_readfirstlane(wave);
     if (wave >= num_nodes) return;
@@ -1271,8 +1264,6 @@ int launch_bwd(const AttnTables& tb, const AttnGraph& gd, int32_t num_src, int32
 
 // flags bits 8..23: hub threshold (0 = the default kHeavyDegree)
 static int32_t heavy_degree(int32_t flags) { const int32_t t = (flags >> 8) & 0xffff; return t ? t : kHeavyDegree; }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace wsi
 

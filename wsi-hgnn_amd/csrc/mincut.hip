@@ -20,12 +20,6 @@ constexpr int MC_THREADS = 256;      // four waves: four rows in flight per work
 constexpr int MC_MAX_K = 128;
 constexpr int MC_MAX_SHARE = 8;
 
-__device__ __forceinline__ float mc_wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-    return x;
-}
-
 // the four waves' lane-uniform partial sums, added in wave order by thread 0
 __device__ __forceinline__ void mc_block_store(float a, int lane, int wave, float* __restrict__ dst) {
     __shared__ float sh[4];
@@ -48,7 +42,7 @@ __global__ __launch_bounds__(MC_THREADS) void mincut_rows_fwd(const float* __res
     for (int r = r0 + (int)blockIdx.y * 4 + wave; r < r1; r += 4 * (int)gridDim.y) {
         const float* __restrict__ zr = z + (int64_t)r * ldz;
         const float z0 = has0 ? zr[lane] : -INFINITY, z1 = has1 ? zr[lane + 64] : -INFINITY;
-        const float m = mc_wave_max(fmaxf(z0, z1));
+        const float m = wave_max(fmaxf(z0, z1));
         const float e0 = has0 ? expf(z0 - m) : 0.f, e1 = has1 ? expf(z1 - m) : 0.f;
         const float inv = 1.f / wave_sum(e0 + e1);
         const float s0 = e0 * inv, s1 = e1 * inv;

@@ -7,7 +7,7 @@
 //   source<0> : a wave per source node, lanes striding its CSC entries: the entry's relation, src_rel[edge] = its row, and per relation of the
 //               node's source type the number of entries (ballot + popcount, running counts in registers) -> counts[row].  Every row (r, u)
 //               belongs to exactly one (wave, relation): counts is written whole, no atomics.
-//   scan      : exclusive prefix sum of counts -> colptr_rel: tile sums, one workgroup scans them, tiles rank (as csrc/slot_aug.hip).
+//   scan      : exclusive prefix sum of counts -> colptr_rel: the two-level scan of common.h (tile sums, launch_tile_scan, tiles rank).
 //   source<1> : the same walk; an entry's rank inside its row is the running count + the popcount under the lane mask, so entries keep their
 //               relative order: csc_eid_rel / csc_dst_rel [colptr_rel[row] + rank].
 // Five launches on the caller's stream; integers only, no atomics, no allocation, no read-back: identical calls give identical bits.
@@ -119,22 +119,6 @@ __global__ __launch_bounds__(256) void pr_zero_kernel(int32_t* __restrict__ out,
     if (i < n) out[i] = 0;
 }
 
-// inclusive prefix of x over the workgroup's 256 lanes; total = the workgroup's sum
-__device__ __forceinline__ int pr_block_scan(int x, int* lds, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[w] = x;
-    __syncthreads();
-    const int t0 = lds[0], t1 = lds[1], t2 = lds[2], t3 = lds[3];
-    __syncthreads();
-    total = t0 + t1 + t2 + t3;
-    return x + (w > 0 ? t0 : 0) + (w > 1 ? t1 : 0) + (w > 2 ? t2 : 0);
-}
-
 __global__ __launch_bounds__(256) void pr_tile_sum_kernel(PlanRel a) {
     __shared__ int lds[4];
     int sum = 0;
@@ -143,22 +127,8 @@ __global__ __launch_bounds__(256) void pr_tile_sum_kernel(PlanRel a) {
         sum += i < a.NS ? a.counts[i] : 0;
     }
     int total;
-    pr_block_scan(sum, lds, total);
+    block_scan_inclusive(sum, lds, total);
     if (threadIdx.x == 0) a.partials[blockIdx.x] = total;
-}
-
-// tile sums -> their exclusive prefix, in place; one workgroup
-__global__ __launch_bounds__(256) void pr_scan_partials_kernel(PlanRel a) {
-    __shared__ int lds[4];
-    int carry = 0;
-    for (int base = 0; base < a.ntiles; base += 256) {
-        const int i = base + threadIdx.x;
-        const int v = i < a.ntiles ? a.partials[i] : 0;
-        int total;
-        const int incl = pr_block_scan(v, lds, total);
-        if (i < a.ntiles) a.partials[i] = carry + incl - v;
-        carry += total;
-    }
 }
 
 __global__ __launch_bounds__(256) void pr_tile_scan_kernel(PlanRel a) {
@@ -168,7 +138,7 @@ __global__ __launch_bounds__(256) void pr_tile_scan_kernel(PlanRel a) {
         const int i = blockIdx.x * PR_TILE + r * 256 + threadIdx.x;
         const int v = i < a.NS ? a.counts[i] : 0;
         int total;
-        const int incl = pr_block_scan(v, lds, total);
+        const int incl = block_scan_inclusive(v, lds, total);
         if (i < a.NS) a.colptr_rel[i] = run + incl - v;
         if (i == a.NS - 1) a.colptr_rel[a.NS] = run + incl;
         run += total;
@@ -225,7 +195,7 @@ extern "C" int wsi_plan_by_relation(const int32_t* src, const int32_t* colptr, c
     const dim3 waves((unsigned)((num_nodes + 3) / 4));
     hipLaunchKernelGGL(pr_source_kernel<0>, waves, dim3(256), 0, s, a);
     hipLaunchKernelGGL(pr_tile_sum_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(pr_scan_partials_kernel, dim3(1), dim3(256), 0, s, a);
+    launch_tile_scan(a.partials, a.ntiles, nullptr, 0, 0, 0, nullptr, s);
     hipLaunchKernelGGL(pr_tile_scan_kernel, dim3((unsigned)a.ntiles), dim3(256), 0, s, a);
     hipLaunchKernelGGL(pr_source_kernel<1>, waves, dim3(256), 0, s, a);
     return check_launch("plan_by_relation");

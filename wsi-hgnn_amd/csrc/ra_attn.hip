@@ -25,14 +25,6 @@ constexpr int RA_BLOCK = 256;
 constexpr int RA_MAX_WIDTH = 4096;
 constexpr int RA_S_LANES = 16;             // group size of the scalar passes B and C
 
-template <int G>
-__device__ __forceinline__ float ra_group_max(float x) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) x = fmaxf(x, __shfl_xor(x, m));
-    return x;
-}
-
-__device__ __forceinline__ float ra_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 __device__ __forceinline__ int ra_type(const int32_t* __restrict__ node_type, int u) { return min(max(node_type[u], 0), 2); }
 __device__ __forceinline__ float ra_pick(int t, float a, float b, float c) { return t == 0 ? a : t == 1 ? b : c; }
 
@@ -53,7 +45,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
     for (int k = 0; k < 3; ++k) { m[k] = -INFINITY; l[k] = 0.f; cn[k] = 0.f; ps[k] = 0.f; }
     for (int e = e0 + gl; e < e1; e += G) {
         const int u = src[e], t = ra_type(node_type, u);
-        const float s = ra_lrelu(sc[(int64_t)u * 4] + erv, slope), p = sc[(int64_t)u * 4 + 2];
+        const float s = leaky_relu(sc[(int64_t)u * 4] + erv, slope), p = sc[(int64_t)u * 4 + 2];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             if (t == k) {
@@ -68,14 +60,14 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
     float qmax = -INFINITY;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float Mk = ra_group_max<G>(m[k]);
+        const float Mk = group_max<G>(m[k]);
         const float L = group_sum<G>(m[k] == -INFINITY ? 0.f : l[k] * expf(m[k] - Mk));
         cn[k] = group_sum<G>(cn[k]);
         ps[k] = group_sum<G>(ps[k]);
         const bool present = cn[k] > 0.f;
         M[k] = present ? Mk : INFINITY;
         LS[k] = present ? logf(L) : 0.f;
-        q[k] = present ? ra_lrelu(ps[k] / cn[k] + prv, slope) : -INFINITY;
+        q[k] = present ? leaky_relu(ps[k] / cn[k] + prv, slope) : -INFINITY;
         qmax = fmaxf(qmax, q[k]);
     }
     float den = 0.f;
@@ -96,7 +88,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
         if (me < e1) {
             u_m = src[me];
             const int t = ra_type(node_type, u_m);
-            const float s = ra_lrelu(sc[(int64_t)u_m * 4] + erv, slope);
+            const float s = leaky_relu(sc[(int64_t)u_m * 4] + erv, slope);
             a_m = expf((s - ra_pick(t, M[0], M[1], M[2])) - ra_pick(t, LS[0], LS[1], LS[2])) * ra_pick(t, beta[0], beta[1], beta[2]);
         }
         const int cnt = min(G, e1 - base);
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_src_kernel(const float* __res
             e_m = csc_eid[me];
             w_m = csc_dst[me];
             const float* __restrict__ st = stat + (int64_t)w_m * 12 + t * 4;
-            a_m = expf((ra_lrelu(el + sc[(int64_t)w_m * 4 + 1], slope) - st[0]) - st[1]) * st[3];
+            a_m = expf((leaky_relu(el + sc[(int64_t)w_m * 4 + 1], slope) - st[0]) - st[1]) * st[3];
         }
         const int cnt = min(G, j1 - base);
         for (int j = 0; j < cnt; ++j) {
@@ -217,7 +209,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_dst_kernel(const float* __res
     }
     for (int e = e0 + gl; e < e1; e += G) {
         const int u = src[e], t = ra_type(node_type, u);
-        const float s = ra_lrelu(sc[(int64_t)u * 4] + erv, slope);
+        const float s = leaky_relu(sc[(int64_t)u * 4] + erv, slope);
         const float a = expf((s - ra_pick(t, M[0], M[1], M[2])) - ra_pick(t, LS[0], LS[1], LS[2]));
         const float ar = a * r[e], p = sc[(int64_t)u * 4 + 2];
 #pragma unroll
@@ -235,7 +227,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_dst_kernel(const float* __res
     for (int e = e0 + gl; e < e1; e += G) {
         const int u = src[e], t = ra_type(node_type, u);
         const float pre = sc[(int64_t)u * 4] + erv;
-        const float a = expf((ra_lrelu(pre, slope) - ra_pick(t, M[0], M[1], M[2])) - ra_pick(t, LS[0], LS[1], LS[2]));
+        const float a = expf((leaky_relu(pre, slope) - ra_pick(t, M[0], M[1], M[2])) - ra_pick(t, LS[0], LS[1], LS[2]));
         const float gp = ra_pick(t, beta[0], beta[1], beta[2]) * a * (r[e] - ra_pick(t, A[0], A[1], A[2])) * (pre > 0.f ? 1.f : slope);
         r[e] = gp;
         ger += gp;
@@ -304,8 +296,6 @@ struct RaCfg {
     int G, VEC, NK;
 };
 
-static bool ra_aligned16(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }
-
 // VEC = 4 when every row and pointer allows 16-byte accesses; G = the smallest power of two (>= 4, <= 64) that covers the row's chunks,
 // NK the power of two of chunks per lane that covers the rest
 static RaCfg ra_cfg(int C, bool vec4_ok) {
@@ -354,7 +344,7 @@ extern "C" int wsi_ra_attn_fwd(const float* ft, int64_t ldf, const float* sc, co
     if (ldf < C || ldo < C) { set_error("ra_attn_fwd: row stride below C"); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
     if (!ft || !sc || !node_type || !rowptr || !src || !out || !stat) { set_error("ra_attn_fwd: null pointer"); return WSI_EINVAL; }
-    const RaCfg cfg = ra_cfg(C, ldf % 4 == 0 && ldo % 4 == 0 && ra_aligned16(ft) && ra_aligned16(out) && ra_aligned16(bias));
+    const RaCfg cfg = ra_cfg(C, ldf % 4 == 0 && ldo % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(bias));
     hipStream_t st = (hipStream_t)stream;
     const int per = RA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((ra_fwd_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(RA_BLOCK), 0, st, ft, ldf, sc, node_type, n, C, \
@@ -382,7 +372,7 @@ extern "C" int wsi_ra_attn_bwd(const float* ft, int64_t ldf, const float* sc, co
         set_error("ra_attn_bwd: null pointer");
         return WSI_EINVAL;
     }
-    const RaCfg cfg = ra_cfg(C, ldf % 4 == 0 && ldg % 4 == 0 && ldgf % 4 == 0 && ra_aligned16(ft) && ra_aligned16(g_out) && ra_aligned16(g_ft));
+    const RaCfg cfg = ra_cfg(C, ldf % 4 == 0 && ldg % 4 == 0 && ldgf % 4 == 0 && aligned16(ft) && aligned16(g_out) && aligned16(g_ft));
     const int per = RA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((ra_bwd_src_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(RA_BLOCK), 0, st, ft, ldf, sc, node_type, stat, \
                                             g_out, ldg, n, C, colptr, csc_eid, csc_dst, negative_slope, g_ft, ldgf, edge_ws)

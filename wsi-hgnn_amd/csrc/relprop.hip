@@ -24,8 +24,6 @@ __device__ __forceinline__ float lrp_sd(float a, float b) {
     return b != 0.f ? a / den : 0.f;
 }
 
-static inline bool lrp_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------ linear
 constexpr int LL_THREADS = 256;
 constexpr int LL_TM = 4;               // token rows per workgroup
@@ -193,25 +191,6 @@ __global__ __launch_bounds__(LR_THREADS) void lrp_residual_kernel(const float* _
 constexpr int LA_MAX_N = 128;
 constexpr int LA_THREADS = 4 * LA_MAX_N;
 
-template <int D>
-__device__ __forceinline__ float la_dot(const float (&a)[D], const float* __restrict__ b) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; c += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(b + c);
-        acc = fmaf(a[c], v.x, acc); acc = fmaf(a[c + 1], v.y, acc); acc = fmaf(a[c + 2], v.z, acc); acc = fmaf(a[c + 3], v.w, acc);
-    }
-    return acc;
-}
-
-template <int D>
-__device__ __forceinline__ void la_stage(float* __restrict__ dst, const float* __restrict__ src, int64_t ld, int n) {
-    for (int i = threadIdx.x; i < n * (D / 4); i += LA_THREADS) {
-        const int row = i / (D / 4), c = (i - row * (D / 4)) * 4;
-        *reinterpret_cast<float4*>(dst + row * D + c) = *reinterpret_cast<const float4*>(src + (int64_t)row * ld + c);
-    }
-}
-
 // dst: the heads' terms [G * C * H, n, n] (H > 1) or M itself (H = 1)
 template <int D>
 __global__ __launch_bounds__(LA_THREADS) void lrp_attention_kernel(const float* __restrict__ qkv, const float* __restrict__ lse, const float* __restrict__ R,
@@ -225,11 +204,11 @@ __global__ __launch_bounds__(LA_THREADS) void lrp_attention_kernel(const float* 
     __shared__ __attribute__((aligned(16))) float sq[LA_MAX_N * D], sk[LA_MAX_N * D], sv[LA_MAX_N * D], sr[LA_MAX_N * D], sg[LA_MAX_N * D],
         ss2[LA_MAX_N * D];
     __shared__ float sl[LA_MAX_N];
-    la_stage<D>(sq, base, ld, n);
-    la_stage<D>(sk, base + lr, ld, n);
-    la_stage<D>(sv, base + 2 * lr, ld, n);
-    la_stage<D>(sr, R + gc * n * lr + h * D, lr, n);
-    if (g_out) la_stage<D>(sg, g_out + gc * n * lr + h * D, lr, n);
+    stage_rows<D, LA_THREADS>(sq, base, ld, n);
+    stage_rows<D, LA_THREADS>(sk, base + lr, ld, n);
+    stage_rows<D, LA_THREADS>(sv, base + 2 * lr, ld, n);
+    stage_rows<D, LA_THREADS>(sr, R + gc * n * lr + h * D, lr, n);
+    if (g_out) stage_rows<D, LA_THREADS>(sg, g_out + gc * n * lr + h * D, lr, n);
     if ((int)threadIdx.x < n) sl[threadIdx.x] = lse[(g * H + h) * n + threadIdx.x];
     __syncthreads();
     const int i = threadIdx.x >> 2, part = threadIdx.x & 3;
@@ -241,7 +220,7 @@ __global__ __launch_bounds__(LA_THREADS) void lrp_attention_kernel(const float* 
         for (int c = 0; c < D; ++c) { q[c] = sq[i * D + c]; acc[c] = 0.f; gi[c] = g_out ? sg[i * D + c] : 0.f; }
         const float li = sl[i];
         for (int j = part; j < n; j += 4) {
-            const float p = expf(la_dot<D>(q, sk + j * D) * scale - li);
+            const float p = expf(dot4<D>(q, sk + j * D) * scale - li);
 #pragma unroll
             for (int c = 0; c < D; ++c) acc[c] = fmaf(p, sv[j * D + c], acc[c]);
         }
@@ -253,12 +232,12 @@ __global__ __launch_bounds__(LA_THREADS) void lrp_attention_kernel(const float* 
         }
         float* __restrict__ m = dst + (blk * n + i) * n;
         for (int j = part; j < n; j += 4) {
-            const float z1 = la_dot<D>(q, sk + j * D);
-            const float ca = expf(z1 * scale - li) * la_dot<D>(s2, sv + j * D) * 0.5f;
+            const float z1 = dot4<D>(q, sk + j * D);
+            const float ca = expf(z1 * scale - li) * dot4<D>(s2, sv + j * D) * 0.5f;
             const float s1 = lrp_sd(ca, z1);
 #pragma unroll
             for (int c = 0; c < D; ++c) acc[c] = fmaf(s1, sk[j * D + c], acc[c]);
-            m[j] = fmaxf(g_out ? la_dot<D>(gi, sv + j * D) * ca : ca, 0.f);
+            m[j] = fmaxf(g_out ? dot4<D>(gi, sv + j * D) * ca : ca, 0.f);
         }
         float* __restrict__ o = cbase + (int64_t)i * ld;
 #pragma unroll
@@ -274,9 +253,9 @@ __global__ __launch_bounds__(LA_THREADS) void lrp_attention_kernel(const float* 
 #pragma unroll
     for (int c = 0; c < D; ++c) { kj[c] = sk[i * D + c]; vj[c] = sv[i * D + c]; ak[c] = 0.f; av[c] = 0.f; }
     for (int r = part; r < n; r += 4) {
-        const float z1 = la_dot<D>(kj, sq + r * D);
+        const float z1 = dot4<D>(kj, sq + r * D);
         const float p = expf(z1 * scale - sl[r]);
-        const float s1 = lrp_sd(p * la_dot<D>(vj, ss2 + r * D) * 0.5f, z1);
+        const float s1 = lrp_sd(p * dot4<D>(vj, ss2 + r * D) * 0.5f, z1);
 #pragma unroll
         for (int c = 0; c < D; ++c) { ak[c] = fmaf(s1, sq[r * D + c], ak[c]); av[c] = fmaf(p, ss2[r * D + c], av[c]); }
     }
@@ -333,7 +312,7 @@ extern "C" int wsi_lrp_residual(const float* X, const float* r1, const float* r2
     if (E % 4) { set_error("lrp_residual: width %d (compiled: a multiple of 4)", (int)E); return WSI_ENOSYS; }
     if (G == 0 || C == 0 || n == 0) return WSI_OK;
     if (!r1 || !A || !B || !out_a || !out_b || (r2 && !X)) { set_error("lrp_residual: null pointer"); return WSI_EINVAL; }
-    if (!lrp_aligned(r1) || !lrp_aligned(A) || !lrp_aligned(B) || !lrp_aligned(out_a) || !lrp_aligned(out_b) || (r2 && (!lrp_aligned(r2) || !lrp_aligned(X)))) {
+    if (!aligned16(r1) || !aligned16(A) || !aligned16(B) || !aligned16(out_a) || !aligned16(out_b) || (r2 && (!aligned16(r2) || !aligned16(X)))) {
         set_error("lrp_residual: every tensor must be 16-byte aligned");
         return WSI_EINVAL;
     }
@@ -350,7 +329,7 @@ extern "C" int wsi_lrp_attention(const float* qkv, const float* lse, const float
     }
     if (G == 0 || C == 0 || n == 0) return WSI_OK;
     if (!qkv || !lse || !R || !cam_qkv || !M || (H > 1 && !partial)) { set_error("lrp_attention: null pointer"); return WSI_EINVAL; }
-    if (!lrp_aligned(qkv) || !lrp_aligned(R) || (g_out && !lrp_aligned(g_out))) {
+    if (!aligned16(qkv) || !aligned16(R) || (g_out && !aligned16(g_out))) {
         set_error("lrp_attention: qkv, R and g_out must be 16-byte aligned");
         return WSI_EINVAL;
     }

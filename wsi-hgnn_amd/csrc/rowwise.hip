@@ -10,12 +10,6 @@ namespace wsi {
 constexpr int RW_BLOCK = 256;
 constexpr int RW_WAVES = RW_BLOCK / 64;
 
-__device__ __forceinline__ int row_of_wave(int n) {
-    int w = (int)blockIdx.x * RW_WAVES + (int)(threadIdx.x >> 6);
-    w = __builtin_amdgcn_readfirstlane(w);
-    return w < n ? w : -1;
-}
-
 // ------------------------------------------------------------------------------------------ LayerNorm
 // y = (x - mean) * rstd * gamma + beta over the last dim (eps inside the sqrt, biased variance: torch.nn.LayerNorm,
 // models/HGT.py:57,124).  gamma/beta are selected per row through row_param[row] (node type -> norms[n_id]).
@@ -24,7 +18,7 @@ __global__ __launch_bounds__(RW_BLOCK) void layernorm_fwd_kernel(const float* __
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                   const int32_t* __restrict__ row_param,
                                                                   float* __restrict__ y, int64_t ldy, float* __restrict__ stats) {
-    const int r = row_of_wave(n);
+    const int r = row_of_wave<RW_WAVES>(n);
     if (r < 0) return;
     const int lane = threadIdx.x & 63;
     float v[NV];
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(RW_BLOCK) void layernorm_bwd_kernel(const float* __
                                                                   int n, int D, const float* __restrict__ gamma, const int32_t* __restrict__ row_param,
                                                                   const float* __restrict__ stats, float* __restrict__ gx, int64_t ldgx,
                                                                   float* __restrict__ xhat_gy, int64_t ldp) {
-    const int r = row_of_wave(n);
+    const int r = row_of_wave<RW_WAVES>(n);
     if (r < 0) return;
     const int lane = threadIdx.x & 63;
     const float mean = stats[2 * (int64_t)r], rstd = stats[2 * (int64_t)r + 1];
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(RW_BLOCK) void spmm_sum_kernel(const float* __restr
                                                              const float* __restrict__ bias, int relu,
                                                              const float* __restrict__ relu_ref, int64_t ldref,
                                                              float* __restrict__ out, int64_t ldo) {
-    const int w = row_of_wave(n_out);
+    const int w = row_of_wave<RW_WAVES>(n_out);
     if (w < 0) return;
     const int lane = threadIdx.x & 63;
     float acc[NV];
@@ -219,9 +213,8 @@ extern "C" int wsi_spmm_sum(const float* x, int64_t ldx, int32_t n_out, int32_t 
 }
 
 // ------------------------------------------------------------------------------------------------
-// wsi_dropout_apply: out = keep(seed, row, col) ? x * scale : 0 with the counter-based mask of WSI_EPI_DROPOUT (gemm_common.h): the backward of the
+// wsi_dropout_apply: out = keep(seed, row, col) ? x * scale : 0 with the counter-based mask of WSI_EPI_DROPOUT (common.h): the backward of the
 // nn.Dropout of models/HEATNet4.py:135 (g_y = g_out * mask) without a stored mask.  HBM-bound streaming: 16-byte lane accesses, two hashes per four columns.
-#include "gemm_common.h"
 namespace wsi {
 __global__ __launch_bounds__(256) void dropout_apply_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ out, int64_t ldo, int rows, int cols,
                                                             int row0, uint32_t pairs, int col0, uint32_t seed0, const uint32_t* __restrict__ seed_base, uint32_t thr, float scale, int vec) {

@@ -312,8 +312,6 @@ __global__ __launch_bounds__(256) void gate_grad_stage2(const float* __restrict_
     }
 }
 
-static inline bool vec_ok(const void* p, int64_t ld) { return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 4 == 0); }
-
 }  // namespace wsi
 
 using namespace wsi;

@@ -78,6 +78,34 @@ __global__ __launch_bounds__(256) void segment_table_kernel(const int64_t* __res
     }
 }
 
+// The middle level of every two-level compaction scan (common.h: launch_tile_scan), for the node/edge draws of augment.hip, the leave-one-out
+// rows of loo.hip, the flag segments of slot_aug.hip and, with nseg == 0 (no counts), the per-relation counts of plan_rel.hip.  One workgroup
+// walks any number of tiles in rounds of 256 and carries the running total from round to round.
+__global__ __launch_bounds__(256) void tile_scan_kernel(int32_t* __restrict__ tile_sum, int ntiles, const int64_t* __restrict__ rows, int stride,
+                                                        int col, int nseg, int32_t* __restrict__ counts) {
+    __shared__ int lds[4];
+    int carry = 0;
+    for (int base = 0; base < ntiles; base += 256) {
+        const int i = base + threadIdx.x;
+        const int v = i < ntiles ? tile_sum[i] : 0;
+        int total;
+        const int incl = block_scan_inclusive(v, lds, total);
+        if (i < ntiles) tile_sum[i] = carry + incl - v;
+        carry += total;
+    }
+    if (threadIdx.x == 0) tile_sum[ntiles] = carry;
+    __syncthreads();                      // the prefix is read back below by other lanes of this workgroup
+    for (int s = threadIdx.x; s < nseg; s += 256) {
+        const int a = (int)rows[(int64_t)s * stride + col];
+        const int b = s + 1 < nseg ? (int)rows[(int64_t)(s + 1) * stride + col] : ntiles;
+        counts[s] = tile_sum[b] - tile_sum[a];
+    }
+}
+
+void launch_tile_scan(int32_t* tile_sum, int ntiles, const int64_t* rows, int stride, int col, int nseg, int32_t* counts, hipStream_t st) {
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, ntiles, rows, stride, col, nseg, counts);
+}
+
 static int launch_segment_table(const char* who, const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
     if (nsegs < 0 || total_blocks < 0) { set_error("%s: bad argument", who); return WSI_EINVAL; }
     if (nsegs == 0 || total_blocks == 0) return WSI_OK;

@@ -20,42 +20,15 @@ constexpr int SA_MAX_N = 128;
 constexpr int SA_THREADS = 4 * SA_MAX_N;
 
 template <int D>
-__device__ __forceinline__ float sa_dot(const float (&a)[D], const float* __restrict__ b) {
-    float acc = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; c += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(b + c);
-        acc = fmaf(a[c], v.x, acc); acc = fmaf(a[c + 1], v.y, acc); acc = fmaf(a[c + 2], v.z, acc); acc = fmaf(a[c + 3], v.w, acc);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ float sa_quad_sum(float x) { return group_sum<4>(x); }
-
-__device__ __forceinline__ float sa_quad_max(float x) {
-    x = fmaxf(x, dpp_mov<0xB1>(x));
-    return fmaxf(x, dpp_mov<0x4E>(x));
-}
-
-// rows [n, D] of one head's column block (src points at its first column of the sequence's first row) -> LDS
-template <int D>
-__device__ __forceinline__ void sa_stage(float* __restrict__ dst, const float* __restrict__ src, int64_t ld, int n) {
-    for (int i = threadIdx.x; i < n * (D / 4); i += SA_THREADS) {
-        const int row = i / (D / 4), c = (i - row * (D / 4)) * 4;
-        *reinterpret_cast<float4*>(dst + row * D + c) = *reinterpret_cast<const float4*>(src + (int64_t)row * ld + c);
-    }
-}
-
-template <int D>
 __global__ __launch_bounds__(SA_THREADS) void seq_attn_fwd(const float* __restrict__ qkv, int32_t n, int32_t H, float scale,
                                                            float* __restrict__ out, float* __restrict__ lse) {
     const int b = blockIdx.x / H, h = blockIdx.x - b * H;
     const int64_t ld = 3 * (int64_t)H * D;
     const float* __restrict__ base = qkv + (int64_t)b * n * ld + h * D;
     __shared__ __attribute__((aligned(16))) float sq[SA_MAX_N * D], sk[SA_MAX_N * D], sv[SA_MAX_N * D];
-    sa_stage<D>(sq, base, ld, n);
-    sa_stage<D>(sk, base + (int64_t)H * D, ld, n);
-    sa_stage<D>(sv, base + 2 * (int64_t)H * D, ld, n);
+    stage_rows<D, SA_THREADS>(sq, base, ld, n);
+    stage_rows<D, SA_THREADS>(sk, base + (int64_t)H * D, ld, n);
+    stage_rows<D, SA_THREADS>(sv, base + 2 * (int64_t)H * D, ld, n);
     __syncthreads();
     const int i = threadIdx.x >> 2, part = threadIdx.x & 3;
     if (i >= n) return;                                   // (whole quads leave together; no barrier follows)
@@ -63,21 +36,21 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attn_fwd(const float* __restri
 #pragma unroll
     for (int c = 0; c < D; ++c) q[c] = sq[i * D + c] * scale;
     float m = -INFINITY;
-    for (int j = part; j < n; j += 4) m = fmaxf(m, sa_dot<D>(q, sk + j * D));
-    m = sa_quad_max(m);                                   // (n >= 1: key 0 belongs to part 0, so the quad's maximum is finite)
+    for (int j = part; j < n; j += 4) m = fmaxf(m, dot4<D>(q, sk + j * D));
+    m = group_max<4>(m);                                   // (n >= 1: key 0 belongs to part 0, so the quad's maximum is finite)
     float l = 0.f, acc[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) acc[c] = 0.f;
     for (int j = part; j < n; j += 4) {
-        const float p = expf(sa_dot<D>(q, sk + j * D) - m);
+        const float p = expf(dot4<D>(q, sk + j * D) - m);
         l += p;
 #pragma unroll
         for (int c = 0; c < D; ++c) acc[c] = fmaf(p, sv[j * D + c], acc[c]);
     }
-    l = sa_quad_sum(l);
+    l = group_sum<4>(l);
     const float inv = 1.f / l;
 #pragma unroll
-    for (int c = 0; c < D; ++c) acc[c] = sa_quad_sum(acc[c]) * inv;
+    for (int c = 0; c < D; ++c) acc[c] = group_sum<4>(acc[c]) * inv;
     // the quad's four lanes write a quarter of the row each
     float* __restrict__ o = out + ((int64_t)b * n + i) * H * D + h * D;
 #pragma unroll
@@ -96,10 +69,10 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attn_bwd(const float* __restri
     float* __restrict__ gbase = g_qkv + (int64_t)b * n * ld + h * D;
     __shared__ __attribute__((aligned(16))) float sq[SA_MAX_N * D], sk[SA_MAX_N * D], sv[SA_MAX_N * D], sg[SA_MAX_N * D];
     __shared__ float sl[SA_MAX_N], sd[SA_MAX_N];
-    sa_stage<D>(sq, base, ld, n);
-    sa_stage<D>(sk, base + (int64_t)H * D, ld, n);
-    sa_stage<D>(sv, base + 2 * (int64_t)H * D, ld, n);
-    sa_stage<D>(sg, g_out + (int64_t)b * n * H * D + h * D, (int64_t)H * D, n);
+    stage_rows<D, SA_THREADS>(sq, base, ld, n);
+    stage_rows<D, SA_THREADS>(sk, base + (int64_t)H * D, ld, n);
+    stage_rows<D, SA_THREADS>(sv, base + 2 * (int64_t)H * D, ld, n);
+    stage_rows<D, SA_THREADS>(sg, g_out + (int64_t)b * n * H * D + h * D, (int64_t)H * D, n);
     if ((int)threadIdx.x < n) sl[threadIdx.x] = lse[((int64_t)b * H + h) * n + threadIdx.x];
     __syncthreads();
     const int i = threadIdx.x >> 2, part = threadIdx.x & 3;
@@ -111,21 +84,21 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attn_bwd(const float* __restri
         for (int c = 0; c < D; ++c) { q[c] = sq[i * D + c] * scale; g[c] = sg[i * D + c]; }
         const float li = sl[i];
         float delta = 0.f;
-        for (int j = part; j < n; j += 4) delta = fmaf(expf(sa_dot<D>(q, sk + j * D) - li), sa_dot<D>(g, sv + j * D), delta);
-        delta = sa_quad_sum(delta);
+        for (int j = part; j < n; j += 4) delta = fmaf(expf(dot4<D>(q, sk + j * D) - li), dot4<D>(g, sv + j * D), delta);
+        delta = group_sum<4>(delta);
         if (part == 0) sd[i] = delta;
         float gq[D];
 #pragma unroll
         for (int c = 0; c < D; ++c) gq[c] = 0.f;
         for (int j = part; j < n; j += 4) {
-            const float ds = expf(sa_dot<D>(q, sk + j * D) - li) * (sa_dot<D>(g, sv + j * D) - delta);
+            const float ds = expf(dot4<D>(q, sk + j * D) - li) * (dot4<D>(g, sv + j * D) - delta);
 #pragma unroll
             for (int c = 0; c < D; ++c) gq[c] = fmaf(ds, sk[j * D + c], gq[c]);
         }
         float* __restrict__ o = gbase + (int64_t)i * ld;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
-            const float tot = sa_quad_sum(gq[c]) * scale;
+            const float tot = group_sum<4>(gq[c]) * scale;
             if (c / (D / 4) == part) o[c] = tot;
         }
     }
@@ -136,8 +109,8 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attn_bwd(const float* __restri
 #pragma unroll
     for (int c = 0; c < D; ++c) { kj[c] = sk[i * D + c] * scale; vj[c] = sv[i * D + c]; gk[c] = 0.f; gv[c] = 0.f; }
     for (int r = part; r < n; r += 4) {
-        const float p = expf(sa_dot<D>(kj, sq + r * D) - sl[r]);
-        const float ds = p * (sa_dot<D>(vj, sg + r * D) - sd[r]);
+        const float p = expf(dot4<D>(kj, sq + r * D) - sl[r]);
+        const float ds = p * (dot4<D>(vj, sg + r * D) - sd[r]);
 #pragma unroll
         for (int c = 0; c < D; ++c) { gv[c] = fmaf(p, sg[r * D + c], gv[c]); gk[c] = fmaf(ds, sq[r * D + c], gk[c]); }
     }
@@ -145,7 +118,7 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attn_bwd(const float* __restri
     float* __restrict__ ov = gbase + (int64_t)i * ld + 2 * (int64_t)H * D;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-        const float tk = sa_quad_sum(gk[c]) * scale, tv = sa_quad_sum(gv[c]);
+        const float tk = group_sum<4>(gk[c]) * scale, tv = group_sum<4>(gv[c]);
         if (c / (D / 4) == part) { ok[c] = tk; ov[c] = tv; }
     }
 }
@@ -159,8 +132,6 @@ static inline int sa_check(const char* what, int32_t B, int32_t n, int32_t H, in
     return WSI_OK;
 }
 
-static inline bool sa_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace wsi
 
 using namespace wsi;
@@ -169,7 +140,7 @@ extern "C" int wsi_seq_attn_fwd(const float* qkv, int32_t B, int32_t n, int32_t 
     if (int rc = sa_check("seq_attn_fwd", B, n, H, d)) return rc;
     if (B == 0 || n == 0) return WSI_OK;
     if (!qkv || !out || !lse) { set_error("seq_attn_fwd: null pointer"); return WSI_EINVAL; }
-    if (!sa_aligned(qkv)) { set_error("seq_attn_fwd: qkv must be 16-byte aligned"); return WSI_EINVAL; }
+    if (!aligned16(qkv)) { set_error("seq_attn_fwd: qkv must be 16-byte aligned"); return WSI_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     if (d == 8) hipLaunchKernelGGL(seq_attn_fwd<8>, dim3(B * H), dim3(SA_THREADS), 0, st, qkv, n, H, scale, out, lse);
     else hipLaunchKernelGGL(seq_attn_fwd<16>, dim3(B * H), dim3(SA_THREADS), 0, st, qkv, n, H, scale, out, lse);
@@ -181,7 +152,7 @@ extern "C" int wsi_seq_attn_bwd(const float* g_out, const float* qkv, const floa
     if (int rc = sa_check("seq_attn_bwd", B, n, H, d)) return rc;
     if (B == 0 || n == 0) return WSI_OK;
     if (!g_out || !qkv || !lse || !g_qkv) { set_error("seq_attn_bwd: null pointer"); return WSI_EINVAL; }
-    if (!sa_aligned(qkv) || !sa_aligned(g_out)) { set_error("seq_attn_bwd: qkv and g_out must be 16-byte aligned"); return WSI_EINVAL; }
+    if (!aligned16(qkv) || !aligned16(g_out)) { set_error("seq_attn_bwd: qkv and g_out must be 16-byte aligned"); return WSI_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     if (d == 8) hipLaunchKernelGGL(seq_attn_bwd<8>, dim3(B * H), dim3(SA_THREADS), 0, st, g_out, qkv, lse, n, H, scale, g_qkv);
     else hipLaunchKernelGGL(seq_attn_bwd<16>, dim3(B * H), dim3(SA_THREADS), 0, st, g_out, qkv, lse, n, H, scale, g_qkv);

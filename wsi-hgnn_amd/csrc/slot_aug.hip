@@ -1,13 +1,12 @@
 // Fill of a padded batch slot with AUGMENTED slides (graph.slot_fill_augmented): the draw is taken on the device (wsi_augment_nodes /
 // wsi_augment_edges over one descriptor row per (slide, node type) / (slide, relation)), and the slot's tables are written from the survivors'
 // counts WITHOUT reading them back.  A stored slide's plan pieces are in CSR order already and DropNode renumbers monotonically, so the pieces of
-// the augmented slide are stable compactions of the stored ones: keep flags -> two-level exclusive scans (tile sums, one workgroup scans them,
-// tiles rank) -> one single-thread layout kernel (csrc/slot_layout.h) turns the counts into every offset -> the real slides PUSH their surviving
-// entries to (device offset + rank), grids sized by the stored counts; the filler and the tails are PULLED by position, grids sized by the
+// the augmented slide are stable compactions of the stored ones: keep flags -> the two-level scans of common.h -> one single-thread layout kernel
+// (csrc/slot_layout.h) turns the counts into every offset -> the real slides PUSH their surviving entries to (device offset + rank), grids sized by the stored counts; the filler and the tails are PULLED by position, grids sized by the
 // capacities, from the closed forms of csrc/slot_math.h.  No atomics: every position is a scan result.  Contract: include/wsi_hgnn.h.
 #include <string.h>
 
-#include "gemm_common.h"
+#include "common.h"
 #include "slot_layout.h"
 #include "slot_math.h"
 
@@ -35,37 +34,12 @@ struct Args {
 constexpr int SA_WORDS = 55;
 static_assert(sizeof(Args) == SA_WORDS * 8, "the argument words and the struct must agree");
 
-__device__ __forceinline__ uint32_t sa_hash(uint32_t i, uint32_t sub) { return drop_fmix32(i * 0x9E3779B1u + sub); }
-__device__ __forceinline__ bool sa_drawn(uint32_t i, uint32_t sub, uint32_t thr) { return (sa_hash(i, sub) & 0xffffu) < thr; }
-
 // misc block: noff[B T] (first element of (b, t) in new_id / kept / keys), nstored[B T], coo_base[B], labels[G], shuffle sub-seeds [B T]
 __device__ __forceinline__ const int64_t* sa_noff(const Args& a) { return a.desc + a.off_misc; }
 __device__ __forceinline__ const int64_t* sa_nstored(const Args& a) { return a.desc + a.off_misc + a.B * a.T; }
 __device__ __forceinline__ const int64_t* sa_coo_base(const Args& a) { return a.desc + a.off_misc + 2 * a.B * a.T; }
 __device__ __forceinline__ const int64_t* sa_labels(const Args& a) { return a.desc + a.off_misc + 2 * a.B * a.T + a.B; }
 __device__ __forceinline__ const int64_t* sa_key_seed(const Args& a) { return a.desc + a.off_misc + 2 * a.B * a.T + a.B + a.G; }
-
-__device__ __forceinline__ int sa_find(const int64_t* __restrict__ rows, int row, int col, int nseg, int b) {      // last row whose word `col` is <= b
-    int lo = 0, hi = nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (rows[(int64_t)mid * row + col] <= b) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// exclusive prefix of a 0/1 flag over the workgroup's 256 lanes (ballot + popcount per wave, the four wave totals through LDS)
-__device__ __forceinline__ int sa_flag_scan(bool flag, int* lds, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int excl = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) lds[w] = __popcll(m);
-    __syncthreads();
-    const int t0 = lds[0], t1 = lds[1], t2 = lds[2], t3 = lds[3];
-    __syncthreads();
-    total = t0 + t1 + t2 + t3;
-    return excl + (w > 0 ? t0 : 0) + (w > 1 ? t1 : 0) + (w > 2 ? t2 : 0);
-}
 
 // does element i of flag segment d survive the draw
 __device__ __forceinline__ bool sa_keep(const Args& a, const int64_t* __restrict__ d, int64_t i) {
@@ -74,7 +48,7 @@ __device__ __forceinline__ bool sa_keep(const Args& a, const int64_t* __restrict
         const int64_t m = reinterpret_cast<const int64_t*>(d[4])[i];
         const int64_t* e = a.desc + a.off_edge + (b * a.R + (m >> 40)) * SA_EROW;
         const int rk = a.rank1[sa_coo_base(a)[b] + (m & SA_COO_MASK)];
-        return rk >= 0 && !(e[10] != 0 && sa_drawn((uint32_t)rk, (uint32_t)e[8], (uint32_t)e[9]));
+        return rk >= 0 && !(e[10] != 0 && drawn((uint32_t)rk, (uint32_t)e[8], (uint32_t)e[9]));
     }
     const int64_t l = reinterpret_cast<const int64_t*>(d[4])[i], t = reinterpret_cast<const int64_t*>(d[5])[i];
     return a.new_id[sa_noff(a)[b * a.T + t] + l] >= 0;
@@ -86,7 +60,7 @@ __global__ __launch_bounds__(256) void sa_flags_kernel(Args a) {
     __shared__ int lds[4];
     const int blk = blockIdx.x;
     const int64_t* rows = a.desc + a.off_flag;
-    const int64_t* d = rows + (int64_t)sa_find(rows, SA_FROW, 2, (int)a.nflag, blk) * SA_FROW;
+    const int64_t* d = rows + (int64_t)find_row(rows, SA_FROW, 2, (int)a.nflag, blk) * SA_FROW;
     const int64_t n = d[0], off = d[1];
     const int ft = (int)d[2];
     const int64_t i0 = (int64_t)(blk - ft) * SA_TILE;
@@ -95,44 +69,11 @@ __global__ __launch_bounds__(256) void sa_flags_kernel(Args a) {
         const int64_t i = i0 + r * 256 + threadIdx.x;
         const bool keep = i < n && sa_keep(a, d, i);
         int total;
-        const int excl = sa_flag_scan(keep, lds, total);
+        const int excl = block_flag_scan(keep, lds, total);
         if (PASS == 1 && i < n) a.frank[off + i] = keep ? run + excl : ~(run + excl);
         run += total;
     }
     if (PASS == 0 && threadIdx.x == 0) a.ftile[blk] = run;
-}
-
-// tile sums -> exclusive prefix in place (ftile[ntiles] = total), fcnt[s] = kept entries of segment s; one workgroup
-__global__ __launch_bounds__(256) void sa_scan_kernel(Args a) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int ntiles = (int)a.flag_tiles, nseg = (int)a.nflag;
-    int carry = 0;
-    for (int base = 0; base < ntiles; base += 256) {
-        const int i = base + threadIdx.x;
-        const int v = i < ntiles ? a.ftile[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        const int t0 = wsum[0], t1 = wsum[1], t2 = wsum[2], t3 = wsum[3];
-        __syncthreads();
-        const int before = (w > 0 ? t0 : 0) + (w > 1 ? t1 : 0) + (w > 2 ? t2 : 0);
-        if (i < ntiles) a.ftile[i] = carry + before + x - v;
-        carry += t0 + t1 + t2 + t3;
-    }
-    if (threadIdx.x == 0) a.ftile[ntiles] = carry;
-    __syncthreads();
-    const int64_t* rows = a.desc + a.off_flag;
-    for (int s = threadIdx.x; s < nseg; s += 256) {
-        const int lo = (int)rows[(int64_t)s * SA_FROW + 2];
-        const int hi = s + 1 < nseg ? (int)rows[(int64_t)(s + 1) * SA_FROW + 2] : ntiles;
-        a.fcnt[s] = a.ftile[hi] - a.ftile[lo];
-    }
 }
 
 // counts -> every offset of the fill and the readout's small tables; labels ride along
@@ -155,7 +96,7 @@ __global__ __launch_bounds__(256) void sa_keys_kernel(Args a) {
     while (s > 0 && noff[s] > x) --s;
     const int64_t i = x - noff[s];
     const int64_t limit = a.ns_mode == 2 ? (int64_t)a.ncnt[s] : sa_nstored(a)[s];
-    const int64_t key = i < limit ? (a.ns_mode == 0 ? i : (int64_t)sa_hash((uint32_t)i, (uint32_t)sa_key_seed(a)[s])) : (1ll << 32);
+    const int64_t key = i < limit ? (a.ns_mode == 0 ? i : (int64_t)index_hash((uint32_t)i, (uint32_t)sa_key_seed(a)[s])) : (1ll << 32);
     a.keys[x] = ((int64_t)s << 33) | key;
 }
 
@@ -171,7 +112,7 @@ __device__ __forceinline__ int64_t sa_prefix(const Args& a, int64_t s, int64_t v
 __global__ __launch_bounds__(256) void sa_push_kernel(Args a) {
     const int blk = blockIdx.x;
     const int64_t* rows = a.desc + a.off_push;
-    const int64_t* d = rows + (int64_t)sa_find(rows, SA_PROW, 1, (int)a.npush, blk) * SA_PROW;
+    const int64_t* d = rows + (int64_t)find_row(rows, SA_PROW, 1, (int)a.npush, blk) * SA_PROW;
     const int64_t n = d[0], kind = d[2], b = d[3], t = d[4], B = a.B, T = a.T;
     const int64_t* L = a.L;
     const int64_t* node = L + SLOT_L_NODE(B, T);
@@ -310,15 +251,15 @@ __global__ __launch_bounds__(256) void sa_feat_kernel(Args a) {
         for (int c = 4 * lane; c < F; c += 256) {
             float4 v = xr ? *reinterpret_cast<const float4*>(xr + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (xr && thr) {
-                if (sa_drawn((uint32_t)c, seed, thr)) v.x = 0.f;
-                if (sa_drawn((uint32_t)c + 1, seed, thr)) v.y = 0.f;
-                if (sa_drawn((uint32_t)c + 2, seed, thr)) v.z = 0.f;
-                if (sa_drawn((uint32_t)c + 3, seed, thr)) v.w = 0.f;
+                if (drawn((uint32_t)c, seed, thr)) v.x = 0.f;
+                if (drawn((uint32_t)c + 1, seed, thr)) v.y = 0.f;
+                if (drawn((uint32_t)c + 2, seed, thr)) v.z = 0.f;
+                if (drawn((uint32_t)c + 3, seed, thr)) v.w = 0.f;
             }
             *reinterpret_cast<float4*>(orow + c) = v;
         }
     } else {
-        for (int c = lane; c < F; c += 64) orow[c] = (xr && !(thr && sa_drawn((uint32_t)c, seed, thr))) ? xr[c] : 0.f;
+        for (int c = lane; c < F; c += 64) orow[c] = (xr && !(thr && drawn((uint32_t)c, seed, thr))) ? xr[c] : 0.f;
     }
 }
 
@@ -356,7 +297,7 @@ extern "C" int wsi_slot_aug_scan(const int64_t* args, void* stream) {
     }
     hipStream_t s = (hipStream_t)stream;
     if (a->flag_tiles > 0) hipLaunchKernelGGL(sa_flags_kernel<0>, dim3((unsigned)a->flag_tiles), dim3(256), 0, s, *a);
-    hipLaunchKernelGGL(sa_scan_kernel, dim3(1), dim3(256), 0, s, *a);
+    launch_tile_scan(a->ftile, (int)a->flag_tiles, a->desc + a->off_flag, SA_FROW, 2, (int)a->nflag, a->fcnt, s);
     if (a->flag_tiles > 0) hipLaunchKernelGGL(sa_flags_kernel<1>, dim3((unsigned)a->flag_tiles), dim3(256), 0, s, *a);
     hipLaunchKernelGGL(sa_layout_kernel, dim3(1), dim3(64), 0, s, *a);
     return check_launch("slot_aug_scan");
