@@ -7,6 +7,7 @@
   (--captured-eval: trainer.CapturedSlotEval, the epoch's metrics kept on the device).
 
 Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation;
+                           --captured-slots 3 --augment --quota --optimizer adam: captured slots sized for the draw;
                            --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers)
 Run data-parallel on N:    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_synthetic.py
 """
@@ -43,6 +44,9 @@ def main(argv=None):
                     help="train through trainer.CapturedSlotStep over K padded batch slots by slide size (DESIGN 3.15): one captured step per slot, "
                          "replayed over every new batch that fits; needs --optimizer adam, sgd or adadelta (capturable).  With --augment the slots draw the "
                          "augmentation on the device in front of every replay (DESIGN 3.16)")
+    ap.add_argument("--quota", action="store_true",
+                    help="with --captured-slots and --augment: size the slots for the draw instead of for the stored slides - survivor quotas "
+                         "(data.BatchSlot(quota=\"bound\"), DESIGN 3.28); the epoch line then reports in how many fills a quota bound (expected 0)")
     ap.add_argument("--captured-eval", action="store_true",
                     help="evaluate through trainer.CapturedSlotEval (DESIGN 3.17): one captured forward per slot, the epoch's metrics accumulated on the "
                          "device and read back once; with --captured-slots the training metrics of the epoch come from the captured step as well")
@@ -114,12 +118,22 @@ def main(argv=None):
         # slot k holds any `batch` slides out of the smallest (k + 1) / K of the data set; the last one every batch
         its, K = sorted(loader.items, key=lambda it: sum(it.num_nodes)), args.captured_slots
         top = lambda xs: sum(sorted(xs, reverse=True)[:args.batch])
+        nodes_of, edges_of = (lambda it: it.num_nodes), (lambda it: it.pieces.ecount)
+        if args.quota:
+            if not args.augment:
+                raise SystemExit("--quota: quotas limit the survivors of a draw; add --augment")
+            # the same classes over the slides' quotas: what a draw leaves of a slide at most (it binds with probability 2 ** -32 per table)
+            spec = data.slot_augment_spec(loader.transform)
+            dst = [its[0].ntypes.index(r[2]) for r in its[0].rels]
+            nodes_of = lambda it: data.slot_quota_bound(it, spec)[0]
+            edges_of = lambda it: [sum(q for q, d in zip(data.slot_quota_bound(it, spec)[1], dst) if d == t) for t in range(len(it.num_nodes))]
         caps = []
         for k in range(K):
             part = its[:max(args.batch, (len(its) * (k + 1) + K - 1) // K)]
-            caps.append(([top([it.num_nodes[t] for it in part]) + 1 for t in range(len(its[0].num_nodes))], [top([it.pieces.ecount[t] for it in part]) for t in range(len(its[0].num_nodes))], args.batch))
+            caps.append(([top([nodes_of(it)[t] for it in part]) + 1 for t in range(len(its[0].num_nodes))], [top([edges_of(it)[t] for it in part]) for t in range(len(its[0].num_nodes))], args.batch))
         gnn.train()
-        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c, per_relation_src=hgt) for c in caps], metrics=train_metrics)
+        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c, per_relation_src=hgt, quota="bound" if args.quota else None) for c in caps],
+                                             metrics=train_metrics)
 
     # 3. epochs
     for epoch in range(args.epochs):
@@ -138,6 +152,8 @@ def main(argv=None):
         metrics = io.evaluate(gnn, eval_loader) if slot_eval is None else slot_eval.evaluate()
         if rank == 0:
             print(f"epoch {epoch}: train loss {tot / max(n, 1):.4f}  eval {metrics}")
+            if slot_step is not None and args.quota:                            # one read-back per slot and epoch
+                print(f"epoch {epoch}: fills truncated by a quota so far {slot_step.overflows()} of {slot_step.replays} replayed steps")
             if train_metrics is not None:                                       # train_gnn.py:104-108, one read-back per epoch
                 print(f"epoch {epoch}: train metrics {train_metrics.compute()}")
             store.save_model(gnn.state_dict(), version=epoch + 1, stats={"epoch": epoch, "loss": tot / max(n, 1), **metrics})

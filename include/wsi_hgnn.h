@@ -850,16 +850,21 @@ int wsi_stas(int32_t fill, int32_t kN, const int64_t* perm, const int32_t* n_idx
  * first_tile = tiles of the segments before it; ntiles = their total.  Outputs of a segment are written at its OWN offset `off` (capacity n):
  * no output position depends on another segment's count, and none on an atomic: two-level exclusive scans, stable order, reproducible.
  *
- * wsi_augment_nodes : rows of 6 words [n, off, first_tile, sub-seed, threshold, 0].  new_id[off + i] <- new id of node i of the type (survivors
- *                     keep their order) or -1; kept[off + r] <- old id of the type's r-th survivor; counts[s] <- survivors of segment s.
- *                     tile_sum: scratch, ntiles + 1 int32.
- * wsi_augment_edges : rows of 14 words [n, off, first_tile, u, v, sim, src_off, dst_off, sub-seed, threshold, mode, n_src, n_dst, 0]; u, v: device
+ * wsi_augment_nodes : rows of 6 words [n, off, first_tile, sub-seed, threshold, quota + 1].  new_id[off + i] <- new id of node i of the type
+ *                     (survivors keep their order) or -1; kept[off + r] <- old id of the type's r-th survivor; counts[s] <- survivors of
+ *                     segment s.  tile_sum: scratch, ntiles + 1 int32.  Last word 0: no quota.  Last word q + 1: of the nodes the draw
+ *                     keeps only the first q (node-id order) stay, the others get new_id -1 exactly as if drawn, counts[s] <- min(kept, q);
+ *                     the tile sums (and tile_sum[ntiles]) stay those of the DRAW.  A quota the draw does not reach changes nothing.
+ * wsi_augment_edges : rows of 14 words [n, off, first_tile, u, v, sim, src_off, dst_off, sub-seed, threshold, mode, n_src, n_dst, quota + 1]; u, v: device
  *                     pointers to the relation's int64 endpoints (local ids), sim: to its fp32 edge scalar or 0; src_off / dst_off: offsets of
  *                     the endpoint types in new_id (new_id NULL: no node was removed).  Stage 1 keeps the edges whose endpoints both survive
  *                     (an endpoint outside [0, n_src) / [0, n_dst) removes the edge) and ranks them; mode 0 draws DropEdge by the edge's
  *                     ORIGINAL position (DropEdge in front of DropNode), mode 1 by that rank (behind it); threshold 0: no DropEdge.
  *                     out_u / out_v [off + r] <- renumbered endpoints of the relation's r-th final survivor, out_sim its sim, out_eid its original
  *                     position; counts[s] <- final survivors.  tile_sum: scratch, 2 * (ntiles + 1) int32; rank1: scratch, one int32 per edge.
+ *                     Last word 0: no quota; rank1 keeps the stage-1 rank.  Last word q + 1: only the first q final survivors (input order) are
+ *                     written, counts[s] <- min(final, q), and rank1[off + i] ends as -1 for EVERY edge that is not among them (by either
+ *                     draw or by the quota), its stage-1 rank otherwise; the second half of tile_sum stays the draw's.
  * wsi_augment_keys  : rows as for wsi_augment_nodes (threshold unused): keys[off + i] <- (segment << 32) | h(i): ONE stable ascending sort of
  *                     keys orders every node type at once.
  * wsi_gather_rows_masked : out[i, c] = zeroed(c) ? 0 : x[row_of[i], c] for i < rows, c < F  (row_of NULL: row i; an index outside
@@ -935,6 +940,14 @@ int wsi_loo_rows(const int64_t* desc, int32_t nrow, int32_t ntiles, const int64_
  * wsi_slot_aug_scan: flags -> ranks and counts (three launches), then the layout kernel: L, readout_ptr, the readout's chunk tables and
  * segment counts, labels.  wsi_slot_aug_write: the real slides push, the filler and tails are pulled, the features are gathered (three launches);
  * every element of every table is written by every fill (scales: wsi_row_absmax over feat afterwards).
+ * Survivor quotas (data.BatchSlot(quota=)): the last word of the rows at off_node / off_edge carries quota + 1.  A kind-0 flag entry
+ * whose relation row has a quota is kept iff rank1 >= 0 (the final decision, left there by wsi_augment_edges); without one the by-rank draw is
+ * re-derived from rank1 as before.  The slot's capacities may then be below the stored counts: every (slide, type) / (slide, relation) count is
+ * clamped where it is produced, and every scattered store of wsi_slot_aug_write is range-checked against its table (N, S, E).
+ * wsi_slot_aug_quota(node_rows, nnode, tsum_n, edge_rows, nedge, etiles, tsum_e, overflow): one single-thread launch behind the two
+ * augmentation calls of a fill, reading the tile sums they leave (tsum_n [ntiles + 1], tsum_e [2 (etiles + 1)]): the draw's survivors of every
+ * row minus its quota.  overflow: DEVICE int64 [3], zeroed by its owner once: [0] += 1 when some quota bound in this fill, [1] / [2] <- max with
+ * the largest node / edge excess.  Plain loads and stores, ordered by the stream.  Entry point added to ABI 26.
  * args: a HOST array of 55 int64 words, read during the call (pointers as integers), the same for the three calls:
  *   [0] desc   [1..7] off_node, off_edge, off_flag, off_push, off_feat, off_shape, off_misc   [8..14] B, T, R, N, S, E, G (= b_cap + 1)
  *   [15..23] nflag, flag_tiles, npush, push_blocks, nodes_stored, ns_mode, F, mask_thr, feat_aligned
@@ -944,6 +957,8 @@ int wsi_loo_rows(const int64_t* desc, int32_t nrow, int32_t ntiles, const int64_
 int wsi_slot_aug_keys(const int64_t* args, void* stream);
 int wsi_slot_aug_scan(const int64_t* args, void* stream);
 int wsi_slot_aug_write(const int64_t* args, void* stream);
+int wsi_slot_aug_quota(const int64_t* node_rows, int32_t nnode, const int32_t* tsum_n, const int64_t* edge_rows, int32_t nedge, int32_t etiles,
+                       const int32_t* tsum_e, int64_t* overflow, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Epoch metrics kept on the device (wsi_hgnn_amd/metrics.py::EpochMetrics): the reference's per-epoch accuracy / precision / recall / F1 / AUC and

@@ -13,11 +13,15 @@ batches behind a device synchronise and ends in one; reported: median / fastest 
 of unrelated work), the share of the slot's rows and edges the filler takes, and which
 slot the batches went to.  A GPU is required: nothing is estimated.
 
-``--augment`` -> profiles/r13_slot_augment.json: the same data set, rounds and alternation with the reference's training pipeline
+``--augment`` (profiles/r13_slot_augment.json is its record before the quota legs): the same data set, rounds and alternation with the reference's training pipeline
 (``transforms.reference_train_transform()``) on the loader.  The yardstick leg is then the only way to train augmented without slots -
 ``GraphBatchLoader(transform=...)``'s batch (fused device augmentation, one read-back per slide, ``graph.batch``, ``plan()``) stepped eagerly - and
 the slots draw the augmentation on the device in front of every replay; also reported: the kernel launches of one fill (torch.profiler) and the
-filler's share from ``BatchSlot.counts()``, read outside the timed windows."""
+filler's share from ``BatchSlot.counts()``, read outside the timed windows.
+
+``--augment`` also runs the QUOTA legs -> profiles/r25_slot_quota.json by default: ``BatchSlot(quota="bound")`` sized for the draw
+instead of for the stored slides, one slot and three slots by size class, in the same alternating rounds as the stored-capacity legs (which are
+the ``quota=None`` code path, unchanged); reported beside them, with the overflow count over the whole run (expected 0)."""
 import argparse
 import json
 import os
@@ -48,6 +52,24 @@ def _class_capacities(loader, batch_size, classes):
     return caps
 
 
+def _quota_class_capacities(loader, batch_size, classes):
+    """``_class_capacities`` from the slides' "bound" quotas (data.slot_quota_bound) instead of their stored counts."""
+    from wsi_hgnn_amd.data import slot_augment_spec, slot_quota_bound
+    spec = slot_augment_spec(loader.transform)
+    its = sorted(loader.items, key=lambda it: sum(it.num_nodes))
+    T = len(its[0].num_nodes)
+    tix = {t: i for i, t in enumerate(its[0].ntypes)}
+    dst = [tix[r[2]] for r in its[0].rels]
+    q = {id(it): slot_quota_bound(it, spec) for it in its}
+    by_dst = lambda it, t: sum(x for x, d in zip(q[id(it)][1], dst) if d == t)
+    caps = []
+    for k in range(classes):
+        part = its[:max(batch_size, (len(its) * (k + 1) + classes - 1) // classes)]
+        top = lambda xs: sum(sorted(xs, reverse=True)[:batch_size])
+        caps.append(([top([q[id(it)][0][t] for it in part]) + 1 for t in range(T)], [top([by_dst(it, t) for it in part]) for t in range(T)], batch_size))
+    return caps
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--slides", type=int, default=64)
@@ -61,7 +83,7 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r13_slot_augment.json" if args.augment else "r12_slot_step.json")
+        args.out = os.path.join(ROOT, "profiles", "r25_slot_quota.json" if args.augment else "r12_slot_step.json")
     if not torch.cuda.is_available():
         raise SystemExit("tools/slot_bench.py measures on the GPU; none is visible (nothing is estimated on the CPU)")
     import __graft_entry__
@@ -112,6 +134,15 @@ def main(argv=None):
             legs = {"eager": eager_round,
                     "one_slot": lambda: [one.step(idxs) for idxs in batches],
                     "three_slots": lambda: [three.step(idxs) for idxs in batches]}
+            steppers = [("one_slot", one), ("three_slots", three)]
+            if args.augment:                                 # the quota legs: slots sized for the draw
+                mq1, oq1 = make(drop)
+                q_one = CapturedSlotStep(mq1, oq1, lf, [BatchSlot(loader, quota="bound")], warmup=2)
+                mq3, oq3 = make(drop)
+                q_three = CapturedSlotStep(mq3, oq3, lf, [BatchSlot(loader, c, quota="bound") for c in _quota_class_capacities(loader, bs, 3)], warmup=2)
+                legs["quota_one_slot"] = lambda: [q_one.step(idxs) for idxs in batches]
+                legs["quota_three_slots"] = lambda: [q_three.step(idxs) for idxs in batches]
+                steppers += [("quota_one_slot", q_one), ("quota_three_slots", q_three)]
             for fn in legs.values():                         # one untimed pass each: caches, allocator pools
                 fn()
             times = {k: [] for k in legs}
@@ -124,7 +155,7 @@ def main(argv=None):
                     times[k].append((time.perf_counter() - t0) / len(batches) * 1e3)
             entry = {"batch_size": bs, "feat_drop": drop, "steps_per_round": len(batches), "legs": {k: _stats(v) for k, v in times.items()}}
             # the fill alone, and what the filler takes
-            for name, step in (("one_slot", one), ("three_slots", three)):
+            for name, step in steppers:
                 wall, devt, rows, edges, routed = [], [], [], [], [0] * len(step.slots)
                 for idxs in batches:
                     i = step.slot_for(idxs)
@@ -167,6 +198,14 @@ def main(argv=None):
             e_ms = entry["legs"]["eager"]["median_ms"]
             entry["speedup_one_slot"] = round(e_ms / entry["legs"]["one_slot"]["median_ms"], 3)
             entry["speedup_three_slots"] = round(e_ms / entry["legs"]["three_slots"]["median_ms"], 3)
+            if args.augment:
+                for name, step in steppers[2:]:
+                    entry[name]["overflows"] = step.overflows()
+                    entry[name]["replays"], entry[name]["eager_steps"] = step.replays, step.eager_steps
+                    entry["speedup_" + name] = round(e_ms / entry["legs"][name]["median_ms"], 3)
+                entry["quota_over_stored_one_slot"] = round(entry["legs"]["one_slot"]["median_ms"] / entry["legs"]["quota_one_slot"]["median_ms"], 3)
+                entry["quota_over_stored_three_slots"] = round(entry["legs"]["three_slots"]["median_ms"] / entry["legs"]["quota_three_slots"]["median_ms"], 3)
+                del q_one, q_three, mq1, mq3
             result["configs"].append(entry)
             print(json.dumps(entry), flush=True)
             del one, three, m1, m3, m_e

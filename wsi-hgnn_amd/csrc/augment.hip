@@ -6,20 +6,27 @@
 namespace wsi {
 
 constexpr int AUG_TILE = 1024;            // elements per workgroup: 4 rounds of 256 lanes
-constexpr int AUG_NROW = 6;               // int64 words per node-segment descriptor: n, off, first_tile, seed, thr, -
-constexpr int AUG_EROW = 14;              // ... per edge segment: n, off, first_tile, u, v, sim, src_off, dst_off, seed, thr, mode, n_src, n_dst, -
+constexpr int AUG_NROW = 6;               // int64 words per node-segment descriptor: n, off, first_tile, seed, thr, quota + 1 (0: none)
+constexpr int AUG_EROW = 14;              // ... per edge segment: n, off, first_tile, u, v, sim, src_off, dst_off, seed, thr, mode, n_src, n_dst, quota + 1
+
+// the survivor quota of a row from its last word (quota + 1; 0 = no quota): ranks at or beyond it are truncated
+__device__ __forceinline__ int aug_quota(int64_t w) { return w > 0 && w - 1 < INT32_MAX ? (int)(w - 1) : INT32_MAX; }
 
 // ---------------------------------------------------------------- nodes
-// pass 0: tile_sum[tile] = kept nodes of the tile;  pass 1 (after the scan): new_id / kept
+// pass 0: tile_sum[tile] = kept nodes of the tile;  pass 1 (after the scan): new_id / kept.  A row with a quota keeps the first `quota` of
+// its survivors (node-id order): the others get new_id -1 as if drawn, and the segment's first tile clamps counts[s] - the tile sums stay
+// those of the draw, so every rank is the untruncated one.
 template <int PASS>
 __global__ __launch_bounds__(256) void aug_nodes_kernel(const int64_t* __restrict__ desc, int nseg, int32_t* __restrict__ tile_sum,
-                                                        int32_t* __restrict__ new_id, int64_t* __restrict__ kept) {
+                                                        int32_t* __restrict__ new_id, int64_t* __restrict__ kept, int32_t* __restrict__ counts) {
     __shared__ int lds[4];
     const int b = blockIdx.x;
-    const int64_t* d = desc + (int64_t)find_row(desc, AUG_NROW, 2, nseg, b) * AUG_NROW;
+    const int seg = find_row(desc, AUG_NROW, 2, nseg, b);
+    const int64_t* d = desc + (int64_t)seg * AUG_NROW;
     const int64_t n = d[0], off = d[1];
     const int ft = (int)d[2];
     const uint32_t seed = (uint32_t)d[3], thr = (uint32_t)d[4];
+    const int quota = aug_quota(d[5]);
     const int64_t i0 = (int64_t)(b - ft) * AUG_TILE;
     int run = PASS == 1 ? tile_sum[b] - tile_sum[ft] : 0;      // position inside the type's compacted range
     for (int r = 0; r < AUG_TILE / 256; ++r) {
@@ -28,12 +35,14 @@ __global__ __launch_bounds__(256) void aug_nodes_kernel(const int64_t* __restric
         int total;
         const int excl = block_flag_scan(keep, lds, total);
         if (PASS == 1 && i < n) {
-            new_id[off + i] = keep ? run + excl : -1;
-            if (keep) kept[off + run + excl] = i;
+            const bool stay = keep && run + excl < quota;
+            new_id[off + i] = stay ? run + excl : -1;
+            if (stay) kept[off + run + excl] = i;
         }
         run += total;
     }
     if (PASS == 0 && threadIdx.x == 0) tile_sum[b] = run;
+    if (PASS == 1 && b == ft && threadIdx.x == 0 && counts[seg] > quota) counts[seg] = quota;
 }
 
 // ---------------------------------------------------------------- edges
@@ -51,15 +60,19 @@ __device__ __forceinline__ bool aug_edge_flag1(const int64_t* d, const int32_t* 
 }
 
 // pass 0: tile sums of stage 1;  pass 1: rank1[e] = rank of e among the stage-1 survivors of its relation (-1: gone), tile sums of stage 2
-// (mode 1: the survivor is drawn BY THAT RANK - its index in the graph DropEdge receives behind DropNode);  pass 2: stable scatter
+// (mode 1: the survivor is drawn BY THAT RANK - its index in the graph DropEdge receives behind DropNode);  pass 2: stable scatter.
+// A row with a quota keeps the first `quota` of its final survivors; pass 2 then leaves the FINAL decision in rank1 (-1: gone, by either draw
+// or by the quota) for csrc/slot_aug.hip, and the segment's first tile clamps counts[s].
 template <int PASS>
 __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restrict__ desc, int nseg, int ntiles, const int32_t* __restrict__ new_id,
                                                         int32_t* __restrict__ tile_sum, int32_t* __restrict__ rank1,
                                                         int64_t* __restrict__ out_u, int64_t* __restrict__ out_v, float* __restrict__ out_sim,
-                                                        int64_t* __restrict__ out_eid) {
+                                                        int64_t* __restrict__ out_eid, int32_t* __restrict__ counts) {
     __shared__ int lds[4];
     const int b = blockIdx.x;
-    const int64_t* d = desc + (int64_t)find_row(desc, AUG_EROW, 2, nseg, b) * AUG_EROW;
+    const int seg = find_row(desc, AUG_EROW, 2, nseg, b);
+    const int64_t* d = desc + (int64_t)seg * AUG_EROW;
+    const int quota = aug_quota(d[13]);
     const int64_t n = d[0], off = d[1];
     const int ft = (int)d[2];
     const uint32_t seed = (uint32_t)d[8], thr = (uint32_t)d[9];
@@ -88,7 +101,8 @@ __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restric
             const bool f2 = f && !(by_rank && drawn((uint32_t)rk, seed, thr));
             cnt2 += __popcll(__ballot(f2));       // per wave; summed over the 4 waves below
         }
-        if (PASS == 2 && f) {
+        if (PASS == 2 && d[13] > 0 && i < n && !(f && run + excl < quota)) rank1[off + i] = -1;
+        if (PASS == 2 && f && run + excl < quota) {
             aug_edge_flag1(d, new_id, i, u, v);   // the renumbered endpoints (its flag is known to hold)
             const int64_t p = off + run + excl;
             out_u[p] = u;
@@ -104,6 +118,7 @@ __global__ __launch_bounds__(256) void aug_edges_kernel(const int64_t* __restric
         __syncthreads();
         if (threadIdx.x == 0) sum2[b] = lds[0] + lds[1] + lds[2] + lds[3];
     }
+    if (PASS == 2 && b == ft && threadIdx.x == 0 && counts[seg] > quota) counts[seg] = quota;
 }
 
 // ---------------------------------------------------------------- NodeShuffle keys: (segment << 32) | hash, one stable sort orders every type at once
@@ -189,9 +204,9 @@ extern "C" int wsi_augment_nodes(const int64_t* desc, int32_t nseg, int32_t ntil
     if (nseg == 0) return WSI_OK;
     if (!desc || !tile_sum || !counts || (ntiles > 0 && (!new_id || !kept))) { set_error("augment_nodes: null pointer"); return WSI_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    if (ntiles > 0) hipLaunchKernelGGL(aug_nodes_kernel<0>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, tile_sum, new_id, kept);
+    if (ntiles > 0) hipLaunchKernelGGL(aug_nodes_kernel<0>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, tile_sum, new_id, kept, counts);
     launch_tile_scan(tile_sum, (int)ntiles, desc, AUG_NROW, 2, (int)nseg, counts, s);
-    if (ntiles > 0) hipLaunchKernelGGL(aug_nodes_kernel<1>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, tile_sum, new_id, kept);
+    if (ntiles > 0) hipLaunchKernelGGL(aug_nodes_kernel<1>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, tile_sum, new_id, kept, counts);
     return check_launch("augment_nodes");
 }
 
@@ -205,11 +220,11 @@ extern "C" int wsi_augment_edges(const int64_t* desc, int32_t nseg, int32_t ntil
     }
     hipStream_t s = (hipStream_t)stream;
     int32_t* sum2 = tile_sum + ntiles + 1;
-    if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<0>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid);
+    if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<0>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid, counts);
     launch_tile_scan(tile_sum, (int)ntiles, desc, AUG_EROW, 2, (int)nseg, counts, s);
-    if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<1>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid);
+    if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<1>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid, counts);
     launch_tile_scan(sum2, (int)ntiles, desc, AUG_EROW, 2, (int)nseg, counts, s);
-    if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<2>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid);
+    if (ntiles > 0) hipLaunchKernelGGL(aug_edges_kernel<2>, dim3(ntiles), dim3(256), 0, s, desc, (int)nseg, (int)ntiles, new_id, tile_sum, rank1, out_u, out_v, out_sim, out_eid, counts);
     return check_launch("augment_edges");
 }
 

@@ -48,6 +48,7 @@ __device__ __forceinline__ bool sa_keep(const Args& a, const int64_t* __restrict
         const int64_t m = reinterpret_cast<const int64_t*>(d[4])[i];
         const int64_t* e = a.desc + a.off_edge + (b * a.R + (m >> 40)) * SA_EROW;
         const int rk = a.rank1[sa_coo_base(a)[b] + (m & SA_COO_MASK)];
+        if (e[13] != 0) return rk >= 0;            // a relation with a quota: wsi_augment_edges left the FINAL decision in rank1
         return rk >= 0 && !(e[10] != 0 && drawn((uint32_t)rk, (uint32_t)e[8], (uint32_t)e[9]));
     }
     const int64_t l = reinterpret_cast<const int64_t*>(d[4])[i], t = reinterpret_cast<const int64_t*>(d[5])[i];
@@ -108,7 +109,11 @@ __device__ __forceinline__ int64_t sa_prefix(const Args& a, int64_t s, int64_t v
     return r >= 0 ? r : ~r;
 }
 
-// the real slides: every surviving node, CSR edge, CSC entry and order entry writes itself at (device offset + rank)
+// the real slides: every surviving node, CSR edge, CSC entry and order entry writes itself at (device offset + rank).  Every position is
+// checked against the table it goes to: with capacities below the stored counts (survivor quotas) a wrong count may misplace an
+// entry, it cannot write outside a table.
+__device__ __forceinline__ bool sa_in(int64_t p, int64_t n) { return p >= 0 && p < n; }
+
 __global__ __launch_bounds__(256) void sa_push_kernel(Args a) {
     const int blk = blockIdx.x;
     const int64_t* rows = a.desc + a.off_push;
@@ -132,7 +137,9 @@ __global__ __launch_bounds__(256) void sa_push_kernel(Args a) {
             if (m < 0) continue;
             const int64_t R = slot_shape_type(a.desc + a.off_shape, t)[SS_R];
             const int64_t* rp = reinterpret_cast<const int64_t*>(d[5]);
-            for (int64_t q = 0; q < R; ++q) a.rowptr[seg[bt] + m * R + q] = (int32_t)(edge[bt] + sa_prefix(a, bt, rp[i * R + q]));
+            for (int64_t q = 0; q < R; ++q)
+                if (sa_in(seg[bt] + m * R + q, a.S)) a.rowptr[seg[bt] + m * R + q] = (int32_t)(edge[bt] + sa_prefix(a, bt, rp[i * R + q]));
+            if (!sa_in(node[bt] + m, a.N)) continue;
             a.colptr[node[bt] + m] = (int32_t)(csc[bt] + sa_prefix(a, B * T + bt, reinterpret_cast<const int64_t*>(d[6])[i]));
             a.row_seg[node[bt] + m] = (int32_t)(t * a.G + b);
         } else if (kind == 1) {                           // CSR edge i into (b, t): p0 = src_l, p1 = src_t, p2 = sim, p3 = local segment (node R + slot)
@@ -140,6 +147,7 @@ __global__ __launch_bounds__(256) void sa_push_kernel(Args a) {
             if (rk < 0) continue;
             const int64_t R = slot_shape_type(a.desc + a.off_shape, t)[SS_R];
             const int64_t pos = edge[bt] + rk;
+            if (!sa_in(pos, a.E)) continue;
             const int64_t st = b * T + reinterpret_cast<const int64_t*>(d[6])[i];
             a.src[pos] = (int32_t)(node[st] + a.new_id[noff[st] + reinterpret_cast<const int64_t*>(d[5])[i]]);
             a.sim[pos] = reinterpret_cast<const float*>(d[7])[i];
@@ -149,6 +157,7 @@ __global__ __launch_bounds__(256) void sa_push_kernel(Args a) {
             const int rk = a.frank[(a.desc + a.off_flag + d[9] * SA_FROW)[1] + i];
             if (rk < 0) continue;
             const int64_t pos = csc[bt] + rk;
+            if (!sa_in(pos, a.E)) continue;
             const int64_t dt = b * T + reinterpret_cast<const int64_t*>(d[6])[i];
             a.csc_eid[pos] = (int32_t)(edge[dt] + sa_prefix(a, dt, reinterpret_cast<const int64_t*>(d[5])[i]));
             a.csc_dst[pos] = (int32_t)(node[dt] + a.new_id[noff[dt] + reinterpret_cast<const int64_t*>(d[7])[i]]);
@@ -157,8 +166,10 @@ __global__ __launch_bounds__(256) void sa_push_kernel(Args a) {
             if (rk < 0) continue;
             const int64_t nt = b * T + reinterpret_cast<const int64_t*>(d[6])[i];
             const int32_t id = (int32_t)(node[nt] + a.new_id[noff[nt] + reinterpret_cast<const int64_t*>(d[5])[i]]);
-            if (kind == 5) a.order_src[ord[2 * B + b] + rk] = id;
-            else a.order_dst[ord[(kind - 3) * B + b] + rk] = id;
+            const int64_t pos = ord[(kind == 5 ? 2 : kind - 3) * B + b] + rk;
+            if (!sa_in(pos, a.N)) continue;
+            if (kind == 5) a.order_src[pos] = id;
+            else a.order_dst[pos] = id;
         }
     }
 }
@@ -263,6 +274,31 @@ __global__ __launch_bounds__(256) void sa_feat_kernel(Args a) {
     }
 }
 
+// survivor quotas: what the draw exceeded them by, from the tile sums the two augmentation calls leave behind (the counts
+// themselves are clamped by then).  ONE thread, plain loads and stores, stream-ordered behind the fill's scans and in front of the next fill's:
+// ovf[0] += 1 when some quota bound in this fill, ovf[1] / ovf[2] = the largest excess any fill has seen of a node / an edge row.
+__device__ __forceinline__ int64_t sa_excess(const int64_t* rows, int stride, int nrow, const int32_t* tsum) {
+    int64_t worst = 0;
+    for (int s = 0; s < nrow; ++s) {
+        const int64_t* d = rows + (int64_t)s * stride;
+        if (d[0] <= 0 || d[stride - 1] <= 0) continue;
+        const int64_t ft = d[2], nt = (d[0] + SA_TILE - 1) / SA_TILE;
+        const int64_t over = (int64_t)tsum[ft + nt] - tsum[ft] - (d[stride - 1] - 1);
+        worst = over > worst ? over : worst;
+    }
+    return worst;
+}
+
+__global__ void sa_quota_kernel(const int64_t* nrows, int nnode, const int32_t* tsum_n, const int64_t* erows, int nedge, const int32_t* tsum_e2,
+                                int64_t* ovf) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t xn = sa_excess(nrows, SA_NROW, nnode, tsum_n);
+    const int64_t xe = nedge > 0 ? sa_excess(erows, SA_EROW, nedge, tsum_e2) : 0;
+    if (xn > 0 || xe > 0) ovf[0] += 1;
+    if (xn > ovf[1]) ovf[1] = xn;
+    if (xe > ovf[2]) ovf[2] = xe;
+}
+
 static bool sa_bad(const int64_t* words, Args* a, const char* what) {
     if (!words) { set_error("%s: null pointer", what); return true; }
     memcpy(a, words, sizeof(Args));
@@ -322,4 +358,13 @@ extern "C" int wsi_slot_aug_write(const int64_t* args, void* stream) {
         else hipLaunchKernelGGL(sa_feat_kernel<false>, grid, dim3(256), 0, s, *a);
     }
     return check_launch("slot_aug_write");
+}
+
+extern "C" int wsi_slot_aug_quota(const int64_t* node_rows, int32_t nnode, const int32_t* tsum_n, const int64_t* edge_rows, int32_t nedge,
+                                  int32_t etiles, const int32_t* tsum_e, int64_t* overflow, void* stream) {
+    if (nnode < 0 || nedge < 0 || etiles < 0) { set_error("slot_aug_quota: bad argument"); return WSI_EINVAL; }
+    if (!node_rows || !tsum_n || !overflow || (nedge > 0 && (!edge_rows || !tsum_e))) { set_error("slot_aug_quota: null pointer"); return WSI_EINVAL; }
+    hipLaunchKernelGGL(sa_quota_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, node_rows, (int)nnode, tsum_n, edge_rows, (int)nedge,
+                       nedge > 0 ? tsum_e + etiles + 1 : tsum_e, overflow);
+    return check_launch("slot_aug_quota");
 }

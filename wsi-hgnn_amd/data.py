@@ -354,6 +354,50 @@ def slot_augment_spec(transform):
     return _graph_mod.AugmentSpec(**{k: v for k, v in found.items() if v is not None})
 
 
+QUOTA_DELTA = 2.0 ** -32           # per table: the probability that the "bound" quota binds (the constant of BatchSlot.fits' type-present rule)
+
+
+def slot_quota_bound(it: StoredGraph, spec):
+    """``(qn[t], qe[j])``: survivor quotas of a stored slide under the pipeline ``spec`` that a draw exceeds with probability at most 2 ** -32
+    per table.  With p_n, p_e the quantised probabilities (threshold / 65536; 0 for an absent stage) and lam = ln(2 ** 32) / 2:
+
+        qn[t] = min(n_t, ceil(n_t (1 - p_n) + sqrt(lam n_t)))                                   (Hoeffding; n_t without DropNode)
+        mu_j  = (E_j - loops_j) (1 - p_n) ** 2 (1 - p_e) + loops_j (1 - p_n) (1 - p_e)
+        qe[j] = min(E_j, ceil(mu_j + sqrt(lam (sum_v c_v ** 2 + E_j))))                         (bounded differences)
+
+    c_v: edges of relation j incident to node v, a self-loop counted once - what one node draw can move the count by; every edge draw (by index
+    or by rank) moves it by at most 1.  Cached on the stored slide per (p_n, p_e); one device -> host copy per slide."""
+    import math
+    key = (spec.node_thr if spec.drop_node is not None else None, spec.edge_thr if spec.drop_edge is not None else None)
+    cache = it.__dict__.setdefault("_quota_bound", {})
+    if key in cache:
+        return cache[key]
+    lam = math.log(1.0 / QUOTA_DELTA) / 2.0
+    pn = spec.node_thr / 65536.0 if spec.drop_node is not None else 0.0
+    pe = spec.edge_thr / 65536.0 if spec.drop_edge is not None else 0.0
+    qn = [int(n) if spec.drop_node is None else min(int(n), math.ceil(n * (1.0 - pn) + math.sqrt(lam * n))) for n in it.num_nodes]
+    tix = {t: i for i, t in enumerate(it.ntypes)}
+    stats = []
+    for r in it.rels:
+        u, v = it.edges[r]
+        ns, nd = it.num_nodes[tix[r[0]]], it.num_nodes[tix[r[2]]]
+        if r[0] == r[2]:
+            loop = u == v
+            c = torch.bincount(u, minlength=ns) + torch.bincount(v, minlength=ns) - torch.bincount(u[loop], minlength=ns)
+            stats += [loop.sum(), (c * c).sum()]
+        else:
+            cu, cv = torch.bincount(u, minlength=ns), torch.bincount(v, minlength=nd)
+            stats += [torch.zeros((), dtype=torch.int64, device=u.device), (cu * cu).sum() + (cv * cv).sum()]
+    vals = torch.stack(stats).tolist() if stats else []
+    qe = []
+    for j, r in enumerate(it.rels):
+        E, loops, csq = int(it.edges[r][0].numel()), vals[2 * j], vals[2 * j + 1]
+        mu = (E - loops) * (1.0 - pn) ** 2 * (1.0 - pe) + loops * (1.0 - pn) * (1.0 - pe)
+        qe.append(min(E, math.ceil(mu + math.sqrt(lam * (csq + E)))))
+    cache[key] = (qn, qe)
+    return cache[key]
+
+
 class _DeviceOnly:
     """Stands where a host copy of an augmented GPU slot's counts would be: those counts live on the device, and reading them fails loudly."""
 
@@ -395,9 +439,16 @@ class BatchSlot:
     one row per (relation, source node), shapes again functions of the capacities - installed as ``slot.graph.plan(per_relation_src=True)`` and
     re-derived on the device from the tables every ``load`` / ``load_augmented`` has just written (``graph.derive_rel_tables``: one C call behind
     the fill, no host arithmetic).  ``rel_sorted``: order those rows by out-degree, as ``graph.finish_plan`` does, instead of leaving them in
-    row order - measured 2 % slower per replayed step (tools/hgt_slot_bench.py), so off.  The default allocates nothing and changes nothing."""
+    row order - measured 2 % slower per replayed step (tools/hgt_slot_bench.py), so off.  The default allocates nothing and changes nothing.
 
-    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0, per_relation_src: bool = False):
+    ``quota`` (augmented slots only): survivor QUOTAS - per stored slide an upper limit on the survivors of every node type and
+    every relation that the host knows, enforced by the fill itself (truncation in node-id / input order: ``transforms.truncated``), so the
+    slot can be sized for the draw instead of for the stored slides.  ``"bound"``: ``slot_quota_bound`` (binds with probability <= 2 ** -32 per
+    table); a callable ``quota(idx) -> (qn, qe)`` sets limits by hand.  ``capacity=None`` then sums the ``batch_size`` largest quotas, ``fits``
+    tests the quota sums, ``counts()`` returns the truncated counts, and ``overflows()`` / ``overflow_excess()`` read back how often and by how
+    much a quota bound.  A truncated batch is a valid graph, just not the eager loader's batch for that draw.  ``None``: today's slot."""
+
+    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0, per_relation_src: bool = False, quota=None):
         if not loader.resident:
             raise RuntimeError("BatchSlot needs a device-resident data set (GraphBatchLoader(..., resident=True)): the fill copies the slides' features "
                                "device to device; a pinned-host loader stays on its own double-buffered path")
@@ -408,7 +459,21 @@ class BatchSlot:
         ntypes, rels = list(key[0]), [tuple(r) for r in key[1]]
         its = [loader.items[i] for i in loader.buckets[key]]
         T = len(ntypes)
-        if capacity is None:
+        self.quota, self._quotas = quota, {}
+        if quota is not None:
+            if self.spec is None:
+                raise RuntimeError("BatchSlot(quota=...): quotas limit the survivors of a draw; the loader has no transform")
+            if quota != "bound" and not callable(quota):
+                raise ValueError('BatchSlot: quota is None, "bound" or a callable quota(idx) -> (qn, qe)')
+            self._overflow = torch.zeros(3, dtype=torch.int64, device=self.device)     # fills in which a quota bound, largest node / edge excess
+        if capacity is None and quota is not None:
+            bs = loader.batch_size
+            top = lambda xs: sum(sorted(xs, reverse=True)[:bs])
+            qs = [self._quota_counts([i]) for i in loader.buckets[key]]
+            n_cap = [top([q[0][0][t] for q in qs]) + 1 for t in range(T)]
+            e_cap = [top([q[1][0][t] for q in qs]) for t in range(T)]
+            b_cap = bs
+        elif capacity is None:
             bs = loader.batch_size
             top = lambda xs: sum(sorted(xs, reverse=True)[:bs])
             n_cap = [top([it.num_nodes[t] for it in its]) + 1 for t in range(T)]
@@ -470,7 +535,25 @@ class BatchSlot:
         if self.rel is not None:
             _graph_mod.derive_rel_tables(self.layout.hd, self.graph._plan, self.rel, sort_sources=self.rel_sorted)
 
+    def quota_of(self, idx: int):
+        """``(qn, qe)`` of the loader's slide ``idx`` under this slot's quota rule, never above the stored counts (cached)."""
+        if idx not in self._quotas:
+            it = self.loader.items[idx]
+            qn, qe = slot_quota_bound(it, self.spec) if self.quota == "bound" else self.quota(idx)
+            if len(qn) != len(it.ntypes) or len(qe) != len(it.rels):
+                raise ValueError("BatchSlot: quota(idx) returns one node quota per node type and one edge quota per relation")
+            self._quotas[idx] = ([max(0, min(int(q), n)) for q, n in zip(qn, it.num_nodes)],
+                                 [max(0, min(int(q), int(it.edges[r][0].numel()))) for q, r in zip(qe, it.rels)])
+        return self._quotas[idx]
+
+    def _quota_counts(self, idxs):
+        """The most the slides ``idxs`` can hold under their quotas: (nodes[b][t], edges[b][t] by destination type)."""
+        it = self.loader.items[idxs[0]]
+        return _graph_mod.quota_counts(it.ntypes, it.rels, [self.loader.items[i].num_nodes for i in idxs], [self.quota_of(i) for i in idxs], self.spec)
+
     def _counts(self, idxs):
+        if self.quota is not None:
+            return self._quota_counts(idxs)
         its = [self.loader.items[i] for i in idxs]
         return [it.num_nodes for it in its], [it.pieces.ecount for it in its]
 
@@ -487,7 +570,8 @@ class BatchSlot:
             # augmented slot: the models switch a node type's head off when the batch has no node of the type - a host-side branch frozen into a
             # capture - so a draw that empties a type must be impossible in practice: p_node ** n[t] <= 2 ** -32 for every type (n >= 32 at 0.5)
             p = self.spec.node_thr / 65536.0
-            if any(p ** sum(c[t] for c in counts) > 2.0 ** -32 for t in range(self.layout.T)):
+            stored = [self.loader.items[i].num_nodes for i in idxs]
+            if any(p ** sum(c[t] for c in stored) > 2.0 ** -32 for t in range(self.layout.T)):
                 return False
         return True
 
@@ -553,9 +637,11 @@ class BatchSlot:
         if any(i not in self.members for i in idxs) or not _graph_mod.SlotBatch.fits(lay, *self._counts(idxs), True):
             raise ValueError(f"BatchSlot.load_augmented: the batch {idxs} does not fit the slot")
         ntypes, rels = G.ntypes, G.canonical_etypes
+        quotas = [self.quota_of(i) for i in idxs] if self.quota is not None else None
         if self.device.type == "cuda":
             _graph_mod.slot_fill_augmented(lay, self.bufs, [it.pieces for it in its], [[it.edges[r] for r in rels] for it in its],
-                                           [it.label for it in its], [it.feat for it in its], draws, self.spec)
+                                           [it.label for it in its], [it.feat for it in its], draws, self.spec, quotas,
+                                           self._overflow if quotas is not None else None)
             # host mirrors of the counts: not current without a read-back - they fail loudly instead (the step reads none of them)
             G._batch_num_nodes = _DeviceOnlyCounts((t, torch.zeros(lay.graphs, dtype=torch.int64)) for t in ntypes)
             G._edges_store, G._edge_thunk = None, _DeviceOnly("the per-relation COO")
@@ -565,11 +651,24 @@ class BatchSlot:
             ops.refresh_constant_cols(self.bufs["feat"])
         else:
             # tensor route (and the kernels' oracle): every slide through the tensor formulation of the pipeline, stored anew, then the ordinary fill
-            aug, keeps = [], []
-            for it, d in zip(its, draws):
+            aug, keeps, over_n, over_e = [], [], 0, 0
+            for b, (it, d) in enumerate(zip(its, draws)):
                 g = HeteroGraph.from_coo(OrderedDict(zip(it.ntypes, it.num_nodes)), it.edges, feat=dict(zip(it.ntypes, it.feat)), sim=it.sims)
-                aug.append(StoredGraph(self.loader.transform(g, draw=d, fused=False), it.label, self.device, True))
-                keeps.append(self.spec.node_keep(d, it.num_nodes, self.device))
+                keep = self.spec.node_keep(d, it.num_nodes, self.device)
+                if quotas is None:
+                    g = self.loader.transform(g, draw=d, fused=False)
+                else:
+                    from . import transforms as _tr
+                    qn, qe = quotas[b]
+                    g, xn, xe = _tr.truncated(self.loader.transform, g, d, qn, qe)
+                    over_n, over_e = max([over_n] + xn), max([over_e] + xe)
+                    if self.spec.drop_node is not None:
+                        keep = [k & (torch.cumsum(k, 0) <= q) for k, q in zip(keep, qn)]
+                aug.append(StoredGraph(g, it.label, self.device, True))
+                keeps.append(keep)
+            if quotas is not None:
+                self._overflow += torch.tensor([int(over_n > 0 or over_e > 0), 0, 0])
+                self._overflow[1:] = torch.maximum(self._overflow[1:], torch.tensor([over_n, over_e]))
             out = _graph_mod.slot_fill_torch(lay, [a.pieces for a in aug], [a.label for a in aug], [a.feat for a in aug], None, self.device, True)
             sb = out["batch"]
             out["order_dst"], out["order_src"] = _graph_mod.restricted_orders(lay, [it.pieces for it in its], keeps, sb)
@@ -615,6 +714,19 @@ class BatchSlot:
                     [[sb.eoff[(t, b + 1)] - sb.eoff[(t, b)] if b + 1 < B else sb.feb[t] - sb.eoff[(t, b)] for t in range(T)] for b in range(B)])
         n, e = self._counts(self.idxs)
         return [list(x) for x in n], [list(x) for x in e]
+
+    def overflows(self) -> int:
+        """Number of fills of this slot in which at least one quota bound, that is, in which the batch was truncated (0 on a slot without
+        quotas).  On a GPU slot the explicit read-back of the slot's overflow words (one synchronising copy): once per epoch, never in a step."""
+        return int(self._overflow[0]) if self.quota is not None else 0
+
+    def overflow_excess(self):
+        """``(nodes, edges)``: the largest number of survivors beyond its quota that any (slide, node type) and any (slide, relation) has had
+        over the slot's life; edges counted in the node-truncated pipeline.  A read-back, as ``overflows``."""
+        if self.quota is None:
+            return 0, 0
+        got = self._overflow.tolist()
+        return got[1], got[2]
 
     def padded_share(self):
         """(share of the slot's rows, share of its edges) that the current batch's filler takes (``counts()``: a read-back on an augmented GPU slot)."""

@@ -1350,6 +1350,15 @@ class AugmentSpec:
         return [~ops.augment_drawn(int(n), ops.augment_subseed(draw, self.drop_node[0], t), self.node_thr, device) for t, n in enumerate(counts)]
 
 
+def quota_counts(ntypes: Sequence[str], rels: Sequence[CanonicalEType], stored: Sequence[Sequence[int]], quotas, spec: "AugmentSpec"):
+    """What a batch under survivor quotas can hold at most, as ``SlotBatch.fits`` takes it: ``(nodes[b][t], edges[b][t])``, edges by destination
+    type.  ``stored[b][t]``: the stored node counts (a node quota holds only with a DropNode in the pipeline); ``quotas[b] = (qn, qe)``."""
+    T, dst = len(ntypes), [list(ntypes).index(r[2]) for r in rels]
+    nodes = [[min(int(q[0][t]), int(st[t])) if spec.drop_node is not None else int(st[t]) for t in range(T)] for q, st in zip(quotas, stored)]
+    edges = [[sum(max(0, int(x)) for x, d in zip(q[1], dst) if d == t) for t in range(T)] for q in quotas]
+    return nodes, edges
+
+
 def restricted_orders(lay: SlotLayout, pieces: Sequence[PlanPieces], keeps: Sequence[Sequence[torch.Tensor]], sb: SlotBatch):
     """The processing orders of an augmented slot: the order tables the unaugmented fill writes for the same slides (heavy destinations of every
     slide, then the light ones; sources apart), restricted to the surviving nodes in the same relative order and renumbered; the filler's nodes
@@ -1375,27 +1384,44 @@ def restricted_orders(lay: SlotLayout, pieces: Sequence[PlanPieces], keeps: Sequ
 
 
 def slot_fill_augmented(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: Sequence[PlanPieces], edges: Sequence[Sequence[Tuple[torch.Tensor, torch.Tensor]]],
-                        labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]], draws: Sequence[int], spec: AugmentSpec) -> None:
+                        labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]], draws: Sequence[int], spec: AugmentSpec,
+                        quotas=None, overflow: Optional[torch.Tensor] = None) -> None:
     """Write the padded batch ``[transform(slide_b, draws[b]).., empty graphs.., filler]`` of the STORED slides ``pieces`` (per-relation COO
     ``edges[b][j]`` in sorted relation order, fp32 feature tables ``feats[b][t]``) into the GPU slot's tables ``bufs``, drawing the augmentation on
     the device: ONE descriptor upload, no read-back, no synchronisation, no atomics, scratch sized by the stored counts, ~20 launches whatever
     the draw and the pipeline (csrc/slot_aug.hip; include/wsi_hgnn.h, wsi_slot_aug_*).  ``bufs["_aug"]`` keeps the scratch of the last fill
-    (``ncnt`` / ``fcnt``: the survivors' counts, for ``BatchSlot.counts``).  ``bufs["scales"]`` = row absmax of the filled feature table."""
+    (``ncnt`` / ``fcnt``: the survivors' counts, for ``BatchSlot.counts``).  ``bufs["scales"]`` = row absmax of the filled feature table.
+
+    ``quotas[b] = (qn[T], qe[R])``: survivor quotas of slide b per node type and per relation - the truncated pipeline of
+    ``transforms.truncated``, enforced by the kernels that produce the counts (the node quota only with a DropNode in the pipeline).  The QUOTA
+    sums must then fit the slot, not the stored counts.  ``overflow``: the slot's device int64 [3] table (fills in which a quota bound, largest
+    node excess, largest edge excess), updated by one single-thread launch."""
     from . import _native as N
     from . import ops
     dev = bufs["rowptr"].device
     if dev.type != "cuda":
         raise RuntimeError("slot_fill_augmented runs on the GPU only (HIP kernels); a CPU slot takes the tensor route (data.BatchSlot.load)")
-    if not SlotBatch.fits(lay, [pc.counts for pc in pieces], [pc.ecount for pc in pieces], True):
-        raise ValueError("the stored batch does not fit the slot")
     T, hd, B, G, F = lay.T, lay.hd, len(pieces), lay.graphs, lay.in_dim
     R = len(lay.rels)
     tix = hd.tindex
+    if quotas is None:
+        if not SlotBatch.fits(lay, [pc.counts for pc in pieces], [pc.ecount for pc in pieces], True):
+            raise ValueError("the stored batch does not fit the slot")
+        qn_word, qe_word = (lambda s: 0), (lambda s: 0)
+    else:
+        if len(quotas) != B or any(len(q[0]) != T or len(q[1]) != R for q in quotas) or overflow is None:
+            raise ValueError("slot_fill_augmented: quotas[b] = (one node quota per type, one edge quota per relation), with the overflow table")
+        qn, qe = quota_counts(lay.ntypes, lay.rels, [pc.counts for pc in pieces], quotas, spec)
+        if not SlotBatch.fits(lay, qn, qe, True):
+            raise ValueError("the batch's quotas do not fit the slot")
+        # the rows carry quota + 1 (0: none); a node quota acts inside DropNode only
+        qn_word = (lambda s: min(int(quotas[s // T][0][s % T]), n_st[s]) + 1) if spec.drop_node is not None else (lambda s: 0)
+        qe_word = lambda s: max(0, int(quotas[s // R][1][s % R])) + 1
     seed = lambda st, draw, j: ops.augment_subseed(draw, st[0], j) if st else 0
     n_st = [pc.counts[t] for pc in pieces for t in range(T)]                      # [b * T + t]
     rel_sizes = [[int(edges[b][j][0].numel()) for j in range(R)] for b in range(B)]
     # ---- wsi_augment_nodes / wsi_augment_edges rows
-    nwords, ntiles, noff = ops._segment_rows(n_st, lambda s: (seed(spec.drop_node, draws[s // T], s % T), spec.node_thr, 0))
+    nwords, ntiles, noff = ops._segment_rows(n_st, lambda s: (seed(spec.drop_node, draws[s // T], s % T), spec.node_thr, qn_word(s)))
     nodes_stored = sum(n_st)
 
     def erow(s):
@@ -1405,7 +1431,7 @@ def slot_fill_augmented(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: 
             raise ValueError("slot_fill_augmented: contiguous int64 COO on the slot's device")
         sr, _, ds = lay.rels[j]
         return (u.data_ptr(), v.data_ptr(), 0, noff[b * T + tix[sr]], noff[b * T + tix[ds]], seed(spec.drop_edge, draws[b], j), spec.edge_thr,
-                spec.by_rank, pieces[b].counts[tix[sr]], pieces[b].counts[tix[ds]], 0)
+                spec.by_rank, pieces[b].counts[tix[sr]], pieces[b].counts[tix[ds]], qe_word(s))
 
     ewords, etiles, eoff = ops._segment_rows([m for rs in rel_sizes for m in rs], erow)
     coo_total = sum(sum(rs) for rs in rel_sizes)
@@ -1472,6 +1498,9 @@ def slot_fill_augmented(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: 
     if R > 0:
         N.check(lib.wsi_augment_edges(dp + 8 * offs["edge"], B * R, etiles, N.ptr(sc["new_id"]), N.ptr(sc["tsum_e"]), N.ptr(sc["rank1"]), N.ptr(sc["out_u"]),
                                       N.ptr(sc["out_v"]), N.ptr(sc["out_sim"]), N.ptr(sc["out_eid"]), N.ptr(sc["ecnt_rel"]), st), "wsi_augment_edges")
+    if quotas is not None:
+        N.check(lib.wsi_slot_aug_quota(dp + 8 * offs["node"], B * T, N.ptr(sc["tsum_n"]), dp + 8 * offs["edge"], B * R, etiles, N.ptr(sc["tsum_e"]),
+                                       N.ptr(overflow), st), "wsi_slot_aug_quota")
     import ctypes
     names = ("desc", "off_node", "off_edge", "off_flag", "off_push", "off_feat", "off_shape", "off_misc", "B", "T", "R", "N", "S", "E", "G", "nflag",
              "flag_tiles", "npush", "push_blocks", "nodes_stored", "ns_mode", "F", "mask_thr", "feat_aligned", "new_id", "kept", "ncnt", "rank1", "ftile",

@@ -230,6 +230,11 @@ class CapturedSlotStep:
         """Index of the smallest slot the batch fits, or None."""
         return capture.first_fit(self.slots, idxs)
 
+    def overflows(self) -> int:
+        """Fills, over all slots, in which a survivor quota bound and the batch was truncated (``BatchSlot.overflows``; 0 for slots without
+        quotas).  A read-back per slot: once per epoch, not per step."""
+        return sum(slot.overflows() for slot in self.slots)
+
     def step(self, idxs: Sequence[int]):
         """One optimisation step on the loader's slides ``idxs``.  Returns ``(loss, logits[:len(idxs)])`` as device tensors; those of a replayed
         step are overwritten by the next replay of the same slot."""

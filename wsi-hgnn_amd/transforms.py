@@ -91,11 +91,17 @@ class DropNode(BaseTransform):
         self.p = float(p)
         self.threshold = ops.augment_threshold(p)
 
-    def apply(self, g, seed, k):
+    def apply(self, g, seed, k, quota=None, excess=None):
+        """``quota[j]`` (``truncated``): of the nodes of type j that the draw keeps only the first ``quota[j]`` in node-id order stay, the others
+        go exactly as if drawn; ``excess``: a list that receives, per type, by how many the draw exceeded its quota."""
         dev = g.device
         keep, new_id, counts = {}, {}, OrderedDict()
         for j, t in enumerate(g.ntypes):
             keep[t] = ~ops.augment_drawn(g.num_nodes(t), ops.augment_subseed(seed, k, j), self.threshold, dev)
+            if quota is not None:
+                if excess is not None:
+                    excess.append(max(0, int(keep[t].sum()) - int(quota[j])))
+                keep[t] = keep[t] & (torch.cumsum(keep[t], 0) <= int(quota[j]))
             new_id[t] = torch.cumsum(keep[t], 0) - 1
             counts[t] = int(keep[t].sum())
         edges, emask = OrderedDict(), {}
@@ -178,7 +184,10 @@ class Compose:
         self.transforms: List[Callable] = list(transforms)
         self.fused = fused
 
-    def __call__(self, g: HeteroGraph, draw=None, fused: Optional[bool] = None) -> HeteroGraph:
+    def __call__(self, g: HeteroGraph, draw=None, fused: Optional[bool] = None, quota=None) -> HeteroGraph:
+        """``quota=(qn, qe)``: the truncated pipeline (``truncated``; tensor formulation on any device).  ``None``: the pipeline as drawn."""
+        if quota is not None:
+            return truncated(self, g, draw, quota[0], quota[1])[0]
         seed = _seed(draw)
         fused = self.fused if fused is None else fused
         run: list = []
@@ -204,6 +213,37 @@ class Compose:
 
     def __repr__(self):
         return "Compose([" + ", ".join(repr(t) for t in self.transforms) + "])"
+
+
+def truncated(pipe: Compose, g: HeteroGraph, draw, qn=None, qe=None):
+    """The pipeline under survivor QUOTAS (what a ``data.BatchSlot(quota=...)`` holds): ``qn[t]`` per node type and ``qe[j]`` per
+    relation, in ``g.ntypes`` / ``g.canonical_etypes`` order, either may be None.
+
+    * The node quota acts inside DropNode: of the nodes of type t it keeps, the first ``qn[t]`` in node-id order stay; the others are removed
+      as if drawn, their edges in the same stage.  A DropEdge behind DropNode ranks the edges that remain, a NodeShuffle behind it permutes the
+      nodes that remain.  Without a DropNode in the pipeline the node quota is ignored.
+    * The edge quota acts behind the last stage: relation j keeps the first ``qe[j]`` of its final edges in input order (which every stage
+      preserves); edge fields follow.
+    * A quota that is not reached changes nothing: the result is ``pipe(g, draw, fused=False)`` bit for bit.
+
+    Tensor formulation, any device.  Returns ``(graph, node_excess, edge_excess)``: by how many the draw exceeded the quota of every node type
+    (survivors of DropNode's draw minus ``qn[t]``; empty without DropNode or ``qn``) and of every relation (final edges of the node-truncated
+    pipeline minus ``qe[j]``), zeros where it did not."""
+    seed = _seed(draw)
+    _single(g)
+    xn: List[int] = []
+    for k, t in enumerate(pipe.transforms):
+        if not isinstance(t, BaseTransform):
+            raise ValueError("truncated: every member of the pipeline must be a transform of this module")
+        g = t.apply(g, seed, k, quota=qn, excess=xn) if isinstance(t, DropNode) and qn is not None else t.apply(g, seed, k)
+    if qe is None:
+        return g, xn, []
+    lim = {r: max(0, int(qe[j])) for j, r in enumerate(g.canonical_etypes)}
+    xe = [max(0, g._edges[r][0].numel() - lim[r]) for r in g.canonical_etypes]
+    if any(xe):
+        edges = OrderedDict((r, (u[:lim[r]], v[:lim[r]])) for r, (u, v) in g._edges.items())
+        g = _copy_frames(g, HeteroGraph(OrderedDict((t, g.num_nodes(t)) for t in g.ntypes), edges), edge=lambda r, key, x: x[:lim[r]])
+    return g, xn, xe
 
 
 def reference_train_transform() -> Compose:
