@@ -8,6 +8,7 @@
 
 Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation;
                            --captured-slots 3 --augment --quota --optimizer adam: captured slots sized for the draw;
+                           add --type-mask: slots that also replay batches lacking a node type, DESIGN 3.29;
                            --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers)
 Run data-parallel on N:    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_synthetic.py
 """
@@ -44,6 +45,10 @@ def main(argv=None):
                     help="train through trainer.CapturedSlotStep over K padded batch slots by slide size (DESIGN 3.15): one captured step per slot, "
                          "replayed over every new batch that fits; needs --optimizer adam, sgd or adadelta (capturable).  With --augment the slots draw the "
                          "augmentation on the device in front of every replay (DESIGN 3.16)")
+    ap.add_argument("--type-mask", action="store_true",
+                    help="with --captured-slots: slots with a device-side presence table (data.BatchSlot(type_mask=True), DESIGN 3.29) - batches "
+                         "that lack a node type, and augmented ones a draw can empty of one, are replayed too instead of stepped eagerly; "
+                         "needs a wsi_hgnn_amd.optim optimizer (--optimizer adam, sgd or adadelta here)")
     ap.add_argument("--quota", action="store_true",
                     help="with --captured-slots and --augment: size the slots for the draw instead of for the stored slides - survivor quotas "
                          "(data.BatchSlot(quota=\"bound\"), DESIGN 3.28); the epoch line then reports in how many fills a quota bound (expected 0)")
@@ -132,7 +137,8 @@ def main(argv=None):
             part = its[:max(args.batch, (len(its) * (k + 1) + K - 1) // K)]
             caps.append(([top([nodes_of(it)[t] for it in part]) + 1 for t in range(len(its[0].num_nodes))], [top([edges_of(it)[t] for it in part]) for t in range(len(its[0].num_nodes))], args.batch))
         gnn.train()
-        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c, per_relation_src=hgt, quota="bound" if args.quota else None) for c in caps],
+        slot_step = trainer.CapturedSlotStep(gnn, opt, loss_fn, [data.BatchSlot(loader, c, per_relation_src=hgt, quota="bound" if args.quota else None,
+                                                                                    type_mask=args.type_mask) for c in caps],
                                              metrics=train_metrics)
 
     # 3. epochs
@@ -152,6 +158,8 @@ def main(argv=None):
         metrics = io.evaluate(gnn, eval_loader) if slot_eval is None else slot_eval.evaluate()
         if rank == 0:
             print(f"epoch {epoch}: train loss {tot / max(n, 1):.4f}  eval {metrics}")
+            if slot_step is not None:
+                print(f"epoch {epoch}: {slot_step.replays} steps replayed, {slot_step.eager_steps} stepped eagerly so far")
             if slot_step is not None and args.quota:                            # one read-back per slot and epoch
                 print(f"epoch {epoch}: fills truncated by a quota so far {slot_step.overflows()} of {slot_step.replays} replayed steps")
             if train_metrics is not None:                                       # train_gnn.py:104-108, one read-back per epoch

@@ -569,6 +569,16 @@ typedef struct wsi_optim_hyper {
 } wsi_optim_hyper_t;
 int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper, void* stream);
 
+/* wsi_optim_step with a per-tensor GATE read on the device (an addition to ABI 26; optim._OneLaunch.gate).  gate_index: HOST array
+ * of `count` words (NULL: nobody is gated), gate_index[i] = 0: tensor i has no gate, k in 1..gate_len: its gate word is gate_table[k - 1], a
+ * DEVICE float table of gate_len <= 255 words that every workgroup of the tensor reads when the launch runs.  A tensor whose gate word is 0.0 is
+ * left alone: p, s0, s1, its `step` word and its `ticket` word stay bit for bit as they were (its workgroups return before they load, store or
+ * take a ticket) - what torch does to a parameter whose gradient is None.  Any other gate word, or no gate: wsi_optim_step's arithmetic, bit
+ * for bit.  wsi_optim_tensor_t and wsi_optim_step are unchanged; a rule that reads t takes a gated tensor with a `step` word only (a host count
+ * would advance whether the tensor was stepped or not). */
+int wsi_optim_step_gated(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
+                         const int32_t* gate_index, const float* gate_table, int32_t gate_len, void* stream);
+
 /* Mean cross entropy of logits [B, C] against int64 labels and its gradient factor in ONE launch (torch.nn.CrossEntropyLoss() with its
  * defaults, parser.py:182-183, applied at trainer/train_gnn.py:67):  *loss = mean over the VALID rows b of (logsumexp(logits[b]) - logits[b, y_b]);
  * dlogits[b, c] = (softmax(logits[b])[c] - [c == y_b]) / #valid  (the caller multiplies it by the incoming gradient of the loss).
@@ -653,6 +663,13 @@ int wsi_pool_bwd_bias(const float* gt_seg, int32_t T, int32_t S, int32_t D, int3
  * every batch that fits.  Accepts every mode. */
 int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
 int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream);
+
+/* Which node types the REAL slides of a filled batch slot hold (an addition to ABI 26; data.BatchSlot(type_mask=...)):
+ *   out[t] = 1.0 if seg_nonempty[t * graphs + b] != 0 for some b < b_cap, else 0.0                                    (t < T)
+ * seg_nonempty: the slot's readout table, float [T * graphs] with segment t * graphs + b (graphs 0 .. b_cap - 1 are the real slides and the
+ * empty graphs behind them, the rest the filler), as wsi_slot_fill and wsi_slot_aug_* have just written it on `stream`.  One wave, plain
+ * loads and stores, no atomics, no read-back; every word of out [T] is written.  1 <= T, 0 <= b_cap <= graphs. */
+int wsi_type_present(const float* seg_nonempty, int32_t T, int32_t graphs, int32_t b_cap, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-wise kernels of the HGT / GCN siblings of the path.

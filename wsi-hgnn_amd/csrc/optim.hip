@@ -33,11 +33,13 @@ struct OptimTable {
     int64_t n[OPTIM_MAX];
     int32_t block_start[OPTIM_MAX + 1];
     uint8_t flags[OPTIM_MAX];
+    uint8_t gate[OPTIM_MAX];                              // 0: no gate; k: the tensor is stepped only when gate_table[k - 1] != 0 (wsi_optim_step_gated)
     int32_t count;
     double lr_d, lr_decay_d, beta1_d, beta2_d;            // what the t-dependent factors are made of, in double
     float lr, weight_decay, momentum, omd, eps, rho, omr, beta2, omb1, omb2;     // omd = 1 - dampening, omr = 1 - rho, omb = 1 - beta
     float f0, f1;                                         // the factors for t = host_step: Adam step_size, bc2_sqrt; Adagrad clr
     int32_t nesterov;
+    const float* gate_table;                              // device words, read by every workgroup of a gated tensor
 };
 static_assert(sizeof(OptimTable) <= 5680, "the table travels in the kernel arguments: no larger than the largest argument block this library has "
                                           "launched with (5680 bytes: the 128-tensor table of the Adam kernel this template replaced)");
@@ -90,6 +92,10 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
     const int blk = (int)blockIdx.x;
     while (t + 1 < T.count && T.block_start[t + 1] <= blk) ++t;            // (block-uniform)
     t = __builtin_amdgcn_readfirstlane(t);                                 // (said to the compiler: every table read below stays a scalar load of the kernel arguments)
+    // a gated tensor whose gate word is 0.0: the whole workgroup leaves before it loads, stores or takes a ticket (block-uniform, in front of
+    // every barrier) - p, the states, the count and the ticket word stay as they were, as torch leaves a parameter without a gradient
+    const int gate = T.gate[t];
+    if (gate && T.gate_table[gate - 1] == 0.f) return;
     const int64_t base = (int64_t)(blk - T.block_start[t]) * OPTIM_BLOCK_ELEMS;
     const int64_t n = T.n[t];
     float* __restrict__ p = T.p[t];
@@ -168,8 +174,10 @@ static int optim_instance(int32_t rule, const wsi_optim_hyper_t& H) {
 }
 static int optim_states(int inst) { return inst == R_SGD ? 0 : (inst == R_SGD_MOMENTUM || inst == R_ADAGRAD) ? 1 : 2; }
 
-// What both entry points do once every argument is checked: the hyper-parameters into the table, then one launch per OPTIM_MAX non-empty tensors.
-static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t& H, hipStream_t st) {
+// What the entry points do once every argument is checked: the hyper-parameters into the table, then one launch per OPTIM_MAX non-empty tensors.
+// gate_index: per tensor 0 (no gate) or the 1-based word of gate_table; null: no tensor is gated.
+static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t& H, hipStream_t st,
+                           const int32_t* gate_index = nullptr, const float* gate_table = nullptr) {
     const int inst = optim_instance(rule, H), ns = optim_states(inst);
     OptimTable T;
     T.lr_d = H.lr; T.lr_decay_d = H.lr_decay; T.beta1_d = H.beta1; T.beta2_d = H.beta2;
@@ -179,6 +187,7 @@ static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int3
     T.beta2 = (float)H.beta2; T.omb1 = (float)(1.0 - H.beta1); T.omb2 = (float)(1.0 - H.beta2);
     T.nesterov = H.nesterov != 0.0;
     T.f0 = T.f1 = 0.f;
+    T.gate_table = gate_table;
     if (H.host_step >= 1.0) {
         if (inst == R_ADAM) optim_factors<R_ADAM>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
         if (inst == R_ADAGRAD) optim_factors<R_ADAGRAD>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
@@ -193,6 +202,7 @@ static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int3
             const int k = T.count++;
             T.p[k] = a.p; T.g[k] = a.g; T.s0[k] = ns >= 1 ? a.s0 : nullptr; T.s1[k] = ns >= 2 ? a.s1 : nullptr;
             T.step[k] = a.step; T.ticket[k] = a.ticket; T.n[k] = a.n; T.flags[k] = (uint8_t)(a.flags & WSI_OPTIM_FIRST);
+            T.gate[k] = gate_index ? (uint8_t)gate_index[i] : 0;
             T.block_start[k] = (int32_t)blocks;
             blocks += (a.n + OPTIM_BLOCK_ELEMS - 1) / OPTIM_BLOCK_ELEMS;
         }
@@ -237,7 +247,8 @@ extern "C" int wsi_adam_step(const wsi_adam_tensor_t* tensors, int32_t count, do
     return check_launch("adam_step");
 }
 
-extern "C" int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper, void* stream) {
+static int optim_step_checked(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
+                              const int32_t* gate_index, const float* gate_table, void* stream) {
     // every argument is checked before the first launch: a bad tensor 200 must not leave tensors 0..87 stepped
     if (rule != WSI_OPTIM_SGD && rule != WSI_OPTIM_ADAGRAD && rule != WSI_OPTIM_ADADELTA && rule != WSI_OPTIM_ADAM) { set_error("optim_step: unknown rule %d", rule); return WSI_EINVAL; }
     if (count < 0) { set_error("optim_step: negative tensor count"); return WSI_EINVAL; }
@@ -268,8 +279,25 @@ extern "C" int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, i
         ++nonempty;
         if (!a.p || !a.g || (ns >= 1 && !a.s0) || (ns >= 2 && !a.s1)) { set_error("optim_step: tensor %d: null pointer (p, g or a state tensor of the rule)", i); return WSI_EINVAL; }
         if (counts && !a.step && !(H.host_step >= 1.0 && std::isfinite(H.host_step))) { set_error("optim_step: tensor %d has no step word and host_step is not a count >= 1", i); return WSI_EINVAL; }
+        if (counts && !a.step && gate_index && gate_index[i]) { set_error("optim_step_gated: tensor %d is gated and has no step word (a host count advances whether it is stepped or not)", i); return WSI_EINVAL; }
     }
     if (nonempty == 0) return WSI_OK;                  // zero-element tensors only: nothing to launch (and no HIP call)
-    optim_launches(rule, tensors, count, H, (hipStream_t)stream);
+    optim_launches(rule, tensors, count, H, (hipStream_t)stream, gate_index, gate_table);
     return check_launch("optim_step");
+}
+
+extern "C" int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper, void* stream) {
+    return optim_step_checked(rule, tensors, count, hyper, nullptr, nullptr, stream);
+}
+
+extern "C" int wsi_optim_step_gated(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
+                                    const int32_t* gate_index, const float* gate_table, int32_t gate_len, void* stream) {
+    if (gate_len < 0 || gate_len > 255) { set_error("optim_step_gated: gate_len %d outside 0..255", gate_len); return WSI_EINVAL; }
+    bool any = false;
+    for (int32_t i = 0; gate_index && i < count; ++i) {
+        if (gate_index[i] < 0 || gate_index[i] > gate_len) { set_error("optim_step_gated: tensor %d: gate index %d outside 0..%d", i, gate_index[i], gate_len); return WSI_EINVAL; }
+        any = any || gate_index[i] != 0;
+    }
+    if (any && !gate_table) { set_error("optim_step_gated: null gate table"); return WSI_EINVAL; }
+    return optim_step_checked(rule, tensors, count, hyper, any ? gate_index : nullptr, gate_table, stream);
 }

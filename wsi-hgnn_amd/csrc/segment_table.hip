@@ -106,6 +106,16 @@ void launch_tile_scan(int32_t* tile_sum, int ntiles, const int64_t* rows, int st
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(256), 0, st, tile_sum, ntiles, rows, stride, col, nseg, counts);
 }
 
+// Which node types the real slides of a filled slot hold (wsi_type_present): one wave, lane t reads the b_cap readout words of node type t.
+__global__ __launch_bounds__(64) void type_present_kernel(const float* __restrict__ seg_nonempty, int T, int graphs, int b_cap,
+                                                          float* __restrict__ out) {
+    for (int t = threadIdx.x; t < T; t += 64) {
+        bool any = false;
+        for (int b = 0; b < b_cap; ++b) any = any || seg_nonempty[(int64_t)t * graphs + b] != 0.f;
+        out[t] = any ? 1.f : 0.f;
+    }
+}
+
 static int launch_segment_table(const char* who, const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
     if (nsegs < 0 || total_blocks < 0) { set_error("%s: bad argument", who); return WSI_EINVAL; }
     if (nsegs == 0 || total_blocks == 0) return WSI_OK;
@@ -124,4 +134,11 @@ extern "C" int wsi_plan_assemble(const int64_t* desc, int32_t nsegs, int32_t tot
 
 extern "C" int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
     return launch_segment_table("slot_fill", desc, nsegs, total_blocks, stream);
+}
+
+extern "C" int wsi_type_present(const float* seg_nonempty, int32_t T, int32_t graphs, int32_t b_cap, float* out, void* stream) {
+    if (T < 1 || graphs < 0 || b_cap < 0 || b_cap > graphs) { set_error("type_present: bad argument"); return WSI_EINVAL; }
+    if (!out || (!seg_nonempty && b_cap > 0)) { set_error("type_present: null pointer"); return WSI_EINVAL; }
+    hipLaunchKernelGGL(type_present_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, seg_nonempty, (int)T, (int)graphs, (int)b_cap, out);
+    return check_launch("type_present");
 }

@@ -446,9 +446,17 @@ class BatchSlot:
     slot can be sized for the draw instead of for the stored slides.  ``"bound"``: ``slot_quota_bound`` (binds with probability <= 2 ** -32 per
     table); a callable ``quota(idx) -> (qn, qe)`` sets limits by hand.  ``capacity=None`` then sums the ``batch_size`` largest quotas, ``fits``
     tests the quota sums, ``counts()`` returns the truncated counts, and ``overflows()`` / ``overflow_excess()`` read back how often and by how
-    much a quota bound.  A truncated batch is a valid graph, just not the eager loader's batch for that draw.  ``None``: today's slot."""
+    much a quota bound.  A truncated batch is a valid graph, just not the eager loader's batch for that draw.  ``None``: today's slot.
 
-    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0, per_relation_src: bool = False, quota=None):
+    ``type_mask``: ``True`` gives the slot ``type_present``, a float32 ``[T]`` table on its device - 1.0 where the REAL slides
+    of the batch just filled (graphs ``0 .. b_cap - 1``, never the filler) hold a node of the type after augmentation and quota truncation,
+    else 0.0 - re-derived on the device behind every fill (``graph.derive_type_present``: one wave next to ``_derive``, no read-back) and
+    attached to the graph as ``slot.graph._type_present``, where the models' heads read it in place of their host-side test
+    (``h[k].shape[0] > 0``) and ``optim``'s gate reads it in place of a ``None`` gradient.  A float32 ``[T]`` device tensor instead of
+    ``True`` makes the slot write the caller's table (several slots then share one: ``share_type_table``).  Such a slot takes batches in
+    which NO slide has a node of some type, and an augmented one drops the ``p ** n`` rule of ``fits``.  ``False``: today's slot."""
+
+    def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0, per_relation_src: bool = False, quota=None, type_mask=False):
         if not loader.resident:
             raise RuntimeError("BatchSlot needs a device-resident data set (GraphBatchLoader(..., resident=True)): the fill copies the slides' features "
                                "device to device; a pinned-host loader stays on its own double-buffered path")
@@ -529,11 +537,29 @@ class BatchSlot:
                                  f"{_graph_mod.PLAN_REL_MAX_RELS}")
             self.rel = _graph_mod.plan_rel_buffers(hd, lay.E, self.device)
             G.__dict__["_plan_rel"] = _graph_mod.rel_plan_over(hd, plan, self.rel)
+        # which node types the real slides hold: a device table behind every fill, read by the heads and by the optimizer's gate
+        self.type_mask, self.type_present = type_mask is not False and type_mask is not None, None
+        if self.type_mask:
+            self.share_type_table(torch.ones(T, dtype=torch.float32, device=self.device) if type_mask is True else type_mask)
+
+    def share_type_table(self, table: torch.Tensor) -> None:
+        """Make ``table`` (float32 ``[T]`` on the slot's device) this slot's presence table: every later fill writes it, and the slot graph
+        carries it.  A step captured over the slot before this call still reads the old table."""
+        if not self.type_mask:
+            raise RuntimeError("BatchSlot.share_type_table: the slot was built without type_mask")
+        T = self.layout.T
+        if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (T,) or not table.is_contiguous()
+                or _resolve_device(table.device) != _resolve_device(self.device)):
+            raise ValueError(f"BatchSlot: type_mask is True or a contiguous float32 [{T}] tensor on the slot's device ({self.device})")
+        self.type_present = table
+        self.graph._type_present = table
 
     def _derive(self) -> None:
         """The per-relation tables of the batch just filled in, on the current stream behind the fill (one C call and the source order)."""
         if self.rel is not None:
             _graph_mod.derive_rel_tables(self.layout.hd, self.graph._plan, self.rel, sort_sources=self.rel_sorted)
+        if self.type_present is not None:
+            _graph_mod.derive_type_present(self.layout, self.bufs, self.type_present)
 
     def quota_of(self, idx: int):
         """``(qn, qe)`` of the loader's slide ``idx`` under this slot's quota rule, never above the stored counts (cached)."""
@@ -559,14 +585,15 @@ class BatchSlot:
 
     def fits(self, idxs: Sequence[int]) -> bool:
         """Does the batch of the loader's slides ``idxs`` fit: same schema bucket, at most ``b_cap`` slides, and per node type at least one
-        node and no fewer than zero edges left for the filler."""
+        node and no fewer than zero edges left for the filler.  Without ``type_mask`` two more rules hold: every node type occurs in some
+        slide, and on an augmented slot no draw can empty a type in practice (below)."""
         idxs = list(idxs)
         if not idxs or any(i not in self.members for i in idxs):
             return False
         counts, ecounts = self._counts(idxs)
-        if not _graph_mod.SlotBatch.fits(self.layout, counts, ecounts):
+        if not _graph_mod.SlotBatch.fits(self.layout, counts, ecounts, self.type_mask):
             return False
-        if self.spec is not None and self.spec.node_thr > 0:
+        if self.spec is not None and self.spec.node_thr > 0 and not self.type_mask:
             # augmented slot: the models switch a node type's head off when the batch has no node of the type - a host-side branch frozen into a
             # capture - so a draw that empties a type must be impossible in practice: p_node ** n[t] <= 2 ** -32 for every type (n >= 32 at 0.5)
             p = self.spec.node_thr / 65536.0
@@ -595,7 +622,8 @@ class BatchSlot:
         scales = None
         if self.device.type == "cuda":
             scales = [[it.feat_scale(t) for t in range(T)] for it in its]
-        sb = _graph_mod.slot_fill(self.layout, self.bufs, [it.pieces for it in its], [it.label for it in its], [it.feat for it in its], scales)
+        sb = _graph_mod.slot_fill(self.layout, self.bufs, [it.pieces for it in its], [it.label for it in its], [it.feat for it in its], scales,
+                                  self.type_mask)
         G, lay = self.graph, self.layout
         for i, t in enumerate(G.ntypes):
             G._batch_num_nodes[t] = torch.tensor(sb.counts[i], dtype=torch.int64)

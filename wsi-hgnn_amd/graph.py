@@ -1071,7 +1071,8 @@ class SlotBatch:
     def fits(lay: SlotLayout, counts: Sequence[Sequence[int]], ecounts: Sequence[Sequence[int]], allow_empty_type: bool = False) -> bool:
         """``counts[b][t]`` / ``ecounts[b][t]``: nodes / edges (by destination type) of slide b.  ``allow_empty_type``: the layout of a batch in
         which some node type has no real node is still defined (an augmented batch after an unlucky draw: the filler takes the whole type) -
-        ``BatchSlot.fits`` never lets such a batch be STEPPED on a slot."""
+        ``BatchSlot.fits`` lets such a batch be STEPPED on a slot only when the slot carries a device-side presence table
+        (``BatchSlot(type_mask=...)``, DESIGN 3.29: heads and optimizer then read, on the device, which types the real slides hold)."""
         if not 1 <= len(counts) <= lay.b_cap:
             return False
         if allow_empty_type:
@@ -1155,33 +1156,35 @@ def _float_bits(xs: Sequence[float]) -> List[int]:
 
 
 def slot_fill(lay: SlotLayout, bufs: Dict[str, torch.Tensor], pieces: Sequence[PlanPieces], labels: Sequence[int],
-              feats: Sequence[Sequence[torch.Tensor]], scales: Optional[Sequence[Sequence[torch.Tensor]]] = None) -> SlotBatch:
+              feats: Sequence[Sequence[torch.Tensor]], scales: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+              allow_empty_type: bool = False) -> SlotBatch:
     """Write the padded batch of the stored graphs ``pieces`` (labels ``labels``, per-type fp32 feature tables ``feats[b][t]`` and, optionally,
     their row scales ``scales[b][t]``) into the slot's static tables ``bufs`` (``SlotLayout.buffers``): on the GPU ONE upload (a descriptor
     table) and ONE launch (``wsi_slot_fill``), no allocation inside the library, no read-back, no synchronisation, on the current stream; the
-    filler's tables come from index arithmetic in the kernel.  On the CPU: ``slot_fill_torch`` copied into ``bufs``.  Features and plan share
+    filler's tables come from index arithmetic in the kernel.  On the CPU: ``slot_fill_torch`` copied into ``bufs``.  ``allow_empty_type``: as ``SlotBatch.fits`` (a slot with a presence
+    table, ``derive_type_present``).  Features and plan share
     the launch: every mode works on 1024-element blocks (the feature copy on 16-byte elements).  The fill writes behind PyTorch's version
     counters - see DESIGN 3.15 for what that means for caches."""
     dev = bufs["rowptr"].device
     if dev.type != "cuda":
-        out = slot_fill_torch(lay, pieces, labels, feats, scales, dev)
+        out = slot_fill_torch(lay, pieces, labels, feats, scales, dev, allow_empty_type)
         with torch.no_grad():
             for k, v in out.items():
                 if k != "batch":
                     bufs[k].copy_(v)
         return out["batch"]
     from . import _native as N
-    sb, tb = _slot_descriptors(lay, bufs, pieces, labels, feats, scales)
+    sb, tb = _slot_descriptors(lay, bufs, pieces, labels, feats, scales, allow_empty_type)
     desc = tb.upload(dev)
     N.check(N.load().wsi_slot_fill(N.ptr(desc), tb.nsegs, tb.blocks, N.stream()), "wsi_slot_fill")
     bufs["_desc"] = desc            # (stream-ordered: the table must outlive the launch; the next fill replaces it behind this one)
     return sb
 
 
-def _slot_descriptors(lay: SlotLayout, bufs, pieces, labels, feats, scales):
+def _slot_descriptors(lay: SlotLayout, bufs, pieces, labels, feats, scales, allow_empty_type: bool = False):
     """The descriptor table of ``slot_fill``: (SlotBatch, SegmentTable)."""
     dev = bufs["rowptr"].device
-    sb = SlotBatch(lay, pieces)
+    sb = SlotBatch(lay, pieces, allow_empty_type)
     T, hd, B, G = lay.T, lay.hd, sb.B, lay.graphs
     F = lay.in_dim
     tb = SegmentTable("slot_fill")
@@ -1237,6 +1240,22 @@ def _slot_descriptors(lay: SlotLayout, bufs, pieces, labels, feats, scales):
     for s_, (a, b_) in enumerate(sb.ranges):
         seg(bufs["row_seg"], a, b_ - a, add=s_)
     return sb, tb
+
+
+def derive_type_present(lay: SlotLayout, bufs: Dict[str, torch.Tensor], out: torch.Tensor) -> None:
+    """``out[t] = 1.0`` when a REAL slide of the batch just filled into ``bufs`` holds a node of type t, else 0.0 (float32 ``[T]``):
+    from the slot's readout table ``seg_nonempty`` (segment ``t * graphs + b``; graphs ``0 .. b_cap - 1`` are never the filler) as the fill
+    has just written it, on the current stream - on the GPU ``wsi_type_present`` (one wave, no read-back, no host arithmetic), on the CPU
+    the same in tensor operations (the kernel's oracle)."""
+    ne = bufs["seg_nonempty"]
+    if tuple(out.shape) != (lay.T,) or out.dtype != torch.float32 or out.device != ne.device or not out.is_contiguous():
+        raise ValueError(f"derive_type_present: the table is a contiguous float32 [{lay.T}] tensor on the slot's device")
+    if ne.device.type != "cuda":
+        with torch.no_grad():
+            out.copy_((ne.reshape(lay.T, lay.graphs)[:, :lay.b_cap] != 0).any(dim=1).to(torch.float32))
+        return
+    from . import _native as N
+    N.check(N.load().wsi_type_present(N.ptr(ne), lay.T, lay.graphs, lay.b_cap, N.ptr(out), N.stream()), "wsi_type_present")
 
 
 def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]],

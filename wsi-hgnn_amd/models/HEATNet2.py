@@ -28,9 +28,21 @@ class HEATNet2(HEATTrunk):
         for layer in range(n_layers + 1):
             self.pools.append(make_pool(graph_pooling_type, layer, in_dim, hidden_dim))
 
+    def type_gated_parameters(self):
+        """Per node-type position (sorted type names) the parameters whose gradient is ``None`` - not zero - when an unpadded batch has no
+        node of the type: what a captured step over ``BatchSlot(type_mask=True)`` must keep from the optimizer (``optim.gate``, DESIGN
+        3.29).  None here: every ``linears_prediction[k]`` is a group of ONE grouped GEMM whether its rows are read or not, so the head of
+        an absent type gets exact zero gradients, on a padded batch too (established by running the eager step: the GPU test holds it)."""
+        return [[] for _ in sorted(self.node_dict)]
+
     def forward(self, G, h=None):
         ctx, hcat, out, B = self.encode(G, h)
+        present = getattr(G, "_type_present", None)                          # a slot's device-side presence table (DESIGN 3.29)
         hg = 0
+        if present is not None:                                              # the filler gives every type rows: the host test below sees them
+            for i in range(len(ctx.rows)):                                   # all present; which head counts is decided on the device
+                hg = hg + present[i] * out[i * B:(i + 1) * B]
+            return hg
         for i, (a, b) in enumerate(ctx.rows):                                # HEATNet2.py:189-194
             if b - a > 0:
                 hg = hg + out[i * B:(i + 1) * B]

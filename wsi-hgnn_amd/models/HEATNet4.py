@@ -86,9 +86,21 @@ class HEATNet4(HEATTrunk):
         self.head_1 = nn.Linear(256, 64)
         self.head = nn.Linear(64, out_dim)
 
+    def type_gated_parameters(self):
+        """Per node-type position (sorted type names) the parameters whose gradient is ``None`` - not zero - when an unpadded batch has no
+        node of the type: what a captured step over ``BatchSlot(type_mask=True)`` must keep from the optimizer (``optim.gate``, DESIGN
+        3.29).  With every block normalised (the fused path) the absent type's projection is not a group of the GEMM and its block is not
+        called: ``linears_prediction[k].weight / .bias`` and ``attn[k].op.weight``.  Otherwise all projections run as one grouped GEMM
+        (exact zero gradients for the absent one) and only ``attn[k].op.weight`` is never reached."""
+        types = sorted(self.node_dict)
+        fused = all(self.attn[t].normalize_attn for t in types)
+        return [(list(self.linears_prediction[t].parameters()) if fused else []) + [self.attn[t].op.weight] for t in types]
+
     def forward(self, G, h=None):
         ctx, hcat, pooled, B = self.encode(G, h, predict=False)
         T = len(ctx.ntypes)
+        mask = getattr(G, "_type_present", None)                             # a slot's device-side presence table (DESIGN 3.29): the filler
+        # gives every type rows, so the host test below is all True there and the table zeroes what belongs to a type the real slides lack
         present = [(b - a) > 0 for (a, b) in ctx.rows]                       # HEATNet4.py:218,230 h[k].shape[0] > 0
         lins = [self.linears_prediction[t] for t in ctx.ntypes]
         width = lins[0].weight.shape[0]
@@ -103,6 +115,8 @@ class HEATNet4(HEATTrunk):
                     out_rows=[(0, B)] * len(idx), num_out_rows=B)             # absent node types: zero columns (:240)
             g = ops.grouped_linear(pooled, spec, [lins[i].weight for i in idx], [lins[i].bias for i in idx])
             g = _IdentityZeroGrads.apply(g, *[self.attn[ctx.ntypes[i]].op.weight for i in idx])
+            if mask is not None:                                             # an absent type: exact zero columns (:240)
+                g = (g.view(B, T, width) * mask.view(1, T, 1)).view(B, T * width)
         else:
             spec = ctx.cache.get(("pred", B, width))
             if spec is None:
@@ -111,11 +125,12 @@ class HEATNet4(HEATTrunk):
             hg = 0
             for i, t in enumerate(ctx.ntypes):                               # :229-232
                 if present[i]:
-                    hg = hg + out[i * B:(i + 1) * B]
+                    hg = hg + (out[i * B:(i + 1) * B] if mask is None else mask[i] * out[i * B:(i + 1) * B])
             parts = []
             for i, t in enumerate(ctx.ntypes):                               # :236-240
                 if present[i]:
-                    parts.append(self.attn[t](out[i * B:(i + 1) * B], hg))
+                    part = self.attn[t](out[i * B:(i + 1) * B], hg)
+                    parts.append(part if mask is None else mask[i] * part)
                 else:
                     parts.append(torch.zeros(B, width, dtype=out.dtype, device=out.device))
             g = torch.cat(parts, dim=1)                                      # :242

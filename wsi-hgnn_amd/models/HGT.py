@@ -247,6 +247,13 @@ class HGT(nn.Module):
     def dead_parameter_names(self) -> List[str]:
         return _readout_sum_dead_parameters(self, "gcs")
 
+    def type_gated_parameters(self):
+        """Per node-type position (sorted type names) the parameters whose gradient is ``None`` - not zero - when an unpadded batch has no
+        node of the type (``optim.gate``).  None here: every ``linears_prediction[k][i]`` is a group of one grouped GEMM whether
+        its rows are read or not, so the heads of an absent type get exact zero gradients, on a padded batch too (established by running
+        the eager step: the GPU test holds it)."""
+        return [[] for _ in sorted(self.node_dict)]
+
     def forward(self, G, h=None):
         return _readout_sum_forward(self, G, h, lambda i, hctx, x: self.gcs[i].forward_cat(
             hctx, hgt_context(G, hctx, self.edge_dict, self.n_hid, x.device, self.gcs[i].n_heads), x))
@@ -288,6 +295,7 @@ def _readout_sum_forward(model, G, h, layer_fn, need_last: bool = False):
                                     [model.adapt_ws[n].bias for n in hctx.nid]))
     B, T = G.batch_size, len(hctx.ntypes)
     present = [(b - a) > 0 for a, b in hctx.rows]
+    mask = getattr(G, "_type_present", None)         # a slot's device-side presence table: the filler gives every type rows
     hg = 0
     for i in range(model.n_layers):
         pool = model.pools[i]
@@ -303,7 +311,7 @@ def _readout_sum_forward(model, G, h, layer_fn, need_last: bool = False):
                                  [model.linears_prediction[t][i].bias for t in hctx.ntypes])
         for j in range(T):
             if present[j]:
-                hg = hg + out[j * B:(j + 1) * B]
+                hg = hg + (out[j * B:(j + 1) * B] if mask is None else mask[j] * out[j * B:(j + 1) * B])
         if need_last or i + 1 < model.n_layers:
             x = layer_fn(i, hctx, x)
     return (hg, x, hctx) if need_last else hg

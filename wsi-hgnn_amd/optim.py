@@ -86,6 +86,42 @@ class _OneLaunch(torch.optim.Optimizer):
             self.__dict__.pop("_wsi_tables", None)                #  and tables that point into the old ones go)
         return idx
 
+    def gate(self, params, table, index: int = 0) -> None:
+        """Bind ``params`` to the gate word ``table[index]`` (``table``: a float32 1-d tensor of at most 255 words on the parameters' device;
+        DESIGN 3.29): the launch reads the word ON THE DEVICE and leaves a parameter whose word is 0.0 alone - ``p``, its state tensors and
+        its ``step`` word stay bit for bit as they were, what torch does to a parameter whose gradient is ``None`` - and steps it as ever
+        when the word is anything else.  That is how a captured step, which differentiates a fixed parameter list, skips the head of a node
+        type the batch lacks (``trainer.CapturedSlotStep`` over ``BatchSlot(type_mask=True)``).  All gated parameters of one optimizer
+        share one table.  ``gate(params, None)`` unbinds.  Adam and Adagrad read the count: a host count advances whether the kernel stepped
+        the tensor or not, so they take a gate under ``capturable=True`` only."""
+        params = list(params)
+        gates = self.__dict__.setdefault("_wsi_gates", {})
+        self.__dict__.pop("_wsi_tables", None)                    # (a cached descriptor table holds the gate indices it was built with)
+        if table is None:
+            for p in params:
+                gates.pop(id(p), None)
+            return
+        name = type(self).__name__
+        group_of = {id(p): g for g in self.param_groups for p in g["params"]}
+        for p in params:
+            if id(p) not in group_of:
+                raise ValueError(f"{name}.gate: a parameter this optimizer does not step")
+            if self.READS_COUNT and not group_of[id(p)]["capturable"]:
+                raise RuntimeError(f"{name}.gate needs capturable=True: this rule reads the step count, and a count kept on the host advances "
+                                   "whether the kernel stepped the tensor or not - the gate is read on the device only")
+        if (not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 1 or not table.is_cuda
+                or not table.is_contiguous() or not 1 <= table.numel() <= 255):
+            raise ValueError(f"{name}.gate: the table is a contiguous float32 1-d tensor of 1 to 255 words on the GPU")
+        if not 0 <= int(index) < table.numel():
+            raise ValueError(f"{name}.gate: index {index} outside the table's {table.numel()} words")
+        if any(p.device != table.device for p in params):
+            raise ValueError(f"{name}.gate: the table and the parameters live on different devices")
+        rebound = {id(p) for p in params}
+        if any(t.data_ptr() != table.data_ptr() for k, (t, _) in gates.items() if k not in rebound):
+            raise ValueError(f"{name}.gate: all gated parameters of one optimizer share one table (one launch reads one)")
+        for p in params:
+            gates[id(p)] = (table, int(index))
+
     def load_state_dict(self, state_dict) -> None:
         # torch replaces the groups by the saved ones and keeps a saved count as it finds it: where the count lives is this OBJECT'S choice
         # (a checkpoint written by torch.optim, host counts, loads into a capturable optimizer and the other way round)
@@ -141,7 +177,12 @@ class _OneLaunch(torch.optim.Optimizer):
                 arr = (N.OptimTensor * len(items))()
                 tick = self._tickets(items[0][0].device)
                 written, empty = [], []                        # every tensor the launch writes; the step words of zero-element tensors
-                for a, (p, _, st, _) in zip(arr, items):
+                gates = self.__dict__.get("_wsi_gates") or {}
+                gidx, gtable = (ctypes.c_int32 * len(items))(), None          # per tensor 0 or the 1-based word of the gate table (gate())
+                for k, (a, (p, _, st, _)) in enumerate(zip(arr, items)):
+                    bound = gates.get(id(p))
+                    if bound is not None:
+                        gtable, gidx[k] = bound[0], bound[1] + 1
                     a.n = p.numel()
                     written.append(p)
                     for field, k in zip(("s0", "s1"), self.STATE):
@@ -153,15 +194,19 @@ class _OneLaunch(torch.optim.Optimizer):
                         a.step, a.ticket = st["step"].data_ptr(), tick.data_ptr() + 4 * index[id(p)]
                         written.append(st["step"])
                         if a.n == 0:
-                            empty.append(st["step"])
-                cached = tables[gi] = (key, arr, ctypes.cast(arr, ctypes.c_void_p), written, empty)
-            _, arr, arr_p, written, empty = cached
+                            empty.append((st["step"], None if bound is None else bound[0][bound[1]]))
+                cached = tables[gi] = (key, arr, ctypes.cast(arr, ctypes.c_void_p), written, empty, gidx, gtable)
+            _, arr, arr_p, written, empty, gidx, gtable = cached
             for a, (p, g, _, flags) in zip(arr, items):
                 a.p, a.g, a.flags = p.data_ptr(), g.data_ptr(), flags
-            for word in empty:
-                word += 1                                        # (no workgroup of the launch covers a zero-element tensor; torch counts its steps too)
+            for word, gate in empty:                             # (no workgroup of the launch covers a zero-element tensor; torch counts its steps too -
+                word += 1 if gate is None else (gate != 0).to(torch.float32)      # those of a gated one where its gate word says so, on the device)
             hyper.host_step = float(t)
-            N.check(lib.wsi_optim_step(self.RULE, arr_p, len(items), ctypes.addressof(hyper), N.stream()), "wsi_optim_step")
+            if gtable is None:
+                N.check(lib.wsi_optim_step(self.RULE, arr_p, len(items), ctypes.addressof(hyper), N.stream()), "wsi_optim_step")
+            else:
+                N.check(lib.wsi_optim_step_gated(self.RULE, arr_p, len(items), ctypes.addressof(hyper), ctypes.cast(gidx, ctypes.c_void_p),
+                                                 N.ptr(gtable), gtable.numel(), N.stream()), "wsi_optim_step_gated")
             # the kernel wrote through raw pointers: move the version counters as torch.optim's in-place ops would, so that autograd's "modified
             # by an inplace operation" check and every version-keyed fact about these tensors (ops._annotate) see the step
             torch.autograd.graph.increment_version(written)
@@ -199,9 +244,22 @@ class SGD(_OneLaunch):
     def _state_keys(self, group):
         return ("momentum_buffer",) if group["momentum"] != 0 else ()
 
+    def gate(self, params, table, index: int = 0) -> None:
+        # a gated tensor's FIRST step may be one the gate skips: its buffer then starts at zero, and the step that does run computes
+        # momentum * 0 + (1 - dampening) * g - torch's first step (buf = g) exactly when dampening is 0
+        params = list(params)
+        if table is not None:
+            group_of = {id(p): g for g in self.param_groups for p in g["params"]}
+            if any(id(p) in group_of and group_of[id(p)]["momentum"] != 0 and group_of[id(p)]["dampening"] != 0 for p in params):
+                raise ValueError("SGD.gate: with momentum, a gate needs dampening = 0 (a tensor whose first step the gate skips starts from a zero "
+                                 "buffer, which equals torch's first step only then)")
+        super().gate(params, table, index)
+
     def _new_state(self, p, group):
         st = self.state[p]
-        st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.contiguous_format)      # written, not read, by the first step
+        gated = id(p) in (self.__dict__.get("_wsi_gates") or {})
+        # written, not read, by the first step - unless a gate skips that step: zeros then (see gate)
+        st["momentum_buffer"] = (torch.zeros_like if gated else torch.empty_like)(p, memory_format=torch.contiguous_format)
         self.__dict__.pop("_wsi_tables", None)
         return st
 

@@ -141,6 +141,9 @@ def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
     slots = [slots] if isinstance(slots, BatchSlot) else list(slots)
     if not slots:
         raise ValueError(f"{who}: no slot")
+    if len({bool(getattr(s, "type_mask", False)) for s in slots}) > 1:
+        raise ValueError(f"{who}: slots with and without type_mask are mixed - the slots of one capture share one presence table (DESIGN 3.29): "
+                         "build all of them with BatchSlot(..., type_mask=True), or none")
     from .models.HGT import HGT
     if type(gnn) is HGT:
         # HGT's attention runs on the per-relation-source plan, which a slot re-derives on the device behind every fill - when it
@@ -160,6 +163,34 @@ def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
     if loader.device.type != "cuda":
         raise RuntimeError(f"{who}: the slots must live on the GPU")
     return slots, loader, loader.device
+
+
+def _share_type_table(slots):
+    """Slots built with ``type_mask``: rebind all of them to ONE presence table, the first slot's, and return it (else None).  Before any
+    warm-up or capture: a recorded step reads the table its slot graph carried when it was recorded."""
+    if not slots[0].type_mask:
+        return None
+    table = slots[0].type_present
+    for s in slots[1:]:
+        s.share_type_table(table)
+    return table
+
+
+def _gate_by_type(who: str, gnn: torch.nn.Module, optimizer, table: torch.Tensor) -> None:
+    """``optimizer.gate(gnn.type_gated_parameters()[t], table, t)`` for every node type t: the parameters an eager step on a
+    batch without the type leaves without a gradient are stepped only when ``table[t]`` says the type is there."""
+    from . import optim as _optim
+    if not isinstance(optimizer, _optim._OneLaunch):
+        raise RuntimeError(f"{who}: slots with type_mask need a wsi_hgnn_amd.optim optimizer (Adam / Adagrad with capturable=True, SGD, Adadelta): "
+                           f"a captured step hands the head of an absent node type exact zero gradients where the eager step hands it None, and "
+                           f"{type(optimizer).__module__}.{type(optimizer).__name__} cannot skip a tensor on a device-side word - "
+                           "wsi_hgnn_amd.optim's one-launch step can (optimizer.gate)")
+    stepped = {id(p) for g in optimizer.param_groups for p in g["params"]}
+    gated = [[p for p in params if id(p) in stepped] for params in gnn.type_gated_parameters()]
+    optimizer.gate([p for params in gated for p in params], None)          # (an earlier capture's table: one optimizer reads one)
+    for t, params in enumerate(gated):
+        if params:
+            optimizer.gate(params, table, t)
 
 
 def _first_slide(who: str, i: int, slot):
@@ -190,7 +221,13 @@ class CapturedSlotStep:
 
     ``metrics``: a ``metrics.EpochMetrics`` on the slots' device; the recorded step and the eager one then end with
     ``metrics.update(logits, labels)`` - the reference's per-epoch training metrics (``train_gnn.py:73-79,104-108``) with no read-back per step
-    (the warm-up steps count too: ``metrics.reset()`` where the epoch starts).  ``None``: the recorded step is exactly what it was."""
+    (the warm-up steps count too: ``metrics.reset()`` where the epoch starts).  ``None``: the recorded step is exactly what it was.
+
+    Slots built with ``type_mask=True`` (all of them or none) also take batches that lack a node type, and augmented ones
+    batches a draw can empty of one: the slots are rebound to ONE presence table (the first slot's), every fill re-derives it on the device,
+    the heads multiply by it, and ``optimizer.gate(gnn.type_gated_parameters()[t], table, t)`` keeps the parameters that an eager step would
+    leave without a gradient - weights, moments and step counts - exactly as they were.  This needs a ``wsi_hgnn_amd.optim`` optimizer
+    (torch's capturable ones cannot skip a tensor and are refused); the eager fallback sets the table to ones before it steps."""
 
     def __init__(self, gnn: torch.nn.Module, optimizer: torch.optim.Optimizer, loss_fcn, slots, warmup: int = 1, warmup_batches=None, metrics=None):
         self.slots, self.loader, dev = _check_slots("CapturedSlotStep", "step", gnn, slots)
@@ -200,6 +237,10 @@ class CapturedSlotStep:
         from .models.heat_layer import HEATLayer
         from .models.HGT import HGTLayer
         capture.require_capturable("CapturedSlotStep", optimizer)
+        # slots with a presence table: one table for all of them, and the optimizer gated on it
+        self.type_table = _share_type_table(self.slots)
+        if self.type_table is not None:
+            _gate_by_type("CapturedSlotStep", gnn, optimizer, self.type_table)
         # (an HGTLayer draws counter-based whenever a seed base is active, which it is throughout this class's steps)
         self.seed_base = capture.new_seed_word(dev) if capture.counter_dropout_only("CapturedSlotStep", gnn, (HEATLayer, HGTLayer)) else None
         self.gnn, self.optimizer, self.loss_fcn = gnn, optimizer, loss_fcn
@@ -249,6 +290,8 @@ class CapturedSlotStep:
                 if ready is not None:
                     torch.cuda.current_stream(self.loader.device).wait_event(ready)
             self.eager_steps += 1
+            if self.type_table is not None:                    # the loader's unpadded batch: the model reads no table and an absent head has no
+                self.type_table.fill_(1.0)                     # gradient of its own - every gate open
             return self._eager(G, labels)
         slot = self.slots[i]
         slot.load(idxs)
@@ -270,6 +313,9 @@ class CapturedSlotEval:
     ``evaluate`` calls changes the result as it must.  A training capture (``CapturedSlotStep``) lives beside this one on slots and a memory
     pool of its own.
 
+    Slots built with ``type_mask=True`` (all or none) are rebound to one presence table and also take batches that lack a node
+    type; nothing else changes.
+
     Refused: what ``CapturedSlotStep`` refuses (HGT on slots without the per-relation plan, the ``att`` readout, slots off the GPU or over several loaders), and slots over a loader
     with ``transform=`` - evaluation sees the stored slides (the reference augments ``type_ == "train"`` only, data.py:116-117).
     ``metrics=None`` builds an ``EpochMetrics`` for ``len(loader.items)`` rows."""
@@ -281,6 +327,7 @@ class CapturedSlotEval:
                                "loader without one")
         self.gnn = gnn
         self.slots = sorted(self.slots, key=lambda s: s.layout.N)                      # smallest first: what run() tries in turn
+        self.type_table = _share_type_table(self.slots)                                # (slots with type_mask: one presence table)
         self.replays, self.eager_runs = 0, 0
         self.graphs, self.outputs = [], []
         with capture.eval_mode(gnn):
