@@ -15,6 +15,7 @@ from __future__ import annotations
 import array
 import ctypes
 import contextlib
+from collections import namedtuple
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -1204,25 +1205,6 @@ class SegmentBroadcast:
 _LOW_RANK = {"enabled": True}
 
 
-# Column block of K / Q / V in a fused layer's [n, 3D] table.  "kqv": K | Q | V (the default).  "kvq": K | V | Q - the two rows an edge GATHERS by its
-# source (k for the logit, v for the message) and the two gradient rows pass 3 writes per source node (g_k, g_v) are ONE contiguous 2 D run
-# (4 KB at D = 512) instead of two runs 2 KB apart.  The kernels take three pointers: the layout is this module's choice.  Measured in round 5
-# (tools/layout_probe.py, both layers at full depth, interleaved): 6.731 vs 6.718 ms per step - no difference (a gather moves whole 128-byte lines
-# either way and the fabric does not care whether a node's two 2 KB runs touch): the default stays, the switch stays for the record.
-_KQV_LAYOUT = {"order": "kqv"}
-
-
-def set_kqv_layout(order: str) -> None:
-    if order not in ("kqv", "kvq"):
-        raise ValueError("kqv layout: 'kqv' or 'kvq'")
-    _KQV_LAYOUT["order"] = order
-
-
-def _kqv_blocks(nproj: int):
-    """(column block of K, of Q, of V) in a table of ``nproj`` blocks (2: K | Q - the last layer under a readout never forms V)."""
-    return (0, 2, 1) if (nproj == 3 and _KQV_LAYOUT["order"] == "kvq") else (0, 1, 2)
-
-
 _COLLAPSE_V = {"enabled": True, "min_work": 4.0e9}
 
 
@@ -1696,26 +1678,508 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
-def _gate_tables(hctx, skip, segs, num_segs: int):
-    """(seg_gate [num_segs] int32: the model gate (index into ``skip``) of the node type a readout segment belongs to, -1 for a type the layer
-    passes through;  type_gate [T] int32: the same per graph node type) - device tables, cached on the layer context per readout plan."""
-    from .graph import host_to_device
-    key = ("gate_tables", tuple(segs), num_segs)
+def _gate_table(hctx, skip, name: str, segs=None, num_segs: int = 0) -> torch.Tensor:
+    """The small host-built tables that map graph node types and readout segments to model gates (indices into ``skip``), uploaded once per layer
+    context and readout plan (``hctx.cache[(name, segs, num_segs)]``).  With gate(i) = hctx.nid[i] for a node type i the layer projects and -1
+    for one it passes through, and gate(s) = that of the type whose run of segments ``segs[i]`` holds s:
+      "type_gate" [T] int32 = gate(i)                          "seg_gate" [num_segs] int32 = gate(s)
+      "gate_of_row_type" [T, G] fp32 = [gate(i) == g]          "gate_of_seg" [G, num_segs] fp32 = [gate(s) == g]"""
+    key = (name, None if segs is None else tuple(segs), num_segs)
     hit = hctx.cache.get(key)
     if hit is None:
-        T = len(hctx.rows)
-        tg = [hctx.nid[i] if (i in hctx.a_types) else -1 for i in range(T)]
+        T, G = len(hctx.rows), skip.shape[0]
+        tg = [hctx.nid[i] if hctx.incoming[i] else -1 for i in range(T)]
         sg = [-1] * num_segs
-        for i, (s0, s1) in enumerate(segs):
-            for s_ in range(s0, s1):
-                sg[s_] = tg[i]
-        hit = hctx.cache[key] = (host_to_device(sg or [-1], torch.int32, skip.device), host_to_device(tg, torch.int32, skip.device))
+        for i, (s0, s1) in enumerate(segs or ()):
+            sg[s0:s1] = [tg[i]] * (s1 - s0)
+        rows, dtype = {"type_gate": (tg, torch.int32),
+                       "seg_gate": (sg or [-1], torch.int32),
+                       "gate_of_seg": ([[float(x == g_) for x in sg] for g_ in range(G)], torch.float32),
+                       "gate_of_row_type": ([[float(x == g_) for g_ in range(G)] for x in tg], torch.float32)}[name]
+        hit = hctx.cache[key] = host_to_device(rows, dtype, skip.device)
     return hit
+
+
+def _gate_ptr(skip, hctx, i: int):
+    """Pointer to the skip-gate logit of graph node type i (the ``gate`` field of a GEMM group)."""
+    return N.ptr(skip, 4 * hctx.nid[i])
+
+
+# What _HeatLayerFused.forward hands its backward, every field set on every path.  Besides tensors: pool = (ReducePlan, WSI_RED_SUM | WSI_RED_MEAN)
+# when the layer returned its readout, None when its output;  no_v: readout-fused and V never formed (kqv is K | Q; ctab, hp, csum are saved);
+# dropout: None, the CounterDropout (regenerated in the backward) or "mask" (the saved keep-mask tensor);  h_cols / t_cols: ColStats or None.
+_HeatState = namedtuple("_HeatState", "hctx H pool no_v dropout h_cols t_cols background_dw")
+# The saved tensors, None where the path does not form one: t, out at full depth;  t_mean, h_mean, z_mean (segment means of t, h and the
+# never-formed output) readout-fused;  ctab, hp, csum (``_pooled_factors``) without V;  mask: the dropout keep mask that came as a tensor.
+_HeatSaved = namedtuple("_HeatSaved", "h kqv score lse skip ew eb sim_csr t out t_mean h_mean z_mean ctab hp csum mask params", defaults=(None,) * 10)
+
+
+def _heat_save(ctx, sv: _HeatSaved) -> None:
+    ctx.save_for_backward(*sv[:-1], *sv.params)
+
+
+def _heat_saved(ctx) -> _HeatSaved:
+    k = len(_HeatSaved._fields) - 1
+    return _HeatSaved(*ctx.saved_tensors[:k], params=ctx.saved_tensors[k:])
+
+
+# ---- stages of _HeatLayerFused.forward ----
+def _heat_project(h, h_max, hctx, P, nproj: int, v_stats: bool):
+    """One grouped NT GEMM with the bias epilogue: kqv [n, nproj * D] = K | Q (| V) in column blocks 0, 1 (, 2), every node type's rows through
+    its own weights.  Returns (kqv, t_cols): with ``v_stats`` the V groups leave their column maxima, which bound t's (a row of t is a convex
+    combination of V rows: a few binades loose at most, which the 17-binade full-precision window of the scaled-fp16 split absorbs)."""
+    n, D = h.shape
+    dev, ldp = h.device, nproj * D
+    v_cols = ColStats.allocate(hctx.rows, D, dev, sums=False) if v_stats else None
+    kqv = torch.empty((n, ldp), dtype=torch.float32, device=dev)
+    groups = []
+    for i, (r0, r1) in enumerate(hctx.rows):
+        for j in range(nproj):
+            groups.append(dict(A=N.ptr(h, r0 * D * 4), lda=D, B=N.ptr(P[i][j]), ldb=D, Bw=[P[i][j]],
+                               C=N.ptr(kqv, (r0 * ldp + j * D) * 4), ldc=ldp, bias=N.ptr(P[i][4 + j]),
+                               M=r1 - r0, N=D, K=D, **_scale_in(h_max, r0),
+                               **(v_cols.produce(r0, r1, 0) if (v_cols is not None and j == 2) else {})))
+    if not _gemm(N.WSI_GEMM_NT, N.WSI_EPI_BIAS, groups, dev) or v_cols is None:
+        return kqv, None
+    # a row of t mixes V rows of EVERY source type that reaches its node: the bound of each of t's row ranges is the maximum over ALL parts
+    return kqv, ColStats(v_cols.bits, None, {r: (0, v_cols.bits.shape[0]) for r in hctx.rows if r[1] > r[0]})
+
+
+def _heat_attend(kqv, t_max, hctx, H: int, edge):
+    """Full attention, one launch (wsi_heat_attn_fwd): (t [n, D], score [E, H], lse [softmax segments, H]); ``t_max`` receives t's row scales.
+    ``edge`` = (e_weight, e_bias, sim in CSR order), here and below."""
+    plan, (ew, eb, sim_csr) = hctx.plan, edge
+    n, D, dev = kqv.shape[0], kqv.shape[1] // 3, kqv.device
+    score = torch.empty((max(plan.num_edges, 1), H), dtype=torch.float32, device=dev)
+    lse = torch.empty((max(plan.num_segs, 1), H), dtype=torch.float32, device=dev)
+    t = torch.empty((n, D), dtype=torch.float32, device=dev)
+    with _Timed("heat_attn"), _Timed("heat_attn_fwd_full"):
+        N.check(N.load().wsi_heat_attn_fwd(
+            N.ptr(kqv, D * 4), 3 * D, N.ptr(kqv), 3 * D, N.ptr(kqv, 2 * D * 4), 3 * D, n, D, H,
+            N.ptr(plan.node_seg), N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(sim_csr), N.ptr(plan.order_dst), plan.num_heavy, _attn_flags(plan),
+            N.ptr(ew), N.ptr(eb), N.ptr(t), D, N.ptr(score), N.ptr(lse), N.ptr(t_max), N.context(), N.stream()), "wsi_heat_attn_fwd")
+    return t, score, lse
+
+
+def _heat_attend_pooled(h, kqv, hctx, H: int, edge, prp, P):
+    """Readout-fused without V: the segment means of t and h without forming V or t.  The scores and softmax statistics alone
+    (wsi_heat_attn_scores_fwd); per source node the coefficients ctab [n, T, H] with which its value row enters each (destination type, graph)
+    segment sum of t (wsi_heat_pool_coeff); the weighted sums of h (``_pooled_factors``, which takes mean_seg(h) in the same pass); their
+    products with W_v per (head, source type) (one grouped NT GEMM into tpart[tau]); the sum over tau + the value-bias term + the 1 / count
+    scaling (wsi_pool_tmean):   sum_seg(t)[:, head hh] = sum_tau ( hp[:, hh, tau, :] (W_v^tau rows of head hh)^T + csum[tau, :, hh] b_v^tau (head hh) ).
+    Returns (score, lse, ctab, hp, csum, h_mean, t_mean)."""
+    plan, (ew, eb, sim_csr) = hctx.plan, edge
+    (n, D), dev, T, S, dk = h.shape, h.device, len(hctx.rows), prp.num_segs, h.shape[1] // H
+    lib = N.load()
+    score = torch.empty((max(plan.num_edges, 1), H), dtype=torch.float32, device=dev)
+    lse = torch.empty((max(plan.num_segs, 1), H), dtype=torch.float32, device=dev)
+    with _Timed("heat_attn"), _Timed("heat_attn_fwd_pooled"):
+        N.check(lib.wsi_heat_attn_scores_fwd(
+            N.ptr(kqv, D * 4), 2 * D, N.ptr(kqv), 2 * D, n, D, H,
+            N.ptr(plan.node_seg), N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(sim_csr), N.ptr(plan.order_dst), plan.num_heavy, _attn_flags(plan),
+            N.ptr(ew), N.ptr(eb), N.ptr(score), N.ptr(lse), N.context(), N.stream()), "wsi_heat_attn_scores_fwd")
+        ctab = torch.empty((n, T, H), dtype=torch.float32, device=dev)
+        N.check(lib.wsi_heat_pool_coeff(N.ptr(score), N.ptr(lse), N.ptr(_edge_segments(plan)), N.ptr(plan.colptr), N.ptr(plan.csc_eid),
+                                        N.ptr(plan.csc_dst), N.ptr(plan.inv_rd), N.ptr(prp.row_segment()), prp.num_segs // T, T, H, n,
+                                        N.ptr(ctab), N.stream()), "wsi_heat_pool_coeff")
+    hp, csum, h_mean = _pooled_factors(h, ctab, prp, T, H, with_mean=True)
+    tpart = torch.empty((T, S, D), dtype=torch.float32, device=dev)
+    groups = [dict(A=N.ptr(hp, (hh * T + tau) * D * 4), lda=H * T * D, B=N.ptr(P[tau][2], hh * dk * D * 4), ldb=D,
+                   C=N.ptr(tpart, (tau * S * D + hh * dk) * 4), ldc=D, M=S, N=dk, K=D) for tau in range(T) for hh in range(H)]
+    _gemm(N.WSI_GEMM_NT, 0, groups, dev)
+    t_mean = torch.empty((S, D), dtype=torch.float32, device=dev)
+    N.check(lib.wsi_pool_tmean(N.ptr(tpart), T, S, D, H, N.ptr(csum), _ptr_array([P[tau][6] for tau in range(T)]),
+                               N.ptr(prp.inv_counts()), N.ptr(t_mean), N.stream()), "wsi_pool_tmean")
+    return score, lse, ctab, hp, csum, h_mean, t_mean
+
+
+def _heat_output_means(t_mean, h_mean, hctx, P, skip, pool):
+    """Readout-fused output stage, one grouped NT GEMM with the gated-skip epilogue on the segment means: z_mean = s (t_mean Wa^T + ba) +
+    (1 - s) h_mean (mean_seg(h) for a type the layer passes through, models/HEATNet4.py:129-133); then the readout.  Returns (z_mean, pooled)."""
+    prp, pop = pool
+    D, segs = h_mean.shape[1], prp.segments_of(hctx.rows)
+    z_mean = torch.empty_like(h_mean) if all(hctx.incoming) else h_mean.clone()
+    groups = []
+    for i in hctx.a_types:
+        s0, s1 = segs[i]
+        groups.append(dict(A=N.ptr(t_mean, s0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, C=N.ptr(z_mean, s0 * D * 4), ldc=D,
+                           bias=N.ptr(P[i][7]), R=N.ptr(h_mean, s0 * D * 4), ldr=D, gate=_gate_ptr(skip, hctx, i),
+                           M=s1 - s0, N=D, K=D))
+    _gemm(N.WSI_GEMM_NT, N.WSI_EPI_GATED_SKIP, groups, h_mean.device)
+    # an empty segment reads 0 (not s * ba): the readout kernels' convention, dgl.readout semantics
+    pooled = z_mean * prp.counts() if pop == N.WSI_RED_SUM else (z_mean * prp.nonempty() if prp.has_empty() else z_mean)
+    return z_mean, pooled
+
+
+def _heat_output_rows(h, t, scales, hctx, P, skip, dropout):
+    """Full-depth output stage, one grouped NT GEMM with the gated-skip epilogue (and the dropout draw or mask in it): out = s * drop(t Wa^T + ba)
+    + (1 - s) * h (models/HEATNet4.py:128-135); then a row copy per node type that no relation enters (:129-133).  ``scales`` = (h's, t's row
+    scales); ``out`` leaves with its own row scales and column statistics attached for the next layer.  Returns out."""
+    n, D = h.shape
+    dev, (h_max, t_max) = h.device, scales
+    counter = dropout if isinstance(dropout, CounterDropout) else None
+    mask = dropout if counter is None else None
+    # every node type gets the projection: its epilogue writes all slots of all rows
+    out_max = _new_row_scale(n, N.gemm_absmax_parts(D), dev, D, zero=not all(hctx.incoming))
+    out = torch.empty((n, D), dtype=torch.float32, device=dev)
+    out_cols = ColStats.allocate([hctx.rows[i] for i in hctx.a_types], D, dev, sums=False) if want_col_stats(n, D, D) else None
+    groups = []
+    for i in hctx.a_types:
+        r0, r1 = hctx.rows[i]
+        groups.append(dict(A=N.ptr(t, r0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, Bw=[P[i][3]], C=N.ptr(out, r0 * D * 4), ldc=D,
+                           bias=N.ptr(P[i][7]), R=N.ptr(h, r0 * D * 4), ldr=D, gate=_gate_ptr(skip, hctx, i),
+                           Mm=N.ptr(mask, r0 * D * 4) if mask is not None else None, ldm=D,
+                           M=r1 - r0, N=D, K=D, **_scale_in(t_max, r0), **_scale_out(out_max, r0),
+                           **(counter.group_fields(r0, D) if counter is not None else {}),
+                           **(out_cols.produce(r0, r1, 0) if out_cols is not None else {})))
+    drop_epi = N.WSI_EPI_DROPOUT if counter is not None else (N.WSI_EPI_MUL_M if mask is not None else 0)
+    if not _gemm(N.WSI_GEMM_NT, N.WSI_EPI_GATED_SKIP | drop_epi, groups, dev):
+        out_cols = None
+    for i, (r0, r1) in enumerate(hctx.rows):
+        if not hctx.incoming[i]:
+            out[r0:r1] = h[r0:r1]
+            if out_max is not None:
+                if h_max is not None and h_max.shape[1] <= out_max.shape[1]:
+                    out_max[r0:r1, :h_max.shape[1]] = h_max[r0:r1]
+                else:
+                    out_max = None                      # (scales of those rows unknown: the consumer makes its own pass)
+    if out_max is not None:
+        attach_row_scales(out, out_max)
+    attach_col_stats(out, out_cols)                    # (after the pass-through copies: they move the version; those row ranges have no entry)
+    return out
+
+
+# ---- stages of _HeatLayerFused.backward ----
+def _heat_row_gradient(g_out, hctx, n: int):
+    """Full-depth intake.  The layer under a sum / mean readout receives a gradient of ONE distinct row per (graph, node type), and the readout's
+    backward says so on the very tensor it hands down (``SegmentBroadcast``).  Returns (g_out contiguous, bc, segs, annotated): the broadcast
+    and each node type's run of its segments - None, None without an annotation whose plan respects the node types; ``annotated``: there was one."""
+    g_out = g_out.contiguous()
+    bc = _annotation(g_out, "_wsi_broadcast") if _LOW_RANK["enabled"] else None
+    if bc is None:
+        return g_out, None, None, False
+    EXCHANGE_STATS["broadcast_hits"] += 1
+    segs = bc.rp.segments_of(hctx.rows) if bc.rp.num_rows == n else None
+    return g_out, (bc if segs is not None else None), segs, True
+
+
+def _heat_pooled_gradient(g_pool, sv: _HeatSaved, st: _HeatState):
+    """Readout-fused intake: the gradient arrives as S rows, one per segment of the readout.  Returns (bc, pre): the factors the low-rank
+    stages work with (row gradient and row-summed gradient per segment) and, up to 8192 segments, pre = (g_skip, omg [T] = 1 - sigmoid(skip)
+    per node type, 1 where the layer passes h through) from the same single launch (wsi_pool_bwd_prep: the two scalings, the segment dots
+    against mean(out) - mean(h), the gate map).  Above that the factors are tensor operations and pre is None."""
+    prp, pop = st.pool
+    g_pool = g_pool.contiguous()
+    if prp.num_segs > 8192:
+        return SegmentBroadcast.from_pooled_gradient(g_pool, prp, pop, sv.z_mean), None
+    T, skip = len(st.hctx.rows), sv.skip
+    seg_gate = _gate_table(st.hctx, skip, "seg_gate", prp.segments_of(st.hctx.rows), prp.num_segs)
+    type_gate = _gate_table(st.hctx, skip, "type_gate")
+    g_row, g_sum = torch.empty_like(g_pool), torch.empty_like(g_pool)
+    pre = (torch.empty_like(skip), torch.empty(T, dtype=torch.float32, device=skip.device))
+    N.check(N.load().wsi_pool_bwd_prep(N.ptr(g_pool), prp.num_segs, g_pool.shape[1], pop, N.ptr(prp.counts()), N.ptr(sv.z_mean), N.ptr(sv.h_mean),
+                                       N.ptr(seg_gate), N.ptr(skip), skip.shape[0], N.ptr(type_gate), T, N.ptr(g_row), N.ptr(g_sum),
+                                       N.ptr(pre[0]), N.ptr(pre[1]), N.stream()), "wsi_pool_bwd_prep")
+    return SegmentBroadcast.from_parts(prp, g_row, g_sum, sv.z_mean), pre
+
+
+def _heat_broadcast_rows(bc, n: int, D: int):
+    """Readout-fused with V kept: the [n, D] gradient of the never-formed output for the residual term of the K|Q|V dX epilogue, one launch."""
+    prp = bc.rp
+    g_out = torch.empty((n, D), dtype=torch.float32, device=bc.g_row.device)
+    N.check(N.load().wsi_segment_reduce_bwd(N.ptr(bc.g_row), D, D, N.WSI_RED_SUM, N.ptr(prp.chunk_row), N.ptr(prp.chunk_seg),
+                                            prp.num_chunks, N.ptr(prp.seg_chunk), prp.num_segs, None,
+                                            N.ptr(g_out), D, N.stream()), "wsi_segment_reduce_bwd")
+    return g_out
+
+
+def _heat_gate_launch(g_out, sv: _HeatSaved, hctx, stream_ptr, before_launch=None):
+    """The skip-gate gradient from the rows, two launches on ``stream_ptr`` (wsi_gate_grad): the per-type dots sum_rows g_out (out - h), then the
+    gate map and the sigmoid factor - a streaming pass over three [n, D] tensors.  Everything the launch reads that is produced on the CALLER's
+    stream - the gate table (an asynchronous upload on a cache miss: the first backward of every new graph context) and the buffers (the
+    caching allocator hands out blocks whose last use is ordered on that stream) - exists before ``before_launch`` (the side stream's wait
+    for the caller's stream) runs.  Returns (g_skip, the scratch it must outlive)."""
+    T, D, rp = len(hctx.rows), sv.h.shape[1], hctx.type_rplan()
+    seg_gate = _gate_table(hctx, sv.skip, "seg_gate", [(i, i + 1) for i in range(T)], T)
+    g_skip = torch.empty_like(sv.skip)
+    partial = torch.empty(max(rp.num_chunks * ((D + 255) // 256), 1), dtype=torch.float32, device=sv.h.device)
+    if before_launch is not None:
+        before_launch()
+    N.check(N.load().wsi_gate_grad(N.ptr(g_out), g_out.stride(0), N.ptr(sv.out), sv.out.stride(0), N.ptr(sv.h), sv.h.stride(0), D,
+                                   N.ptr(rp.chunk_row), rp.num_chunks, N.ptr(rp.seg_chunk), rp.num_segs, N.ptr(seg_gate), N.ptr(sv.skip),
+                                   sv.skip.shape[0], N.ptr(partial), N.ptr(g_skip), stream_ptr), "wsi_gate_grad")
+    return g_skip, partial
+
+
+def _heat_early_gate(g_out, sv: _HeatSaved, hctx):
+    """``_heat_gate_launch`` on the statistics stream, beside the matrix-bound output-projection gradient that follows: the pass is
+    bandwidth-bound and nobody reads g_skip before the backward returns.  Returns (g_skip, the event the backward joins on)."""
+    dev = sv.h.device
+    side = side_stream(dev, "stats")
+    g_skip, partial = _heat_gate_launch(g_out, sv, hctx, ctypes.c_void_p(side.cuda_stream), lambda: side.wait_stream(torch.cuda.current_stream(dev)))
+    ev = torch.cuda.Event()
+    ev.record(side)
+    for t_ in (g_out, sv.out, sv.h, g_skip, partial, sv.skip):
+        t_.record_stream(side)
+    return g_skip, ev
+
+
+def _heat_out_proj_low_rank(bc, segs, sv: _HeatSaved, hctx, P, grads):
+    """Output-projection gradients from the S distinct gradient rows, in one paired launch of small GEMMs (else an NN and a TN one):
+        g_t[row] = s * g_row[seg] Wa : S rows through the projection (the attention backward reads them through row -> segment);
+        gWa = s * sum_seg g_sum[seg] (x) mean_seg(t)  (= s * g_out^T t with the rows of a segment summed first);  gba = s * sum_seg g_sum[seg].
+    A full-depth layer takes mean_seg(t) first (wsi_segment_reduce_fwd).  Fills ``grads``; returns (gt_seg [S, D], row -> segment [n])."""
+    S, D, dev, T = bc.rp.num_segs, sv.h.shape[1], sv.h.device, len(hctx.rows)
+    gt_seg = (torch.empty if len(hctx.a_types) == T else torch.zeros)((S, D), dtype=torch.float32, device=dev)
+    t_mean = sv.t_mean if sv.t_mean is not None else _segment_reduce_raw(sv.t, bc.rp, N.WSI_RED_MEAN)[0]
+    groups, wgroups = [], []
+    for i in hctx.a_types:
+        s0, s1 = segs[i]
+        groups.append(dict(A=N.ptr(bc.g_row, s0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, C=N.ptr(gt_seg, s0 * D * 4), ldc=D,
+                           gate=_gate_ptr(sv.skip, hctx, i), M=s1 - s0, N=D, K=D))
+        gw, gb = torch.empty_like(P[i][3]), torch.empty_like(P[i][7])
+        grads[8 * i + 3], grads[8 * i + 7] = gw, gb
+        wgroups.append(dict(A=N.ptr(bc.g_sum, s0 * D * 4), lda=D, B=N.ptr(t_mean, s0 * D * 4), ldb=D, C=N.ptr(gw), ldc=D,
+                            gate=_gate_ptr(sv.skip, hctx, i), colsum_out=N.ptr(gb), M=D, N=D, K=s1 - s0))
+    if not _gemm_small_pair(groups, N.WSI_EPI_SCALE_GATE, wgroups, N.WSI_EPI_SCALE_GATE, dev):
+        _gemm(N.WSI_GEMM_NN, N.WSI_EPI_SCALE_GATE, groups, dev)
+        _gemm(N.WSI_GEMM_TN, N.WSI_EPI_SCALE_GATE, wgroups, dev)
+    return gt_seg, bc.rp.row_segment()
+
+
+def _heat_out_proj_rows(g_y, sv: _HeatSaved, st: _HeatState, P, grads):
+    """Output-projection gradients at full depth: g_t = s * g_y Wa (one grouped NN GEMM), then gWa = s * g_y^T t and gba = s * colsum(g_y)
+    (one grouped TN GEMM) - which has the whole attention backward of this layer in front of it: queued for the background.
+    Fills ``grads``; returns g_t [n, D]."""
+    hctx, (n, D), dev, t, skip = st.hctx, sv.h.shape, sv.h.device, sv.t, sv.skip
+    g_t = torch.empty((n, D), dtype=torch.float32, device=dev)
+    gy_max = row_scales_of(g_y)                # fp16x3 row scales: left by the layer above (its dX epilogue), if any
+    gy_cols, t_cols = col_stats_of(g_y), st.t_cols      # column statistics for the weight gradient, likewise
+    groups, wgroups = [], []
+    for i in hctx.a_types:
+        r0, r1 = hctx.rows[i]
+        groups.append(dict(A=N.ptr(g_y, r0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, Bw=[P[i][3]], C=N.ptr(g_t, r0 * D * 4), ldc=D,
+                           gate=_gate_ptr(skip, hctx, i), M=r1 - r0, N=D, K=D, **_scale_in(gy_max, r0)))
+        gw, gb = torch.empty_like(P[i][3]), torch.empty_like(P[i][7])
+        grads[8 * i + 3], grads[8 * i + 7] = gw, gb
+        wgroups.append(dict(A=N.ptr(g_y, r0 * D * 4), lda=D, B=N.ptr(t, r0 * D * 4), ldb=D, C=N.ptr(gw), ldc=D,
+                            gate=_gate_ptr(skip, hctx, i), colsum_out=N.ptr(gb), M=D, N=D, K=r1 - r0,
+                            **(gy_cols.consume("a", r0, r1, 0, want_sums=True) if gy_cols is not None else {}),
+                            **(t_cols.consume("b", r0, r1, 0) if t_cols is not None else {})))
+    _gemm(N.WSI_GEMM_NN, N.WSI_EPI_SCALE_GATE, groups, dev)
+    wr = [P[i][k] for i in hctx.a_types for k in (3, 7)]
+    keep = [g_y, t, skip] + [c_.bits for c_ in (gy_cols, t_cols) if c_ is not None] + [c_.sums for c_ in (gy_cols,) if c_ is not None and c_.sums is not None]
+    outs = [(P[i][k], grads[8 * i + k]) for i in hctx.a_types for k in (3, 7)]
+    if not (_background_safe(wr) and _gemm_tn_background(N.WSI_EPI_SCALE_GATE, wgroups, dev, keep, wr, outs=outs)):
+        _gemm(N.WSI_GEMM_TN, N.WSI_EPI_SCALE_GATE, wgroups, dev)
+    return g_t
+
+
+def _heat_skip_gate_grad(g_out, sv: _HeatSaved, hctx, bc, segs, pre, early):
+    """d loss / d skip[g] = (1 - sigmoid(skip[g])) * sum over the graph node types i mapped to g of dots[i],
+    dots[i] = sum over the rows of type i of g_out * (out - h).  Four sources, the first that applies:
+      1. ``pre``: a readout-fused layer of up to 8192 segments got it from wsi_pool_bwd_prep with the scalings of the gradient - no launch here;
+      2. ``bc`` for the layer's own output (a readout-fused layer never formed it; at full depth the annotation must be of this very ``out``):
+         sum_rows g_out * (out - h) = sum_seg g_sum[seg] . (mean_seg(out) - mean_seg(h)), and the readout already holds mean_seg(out) -
+         S-row tensor operations (after wsi_segment_reduce_fwd for mean_seg(h) at full depth) instead of a pass over three [n, D] tensors;
+      3. ``early``: at full depth and large n the row pass was launched on the statistics stream before the output-projection gradients;
+      4. otherwise that row pass now, on the caller's stream (``_heat_gate_launch``)."""
+    if pre is not None:
+        return pre[0]
+    if bc is not None and (sv.out is None or (bc.x_ptr == sv.out.data_ptr() and bc.x_version == sv.out._version)):
+        h_mean = sv.h_mean if sv.h_mean is not None else _segment_reduce_raw(sv.h, bc.rp, N.WSI_RED_MEAN)[0]
+        qs = _gate_table(hctx, sv.skip, "gate_of_seg", segs, bc.rp.num_segs)
+        return (qs @ (bc.g_sum * (bc.x_mean - h_mean)).sum(dim=1)) * (1.0 - torch.sigmoid(sv.skip))
+    if early is not None:
+        return early[0]
+    return _heat_gate_launch(g_out, sv, hctx, N.stream())[0]
+
+
+def _heat_collapse_tables(gt_seg, bc, sv: _HeatSaved, st: _HeatState, P, omg):
+    """The tables with which the attention backward never forms g_v (rank <= S x H; ``wsi_attn_pool_t``).  One grouped NN GEMM:
+        y[tau, seg, hh, :] = g_t[seg]_hh (W_v^tau rows of head hh): what one unit of c[u, bin, hh] adds to g_h[u].
+    When the forward never computed V (``_heat_collapse_lookups``): beta, the value-bias gradients and, where it fits, gtab.
+    ``omg`` [T] = 1 - sigmoid(skip) of the type from wsi_pool_bwd_prep, or None: taken here by tensor operations.
+    Returns (the N.AttnPool descriptor;  r_out [n, D], where pass 3 leaves the residual term of the K|Q dX epilogue, g_v W_v included;  ctab [n, T, H],
+    the forward's coefficients or where pass 3 leaves them;  gbv [T, D] when the forward's coefficient sums gave it already;  what the descriptor points at)."""
+    hctx, H, h, skip = st.hctx, st.H, sv.h, sv.skip
+    (n, D), dev, T, S, plan = h.shape, h.device, len(hctx.rows), bc.rp.num_segs, hctx.plan
+    dk = D // H
+    ytab = torch.empty((T, S, H, D), dtype=torch.float32, device=dev)
+    groups = [dict(A=N.ptr(gt_seg, hh * dk * 4), lda=D, B=N.ptr(P[tau][2], hh * dk * D * 4), ldb=D,
+                   C=N.ptr(ytab, ((tau * S) * H + hh) * D * 4), ldc=H * D, M=S, N=D, K=dk) for tau in range(T) for hh in range(H)]
+    _gemm(N.WSI_GEMM_NN, 0, groups, dev)
+    if omg is None:           # [T]: 1 - s of the type; 1 where the layer passes h through
+        omg = 1.0 - _gate_table(hctx, skip, "gate_of_row_type") @ torch.sigmoid(skip)
+    r_out = torch.empty((n, D), dtype=torch.float32, device=dev)
+    if st.no_v:
+        ctab, (beta, gbv, gtab) = sv.ctab, _heat_collapse_lookups(gt_seg, ytab, bc.rp, sv, P, H)
+    else:
+        ctab, beta, gbv, gtab = torch.empty((n, T, H), dtype=torch.float32, device=dev), None, None, None
+    desc = N.AttnPool(row_seg=N.ptr(bc.rp.row_segment()), segs_per_type=S // T, n_types=T, y=N.ptr(ytab), g_row=N.ptr(bc.g_row),
+                      omg=N.ptr(omg), r_out=N.ptr(r_out), ldr=D, ctab=N.ptr(ctab), ctab_ready=1 if st.no_v else 0,
+                      h=N.ptr(h) if st.no_v else None, ldh=D, beta=N.ptr(beta), gtab=N.ptr(gtab),
+                      edge_seg=N.ptr(_edge_segments(plan)) if gtab is not None else None,
+                      seg_dst=N.ptr(_segment_dst(plan)) if gtab is not None else None)
+    return desc, r_out, ctab, gbv, (ytab, omg, beta, gtab)
+
+
+def _heat_collapse_lookups(gt_seg, ytab, prp, sv: _HeatSaved, P, H: int):
+    """Collapse after a forward without V.  One launch (wsi_pool_bwd_bias): beta[tau, s, hh] = g_t[seg]_hh . b_v^tau (head hh), and the
+    value-bias gradients gbv [T, D] from the forward's coefficient sums.  Then, within wsi_heat_pool_gtab's limits (J = T * H <= 32 columns,
+    table in 64 KB of LDS), gtab [n, T, H]: pass 1's dot products taken once per SOURCE node (T * H per node, one pass over h) instead of H per
+    edge against gathered rows.  Returns (beta, gbv, gtab or None)."""
+    h, T, S = sv.h, len(P), prp.num_segs
+    (n, D), dev, lib = h.shape, h.device, N.load()
+    gbv = torch.empty((T, D), dtype=torch.float32, device=dev)
+    beta = torch.empty((T, S, H), dtype=torch.float32, device=dev)
+    N.check(lib.wsi_pool_bwd_bias(N.ptr(gt_seg), T, S, D, H, _ptr_array([P[tau][6] for tau in range(T)]), N.ptr(sv.csum), N.ptr(beta), N.ptr(gbv),
+                                  N.stream()), "wsi_pool_bwd_bias")
+    if not (T * H <= 32 and T * H * (D + 4) * 4 <= 64 * 1024):
+        return beta, gbv, None
+    gtab = torch.empty((n, T, H), dtype=torch.float32, device=dev)
+    with _Timed("heat_attn"), _Timed("heat_attn_bwd_pooled"):
+        N.check(lib.wsi_heat_pool_gtab(N.ptr(h), D, D, H, N.ptr(ytab), N.ptr(beta), N.ptr(prp.chunk_row), N.ptr(prp.chunk_seg),
+                                       prp.num_chunks, S // T, T, N.ptr(gtab), N.stream()), "wsi_heat_pool_gtab")
+    return beta, gbv, gtab
+
+
+def _heat_attention_backward(g_t, gt_row, sv: _HeatSaved, st: _HeatState, pool_desc):
+    """Relation attention backward, one C call (wsi_heat_attn_bwd; pass 1 reads the saved logits and writes the probabilities): the queued weight
+    gradients (this layer's a_linear, the layer above's K|Q|V) are flushed to run under it, and the column statistics of its result go to the
+    side stream right after it, beside the dX projection (``_col_stats_side``).  ``g_t`` [n, D], or [S, D] read through ``gt_row``.
+    Returns (gkqv like kqv - the V block is not written under a collapse -, its row scales, g_e [2], the side statistics or None)."""
+    hctx, H, kqv = st.hctx, st.H, sv.kqv
+    plan, (n, D), dev, ldp = hctx.plan, sv.h.shape, sv.h.device, kqv.shape[1]
+    a = torch.empty_like(sv.score)
+    scratch = torch.empty((3, max(plan.num_edges, 1), H), dtype=torch.float32, device=dev)
+    red_ws = torch.empty(1024, dtype=torch.float32, device=dev)
+    gkqv = torch.empty_like(kqv)
+    g_e = torch.empty(2, dtype=torch.float32, device=dev)
+    # pass 2: slot 0 of all n, pass 3: slot 1 of the source rows
+    gkqv_max = _new_row_scale(max(n, plan.num_src_rows), 2, dev, 3 * D, zero=plan.num_src_rows != n)
+    v, gv = (None, None) if st.no_v else (N.ptr(kqv, 2 * D * 4), N.ptr(gkqv, 2 * D * 4))
+    _background_flush(dev)
+    with _Timed("heat_attn"), _Timed("heat_attn_bwd_pooled" if pool_desc is not None else "heat_attn_bwd_full"):
+        N.check(N.load().wsi_heat_attn_bwd(
+            N.ptr(kqv, D * 4), ldp, N.ptr(kqv), ldp, v, ldp, n, plan.num_src_rows, plan.num_edges, D, H,
+            N.ptr(plan.node_seg), N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(sv.sim_csr),
+            N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
+            N.ptr(plan.inv_rd), N.ptr(plan.order_dst), plan.num_heavy, N.ptr(plan.order_src), _attn_flags(plan), N.ptr(sv.ew), N.ptr(sv.eb),
+            N.ptr(g_t), D, N.ptr(gt_row), N.ptr(sv.score), N.ptr(a), N.ptr(sv.lse), N.ptr(scratch[0]), N.ptr(scratch[1]), N.ptr(scratch[2]), N.ptr(red_ws),
+            N.ptr(gkqv, D * 4), ldp, N.ptr(gkqv), ldp, gv, ldp,
+            N.ptr(g_e), N.ptr(gkqv_max), ctypes.byref(pool_desc) if pool_desc is not None else None, N.context(), N.stream()), "wsi_heat_attn_bwd")
+    gk_side = _col_stats_side(gkqv, hctx.rows, dev) if (want_col_stats(n, D, D) and (D % 32 == 0)) else None
+    return gkqv, gkqv_max, g_e, gk_side
+
+
+def _heat_dx_chunked(gkqv, gkqv_max, resid, nproj: int, hctx, P, skip):
+    """K|Q(|V) dX for D % 32 == 0: g_h = gkqv [Wk; Wq(; Wv)] + residual, the weights as chunks of one reduction (K = nproj * D) - one grouped NN
+    GEMM per epilogue.  ``skip`` None (collapsed: ``resid`` = r_out already carries the 1 - s factor and g_v W_v): one launch over all node
+    types.  Else ``resid`` = g_out: the gated types with (1 - s) * g_out in the epilogue, then the passed-through types with g_out as it is.
+    g_h is the dY of the weight gradient below it (the lower layer's output projection, or the input projection): the epilogue leaves its row
+    scales and column statistics - absmax and sums (the bias gradient) - that launch would otherwise take a pass over g_h for.  Returns g_h."""
+    T, n, D, dev, ldp = len(hctx.rows), gkqv.shape[0], resid.shape[1], gkqv.device, gkqv.shape[1]
+    g_h = torch.empty((n, D), dtype=torch.float32, device=dev)
+    gh_max = _new_row_scale(n, N.gemm_absmax_parts(D), dev, D, zero=False)   # the launches cover every row
+    gh_cols = ColStats.allocate(hctx.rows, D, dev, sums=True) if want_col_stats(n, D, D) else None
+    wrote = True
+    for idxs in ([list(range(T))] if skip is None else [[i for i in range(T) if hctx.incoming[i] == w_] for w_ in (True, False)]):
+        if not idxs:
+            continue
+        gated = skip is not None and hctx.incoming[idxs[0]]
+        groups = []
+        for i in idxs:
+            r0, r1 = hctx.rows[i]
+            ws = list(P[i][:nproj])
+            groups.append(dict(A=N.ptr(gkqv, r0 * ldp * 4), lda=ldp, b_chunk=D, ldb=D, Bw=ws, **dict(zip(("B", "B1", "B2"), map(N.ptr, ws))),
+                               C=N.ptr(g_h, r0 * D * 4), ldc=D, R=N.ptr(resid, r0 * D * 4), ldr=D,
+                               gate=_gate_ptr(skip, hctx, i) if gated else None, M=r1 - r0, N=D, K=nproj * D,
+                               **_scale_in(gkqv_max, r0), **_scale_out(gh_max, r0),
+                               **(gh_cols.produce(r0, r1, 0) if gh_cols is not None else {})))
+        wrote = _gemm(N.WSI_GEMM_NN, N.WSI_EPI_ADD_R | (N.WSI_EPI_R_1MG if gated else 0), groups, dev) and wrote
+    if gh_max is not None:
+        attach_row_scales(g_h, gh_max)
+    if gh_cols is not None and wrote:
+        attach_col_stats(g_h, gh_cols)
+    return g_h
+
+
+def _heat_dx_by_block(gkqv, g_out, hctx, P, skip):
+    """K|Q|V dX for a width that is no multiple of 32 (the chunked launch needs it): per epilogue - gated types, then passed-through ones -
+    three grouped NN GEMMs, the K block with the residual epilogue and the Q and V blocks accumulating.  Returns g_h (no statistics attached)."""
+    T, (n, D), dev = len(hctx.rows), g_out.shape, gkqv.device
+    g_h = torch.empty((n, D), dtype=torch.float32, device=dev)
+    for with_gate in (True, False):
+        idxs = [i for i in range(T) if hctx.incoming[i] == with_gate]
+        if not idxs:
+            continue
+        epi = N.WSI_EPI_ADD_R | (N.WSI_EPI_R_1MG if with_gate else 0)
+        for j in range(3):
+            groups = []
+            for i in idxs:
+                r0, r1 = hctx.rows[i]
+                groups.append(dict(A=N.ptr(gkqv, (r0 * 3 * D + j * D) * 4), lda=3 * D, B=N.ptr(P[i][j]), ldb=D,
+                                   C=N.ptr(g_h, r0 * D * 4), ldc=D, R=N.ptr(g_out, r0 * D * 4), ldr=D,
+                                   gate=_gate_ptr(skip, hctx, i) if with_gate else None, M=r1 - r0, N=D, K=D))
+            _gemm(N.WSI_GEMM_NN, epi if j == 0 else N.WSI_EPI_ACCUMULATE, groups, dev)
+    return g_h
+
+
+def _heat_kqv_weight_grads(gkqv, gk_side, nproj: int, sv: _HeatSaved, st: _HeatState, P, grads) -> None:
+    """K|Q(|V) weight and bias gradients, one grouped TN GEMM: gW = gkqv^T h, gb = colsum(gkqv), per node type and column block.  In a layer
+    with another HEAT layer below it (``st.background_dw``) it is queued to run under THAT layer's attention backward; else it runs here,
+    after the side stream's column statistics (``gk_side``) are there.  Fills ``grads``."""
+    hctx, h, h_cols, dev = st.hctx, sv.h, st.h_cols, sv.h.device
+    T, D, ldp = len(hctx.rows), h.shape[1], gkqv.shape[1]
+    wgroups = []
+    for i, (r0, r1) in enumerate(hctx.rows):
+        for j in range(nproj):
+            gw, gb = torch.empty_like(P[i][j]), torch.empty_like(P[i][4 + j])
+            grads[8 * i + j], grads[8 * i + 4 + j] = gw, gb
+            wgroups.append(dict(A=N.ptr(gkqv, (r0 * ldp + j * D) * 4), lda=ldp, B=N.ptr(h, r0 * D * 4), ldb=D,
+                                C=N.ptr(gw), ldc=D, colsum_out=N.ptr(gb), M=D, N=D, K=r1 - r0,
+                                **(gk_side[0].consume("a", r0, r1, j * D, want_sums=True) if gk_side is not None else {}),
+                                **(h_cols.consume("b", r0, r1, 0) if h_cols is not None else {})))
+    wr = [P[i][k] for i in range(T) for j in range(nproj) for k in (j, 4 + j)]
+    keep = [gkqv, h] + ([h_cols.bits] if h_cols is not None else []) + ([gk_side[0].bits, gk_side[0].sums] if gk_side is not None else [])
+    outs = [(P[i][k], grads[8 * i + k]) for i in range(T) for j in range(nproj) for k in (j, 4 + j)]
+    evs = [gk_side[1]] if gk_side is not None else []
+    if not (st.background_dw and _background_safe(wr) and _gemm_tn_background(0, wgroups, dev, keep, wr, evs, outs=outs)):
+        for ev in evs:
+            torch.cuda.current_stream(dev).wait_event(ev)
+        _gemm(N.WSI_GEMM_TN, 0, wgroups, dev)
+
+
+def _heat_factors_from_pass3(gt_seg, ctab, prp, h, T: int, H: int):
+    """Collapse after a forward that kept V: the weighted sums of h from the coefficients pass 3 left (``_pooled_factors``: two launches),
+    and the value-bias gradients from their sums (wsi_pool_bwd_bias).  Returns (hp, gbv [T, D])."""
+    hp, csum = _pooled_factors(h, ctab, prp, T, H)
+    gbv = torch.empty((T, h.shape[1]), dtype=torch.float32, device=h.device)
+    N.check(N.load().wsi_pool_bwd_bias(N.ptr(gt_seg), T, prp.num_segs, h.shape[1], H, None, N.ptr(csum), None, N.ptr(gbv), N.stream()),
+            "wsi_pool_bwd_bias")
+    return hp, gbv
+
+
+def _heat_value_weight_grads(gt_seg, hp, gbv, P, H: int, grads) -> None:
+    """Value-weight gradients under the collapse, one grouped TN GEMM over the S segment rows:
+        dW_v^tau (rows of head hh) = sum_seg g_t[seg]_hh (x) hp[seg, hh, tau, :]    (hp: weighted sums of h over the (source type, graph) segments);
+    db_v^tau = gbv[tau].  Fills ``grads``."""
+    T, (S, D) = len(P), gt_seg.shape
+    dk = D // H
+    wgroups = []
+    for tau in range(T):
+        gw = torch.empty_like(P[tau][2])
+        grads[8 * tau + 2], grads[8 * tau + 6] = gw, gbv[tau]
+        for hh in range(H):
+            wgroups.append(dict(A=N.ptr(gt_seg, hh * dk * 4), lda=D, B=N.ptr(hp, (hh * T + tau) * D * 4), ldb=H * T * D,
+                                C=N.ptr(gw, hh * dk * D * 4), ldc=D, M=dk, N=D, K=S))
+    _gemm(N.WSI_GEMM_TN, 0, wgroups, gt_seg.device)
 
 
 class _HeatLayerFused(torch.autograd.Function):
     """inputs: h [N,D], hctx (HeatContext), H, skip [T_model], e_weight [1,1], e_bias [1], drop_mask ([N,D] keep mask
-    scaled by 1/(1-p) for the nn.Dropout of HEATNet4.py:135, or None), then per graph node type i (in hctx order) 8 tensors:
+    scaled by 1/(1-p) for the nn.Dropout of HEATNet4.py:135, a CounterDropout, or None), then per graph node type i (in hctx order) 8 tensors:
     Wk, Wq, Wv, Wa, bk, bq, bv, ba.
 
     ``pool`` = (ReducePlan, WSI_RED_SUM | WSI_RED_MEAN) or None.  With a pool the function returns the READOUT of the layer's output,
@@ -1723,467 +2187,95 @@ class _HeatLayerFused(torch.autograd.Function):
         mean_seg( s (t Wa^T + ba) + (1 - s) h ) = s (mean_seg(t) Wa^T + ba) + (1 - s) mean_seg(h)
     (models/HEATNet4.py:128-135 followed by pools[0] at :219, with no dropout between them) - the [N, D] x [D, D] projection becomes
     two segment means and an [S, D] x [D, D] one, and the backward starts from the S gradient rows it would otherwise meet broadcast
-    to N (``SegmentBroadcast``).  Every segment of the plan must lie inside one node type's row range."""
+    to N (``SegmentBroadcast``).  Every segment of the plan must lie inside one node type's row range.
+
+    Four formulations share the stages (``_heat_*`` above, one per launch group; DESIGN 3.7 has the table): full depth (pool None);
+    full depth under a broadcast gradient (``_heat_row_gradient`` finds the readout's annotation: the output projection works on S rows);
+    readout-fused (t formed, then the segment means of t and h); readout-fused without V.  The two predicates of the last:
+      no_v     (forward)  = pool is not None and _value_collapse_applies(...): V is never projected, kqv is K | Q;
+      collapse (backward) = no_v or the same question asked again: g_v is never formed - the attention backward takes the pool descriptor,
+                            dX and dW the K and Q blocks only.  They differ only if ``set_value_collapse`` moved between the two passes."""
 
     @staticmethod
     def forward(ctx, h, hctx, H, skip, e_weight, e_bias, drop_mask, pool, background_dw, *params):
         N.require_cuda(h)
         _background_recover()                  # (leftovers of a backward pass that raised: nothing in the normal case)
-        ctx.background_dw = bool(background_dw)
-        lib = N.load()
         h = h.contiguous()
-        dev = h.device
-        T = len(hctx.rows)
         n, D = h.shape
-        plan = hctx.plan
-        P = [params[8 * i:8 * i + 8] for i in range(T)]
+        P = [params[8 * i:8 * i + 8] for i in range(len(hctx.rows))]
+        if isinstance(drop_mask, CounterDropout) and drop_mask.threshold == 0:
+            drop_mask = None                    # p quantises to 0: nothing is dropped
+        if pool is not None and (drop_mask is not None or pool[0].segments_of(hctx.rows) is None or pool[0].num_rows != n
+                                 or pool[1] not in (N.WSI_RED_SUM, N.WSI_RED_MEAN)):        # refused before anything is launched
+            raise ValueError("heat_layer_fused(pool=...): needs a sum / mean plan over all rows whose segments respect the node types, and no dropout mask")
+        no_v = pool is not None and _value_collapse_applies(hctx, pool[0], n, D, H)
         # fp16x3 row scales (absmax bits) travel with the activations: h's from its producer, t's from the attention kernel,
         # out's from the epilogue that writes it - no projection makes its own pass over an operand the path just produced
         h_max = row_scales_of(h)
-        everywhere = all(hctx.incoming)              # every node type gets the out projection: its epilogue writes all slots of all rows
-        t_max = _new_row_scale(n, 1, dev, D, zero=False)                          # the attention kernel writes every row
-        out_max = None if pool is not None else _new_row_scale(n, N.gemm_absmax_parts(D), dev, D, zero=not everywhere)
-        # a readout-fused last layer never needs V (its aggregate is read through S x H weighted sums of h): K and Q only
-        counter = drop_mask if isinstance(drop_mask, CounterDropout) else None       # the draw as a function (no tensor) ...
-        if counter is not None and counter.threshold == 0:
-            counter = drop_mask = None                                                  # p quantises to 0: nothing is dropped
-        no_v = pool is not None and drop_mask is None and _value_collapse_applies(hctx, pool[0], n, D, H)
-        nproj = 2 if no_v else 3
-        ldp = nproj * D
-        # column statistics for the weight gradients (scaled-fp16 TN: ColStats).  h's come with it; a row of t is a convex combination of V rows
-        # (softmax weights within a relation slot, then a mean over the slots: |t[w, c]| <= max_u |v[u, c]| over the source nodes u), so V's column
-        # maxima bound t's - a few binades loose at most, which the 17-binade full-precision window of the split absorbs: the V groups of the
-        # projection leave them; the output projection leaves those of `out` for the next layer
-        full = pool is None
-        cs_on = full and want_col_stats(n, D, D)
-        ctx.h_cols = col_stats_of(h)
-        v_cols = ColStats.allocate(hctx.rows, D, dev, sums=False) if cs_on else None
-        # 1) K|Q(|V) table
-        kqv = torch.empty((n, ldp), dtype=torch.float32, device=dev)
-        blk = _kqv_blocks(nproj) if pool is None else (0, 1, 2)      # column block of K, Q, V (under a readout the backward may walk K | Q as columns [0, 2D))
-        ctx.blk = blk
-        kO, qO, vO = blk[0] * D * 4, blk[1] * D * 4, blk[2] * D * 4
-        groups = []
-        for i, (r0, r1) in enumerate(hctx.rows):
-            for j in range(nproj):
-                groups.append(dict(A=N.ptr(h, r0 * D * 4), lda=D, B=N.ptr(P[i][j]), ldb=D, Bw=[P[i][j]],
-                                   C=N.ptr(kqv, (r0 * ldp + blk[j] * D) * 4), ldc=ldp, bias=N.ptr(P[i][4 + j]),
-                                   M=r1 - r0, N=D, K=D, **_scale_in(h_max, r0),
-                                   **(v_cols.produce(r0, r1, 0) if (v_cols is not None and j == 2) else {})))
-        if not _gemm(N.WSI_GEMM_NT, N.WSI_EPI_BIAS, groups, dev):
-            v_cols = None
-        # a row of t mixes V rows of EVERY source type that reaches its node: the bound of each of t's row ranges is the maximum over ALL parts
-        ctx.t_cols = ColStats(v_cols.bits, None, {r: (0, v_cols.bits.shape[0]) for r in hctx.rows if r[1] > r[0]}) if v_cols is not None else None
-        # 2) relation attention
-        score = torch.empty((max(plan.num_edges, 1), H), dtype=torch.float32, device=dev)
-        lse = torch.empty((max(plan.num_segs, 1), H), dtype=torch.float32, device=dev)
-        ew, eb = e_weight.reshape(-1), e_bias.reshape(-1)
-        sim_csr = hctx.sim_csr                  # fetched once per forward; backward uses the same tensor
-        ctx.no_v = no_v
+        h_cols = col_stats_of(h)
+        edge = (e_weight.reshape(-1), e_bias.reshape(-1), hctx.sim_csr)          # (sim fetched once per forward; the backward uses the same tensor)
+        kqv, t_cols = _heat_project(h, h_max, hctx, P, 2 if no_v else 3, v_stats=pool is None and want_col_stats(n, D, D))
+        st = _HeatState(hctx, H, pool, no_v, "mask" if isinstance(drop_mask, torch.Tensor) else drop_mask, h_cols, t_cols, bool(background_dw))
+        ctx.st = st
         if no_v:
-            prp = pool[0]
-            S, dk = prp.num_segs, D // H
-            with _Timed("heat_attn"), _Timed("heat_attn_fwd_pooled"):
-                N.check(lib.wsi_heat_attn_scores_fwd(
-                    N.ptr(kqv, qO), ldp, N.ptr(kqv, kO), ldp, n, D, H,
-                    N.ptr(plan.node_seg), N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(sim_csr), N.ptr(plan.order_dst), plan.num_heavy, _attn_flags(plan),
-                    N.ptr(ew), N.ptr(eb), N.ptr(score), N.ptr(lse), N.context(), N.stream()), "wsi_heat_attn_scores_fwd")
-                ctab = torch.empty((n, T, H), dtype=torch.float32, device=dev)
-                N.check(lib.wsi_heat_pool_coeff(N.ptr(score), N.ptr(lse), N.ptr(_edge_segments(plan)), N.ptr(plan.colptr), N.ptr(plan.csc_eid),
-                                                N.ptr(plan.csc_dst), N.ptr(plan.inv_rd), N.ptr(prp.row_segment()), S // T, T, H, n,
-                                                N.ptr(ctab), N.stream()), "wsi_heat_pool_coeff")
-            # sum_seg(t)[:, head h] = sum_tau ( hp[:, h, tau, :] (W_v^tau rows of head h)^T + csum[tau, :, h] b_v^tau (head h) )
-            hp, csum, h_mean_pre = _pooled_factors(h, ctab, prp, T, H, with_mean=True)
-            # one launch per stage: the per-(head, source type) products with W_v into tpart[tau], then their sum over tau + the value-bias
-            # term + the 1 / count scaling in wsi_pool_tmean
-            tpart = torch.empty((T, S, D), dtype=torch.float32, device=dev)
-            groups = [dict(A=N.ptr(hp, (hh * T + tau) * D * 4), lda=H * T * D, B=N.ptr(P[tau][2], hh * dk * D * 4), ldb=D,
-                           C=N.ptr(tpart, (tau * S * D + hh * dk) * 4), ldc=D, M=S, N=dk, K=D) for tau in range(T) for hh in range(H)]
-            _gemm(N.WSI_GEMM_NT, 0, groups, dev)
-            t = None
-            t_mean_pre = torch.empty((S, D), dtype=torch.float32, device=dev)
-            N.check(lib.wsi_pool_tmean(N.ptr(tpart), T, S, D, H, N.ptr(csum), _ptr_array([P[tau][6] for tau in range(T)]),
-                                       N.ptr(prp.inv_counts()), N.ptr(t_mean_pre), N.stream()), "wsi_pool_tmean")
-        else:
-            t = torch.empty((n, D), dtype=torch.float32, device=dev)
-            with _Timed("heat_attn"), _Timed("heat_attn_fwd_full"):
-                N.check(lib.wsi_heat_attn_fwd(
-                    N.ptr(kqv, qO), 3 * D, N.ptr(kqv, kO), 3 * D, N.ptr(kqv, vO), 3 * D, n, D, H,
-                    N.ptr(plan.node_seg), N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(sim_csr), N.ptr(plan.order_dst), plan.num_heavy, _attn_flags(plan),
-                    N.ptr(ew), N.ptr(eb), N.ptr(t), D, N.ptr(score), N.ptr(lse), N.ptr(t_max), N.context(), N.stream()), "wsi_heat_attn_fwd")
-        ctx.hctx, ctx.H, ctx.T = hctx, H, T
-        ctx.has_mask = drop_mask is not None
-        ctx.pool = pool
-        if pool is not None:
-            # 3') the readout of the output, straight from the segment means of t and h
-            prp, pop = pool
-            segs = prp.segments_of(hctx.rows)
-            if drop_mask is not None or segs is None or prp.num_rows != n or pop not in (N.WSI_RED_SUM, N.WSI_RED_MEAN):
-                raise ValueError("heat_layer_fused(pool=...): needs a sum / mean plan over all rows whose segments respect the node types, and no dropout mask")
-            t_mean = t_mean_pre if no_v else _segment_reduce_raw(t, prp, N.WSI_RED_MEAN)[0]
-            h_mean = h_mean_pre if no_v else _segment_reduce_raw(h, prp, N.WSI_RED_MEAN)[0]     # (no_v: taken by the weighted-sums pass over h)
-            z_mean = torch.empty_like(h_mean) if everywhere else h_mean.clone()       # passthrough types (:129-133): mean_seg(h)
-            groups = []
-            for i in hctx.a_types:
-                s0, s1 = segs[i]
-                groups.append(dict(A=N.ptr(t_mean, s0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, C=N.ptr(z_mean, s0 * D * 4), ldc=D,
-                                   bias=N.ptr(P[i][7]), R=N.ptr(h_mean, s0 * D * 4), ldr=D, gate=N.ptr(skip, 4 * hctx.nid[i]),
-                                   M=s1 - s0, N=D, K=D))
-            _gemm(N.WSI_GEMM_NT, N.WSI_EPI_GATED_SKIP, groups, dev)
-            # an empty segment reads 0 (not s * ba): the readout kernels' convention, dgl.readout semantics
-            pooled = z_mean * prp.counts() if pop == N.WSI_RED_SUM else (z_mean * prp.nonempty() if prp.has_empty() else z_mean)
-            extra = (ctab, hp, csum) if no_v else ()
-            ctx.save_for_backward(h, kqv, t_mean, h_mean, z_mean, score, lse, skip, ew, eb, sim_csr, *extra, *params)
+            score, lse, ctab, hp, csum, h_mean, t_mean = _heat_attend_pooled(h, kqv, hctx, H, edge, pool[0], P)
+            z_mean, pooled = _heat_output_means(t_mean, h_mean, hctx, P, skip, pool)
+            _heat_save(ctx, _HeatSaved(h, kqv, score, lse, skip, *edge, t_mean=t_mean, h_mean=h_mean, z_mean=z_mean, ctab=ctab, hp=hp, csum=csum, params=params))
             return pooled
-        # 3) out = sigma(skip) * (t Wa^T + ba) + (1 - sigma(skip)) * h      (HEATNet4.py:128-135)
-        out = torch.empty((n, D), dtype=torch.float32, device=dev)
-        out_cols = ColStats.allocate([hctx.rows[i] for i in hctx.a_types], D, dev, sums=False) if cs_on else None
-        groups = []
-        for i in hctx.a_types:
-            r0, r1 = hctx.rows[i]
-            groups.append(dict(A=N.ptr(t, r0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, Bw=[P[i][3]], C=N.ptr(out, r0 * D * 4), ldc=D,
-                               bias=N.ptr(P[i][7]), R=N.ptr(h, r0 * D * 4), ldr=D, gate=N.ptr(skip, 4 * hctx.nid[i]),
-                               Mm=N.ptr(drop_mask, r0 * D * 4) if (drop_mask is not None and counter is None) else None, ldm=D,
-                               M=r1 - r0, N=D, K=D, **_scale_in(t_max, r0), **_scale_out(out_max, r0),
-                               **(counter.group_fields(r0, D) if counter is not None else {}),
-                               **(out_cols.produce(r0, r1, 0) if out_cols is not None else {})))
-        if not _gemm(N.WSI_GEMM_NT, N.WSI_EPI_GATED_SKIP | (N.WSI_EPI_DROPOUT if counter is not None else (N.WSI_EPI_MUL_M if drop_mask is not None else 0)), groups, dev):
-            out_cols = None
-        for i, (r0, r1) in enumerate(hctx.rows):
-            if not hctx.incoming[i]:
-                out[r0:r1] = h[r0:r1]                       # no incoming relation: passthrough (:129-133)
-                if out_max is not None:
-                    if h_max is not None and h_max.shape[1] <= out_max.shape[1]:
-                        out_max[r0:r1, :h_max.shape[1]] = h_max[r0:r1]
-                    else:
-                        out_max = None                      # (scales of those rows unknown: the consumer makes its own pass)
-        if out_max is not None:
-            attach_row_scales(out, out_max)
-        attach_col_stats(out, out_cols)                    # (after the pass-through copies: they move the version; those row ranges have no entry)
-        ctx.counter = counter
-        ctx.save_for_backward(h, kqv, t, out, score, lse, skip, ew, eb, sim_csr, *(() if (drop_mask is None or counter is not None) else (drop_mask,)), *params)
+        t_max = _new_row_scale(n, 1, h.device, D, zero=False)                          # the attention kernel writes every row
+        t, score, lse = _heat_attend(kqv, t_max, hctx, H, edge)
+        if pool is not None:
+            t_mean = _segment_reduce_raw(t, pool[0], N.WSI_RED_MEAN)[0]
+            h_mean = _segment_reduce_raw(h, pool[0], N.WSI_RED_MEAN)[0]
+            z_mean, pooled = _heat_output_means(t_mean, h_mean, hctx, P, skip, pool)
+            _heat_save(ctx, _HeatSaved(h, kqv, score, lse, skip, *edge, t_mean=t_mean, h_mean=h_mean, z_mean=z_mean, params=params))
+            return pooled
+        out = _heat_output_rows(h, t, (h_max, t_max), hctx, P, skip, drop_mask)
+        _heat_save(ctx, _HeatSaved(h, kqv, score, lse, skip, *edge, t=t, out=out, mask=drop_mask if st.dropout == "mask" else None, params=params))
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = N.load()
-        hctx, H, T = ctx.hctx, ctx.H, ctx.T
-        bc = None
-        if ctx.pool is not None:
-            # the gradient arrives as S rows (one per segment of the readout): build the factors the low-rank path below works with,
-            # and the [N, D] broadcast only the residual term of the K|Q|V dX epilogue still reads
-            h, kqv, t_mean, h_mean, z_mean, score, lse, skip, ew, eb, sim_csr, *params = ctx.saved_tensors
-            fwd_factors = None
-            if ctx.no_v:
-                fwd_factors, params = params[:3], params[3:]
-            t = out = None
-            prp, pop = ctx.pool
-            n_rows, D_ = h.shape
-            pre = None
-            segs_p = prp.segments_of(hctx.rows)
-            if prp.num_segs <= 8192 and segs_p is not None:
-                # one launch: the two scalings of the gradient, the skip-gate gradient (segment dots against mean(out) - mean(h), gate map,
-                # 1 - sigmoid) and the 1 - sigmoid(skip) factors of the residual term
-                seg_gate, type_gate = _gate_tables(hctx, skip, segs_p, prp.num_segs)
-                g_pool = g_out.contiguous()
-                g_row, g_sum = torch.empty_like(g_pool), torch.empty_like(g_pool)
-                pre = (torch.empty_like(skip), torch.empty(T, dtype=torch.float32, device=h.device))
-                N.check(lib.wsi_pool_bwd_prep(N.ptr(g_pool), prp.num_segs, D_, pop, N.ptr(prp.counts()), N.ptr(z_mean), N.ptr(h_mean), N.ptr(seg_gate),
-                                              N.ptr(skip), skip.shape[0], N.ptr(type_gate), T, N.ptr(g_row), N.ptr(g_sum), N.ptr(pre[0]), N.ptr(pre[1]),
-                                              N.stream()), "wsi_pool_bwd_prep")
-                bc = SegmentBroadcast.from_parts(prp, g_row, g_sum, z_mean)
-            else:
-                bc = SegmentBroadcast.from_pooled_gradient(g_out.contiguous(), prp, pop, z_mean)
-            # g_v has rank <= S x H: never formed when the fast attention kernels apply (wsi_attn_pool_t; segments numbered type-major)
-            collapse = ctx.no_v or _value_collapse_applies(hctx, prp, n_rows, D_, H)
-            if collapse:
-                g_out = None                      # (the residual term of the dX epilogue comes out of pass 3)
-            else:
-                g_out = torch.empty((n_rows, D_), dtype=torch.float32, device=h.device)
-                N.check(lib.wsi_segment_reduce_bwd(N.ptr(bc.g_row), D_, D_, N.WSI_RED_SUM, N.ptr(prp.chunk_row), N.ptr(prp.chunk_seg),
-                                                   prp.num_chunks, N.ptr(prp.seg_chunk), prp.num_segs, None,
-                                                   N.ptr(g_out), D_, N.stream()), "wsi_segment_reduce_bwd")
-        else:
-            h, kqv, t, out, score, lse, skip, ew, eb, sim_csr, *params = ctx.saved_tensors
-            t_mean = h_mean = None
-            collapse = False
-            fwd_factors = None
-            pre = None
-            g_out = g_out.contiguous()
-        g_y = g_out                       # gradient w.r.t. the (un-dropped) a_linear output, before the gate scaling
-        if ctx.has_mask and getattr(ctx, "counter", None) is not None:
-            g_y = dropout_apply(g_out, ctx.counter)             # the mask regenerated from (seed, row, col): never stored
-        elif ctx.has_mask:
-            g_y = g_out * params[0]
-            params = params[1:]
-        P = [params[8 * i:8 * i + 8] for i in range(T)]
-        dev = h.device
-        n, D = h.shape
-        plan = hctx.plan
-        E = plan.num_edges
-        a_types = hctx.a_types
-        rp = hctx.type_rplan()
+        st, sv = ctx.st, _heat_saved(ctx)
+        hctx, H, T, (n, D) = st.hctx, st.H, len(st.hctx.rows), sv.h.shape
+        P = [sv.params[8 * i:8 * i + 8] for i in range(T)]
         grads = [None] * (8 * T)
-        gate = lambda i: N.ptr(skip, 4 * hctx.nid[i])
-
-        def gate_grad_launch(stream_ptr, before_launch=None):
-            # two launches: the per-type dots sum_rows g_out (out - h), then gate map and sigmoid factor (wsi_gate_grad): a streaming pass over three [n, D] tensors.
-            # Everything the launch reads that is produced on the CALLER's stream - the gate table (an asynchronous upload on a cache miss: the first
-            # backward of every new graph context) and the buffers (the caching allocator hands out blocks whose last use is ordered on that stream) -
-            # exists before `before_launch` (the side stream's wait for the caller's stream) runs.
-            seg_gate, _ = _gate_tables(hctx, skip, [(i, i + 1) for i in range(T)], T)
-            gs_ = torch.empty_like(skip)
-            partial = torch.empty(max(rp.num_chunks * ((D + 255) // 256), 1), dtype=torch.float32, device=dev)
-            if before_launch is not None:
-                before_launch()
-            N.check(lib.wsi_gate_grad(N.ptr(g_out), g_out.stride(0), N.ptr(out), out.stride(0), N.ptr(h), h.stride(0), D, N.ptr(rp.chunk_row), rp.num_chunks,
-                                      N.ptr(rp.seg_chunk), rp.num_segs, N.ptr(seg_gate), N.ptr(skip), skip.shape[0], N.ptr(partial), N.ptr(gs_),
-                                      stream_ptr), "wsi_gate_grad")
-            return gs_, partial
-
-        # a full-depth layer's skip-gate gradient is bandwidth-bound and nobody reads it before this function returns: on the statistics stream,
-        # beside the matrix-bound output-projection gradient below (joined at the end)
-        early_gate = None
-        if (out is not None and g_out is not None and pre is None and _side_stats_on()
-                and float(n) * D >= 2.0e7 and not (_LOW_RANK["enabled"] and _annotation(g_out, "_wsi_broadcast") is not None)):
-            side = side_stream(dev, "stats")
-            gs_, partial_ = gate_grad_launch(ctypes.c_void_p(side.cuda_stream), lambda: side.wait_stream(torch.cuda.current_stream(dev)))
-            ev_ = torch.cuda.Event()
-            ev_.record(side)
-            for t_ in (g_out, out, h, gs_, partial_, skip):
-                t_.record_stream(side)
-            early_gate = (gs_, ev_)
-        # --- output projection: g_t = s * g_out Wa ; gWa = s * g_out^T t ; gba = s * colsum(g_out)
-        gkqv_max = _new_row_scale(max(n, plan.num_src_rows), 2, dev, 3 * D, zero=plan.num_src_rows != n)   # pass 2: slot 0 of all n, pass 3: slot 1 of the source rows
-        gh_max = _new_row_scale(n, N.gemm_absmax_parts(D), dev, D, zero=False)   # the two dX launches cover every row
-        # the layer under a sum / mean readout receives a gradient with ONE distinct row per (graph, node type): rank S = graphs x types
-        if bc is None and _LOW_RANK["enabled"] and g_out is not None:
-            bc = _annotation(g_out, "_wsi_broadcast")       # attached by the readout's backward to the very tensor it handed down
-            if bc is not None:
-                EXCHANGE_STATS["broadcast_hits"] += 1
-        segs = bc.rp.segments_of(hctx.rows) if bc is not None and bc.rp.num_rows == n else None
-        if segs is None:
-            bc = None
-        groups, wgroups = [], []
-        if bc is not None and not ctx.has_mask:
-            # g_t[row] = s * g_row[seg] Wa: S rows through the projection, then one broadcast;  gWa = s * sum_seg g_sum[seg] (x) mean_seg(t)
-            # (= s * g_out^T t with the rows of a segment summed first);  gba = s * sum_seg g_sum[seg]
-            S = bc.rp.num_segs
-            gt_seg = (torch.empty if len(a_types) == T else torch.zeros)((S, D), dtype=torch.float32, device=dev)
-            if t_mean is None:
-                t_mean, _ = _segment_reduce_raw(t, bc.rp, N.WSI_RED_MEAN)
-            for i in a_types:
-                s0, s1 = segs[i]
-                groups.append(dict(A=N.ptr(bc.g_row, s0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, C=N.ptr(gt_seg, s0 * D * 4), ldc=D,
-                                   gate=gate(i), M=s1 - s0, N=D, K=D))
-                gw = torch.empty_like(P[i][3])
-                gb = torch.empty_like(P[i][7])
-                grads[8 * i + 3] = gw
-                grads[8 * i + 7] = gb
-                wgroups.append(dict(A=N.ptr(bc.g_sum, s0 * D * 4), lda=D, B=N.ptr(t_mean, s0 * D * 4), ldb=D, C=N.ptr(gw), ldc=D,
-                                    gate=gate(i), colsum_out=N.ptr(gb), M=D, N=D, K=s1 - s0))
-            if not _gemm_small_pair(groups, N.WSI_EPI_SCALE_GATE, wgroups, N.WSI_EPI_SCALE_GATE, dev):
-                _gemm(N.WSI_GEMM_NN, N.WSI_EPI_SCALE_GATE, groups, dev)
-                _gemm(N.WSI_GEMM_TN, N.WSI_EPI_SCALE_GATE, wgroups, dev)
-            g_t, gt_row = gt_seg, bc.rp.row_segment()       # the attention backward reads g_t[gt_row[w]]: S rows that stay in the L2
+        collapse = st.pool is not None and (st.no_v or _value_collapse_applies(hctx, st.pool[0], n, D, H))
+        # 1) gradient intake, 2) dropout on the gradient; at full depth and size the skip-gate launch goes to the statistics stream here,
+        # in front of the output-projection groups
+        if st.pool is None:
+            g_out, bc, segs, annotated = _heat_row_gradient(g_out, hctx, n)
+            # (the counter's mask regenerated from (seed, row, column) in one launch, never stored; or the saved mask tensor)
+            g_y = dropout_apply(g_out, st.dropout) if isinstance(st.dropout, CounterDropout) else (g_out if st.dropout is None else g_out * sv.mask)
+            pre = None
+            early = _heat_early_gate(g_out, sv, hctx) if (not annotated and _side_stats_on() and float(n) * D >= 2.0e7) else None
         else:
-            gt_row = None
-            g_t = torch.empty((n, D), dtype=torch.float32, device=dev)
-            gy_max = row_scales_of(g_y)                # fp16x3 row scales: left by the layer above (its dX epilogue), if any
-            gy_cols, t_cols = col_stats_of(g_y), getattr(ctx, "t_cols", None)      # column statistics for the weight gradient, likewise
-            for i in a_types:
-                r0, r1 = hctx.rows[i]
-                groups.append(dict(A=N.ptr(g_y, r0 * D * 4), lda=D, B=N.ptr(P[i][3]), ldb=D, Bw=[P[i][3]], C=N.ptr(g_t, r0 * D * 4), ldc=D,
-                                   gate=gate(i), M=r1 - r0, N=D, K=D, **_scale_in(gy_max, r0)))
-                gw = torch.empty_like(P[i][3])
-                gb = torch.empty_like(P[i][7])
-                grads[8 * i + 3] = gw
-                grads[8 * i + 7] = gb
-                wgroups.append(dict(A=N.ptr(g_y, r0 * D * 4), lda=D, B=N.ptr(t, r0 * D * 4), ldb=D, C=N.ptr(gw), ldc=D,
-                                    gate=gate(i), colsum_out=N.ptr(gb), M=D, N=D, K=r1 - r0,
-                                    **(gy_cols.consume("a", r0, r1, 0, want_sums=True) if gy_cols is not None else {}),
-                                    **(t_cols.consume("b", r0, r1, 0) if t_cols is not None else {})))
-            _gemm(N.WSI_GEMM_NN, N.WSI_EPI_SCALE_GATE, groups, dev)
-            # the a_linear weight gradient has the whole attention backward of this layer in front of it: in the background (DESIGN 3.8)
-            wr = [P[i][k] for i in a_types for k in (3, 7)]
-            keep = [g_y, t, skip] + [c_.bits for c_ in (gy_cols, t_cols) if c_ is not None] + [c_.sums for c_ in (gy_cols,) if c_ is not None and c_.sums is not None]
-            outs = [(P[i][k], grads[8 * i + k]) for i in a_types for k in (3, 7)]
-            if not (_background_safe(wr) and _gemm_tn_background(N.WSI_EPI_SCALE_GATE, wgroups, dev, keep, wr, outs=outs)):
-                _gemm(N.WSI_GEMM_TN, N.WSI_EPI_SCALE_GATE, wgroups, dev)
-        # d loss / d skip[nid] = (1 - sigmoid(skip[nid])) * sum over the graph node types i mapped to nid of dots[i],
-        # dots[i] = sum over the rows of type i of g_out * (out - h)
-        sig_skip = None
-        if pre is not None:
-            g_skip = pre[0]                            # (wsi_pool_bwd_prep: from the segment means, with the scalings of the gradient)
-        elif bc is not None and (out is None or (bc.x_ptr == out.data_ptr() and bc.x_version == out._version)):
-            # sum_rows g_out * (out - h) = sum_seg g_sum[seg] . (mean_seg(out) - mean_seg(h)); the readout already holds mean_seg(out)
-            from .graph import host_to_device
-            q = hctx.cache.get("gate_of_type")
-            if q is None:
-                q = hctx.cache["gate_of_type"] = host_to_device(
-                    [[1.0 if (i in a_types and hctx.nid[i] == g_) else 0.0 for i in range(T)] for g_ in range(skip.shape[0])], torch.float32, dev).view(skip.shape[0], T)
-            if h_mean is None:
-                h_mean, _ = _segment_reduce_raw(h, bc.rp, N.WSI_RED_MEAN)
-            hit = hctx.cache.get("gate_of_seg")            # (rp, matrix): matched by identity of the plan object, which the entry keeps alive
-            if hit is None or hit[0] is not bc.rp:
-                m = host_to_device([[1.0 if segs[i][0] <= s_ < segs[i][1] else 0.0 for s_ in range(bc.rp.num_segs)] for i in range(T)], torch.float32, dev)
-                hit = hctx.cache["gate_of_seg"] = (bc.rp, q @ m.view(T, -1))
-            qs = hit[1]
-            sig_skip = torch.sigmoid(skip)
-            g_skip = (qs @ (bc.g_sum * (bc.x_mean - h_mean)).sum(dim=1)) * (1.0 - sig_skip)
-        elif early_gate is not None:
-            g_skip = early_gate[0]                     # (launched on the statistics stream at the top of this function; joined before it returns)
+            bc, pre = _heat_pooled_gradient(g_out, sv, st)
+            segs = bc.rp.segments_of(hctx.rows)
+            g_out = None if collapse else _heat_broadcast_rows(bc, n, D)       # (collapse: the residual term of the dX epilogue comes out of pass 3)
+            g_y = early = None                                                  # (no dropout under a readout; the S rows go through stage 3 as they are)
+        # 3) output-projection gradients
+        if bc is not None and st.dropout is None:
+            g_t, gt_row = _heat_out_proj_low_rank(bc, segs, sv, hctx, P, grads)
         else:
-            g_skip = gate_grad_launch(N.stream())[0]
-        # --- relation attention backward (pass 1 reads the saved logits and writes the probabilities to `a`)
-        a = torch.empty_like(score)
-        scratch = torch.empty((3, max(E, 1), H), dtype=torch.float32, device=dev)
-        red_ws = torch.empty(1024, dtype=torch.float32, device=dev)
-        no_v = fwd_factors is not None            # the forward never computed V: kqv is [n, 2D] (K | Q) and so is its gradient
-        ldp = kqv.shape[1]
-        blk = ctx.blk                             # column block of K, Q, V (the forward's choice)
-        kO, qO, vO = blk[0] * D * 4, blk[1] * D * 4, blk[2] * D * 4
-        gkqv = torch.empty_like(kqv)
-        g_e = torch.empty(2, dtype=torch.float32, device=dev)
-        pool_arg = None
+            g_t, gt_row = _heat_out_proj_rows(g_y, sv, st, P, grads), None
+        # 4) skip-gate gradient
+        g_skip = _heat_skip_gate_grad(g_out, sv, hctx, bc, segs, pre, early)
         if collapse:
-            S, dk = bc.rp.num_segs, D // H
-            from .graph import host_to_device
-            # y[tau, seg, h, :] = g_t[seg]_h (W_v^tau rows of head h): what one unit of c[u, bin, h] adds to g_h[u]
-            ytab = torch.empty((T, S, H, D), dtype=torch.float32, device=dev)
-            groups = []
-            for tau in range(T):
-                for hh in range(H):
-                    groups.append(dict(A=N.ptr(gt_seg, hh * dk * 4), lda=D, B=N.ptr(P[tau][2], hh * dk * D * 4), ldb=D,
-                                       C=N.ptr(ytab, ((tau * S) * H + hh) * D * 4), ldc=H * D, M=S, N=D, K=dk))
-            _gemm(N.WSI_GEMM_NN, 0, groups, dev)
-            if pre is not None:
-                omg = pre[1]
-            else:
-                qt = hctx.cache.get("gate_of_row_type")
-                if qt is None:
-                    qt = hctx.cache["gate_of_row_type"] = host_to_device(
-                        [[1.0 if (hctx.incoming[i] and hctx.nid[i] == g_) else 0.0 for g_ in range(skip.shape[0])] for i in range(T)], torch.float32, dev).view(T, -1)
-                omg = 1.0 - qt @ (sig_skip if sig_skip is not None else torch.sigmoid(skip))      # [T]: 1 - s of the type; 1 where the layer passes h through
-            r_out = torch.empty((n, D), dtype=torch.float32, device=dev)
-            bv_ptrs = _ptr_array([P[tau][6] for tau in range(T)])
-            gbv = torch.empty((T, D), dtype=torch.float32, device=dev)
-            if no_v:
-                ctab, hp, csum = fwd_factors
-                # beta[tau, s, h] = g_t[seg]_h . b_v^tau (head h), and the value-bias gradients from the forward's coefficient sums: one launch
-                beta = torch.empty((T, S, H), dtype=torch.float32, device=dev)
-                N.check(lib.wsi_pool_bwd_bias(N.ptr(gt_seg), T, S, D, H, bv_ptrs, N.ptr(csum), N.ptr(beta), N.ptr(gbv), N.stream()), "wsi_pool_bwd_bias")
-            else:
-                ctab = torch.empty((n, T, H), dtype=torch.float32, device=dev)
-                beta = None
-            gtab = None
-            if no_v and T * H <= 32 and T * H * (D + 4) * 4 <= 64 * 1024:     # (wsi_heat_pool_gtab's limits: J = T*H <= 32 columns, table in 64 KB of LDS)
-                # pass 1's dot products taken once per SOURCE node (T*H per node, one pass over h) instead of H per edge against gathered rows
-                gtab = torch.empty((n, T, H), dtype=torch.float32, device=dev)
-                with _Timed("heat_attn"), _Timed("heat_attn_bwd_pooled"):
-                    N.check(lib.wsi_heat_pool_gtab(N.ptr(h), D, D, H, N.ptr(ytab), N.ptr(beta), N.ptr(bc.rp.chunk_row), N.ptr(bc.rp.chunk_seg),
-                                                   bc.rp.num_chunks, S // T, T, N.ptr(gtab), N.stream()), "wsi_heat_pool_gtab")
-            pool_desc = N.AttnPool(row_seg=N.ptr(bc.rp.row_segment()), segs_per_type=S // T, n_types=T, y=N.ptr(ytab), g_row=N.ptr(bc.g_row),
-                                   omg=N.ptr(omg), r_out=N.ptr(r_out), ldr=D, ctab=N.ptr(ctab), ctab_ready=1 if no_v else 0,
-                                   h=N.ptr(h) if no_v else None, ldh=D, beta=N.ptr(beta), gtab=N.ptr(gtab),
-                                   edge_seg=N.ptr(_edge_segments(plan)) if gtab is not None else None,
-                                   seg_dst=N.ptr(_segment_dst(plan)) if gtab is not None else None)
-            pool_arg = ctypes.byref(pool_desc)
-        _background_flush(dev)                 # queued weight gradients (this layer's a_linear, the layer above's K|Q|V) run under the attention backward
-        with _Timed("heat_attn"), _Timed("heat_attn_bwd_pooled" if collapse else "heat_attn_bwd_full"):
-            N.check(lib.wsi_heat_attn_bwd(
-                N.ptr(kqv, qO), ldp, N.ptr(kqv, kO), ldp, None if no_v else N.ptr(kqv, vO), ldp, n, plan.num_src_rows, E, D, H,
-                N.ptr(plan.node_seg), N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(sim_csr),
-                N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
-                N.ptr(plan.inv_rd), N.ptr(plan.order_dst), plan.num_heavy, N.ptr(plan.order_src), _attn_flags(plan), N.ptr(ew), N.ptr(eb),
-                N.ptr(g_t), D, N.ptr(gt_row), N.ptr(score), N.ptr(a), N.ptr(lse), N.ptr(scratch[0]), N.ptr(scratch[1]), N.ptr(scratch[2]), N.ptr(red_ws),
-                N.ptr(gkqv, qO), ldp, N.ptr(gkqv, kO), ldp, None if no_v else N.ptr(gkqv, vO), ldp,
-                N.ptr(g_e), N.ptr(gkqv_max), pool_arg, N.context(), N.stream()), "wsi_heat_attn_bwd")
-        # column statistics of the attention gradients for their weight gradient, beside the dX projection below (ops._col_stats_side)
-        gk_side = _col_stats_side(gkqv, hctx.rows, dev) if (want_col_stats(n, D, D) and (D % 32 == 0)) else None
-        # --- K|Q|V projections: g_h = gkqv [Wk;Wq;Wv] + (1-s) g_out ; gW = gkqv^T h ; gb = colsum(gkqv)
-        g_h = torch.empty((n, D), dtype=torch.float32, device=dev)
-        chunked = (D % 32 == 0)
-        nproj = 2 if collapse else 3              # collapse: K and Q chunks only (columns [0, 2D) of gkqv; V columns, if any, are not written)
-        # g_h is the dY of the weight gradient below (the lower layer's output projection, or the input projection): its dX epilogue leaves the
-        # column statistics - absmax and sums (the bias gradient) - that launch would otherwise take a pass over g_h for
-        gh_cols = ColStats.allocate(hctx.rows, D, dev, sums=True) if (chunked and want_col_stats(n, D, D)) else None
-        gh_wrote = True
-        if collapse:
-            groups = []
-            for i, (r0, r1) in enumerate(hctx.rows):
-                groups.append(dict(A=N.ptr(gkqv, r0 * ldp * 4), lda=ldp, B=N.ptr(P[i][0]), B1=N.ptr(P[i][1]), b_chunk=D, ldb=D, Bw=[P[i][0], P[i][1]],
-                                   C=N.ptr(g_h, r0 * D * 4), ldc=D, R=N.ptr(r_out, r0 * D * 4), ldr=D, M=r1 - r0, N=D, K=2 * D,
-                                   **_scale_in(gkqv_max, r0), **_scale_out(gh_max, r0),
-                                   **(gh_cols.produce(r0, r1, 0) if gh_cols is not None else {})))
-            gh_wrote = _gemm(N.WSI_GEMM_NN, N.WSI_EPI_ADD_R, groups, dev)
-        for with_gate in ((True, False) if not collapse else ()):
-            idxs = [i for i in range(T) if hctx.incoming[i] == with_gate]
-            if not idxs:
-                continue
-            epi = N.WSI_EPI_ADD_R | (N.WSI_EPI_R_1MG if with_gate else 0)
-            if chunked:
-                groups = []
-                for i in idxs:
-                    r0, r1 = hctx.rows[i]
-                    wb = sorted(range(3), key=lambda j_: blk[j_])      # the weight of column block 0, 1, 2
-                    groups.append(dict(A=N.ptr(gkqv, r0 * 3 * D * 4), lda=3 * D, B=N.ptr(P[i][wb[0]]), B1=N.ptr(P[i][wb[1]]), B2=N.ptr(P[i][wb[2]]),
-                                       Bw=[P[i][wb[0]], P[i][wb[1]], P[i][wb[2]]], b_chunk=D, ldb=D, C=N.ptr(g_h, r0 * D * 4), ldc=D, R=N.ptr(g_out, r0 * D * 4), ldr=D,
-                                       gate=gate(i) if with_gate else None, M=r1 - r0, N=D, K=3 * D,
-                                       **_scale_in(gkqv_max, r0), **_scale_out(gh_max, r0),
-                                       **(gh_cols.produce(r0, r1, 0) if gh_cols is not None else {})))
-                gh_wrote = _gemm(N.WSI_GEMM_NN, epi, groups, dev) and gh_wrote
-            else:
-                for j in range(3):
-                    groups = []
-                    for i in idxs:
-                        r0, r1 = hctx.rows[i]
-                        groups.append(dict(A=N.ptr(gkqv, (r0 * 3 * D + blk[j] * D) * 4), lda=3 * D, B=N.ptr(P[i][j]), ldb=D,
-                                           C=N.ptr(g_h, r0 * D * 4), ldc=D, R=N.ptr(g_out, r0 * D * 4), ldr=D,
-                                           gate=gate(i) if with_gate else None, M=r1 - r0, N=D, K=D))
-                    _gemm(N.WSI_GEMM_NN, epi if j == 0 else N.WSI_EPI_ACCUMULATE, groups, dev)
-        wgroups = []
-        h_cols = getattr(ctx, "h_cols", None)
-        for i, (r0, r1) in enumerate(hctx.rows):
-            for j in range(nproj):
-                gw = torch.empty_like(P[i][j])
-                gb = torch.empty_like(P[i][4 + j])
-                grads[8 * i + j] = gw
-                grads[8 * i + 4 + j] = gb
-                wgroups.append(dict(A=N.ptr(gkqv, (r0 * ldp + blk[j] * D) * 4), lda=ldp, B=N.ptr(h, r0 * D * 4), ldb=D,
-                                    C=N.ptr(gw), ldc=D, colsum_out=N.ptr(gb), M=D, N=D, K=r1 - r0,
-                                    **(gk_side[0].consume("a", r0, r1, blk[j] * D, want_sums=True) if gk_side is not None else {}),
-                                    **(h_cols.consume("b", r0, r1, 0) if h_cols is not None else {})))
-        # a layer with another HEAT layer below it: its K|Q|V weight gradient runs under THAT layer's attention backward
-        wr = [P[i][k] for i in range(T) for j in range(nproj) for k in (j, 4 + j)]
-        keep = [gkqv, h] + ([h_cols.bits] if h_cols is not None else []) + ([gk_side[0].bits, gk_side[0].sums] if gk_side is not None else [])
-        outs = [(P[i][k], grads[8 * i + k]) for i in range(T) for j in range(nproj) for k in (j, 4 + j)]
-        evs = [gk_side[1]] if gk_side is not None else []
-        if not (ctx.background_dw and _background_safe(wr) and _gemm_tn_background(0, wgroups, dev, keep, wr, evs, outs=outs)):
-            for ev in evs:
-                torch.cuda.current_stream(dev).wait_event(ev)
-            _gemm(N.WSI_GEMM_TN, 0, wgroups, dev)
-        if collapse:
-            # dW_v^tau (rows of head h) = sum_seg g_t[seg]_h (x) hp[seg, h, tau, :]  (hp: weighted sums of h over the (source type, graph) segments, from
-            # the forward when it never computed V, else taken here from pass 3's coefficients);  db_v likewise with the sums of the coefficients
-            if not no_v:
-                hp, csum = _pooled_factors(h, ctab, bc.rp, T, H)
-                N.check(lib.wsi_pool_bwd_bias(N.ptr(gt_seg), T, S, D, H, None, N.ptr(csum), None, N.ptr(gbv), N.stream()), "wsi_pool_bwd_bias")
-            wgroups = []
-            for tau in range(T):
-                gw = torch.empty_like(P[tau][2])
-                grads[8 * tau + 2] = gw
-                grads[8 * tau + 6] = gbv[tau]
-                for hh in range(H):
-                    wgroups.append(dict(A=N.ptr(gt_seg, hh * dk * 4), lda=D, B=N.ptr(hp, (hh * T + tau) * D * 4), ldb=H * T * D,
-                                        C=N.ptr(gw, hh * dk * D * 4), ldc=D, M=dk, N=D, K=S))
-            _gemm(N.WSI_GEMM_TN, 0, wgroups, dev)
-        if gh_max is not None and chunked:
-            attach_row_scales(g_h, gh_max)
-        if gh_cols is not None and gh_wrote and chunked:
-            attach_col_stats(g_h, gh_cols)
-        if early_gate is not None:
-            torch.cuda.current_stream(dev).wait_event(early_gate[1])
+            # 5) collapse tables, 6) attention backward, 7) dX and 8) dW on the K and Q blocks, 9) value-weight gradients from the factors
+            pool_desc, r_out, ctab, gbv, _alive = _heat_collapse_tables(g_t, bc, sv, st, P, pre[1] if pre is not None else None)
+            gkqv, gkqv_max, g_e, gk_side = _heat_attention_backward(g_t, gt_row, sv, st, pool_desc)
+            g_h = _heat_dx_chunked(gkqv, gkqv_max, r_out, 2, hctx, P, None)
+            _heat_kqv_weight_grads(gkqv, gk_side, 2, sv, st, P, grads)
+            hp, gbv = (sv.hp, gbv) if st.no_v else _heat_factors_from_pass3(g_t, ctab, bc.rp, sv.h, T, H)
+            _heat_value_weight_grads(g_t, hp, gbv, P, H, grads)
+        else:
+            # 6) attention backward, 7) K|Q|V dX: g_h = gkqv [Wk; Wq; Wv] + (1 - s) g_out, 8) K|Q|V dW
+            gkqv, gkqv_max, g_e, gk_side = _heat_attention_backward(g_t, gt_row, sv, st, None)
+            g_h = _heat_dx_chunked(gkqv, gkqv_max, g_out, 3, hctx, P, sv.skip) if D % 32 == 0 else _heat_dx_by_block(gkqv, g_out, hctx, P, sv.skip)
+            _heat_kqv_weight_grads(gkqv, gk_side, 3, sv, st, P, grads)
+        if early is not None:
+            torch.cuda.current_stream(sv.h.device).wait_event(early[1])
         return (g_h, None, None, g_skip, g_e[0:1].view(1, 1), g_e[1:2], None, None, None, *grads)
 
 
