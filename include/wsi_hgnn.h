@@ -464,6 +464,35 @@ int wsi_bag_scores_bwd(const float* w, int64_t ldw, const float* t, const float*
                        int32_t C, int32_t D, const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks,
                        float* gx, int64_t ldgx, void* stream);
 
+/* Global attention readout (an addition to ABI 26): dgl.nn.GlobalAttentionPooling over the rows of many segments at once - what
+ * graph_pooling_type 'att' selects (models/HEATNet4.py:182-187 applied at :219, models/GCN.py), with the one-column gate_nn folded in:
+ *   gate[r]   = <x[r, :], w> + bias[0]                                   [rows]
+ *   p[r]      = softmax of gate over the rows of r's segment
+ *   out[s, :] = sum_{r in s} p[r] * x[r, :]                              [num_segs, D] contiguous
+ *   stats[s]  = (the segment's maximum gate, the log of the sum of e^(gate - maximum))   [num_segs, 2], kept apart for the reason
+ *               wsi_bag_softmax_pool_fwd gives: at gates near -1e4 their float32 sum has an ulp of 1e-3
+ * x [rows, D] with row stride ldx; w [D] and bias [1] are DEVICE pointers (bias may be NULL: 0); chunk tables as for wsi_segment_reduce_fwd
+ * (empty chunks nobody owns - the padding of a slot's tables - are fine).  An empty segment gives out = 0 and stats = (0, 0).
+ * 1 <= D <= 2048 (more: WSI_ENOSYS); 16-byte row loads when x and ldx are 16-byte aligned, a scalar path otherwise.  Two stages (per chunk an
+ * online softmax with the row's dot product taken in the same pass over the row, then the segment's chunks combined in chunk order): x is read
+ * once, no atomics, bit-reproducible.  partial: caller scratch, num_chunks * (D + 2) floats. */
+int wsi_attn_readout_fwd(const float* x, int64_t ldx, int32_t D, const float* w, const float* bias,
+                         const int32_t* chunk_row, int32_t num_chunks, const int32_t* seg_chunk, int32_t num_segs,
+                         float* partial, float* out, float* gate, float* stats, void* stream);
+
+/* Its gradients, from g_out [num_segs, D] contiguous and the forward's out, gate and stats (p[r] = exp((gate[r] - stats[s, 0]) - stats[s, 1])):
+ *   delta[s]   = <g_out[s], out[s]>
+ *   g_gate[r]  = p[r] * (<g_out[s], x[r]> - delta[s])
+ *   g_x[r, :]  = p[r] * g_out[s, :] + g_gate[r] * w              [rows, D] with row stride ldgx; may be NULL: not computed, not written
+ *   g_wb       = sum_r g_gate[r] * x[r, :]  |  sum_r g_gate[r]   [D + 1]: the gate's weight gradient, then its bias gradient
+ * x is read once and g_x written once; g_wb is a per-chunk partial added in chunk order by a second launch - no atomics, fixed summation order.
+ * A segment whose g_out row is zero gets exactly zero gradients.  The limits of D and the scalar path are the forward's.
+ * scratch: caller scratch, num_segs + num_chunks * (D + 1) floats. */
+int wsi_attn_readout_bwd(const float* g_out, const float* out, const float* gate, const float* stats,
+                         const float* x, int64_t ldx, int32_t D, const float* w,
+                         const int32_t* chunk_row, const int32_t* chunk_seg, int32_t num_chunks, int32_t num_segs,
+                         float* scratch, float* g_x, int64_t ldgx, float* g_wb, void* stream);
+
 /* ReMix's bag reduction (an addition to ABI 26): ONE Lloyd iteration of a k-means over the rows of many bags at once - what faiss does per slide
  * for baselines/ReMix_DSMIL_ABMIL/reduce.py:18-19 (tools/clustering.py).  x [rows, D] with row stride ldx, the bags one after the other under the
  * chunk tables of wsi_segment_reduce_fwd (chunk_seg as for wsi_segment_reduce_bwd); centroids [num_segs, K, D] contiguous.  Per row
@@ -670,6 +699,13 @@ int wsi_slot_fill(const int64_t* desc, int32_t nsegs, int32_t total_blocks, void
  * empty graphs behind them, the rest the filler), as wsi_slot_fill and wsi_slot_aug_* have just written it on `stream`.  One wave, plain
  * loads and stores, no atomics, no read-back; every word of out [T] is written.  1 <= T, 0 <= b_cap <= graphs. */
 int wsi_type_present(const float* seg_nonempty, int32_t T, int32_t graphs, int32_t b_cap, float* out, void* stream);
+
+/* GraphConv's degree norms of a homogeneous slot (an addition to ABI 26; models/GCN.py: dgl GraphConv(norm='both')), re-derived behind every
+ * fill as wsi_type_present is: in_norm[i] = max(rowptr[i + 1] - rowptr[i], 1) ** -0.5 and out_norm[i] = max(colptr[i + 1] - colptr[i], 1) ** -0.5
+ * for the n nodes of the slot, the filler's included (rowptr: one segment per node - one relation; colptr: the CSC pointer; n + 1 words each).
+ * One launch, no read-back; the reciprocal square root is taken in double and rounded once, which is what ``clamp(min=1).pow(-0.5)`` on a
+ * float32 device tensor gives (models/GCN.py HomoPlan): the same bits. */
+int wsi_degree_norms(const int32_t* rowptr, const int32_t* colptr, int32_t n, float* in_norm, float* out_norm, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-wise kernels of the HGT / GCN siblings of the path.

@@ -116,6 +116,19 @@ __global__ __launch_bounds__(64) void type_present_kernel(const float* __restric
     }
 }
 
+// GraphConv's degree norms of a filled homogeneous slot (wsi_degree_norms): thread i reads two words of each pointer table.  The reciprocal
+// square root is taken in double and rounded once: torch's float32 rsqrt on this device returns that value for every degree, the one-ulp
+// v_rsq_f32 behind rsqrtf does not (418 of the degrees 1 .. 4096 differ), and an eager step on the slot's graph must see torch's bits.
+__device__ __forceinline__ float degree_norm(int deg) { return (float)(1.0 / sqrt((double)(deg > 1 ? deg : 1))); }
+
+__global__ __launch_bounds__(256) void degree_norms_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colptr, int n,
+                                                           float* __restrict__ in_norm, float* __restrict__ out_norm) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    in_norm[i] = degree_norm(rowptr[i + 1] - rowptr[i]);
+    out_norm[i] = degree_norm(colptr[i + 1] - colptr[i]);
+}
+
 static int launch_segment_table(const char* who, const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
     if (nsegs < 0 || total_blocks < 0) { set_error("%s: bad argument", who); return WSI_EINVAL; }
     if (nsegs == 0 || total_blocks == 0) return WSI_OK;
@@ -141,4 +154,12 @@ extern "C" int wsi_type_present(const float* seg_nonempty, int32_t T, int32_t gr
     if (!out || (!seg_nonempty && b_cap > 0)) { set_error("type_present: null pointer"); return WSI_EINVAL; }
     hipLaunchKernelGGL(type_present_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, seg_nonempty, (int)T, (int)graphs, (int)b_cap, out);
     return check_launch("type_present");
+}
+
+extern "C" int wsi_degree_norms(const int32_t* rowptr, const int32_t* colptr, int32_t n, float* in_norm, float* out_norm, void* stream) {
+    if (n < 0) { set_error("degree_norms: bad argument"); return WSI_EINVAL; }
+    if (n == 0) return WSI_OK;
+    if (!rowptr || !colptr || !in_norm || !out_norm) { set_error("degree_norms: null pointer"); return WSI_EINVAL; }
+    hipLaunchKernelGGL(degree_norms_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rowptr, colptr, (int)n, in_norm, out_norm);
+    return check_launch("degree_norms");
 }

@@ -49,7 +49,9 @@ class StoredGraph:
         self.label = int(label)
         # the graph's own kernel plan, cut into per-node-type pieces (device-resident, ~2 MB per 10k-node graph)
         edges = OrderedDict((r, tuple(x.to(device) for x in g.edges(r))) for r in self.rels)
-        sims = {r: g._eframes[r]["sim"].to(device=device, dtype=torch.float32) for r in self.rels}
+        # (a graph without the ``sim`` edge field - graph.to_homogeneous output, which GraphConv reads no edge field of - stores zeros)
+        sims = {r: (g._eframes[r]["sim"].to(device=device, dtype=torch.float32) if "sim" in g._eframes[r]
+                    else torch.zeros(edges[r][0].numel(), dtype=torch.float32, device=device)) for r in self.rels}
         topo = HeteroGraph.from_coo(OrderedDict(zip(self.ntypes, self.num_nodes)), edges, sim=sims)
         self.edges, self.sims = edges, sims      # per-relation COO (local ids): the batch's COO is an offset-concat of these, built
         plan = topo.plan()                       # only if something asks for it (HeteroGraph._edges)
@@ -542,6 +544,15 @@ class BatchSlot:
         if self.type_mask:
             self.share_type_table(torch.ones(T, dtype=torch.float32, device=self.device) if type_mask is True else type_mask)
 
+        # a homogeneous slot (one node type, one relation: graph.to_homogeneous slides): GraphConv's degree norms as two more
+        # static tables, re-derived on the device behind every fill, under the slot graph's cached models.GCN.HomoPlan
+        self.degree_norms = None
+        if T == 1 and len(rels) == 1:
+            from .models.GCN import HomoPlan
+            mk = lambda: torch.empty(lay.N, dtype=torch.float32, device=self.device)
+            self.degree_norms = self.bufs["in_norm"], self.bufs["out_norm"] = mk(), mk()
+            G.__dict__["_homo_plan"] = HomoPlan.over_tables(plan, lay.N, lay.E, *self.degree_norms)
+
     def share_type_table(self, table: torch.Tensor) -> None:
         """Make ``table`` (float32 ``[T]`` on the slot's device) this slot's presence table: every later fill writes it, and the slot graph
         carries it.  A step captured over the slot before this call still reads the old table."""
@@ -560,6 +571,8 @@ class BatchSlot:
             _graph_mod.derive_rel_tables(self.layout.hd, self.graph._plan, self.rel, sort_sources=self.rel_sorted)
         if self.type_present is not None:
             _graph_mod.derive_type_present(self.layout, self.bufs, self.type_present)
+        if self.degree_norms is not None:
+            _graph_mod.derive_degree_norms(self.layout, self.bufs, *self.degree_norms)
 
     def quota_of(self, idx: int):
         """``(qn, qe)`` of the loader's slide ``idx`` under this slot's quota rule, never above the stored counts (cached)."""
@@ -767,6 +780,8 @@ def _slot_reduce_plan(ops):
     class SlotReducePlan(ops.ReducePlan):
         """The readout plan of a slot: its tables are static buffers the fill rewrites, so nothing a step decides on the HOST may depend on the
         current batch - a slot always counts as having empty segments (the mask of empty segments is then always applied; it is exact)."""
+
+        is_slot = True          # pooling.readout.slot_plan: the attention readout then reads these tables instead of host-side node counts
 
         def has_empty(self) -> bool:
             return True

@@ -1258,6 +1258,26 @@ def derive_type_present(lay: SlotLayout, bufs: Dict[str, torch.Tensor], out: tor
     N.check(N.load().wsi_type_present(N.ptr(ne), lay.T, lay.graphs, lay.b_cap, N.ptr(out), N.stream()), "wsi_type_present")
 
 
+def derive_degree_norms(lay: SlotLayout, bufs: Dict[str, torch.Tensor], in_norm: torch.Tensor, out_norm: torch.Tensor) -> None:
+    """GraphConv's degree norms of the batch just filled into a HOMOGENEOUS slot's ``bufs`` (one node type, one relation: ``rowptr`` has one
+    segment per node): ``clamp(in-degree, min=1) ** -0.5`` and the same of the out-degree for all ``lay.N`` nodes, the filler's included - what
+    ``models.GCN.HomoPlan`` computes per graph - on the current stream behind the fill: ``wsi_degree_norms`` on the GPU (one launch, no
+    read-back), the same tensor operations on the CPU (the kernel's oracle)."""
+    if lay.T != 1 or len(lay.rels) != 1:
+        raise ValueError("derive_degree_norms: a homogeneous slot (one node type, one relation)")
+    n, rowptr, colptr = lay.N, bufs["rowptr"], bufs["colptr"]
+    for t in (in_norm, out_norm):
+        if tuple(t.shape) != (n,) or t.dtype != torch.float32 or t.device != rowptr.device or not t.is_contiguous():
+            raise ValueError(f"derive_degree_norms: the tables are contiguous float32 [{n}] tensors on the slot's device")
+    if rowptr.device.type != "cuda":
+        with torch.no_grad():
+            in_norm.copy_((rowptr[1:n + 1] - rowptr[:n]).to(torch.float32).clamp(min=1).pow(-0.5))
+            out_norm.copy_((colptr[1:n + 1] - colptr[:n]).to(torch.float32).clamp(min=1).pow(-0.5))
+        return
+    from . import _native as N
+    N.check(N.load().wsi_degree_norms(N.ptr(rowptr), N.ptr(colptr), n, N.ptr(in_norm), N.ptr(out_norm), N.stream()), "wsi_degree_norms")
+
+
 def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]],
                     scales: Optional[Sequence[Sequence[torch.Tensor]]] = None, device="cpu", allow_empty_type: bool = False) -> Dict[str, object]:
     """``slot_fill`` as tensor operations: the CPU path and the kernel's test oracle (the GPU test compares the two bit for bit).  The real

@@ -28,6 +28,15 @@ class HomoPlan:
         self.out_norm = outdeg.clamp(min=1).pow(-0.5).contiguous()
         self.num_nodes = n
 
+    @classmethod
+    def over_tables(cls, plan, num_nodes: int, num_edges: int, in_norm: torch.Tensor, out_norm: torch.Tensor) -> "HomoPlan":
+        """The plan of a slot's padded batch (``data.BatchSlot``): ``plan``'s tables and the two norm tables are static buffers that every fill
+        rewrites (``graph.derive_degree_norms``), so nothing is computed here."""
+        self = cls.__new__(cls)
+        self.rowptr, self.src, self.colptr, self.csc_dst, self.csc_eid = plan.rowptr, plan.src, plan.colptr, plan.csc_dst, plan.csc_eid
+        self.num_edges, self.num_nodes, self.in_norm, self.out_norm = num_edges, num_nodes, in_norm, out_norm
+        return self
+
 
 def homo_plan(g) -> HomoPlan:
     if "_homo_plan" not in g.__dict__:
@@ -120,6 +129,15 @@ class GCN(nn.Module):
         """``linears_prediction[n_layers]`` is created (GCN.py:41-62) and never applied (:75 uses ``classify``)."""
         return [n for n, _ in self.named_parameters() if n.startswith(f"linears_prediction.{self.n_layers}.")]
 
+    def _drop(self, h):
+        """The inter-layer ``nn.Dropout`` (GCN.py:71).  Under an active dropout seed base (``ops.dropout_seed_base``: a captured step) the
+        train-mode draw is counter-based - ``ops.CounterDropout`` of (p, a host seed, the DEVICE word), regenerated in the backward - so that
+        every replay drops other entries; otherwise torch's own draw, as before."""
+        base = ops.current_dropout_seed_base(h.device) if (self.training and self.dropout.p > 0.0 and h.is_cuda) else None
+        if base is None:
+            return self.dropout(h)
+        return ops.counter_dropout(h, ops.CounterDropout(self.dropout.p, ops.next_dropout_seed(), base))
+
     def forward(self, g, h=None):
         if h is None:
             h = g.ndata["feat"]                                                         # GCN.py:65-66
@@ -127,7 +145,7 @@ class GCN(nn.Module):
         h_list = []
         for i, layer in enumerate(self.layers):                                         # :69-73
             if i != 0:
-                h = self.dropout(h)
+                h = self._drop(h)
             p = self.pools[i](g, h)
             h_list.append(ops.linear(p, self.linears_prediction[i].weight, self.linears_prediction[i].bias))
             h = layer(g, h)

@@ -299,7 +299,9 @@ def _readout_sum_forward(model, G, h, layer_fn, need_last: bool = False):
     hg = 0
     for i in range(model.n_layers):
         pool = model.pools[i]
-        if isinstance(pool, GlobalAttentionPooling):
+        if isinstance(pool, GlobalAttentionPooling) and pool.fused(G):
+            pooled = pool.forward_all_types(G, x)
+        elif isinstance(pool, GlobalAttentionPooling):
             pooled = torch.cat([pool(G, x[a:b], ntype=t) for t, (a, b) in zip(hctx.ntypes, hctx.rows)], dim=0)
         else:
             pooled = ops.segment_reduce(x, all_types_plan(G, dev), pool.op)

@@ -89,6 +89,8 @@ class HEATTrunk(nn.Module):
             hcat = self.gcs[i].forward_cat(ctx, hcat, pool=(rp, pool.op) if (fuse and last) else None, first_layer=(i == 0))
         if fuse:
             pooled, hcat = hcat, None
+        elif isinstance(pool, GlobalAttentionPooling) and pool.fused(G):
+            pooled = pool.forward_all_types(G, hcat)               # one launch for all (node type, graph) segments: the one gate serves every type
         elif isinstance(pool, GlobalAttentionPooling):
             pooled = torch.cat([pool(G, hcat[a:b], ntype=t) for t, (a, b) in zip(ctx.ntypes, ctx.rows)], dim=0)
         else:

@@ -1377,6 +1377,101 @@ def bag_scores(q: torch.Tensor, onehot: torch.Tensor, rp: ReducePlan) -> torch.T
 
 
 # ------------------------------------------------------------------------------------------------
+# global attention readout (wsi_attn_readout_*: pooling.GlobalAttentionPooling, graph_pooling_type 'att')
+# ------------------------------------------------------------------------------------------------
+_FUSED_ATT_READOUT = {"enabled": False}
+
+
+def set_fused_attention_readout(on: bool) -> None:
+    """On: ``pooling.GlobalAttentionPooling`` runs as ``attention_readout`` (one pass over the node table, wsi_attn_readout_fwd / _bwd) on
+    every graph.  Off (default): the composite form (a one-column GEMM, three segmented reductions, an exp and ``x * (ex / den)``) - except
+    on a slot's padded batch, which has no host-side node counts to expand and always takes the fused path."""
+    _FUSED_ATT_READOUT["enabled"] = bool(on)
+
+
+def fused_attention_readout() -> bool:
+    return _FUSED_ATT_READOUT["enabled"]
+
+
+def attention_readout_reference(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rp: ReducePlan) -> torch.Tensor:
+    """``attention_readout`` as tensor operations under autograd, in the dtype of ``x``: what a CPU tensor takes, and the oracle the kernels
+    are held against.  The row -> segment table is the plan's (``rp.row_segment()``), so it runs from a slot's device tables as well."""
+    seg = rp.row_segment().to(torch.int64)
+    S = rp.num_segs
+    gate = x @ weight.reshape(-1).to(x.dtype)
+    if bias is not None:
+        gate = gate + bias.reshape(()).to(x.dtype)
+    mx = torch.zeros(S, dtype=x.dtype, device=x.device).scatter_reduce(0, seg, gate.detach(), "amax", include_self=False)
+    ex = torch.exp(gate - mx.index_select(0, seg))
+    den = torch.zeros(S, dtype=x.dtype, device=x.device).index_add(0, seg, ex)
+    p = ex / den.index_select(0, seg)
+    return torch.zeros((S, x.shape[1]), dtype=x.dtype, device=x.device).index_add(0, seg, p.unsqueeze(1) * x)
+
+
+def _attn_readout_forward(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], rp: ReducePlan):
+    """Both forward stages, one C call (wsi_attn_readout_fwd).  Returns (out [S, D], gate [rows], stats [S, 2])."""
+    (n, D), dev = x.shape, x.device
+    out = torch.empty((rp.num_segs, D), dtype=torch.float32, device=dev)
+    gate = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n]
+    stats = torch.empty((rp.num_segs, 2), dtype=torch.float32, device=dev)
+    partial = torch.empty(max(rp.num_chunks * (D + 2), 1), dtype=torch.float32, device=dev)
+    N.check(N.load().wsi_attn_readout_fwd(N.ptr(x), x.stride(0), D, N.ptr(w), N.ptr(b), N.ptr(rp.chunk_row), rp.num_chunks, N.ptr(rp.seg_chunk),
+                                          rp.num_segs, N.ptr(partial), N.ptr(out), N.ptr(gate), N.ptr(stats), N.stream()), "wsi_attn_readout_fwd")
+    return out, gate, stats
+
+
+def _attn_readout_backward(g_out: torch.Tensor, out, gate, stats, x, w, rp: ReducePlan, want_gx: bool):
+    """delta, the row pass and the reduction of the chunks' g_w | g_b partials, one C call (wsi_attn_readout_bwd).  ``want_gx`` False: the
+    [rows, D] gradient is neither formed nor written (layer 0's input is the feature table).  Returns (g_x or None, g_wb [D + 1])."""
+    (n, D), dev = x.shape, x.device
+    g_x = torch.empty((n, D), dtype=torch.float32, device=dev) if want_gx else None
+    g_wb = torch.empty(D + 1, dtype=torch.float32, device=dev)
+    scratch = torch.empty(rp.num_segs + rp.num_chunks * (D + 1) + 1, dtype=torch.float32, device=dev)
+    N.check(N.load().wsi_attn_readout_bwd(N.ptr(g_out), N.ptr(out), N.ptr(gate), N.ptr(stats), N.ptr(x), x.stride(0), D, N.ptr(w),
+                                          N.ptr(rp.chunk_row), N.ptr(rp.chunk_seg), rp.num_chunks, rp.num_segs, N.ptr(scratch),
+                                          N.ptr(g_x), D, N.ptr(g_wb), N.stream()), "wsi_attn_readout_bwd")
+    return g_x, g_wb
+
+
+class _AttentionReadout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, rp: ReducePlan):
+        N.require_cuda(x, weight, bias)
+        _bag_rows("attention_readout", rp, x)
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        w = weight.reshape(-1).contiguous()
+        out, gate, stats = _attn_readout_forward(x, w, bias, rp)
+        ctx.rp = rp
+        ctx.weight_shape, ctx.has_bias = weight.shape, bias is not None
+        ctx.save_for_backward(x, w, out, gate, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, w, out, gate, stats = ctx.saved_tensors
+        g_x, g_wb = _attn_readout_backward(g_out.contiguous(), out, gate, stats, x, w, ctx.rp, ctx.needs_input_grad[0])
+        D = x.shape[1]
+        g_w = g_wb[:D].reshape(ctx.weight_shape) if ctx.needs_input_grad[1] else None
+        g_b = g_wb[D:].reshape(1) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+        return g_x, g_w, g_b, None
+
+
+def attention_readout(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], rp: ReducePlan) -> torch.Tensor:
+    """dgl's GlobalAttentionPooling with a one-column ``gate_nn`` over the segments of ``rp``, as one autograd node:
+    gate = x @ weight^T + bias;  p = softmax of gate over the rows of each segment;  out[s] = sum of p[r] * x[r] -> [num_segs, D].
+    ``x`` [rows, D] float32 (a row stride of its own is fine), ``weight`` [1, D] or [D], ``bias`` [1] or None; an empty segment gives 0.
+    On the GPU: wsi_attn_readout_fwd / _bwd (D <= 2048), reading only the plan's device tables - a slot's static ones included.  A CPU
+    tensor, or any other dtype, takes ``attention_readout_reference``."""
+    if x.dim() != 2 or weight.numel() != x.shape[1] or (bias is not None and bias.numel() != 1):
+        raise ValueError(f"attention_readout: x {tuple(x.shape)} needs a gate weight of {x.shape[-1]} entries and a bias of one, got "
+                         f"{tuple(weight.shape)} and {None if bias is None else tuple(bias.shape)}")
+    if not x.is_cuda or x.dtype != torch.float32:
+        return attention_readout_reference(x, weight, bias, rp)
+    return _AttentionReadout.apply(x, weight, bias, rp)
+
+
+# ------------------------------------------------------------------------------------------------
 # patch dropout of many bags and the fill of a padded bag slot (wsi_bag_dropout_select / wsi_bag_slot_fill: mil.dropout_patches, mil.BagSlot)
 # ------------------------------------------------------------------------------------------------
 BAG_DESC_WORDS = 8

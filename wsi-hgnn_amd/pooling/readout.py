@@ -48,6 +48,14 @@ def all_types_plan(graph, device):
     return cache[key]
 
 
+def slot_plan(graph):
+    """The static readout plan of a slot's padded batch (``data.BatchSlot`` installs it where ``all_types_plan`` looks); None for any other graph."""
+    for key, rp in graph.__dict__.get("_readout_plans", {}).items():
+        if key[0] == "all" and getattr(rp, "is_slot", False):
+            return rp
+    return None
+
+
 class _Readout(nn.Module):
     op = "mean"
 
@@ -64,7 +72,8 @@ class _Readout(nn.Module):
                 ntype = graph.ntypes[0]
         if x.dim() != 2:
             x = x.reshape(x.shape[0], -1)
-        return ops.segment_reduce(x, _rows_plan(graph, ntype, x.device, "one"), self.op)
+        sp = slot_plan(graph)             # a slot's padded batch of one node type: its static plan (the node counts live on the device)
+        return ops.segment_reduce(x, sp if sp is not None and len(graph.ntypes) == 1 else _rows_plan(graph, ntype, x.device, "one"), self.op)
 
 
 class AvgPooling(_Readout):
@@ -109,12 +118,29 @@ class GlobalAttentionPooling(nn.Module):
         super().__init__()
         self.gate_nn = gate_nn
 
+    def fused(self, graph) -> bool:
+        """Whether this graph takes ``ops.attention_readout`` (one pass, the plan's device tables only) instead of the composite form below:
+        after ``ops.set_fused_attention_readout(True)``, and always on a slot's padded batch - its node counts live on the device."""
+        return ops.fused_attention_readout() or slot_plan(graph) is not None
+
+    def forward_all_types(self, graph, xcat: torch.Tensor) -> torch.Tensor:
+        """The readout of every node type in one launch: ``xcat`` = the type-major concatenated node table -> [T * B, D], row t * B + b the
+        readout of (node type t, graph b) - what ``cat([self(graph, x_t, ntype=t) for t])`` gives, the one gate applied to every type."""
+        return ops.attention_readout(xcat, self.gate_nn.weight, self.gate_nn.bias, all_types_plan(graph, xcat.device))
+
     def forward(self, graph, feat, ntype: Optional[str] = None) -> torch.Tensor:
         if isinstance(feat, dict):
             x = feat[ntype if ntype is not None else next(iter(feat))]
         else:
             x = feat
         nt = ntype if ntype is not None else graph.ntypes[0]
+        if self.fused(graph):
+            if slot_plan(graph) is None:
+                return ops.attention_readout(x, self.gate_nn.weight, self.gate_nn.bias, _rows_plan(graph, nt, x.device, "one"))
+            if len(graph.ntypes) != 1:
+                raise RuntimeError("GlobalAttentionPooling: a slot's padded batch keeps one plan over all node types; call forward_all_types "
+                                   "on the concatenated node table")
+            return self.forward_all_types(graph, x)
         rp = _rows_plan(graph, nt, x.device, "one")
         bnn = graph.batch_num_nodes(nt).to(x.device)
         seg = torch.repeat_interleave(torch.arange(bnn.numel(), device=x.device), bnn, output_size=x.shape[0])

@@ -132,31 +132,41 @@ class CapturedStep:
 
 
 def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
-    """What a capture over batch slots needs of the model and the slots (``CapturedSlotStep``, ``CapturedSlotEval``): a HEAT trunk, or HGT over
-    slots that carry the per-relation-source plan, with a sum / mean / max readout; slots on the GPU fed by one loader.  Returns (slots as a
-    list, their loader, its device)."""
+    """What a capture over batch slots needs of the model and the slots (``CapturedSlotStep``, ``CapturedSlotEval``): a HEAT trunk, HGT over
+    slots that carry the per-relation-source plan, or GCN over homogeneous slots (one node type, one relation: the slot then keeps GraphConv's
+    degree norms current), with any readout ('att' runs from the slot's device tables, ``ops.attention_readout``); slots on the
+    GPU fed by one loader.  Returns (slots as a list, their loader, its device)."""
     from .data import BatchSlot
     from .models.heat_net import HEATTrunk
-    from .pooling import GlobalAttentionPooling
     slots = [slots] if isinstance(slots, BatchSlot) else list(slots)
     if not slots:
         raise ValueError(f"{who}: no slot")
     if len({bool(getattr(s, "type_mask", False)) for s in slots}) > 1:
         raise ValueError(f"{who}: slots with and without type_mask are mixed - the slots of one capture share one presence table (DESIGN 3.29): "
                          "build all of them with BatchSlot(..., type_mask=True), or none")
+    from .models.GCN import GCN
     from .models.HGT import HGT
-    if type(gnn) is HGT:
+    from .pooling import GlobalAttentionPooling
+    if type(gnn) is GCN:
+        if not all(s.degree_norms is not None for s in slots):
+            raise RuntimeError(f"{who}: GCN needs homogeneous slots - a loader of graph.to_homogeneous slides (one node type, one relation) - "
+                               f"or {verb} it eagerly")
+        if any(s.type_mask for s in slots):
+            raise ValueError(f"{who}: type_mask tells the heads of a heterogeneous model which node types a batch holds; GCN has one")
+    elif type(gnn) is HGT:
         # HGT's attention runs on the per-relation-source plan, which a slot re-derives on the device behind every fill (DESIGN 3.27) - when it
         # was built with the tables for it
         if not all(getattr(s, "per_relation_src", False) for s in slots):
             raise RuntimeError(f"{who}: HGT needs slots that carry the per-relation-source plan - build every slot with "
                                f"BatchSlot(loader, capacity, per_relation_src=True) - or {verb} it eagerly")
     elif not isinstance(gnn, HEATTrunk):
-        raise RuntimeError(f"{who}: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4, and HGT over slots built with "
-                           f"per_relation_src=True (HGT + ASAP and HeteroRGCN rebuild host-side structure per batch); {verb} it eagerly")
-    if isinstance(gnn.pools[0], GlobalAttentionPooling):
-        raise RuntimeError(f"{who}: the attention readout ('att') expands host-side node counts per batch; use a sum / mean / max readout "
-                           f"or {verb} eagerly")
+        raise RuntimeError(f"{who}: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4, HGT over slots built with "
+                           f"per_relation_src=True and GCN over homogeneous slots (HGT + ASAP and HeteroRGCN rebuild host-side structure per "
+                           f"batch); {verb} it eagerly")
+    if type(gnn) is not GCN and isinstance(gnn.pools[0], GlobalAttentionPooling) and gnn.pools[0].gate_nn.in_features != gnn.n_hid:
+        # (the reference sizes pools[0]'s gate for in_dim and applies it to hidden_dim-wide node states, models/HEATNet4.py:182-187 and :219)
+        raise RuntimeError(f"{who}: the attention readout's first gate reads {gnn.pools[0].gate_nn.in_features} columns but the node states it "
+                           f"pools have {gnn.n_hid}: 'att' needs in_dim == hidden_dim; use a sum / mean / max readout")
     loader = slots[0].loader
     if any(s.loader is not loader for s in slots):
         raise ValueError(f"{who}: all slots must be fed by one loader")
@@ -213,7 +223,8 @@ class CapturedSlotStep:
     first fitting batch of one slide) and the slot is captured before the next one warms up; train-mode dropout may be the HEAT and the HGT
     layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4, and HGT over
     slots built with ``per_relation_src=True`` (the slot re-derives HGT's plan on the device behind every fill), with a sum / mean /
-    max readout: the attention readout reads host-side node counts, HGT + ASAP and HeteroRGCN rebuild host-side structure - those are refused.
+    max readout or the attention readout ('att': one pass over the slot's readout tables); HGT + ASAP and HeteroRGCN rebuild
+    host-side structure - those are refused.
 
     Slots over a loader with a slot-compatible ``transform=`` (``data.slot_augment_spec``) are AUGMENTED: every ``step`` fills its slot with a fresh
     draw taken on the device (no read-back) in front of the replay, a batch no slot fits goes through ``loader._augmented``, and either way the
@@ -236,13 +247,14 @@ class CapturedSlotStep:
         self.metrics = metrics
         from .models.heat_layer import HEATLayer
         from .models.HGT import HGTLayer
+        from .models.GCN import GCN
         capture.require_capturable("CapturedSlotStep", optimizer)
         # slots with a presence table: one table for all of them, and the optimizer gated on it
         self.type_table = _share_type_table(self.slots)
         if self.type_table is not None:
             _gate_by_type("CapturedSlotStep", gnn, optimizer, self.type_table)
-        # (an HGTLayer draws counter-based whenever a seed base is active, which it is throughout this class's steps)
-        self.seed_base = capture.new_seed_word(dev) if capture.counter_dropout_only("CapturedSlotStep", gnn, (HEATLayer, HGTLayer)) else None
+        # (an HGTLayer, and GCN's inter-layer dropout, draw counter-based whenever a seed base is active, which it is throughout this class's steps)
+        self.seed_base = capture.new_seed_word(dev) if capture.counter_dropout_only("CapturedSlotStep", gnn, (HEATLayer, HGTLayer, GCN)) else None
         self.gnn, self.optimizer, self.loss_fcn = gnn, optimizer, loss_fcn
         self.slots, warmup_batches = capture.smallest_first(self.slots, lambda s: s.layout.N, warmup_batches)
         self.params = capture.trainable_params(optimizer)
@@ -316,7 +328,7 @@ class CapturedSlotEval:
     Slots built with ``type_mask=True`` (all or none) are rebound to one presence table and also take batches that lack a node
     type; nothing else changes.
 
-    Refused: what ``CapturedSlotStep`` refuses (HGT on slots without the per-relation plan, the ``att`` readout, slots off the GPU or over several loaders), and slots over a loader
+    Refused: what ``CapturedSlotStep`` refuses (HGT on slots without the per-relation plan, slots off the GPU or over several loaders), and slots over a loader
     with ``transform=`` - evaluation sees the stored slides (the reference augments ``type_ == "train"`` only, data.py:116-117).
     ``metrics=None`` builds an ``EpochMetrics`` for ``len(loader.items)`` rows."""
 
