@@ -1315,6 +1315,50 @@ int wsi_plan_by_relation(const int32_t* src, const int32_t* colptr, const int32_
                          int32_t max_src_rels, int32_t* src_rel, int32_t* colptr_rel, int32_t* csc_eid_rel, int32_t* csc_dst_rel,
                          int32_t* scratch, int64_t scratch_words, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Explanations scored against annotations (wsi_hgnn_amd/localization.py; entry points added to ABI 26): the reference's
+ * evaluator/explain_graphs.py:81-119 (patch labels), :179-184 (per-slide AUROC and its NaN-skipping mean) and :136-141 (the heat-map fill).
+ * A packed batch of B slides; every table is built by the host, which knows all sizes, and lives on the device:
+ *   tiles  int32 [T, 4], 16-byte aligned: (slide, first row, rows <= WSI_LOC_TILE, position of the first row within its slide); the tiles of a
+ *          slide are consecutive and cover its rows in order; a slide without rows has no tile.
+ *   slides int64 [B, 3]: (first scratch word of the slide, rows of the slide, first tile of the slide).
+ * No launch allocates, synchronises or reads back; all run on `stream`; identical calls give identical bits.
+ *
+ * wsi_loc_labels: labels int32 [N] <- 1 iff centre i (centres fp64 [N, 2]) lies STRICTLY inside at least one ring of its own slide, by the
+ *   even-odd rule; a centre on a ring's boundary (an edge or a vertex) is not inside that ring.  Rings are independent.  vertices fp64 [V, 2],
+ *   ring r = the vertices [ring_ptr[r], ring_ptr[r + 1]) closed from its last vertex to its first; ring_box fp64 [R, 4] = (min x, min y, max x,
+ *   max y) of every ring.  chunks int32 [K, 4], 16-byte aligned: (ring, first edge, edges <= chunk_edges, slide) - every ring cut into runs of
+ *   edges, a chunk never spanning two rings, the chunks of a ring consecutive, those of a slide [slide_chunk_ptr[s], slide_chunk_ptr[s + 1]);
+ *   max_slide_chunks = the most chunks a slide has (<= WSI_LOC_MAX_SLIDE_CHUNKS).  1 <= chunk_edges <= WSI_LOC_CHUNK_MAX.  All arithmetic is
+ *   fp64 without a division: edge (x0, y0) -> (x1, y1) against (x, y): o = (x1 - x0)(y - y0) - (x - x0)(y1 - y0); a crossing iff
+ *   (y0 > y) != (y1 > y) and (o > 0) == (y1 > y0); on the boundary iff o == 0 and (x, y) lies in the edge's closed bounding box.  A centre outside
+ *   a ring's closed box is outside the ring without an edge being read.  scratch: int32, slide s owning chunks(s) * rows(s) words from
+ *   slides[s][0] on (bit 0 = parity of a chunk's crossings, bit 1 = on its boundary); nothing at or beyond scratch_words is touched.  Two
+ *   launches, no atomics.
+ * wsi_loc_score: scores fp32 [N, C] (dense), labels int32 [N] (0 = negative, anything else positive).  Per slide s and column c, by exact
+ *   pair counting within the slide: counts int64 [B, C, 4] = (P, N, gt, eq) - positives, negatives, (positive, negative) pairs with s_pos >
+ *   s_neg, pairs with s_pos == s_neg; auc fp64 [B, C] = (2 gt + eq) / (2 P N), one division, NaN when P == 0 or N == 0; flags int32 [B, C] =
+ *   WSI_LOC_NONFINITE when a score of (s, c) is not finite, whose auc is NaN.  mean fp64 [C] = the mean over the slides whose auc is not NaN,
+ *   summed in the order of numpy's pairwise summation (= numpy.nanmean of the column, to the last bit); NaN when there is none.
+ *   partial: int64 [C * T * 5] of workspace.  Three launches, integer partials, no atomics.
+ * wsi_loc_owner: owner int32 [height, width] (the caller presets -1) <- max(owner, i) over the pixels x .. x + patch, y .. y + patch
+ *   (inclusive: patch + 1 pixels a side, clipped to the image) of every patch i at grid_xy int32 [n, 2] = (x, y): where patches overlap the
+ *   highest index owns the pixel, the result of drawing them in order.  One launch; the integer atomic maximum does not depend on the order. */
+#define WSI_LOC_TILE              256
+#define WSI_LOC_CHUNK_MAX         1024
+#define WSI_LOC_MAX_SLIDE_CHUNKS  65535
+#define WSI_LOC_MAX_COLUMNS       1024
+#define WSI_LOC_MAX_PATCH         4096
+#define WSI_LOC_NONFINITE         1
+int wsi_loc_labels(const double* centres, int32_t num_centres, const int32_t* tiles, int32_t num_tiles, const int64_t* slides,
+                   int32_t num_slides, const double* vertices, int64_t num_vertices, const int64_t* ring_ptr, const double* ring_box,
+                   int32_t num_rings, const int32_t* chunks, int32_t num_chunks, const int32_t* slide_chunk_ptr, int32_t max_slide_chunks,
+                   int32_t chunk_edges, int32_t* scratch, int64_t scratch_words, int32_t* labels, void* stream);
+int wsi_loc_score(const float* scores, int32_t num_rows, int32_t C, const int32_t* labels, const int32_t* tiles, int32_t num_tiles,
+                  const int64_t* slides, int32_t num_slides, int64_t* partial, int64_t* counts, int32_t* flags, double* auc, double* mean,
+                  void* stream);
+int wsi_loc_owner(const int32_t* grid_xy, int32_t num_patches, int32_t patch, int32_t height, int32_t width, int32_t* owner, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

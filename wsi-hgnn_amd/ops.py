@@ -3824,3 +3824,98 @@ def grid_write(index: GridIndex, mode: str, counts: torch.Tensor, offsets_incl: 
                                    N.ptr(index.set_max), N.ptr(edges), N.ptr(edges, edges.shape[1] * 8), N.ptr(node_type), N.ptr(node_tree),
                                    N.ptr(xy), N.ptr(index.flags), st), "wsi_grid_write")
     return edges, node_type, node_tree, xy
+
+
+# ------------------------------------------------------------------------------------------------
+# Explanations scored against annotations (csrc/localization.hip; the host layer is localization.patch_labels / score / heat_image)
+# ------------------------------------------------------------------------------------------------
+LOC_TILE = N.WSI_LOC_TILE
+LOC_CHUNK = 512                                   # edges per chunk unless the caller of localization.AnnotationBatch says otherwise
+LOC_CHUNK_MAX = N.WSI_LOC_CHUNK_MAX
+LOC_MAX_SCRATCH_WORDS = 1 << 28                   # 1 GiB of (chunk, centre) words: patch_labels refuses a batch that needs more
+
+
+def loc_tables(sizes: Sequence[int], chunks_per_slide: Optional[Sequence[int]] = None):
+    """The host tables of a packed batch (include/wsi_hgnn.h): ``tiles`` rows (slide, first row, rows, position within the slide), ``slides``
+    rows (first scratch word, rows, first tile) as flat lists, and the scratch words needed (0 without ``chunks_per_slide``)."""
+    tiles, slides, row, word = [], [], 0, 0
+    for s, n in enumerate(sizes):
+        slides += [word, n, len(tiles) // 4]
+        for at in range(0, n, LOC_TILE):
+            tiles += [s, row + at, min(LOC_TILE, n - at), at]
+        row += n
+        word += n * (chunks_per_slide[s] if chunks_per_slide is not None else 0)
+    return tiles, slides, word
+
+
+def _loc_device_tables(sizes, chunks_per_slide, device):
+    tiles, slides, words = loc_tables(sizes, chunks_per_slide)
+    t = host_to_device(tiles, torch.int32, device).reshape(len(tiles) // 4, 4)
+    s = host_to_device(slides, torch.int64, device).reshape(len(slides) // 3, 3)
+    return t, s, words
+
+
+def loc_labels(centres: torch.Tensor, sizes: Sequence[int], vertices: torch.Tensor, ring_ptr: torch.Tensor, ring_box: torch.Tensor,
+               chunks: torch.Tensor, slide_chunk_ptr: torch.Tensor, chunks_per_slide: Sequence[int], chunk_edges: int,
+               max_scratch_words: int = LOC_MAX_SCRATCH_WORDS) -> torch.Tensor:
+    """``wsi_loc_labels``: int32 [N], 1 where centre i (fp64 [N, 2], the slides one after the other, ``sizes`` rows each) lies strictly inside a
+    ring of its slide.  The ring tables are those of ``localization.AnnotationBatch`` on the device.  ``ValueError`` when the (chunk, centre)
+    scratch would exceed ``max_scratch_words``.  No read-back."""
+    N.require_cuda(centres, vertices, ring_ptr, ring_box, chunks, slide_chunk_ptr)
+    if centres.dim() != 2 or centres.shape[1] != 2 or centres.dtype != torch.float64:
+        raise ValueError(f"loc_labels: centres is an fp64 [N, 2] tensor, got {tuple(centres.shape)} {centres.dtype}")
+    sizes = [int(n) for n in sizes]
+    if len(sizes) != len(chunks_per_slide) or any(n < 0 for n in sizes) or sum(sizes) != centres.shape[0]:
+        raise ValueError(f"loc_labels: the sizes {sizes} do not match {centres.shape[0]} centres in {len(chunks_per_slide)} annotated slides")
+    if (vertices.dtype, ring_ptr.dtype, ring_box.dtype, chunks.dtype, slide_chunk_ptr.dtype) != (torch.float64, torch.int64, torch.float64,
+                                                                                                 torch.int32, torch.int32):
+        raise ValueError("loc_labels: vertices / ring_box fp64, ring_ptr int64, chunks / slide_chunk_ptr int32")
+    centres = centres.contiguous()
+    dev, n = centres.device, centres.shape[0]
+    tiles, slides, words = _loc_device_tables(sizes, chunks_per_slide, dev)
+    if words > max_scratch_words:
+        raise ValueError(f"loc_labels: {words} (chunk, centre) words of scratch exceed the limit of {max_scratch_words}; label fewer slides per call")
+    scratch = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    with _Timed("loc_labels"):
+        N.check(N.load().wsi_loc_labels(N.ptr(centres), n, N.ptr(tiles), tiles.shape[0], N.ptr(slides), len(sizes), N.ptr(vertices), vertices.shape[0],
+                                        N.ptr(ring_ptr), N.ptr(ring_box), ring_box.shape[0], N.ptr(chunks), chunks.shape[0], N.ptr(slide_chunk_ptr),
+                                        max(chunks_per_slide, default=0), int(chunk_edges), N.ptr(scratch), words, N.ptr(labels), N.stream()),
+                "wsi_loc_labels")
+    return labels
+
+
+def loc_score(scores: torch.Tensor, labels: torch.Tensor, sizes: Sequence[int]):
+    """``wsi_loc_score``: (auc fp64 [B, C], counts int64 [B, C, 4] = (P, N, gt, eq), flags int32 [B, C], mean fp64 [C]) of fp32 ``scores`` [N, C]
+    against int32 ``labels`` [N], per slide of ``sizes`` rows.  No read-back."""
+    N.require_cuda(scores, labels)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or labels.dtype != torch.int32 or labels.shape != scores.shape[:1]:
+        raise ValueError(f"loc_score: scores fp32 [N, C] and labels int32 [N], got {tuple(scores.shape)} {scores.dtype} / {tuple(labels.shape)} {labels.dtype}")
+    sizes = [int(n) for n in sizes]
+    if any(n < 0 for n in sizes) or sum(sizes) != scores.shape[0]:
+        raise ValueError(f"loc_score: the sizes {sizes} do not add up to the {scores.shape[0]} rows given")
+    scores, labels = scores.contiguous(), labels.contiguous()
+    dev, (n, C), B = scores.device, scores.shape, len(sizes)
+    tiles, slides, _ = _loc_device_tables(sizes, None, dev)
+    T = tiles.shape[0]
+    partial = torch.empty(max(C * T * 5, 1), dtype=torch.int64, device=dev)
+    counts = torch.empty((B, C, 4), dtype=torch.int64, device=dev)
+    flags = torch.empty((B, C), dtype=torch.int32, device=dev)
+    auc = torch.empty((B, C), dtype=torch.float64, device=dev)
+    mean = torch.empty(C, dtype=torch.float64, device=dev)
+    with _Timed("loc_score"):
+        N.check(N.load().wsi_loc_score(N.ptr(scores), n, C, N.ptr(labels), N.ptr(tiles), T, N.ptr(slides), B, N.ptr(partial), N.ptr(counts),
+                                       N.ptr(flags), N.ptr(auc), N.ptr(mean), N.stream()), "wsi_loc_score")
+    return auc, counts, flags, mean
+
+
+def loc_owner(grid_xy: torch.Tensor, patch: int, height: int, width: int) -> torch.Tensor:
+    """``wsi_loc_owner``: int32 [height, width], the highest patch index whose square x .. x + patch, y .. y + patch covers the pixel, -1 for none."""
+    N.require_cuda(grid_xy)
+    if grid_xy.dim() != 2 or grid_xy.shape[1] != 2 or grid_xy.dtype != torch.int32:
+        raise ValueError(f"loc_owner: grid_xy is an int32 [n, 2] tensor, got {tuple(grid_xy.shape)} {grid_xy.dtype}")
+    grid_xy = grid_xy.contiguous()
+    owner = torch.full((int(height), int(width)), -1, dtype=torch.int32, device=grid_xy.device)
+    with _Timed("loc_owner"):
+        N.check(N.load().wsi_loc_owner(N.ptr(grid_xy), grid_xy.shape[0], int(patch), int(height), int(width), N.ptr(owner), N.stream()), "wsi_loc_owner")
+    return owner
