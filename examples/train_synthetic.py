@@ -3,7 +3,7 @@
 (trainer/train_gnn.py:19-120), on synthetic WSI-shaped graphs:
 
   graph files (io.save_graph / load_graph)  ->  GraphBatchLoader (replaces GraphDataLoader + g.to(device))  ->
-  HEATNet4 (or --model HGT | GCN) + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate
+  HEATNet4 (or --model HGT | GCN | GIN) + Adam + CrossEntropy via trainer.train_one_step  ->  CheckpointStore (reference file layout)  ->  io.evaluate
   (--captured-eval: trainer.CapturedSlotEval, the epoch's metrics kept on the device).
 
 Run on one GPU:            python examples/train_synthetic.py --epochs 2          (--augment: the reference's train-time augmentation;
@@ -34,11 +34,12 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--dropout", type=float, default=0.2)
-    ap.add_argument("--model", choices=("HEATNet4", "HGT", "GCN"), default="HEATNet4",
+    ap.add_argument("--model", choices=("HEATNet4", "HGT", "GCN", "GIN"), default="HEATNet4",
                     help="HGT: the heterogeneous baseline (its layers' own dropout 0.2; --dropout is HEATNet4's and GCN's).  With --captured-slots / "
                          "--captured-eval its slots carry the per-relation-source plan, re-derived on the device behind every fill (DESIGN 3.27).  "
                          "GCN: the homogeneous baseline over graph.to_homogeneous slides with self-loops; its slots keep GraphConv's degree norms "
-                         "current on the device (DESIGN 3.30)")
+                         "current on the device (DESIGN 3.30).  GIN: the reference's GIN_COAD shape (2 layers, 2-layer MLPs, mean neighbours) over "
+                         "the same homogeneous slides, on the eager path only (DESIGN 3.32)")
     ap.add_argument("--pooling", choices=("mean", "sum", "max", "att"), default="mean",
                     help="graph_pooling_type.  att: the attention readout - in captured slots one pass over the slot's readout tables (DESIGN 3.30); "
                          "HEATNet4 and HGT apply its first gate, sized for --in-dim, to --hidden-wide states: they need --hidden == --in-dim")
@@ -90,10 +91,12 @@ def main(argv=None):
         td.barrier(device_ids=[local])
     mine = dist.shard(paths, rank, world)                                   # WSI-sharded data parallelism
     graphs = [io.load_graph(p) for p in mine]
-    if args.model == "GCN":                                                 # the reference's homogeneous data set: one node type, self-loops added
+    if args.model == "GIN" and (args.captured_slots or args.captured_eval):
+        raise SystemExit("--model GIN runs on the eager path only (no captured slots: DESIGN 3.32)")
+    if args.model in ("GCN", "GIN"):                                        # the reference's homogeneous data set: one node type, self-loops added
         from wsi_hgnn_amd import graph as graph_mod
         graphs = [graph_mod.to_homogeneous(g, add_self_loop=True) for g in graphs]
-    if args.pooling == "att" and args.model != "GCN" and args.hidden != args.in_dim:
+    if args.pooling == "att" and args.model not in ("GCN", "GIN") and args.hidden != args.in_dim:
         raise SystemExit("--pooling att with HEATNet4 / HGT: --hidden must equal --in-dim (the first gate is sized for the input features)")
     labels = [io.label_tumour_vs_normal(p, normal) for p in mine]
     loader = data.GraphBatchLoader(graphs, labels, args.batch, dev, shuffle=True, drop_last=False, seed=611 + rank,
@@ -110,6 +113,8 @@ def main(argv=None):
         gnn = models.HGT(nd, edge_dict, args.in_dim, args.hidden, 2, 2, 4, use_norm=True, graph_pooling_type=args.pooling).to(dev)
     elif args.model == "GCN":
         gnn = models.GCN(args.in_dim, args.hidden, 2, 2, torch.nn.functional.relu, args.dropout, args.pooling).to(dev)
+    elif args.model == "GIN":                                               # configs/COAD/GIN_COAD.yml: 2 layers, 2-layer MLPs, mean neighbours
+        gnn = models.GIN(args.in_dim, args.hidden, 2, 2, 2, args.dropout, args.pooling, "mean").to(dev)
     else:
         gnn = models.HEATNet4(args.in_dim, args.hidden, 2, 2, 4, nd, args.dropout, args.pooling).to(dev)
     if args.optimizer is None:

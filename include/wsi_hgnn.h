@@ -1359,6 +1359,39 @@ int wsi_loc_score(const float* scores, int32_t num_rows, int32_t C, const int32_
                   void* stream);
 int wsi_loc_owner(const int32_t* grid_xy, int32_t num_patches, int32_t patch, int32_t height, int32_t width, int32_t* owner, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * GINConv aggregation (an addition to ABI 26; dgl.nn.pytorch.GINConv as models/GIN.py:120-121 constructs it; ops.gin_aggregate).
+ *   neigh[w] = reduce_{e: u -> w} (s_e x[u]),  reduce = sum | mean | max (mode),  s_e = edge_s[e] (NULL: 1)
+ *   out[w]   = (1 + eps) x[w] + neigh[w] (+ bias)
+ * mean divides by the in-degree (the number of messages, not the sum of s_e); a node without in-edges has neigh = 0 under every mode; under
+ * max the scale multiplies the message BEFORE the maximum (the reference's update_all hijack, explainers/gnn_explainer.py:21-33).
+ * The graph: rowptr [n + 1] / src [E] = CSR by destination, colptr [n + 1] / csc_eid [E] (CSR position) / csc_dst [E] = the CSC of the same edge
+ * numbering by source (the [E] arrays may be NULL for a graph without edges: they are never read then).  fp32 throughout, row strides as arguments (>= D), any 1 <= D <= 1024 (beyond: WSI_ENOSYS), n == 0: WSI_OK without a
+ * launch.  eps is a DEVICE pointer to one float (the parameter's own storage): nothing about it crosses to the host.  A group of G lanes
+ * owns a row and 256 / G rows share a workgroup; 16-byte chunks when D % 4 == 0 and every pointer and stride allows, scalar otherwise; two
+ * or four edges' gathers are in flight per group into independent accumulators that are combined in one fixed order.  No atomics: identical
+ * calls give identical bits.
+ * wsi_gin_aggregate_fwd : out as above.  mode = WSI_GIN_MAX: arg int32 [n, D] (dense; may be NULL) <- the CSR position of the FIRST maximum of
+ *   every (row, column), -1 in rows without in-edges.  Other modes never touch arg.
+ * wsi_gin_aggregate_bwd : gx[u] = (1 + eps) g[u] + sum_{e: u -> w} s_e c_w m(w, c, e) g[w];  c_w = 1 / indeg(w) under mean (from rowptr), else 1;
+ *   m = [arg[w, c] == e] under max (arg required), else 1.
+ * wsi_gin_edge_grad     : g_s[e] = c_w sum_c m(w, c, e) g[w, c] x[src[e], c] for every CSR entry e (g_s [E], CSR order): the gradient of edge_s.
+ * wsi_gin_eps_grad      : g_eps[0] = sum_{w, c} g[w, c] x[w, c].  A fixed grid writes wsi_gin_eps_partials() floats into `partial`, a second
+ *   launch of one workgroup adds them in order.  (n == 0 launches nothing and leaves g_eps as it is.) */
+#define WSI_GIN_SUM   0
+#define WSI_GIN_MEAN  1
+#define WSI_GIN_MAX   2
+int wsi_gin_aggregate_fwd(const float* x, int64_t ldx, int32_t n, int32_t D, const int32_t* rowptr, const int32_t* src, const float* edge_s,
+                          const float* eps, int32_t mode, const float* bias, float* out, int64_t ldo, int32_t* arg, void* stream);
+int wsi_gin_aggregate_bwd(const float* g, int64_t ldg, int32_t n, int32_t D, const int32_t* rowptr, const int32_t* colptr,
+                          const int32_t* csc_eid, const int32_t* csc_dst, const float* edge_s, const float* eps, int32_t mode,
+                          const int32_t* arg, float* gx, int64_t ldgx, void* stream);
+int wsi_gin_edge_grad(const float* g, int64_t ldg, const float* x, int64_t ldx, int32_t n, int32_t D, const int32_t* rowptr,
+                      const int32_t* src, int32_t mode, const int32_t* arg, float* g_s, void* stream);
+int32_t wsi_gin_eps_partials(void);
+int wsi_gin_eps_grad(const float* g, int64_t ldg, const float* x, int64_t ldx, int32_t n, int32_t D, float* partial, float* g_eps,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from .HetRGCN import HeteroRGCN  # noqa: F401
 from .GCN import GCN  # noqa: F401
 from .GCN_NTPool import NTPoolGCN  # noqa: F401
 from .GAT import GAT  # noqa: F401
-
+from .GIN import GIN  # noqa: F401
 
 
 def from_config(config_gnn):
@@ -18,4 +18,4 @@ def from_config(config_gnn):
     return parse_gnn_model(config_gnn)
 
 
-__all__ = ["HEATNet2", "HEATNet4", "HGT", "HGTASAP", "HeteroRGCN", "GCN", "NTPoolGCN", "GAT", "from_config"]
+__all__ = ["HEATNet2", "HEATNet4", "HGT", "HGTASAP", "HeteroRGCN", "GCN", "NTPoolGCN", "GAT", "GIN", "from_config"]

@@ -2675,6 +2675,140 @@ def graph_conv_aggregate(z, bias, hplan, relu: bool, edge_scale: Optional[torch.
 
 
 # ------------------------------------------------------------------------------------------------
+# GINConv aggregation (csrc/gin.hip; models/GIN.py)
+# ------------------------------------------------------------------------------------------------
+GIN_MODES = {"sum": N.WSI_GIN_SUM, "mean": N.WSI_GIN_MEAN, "max": N.WSI_GIN_MAX}
+_gin_project_first = True
+
+
+def set_gin_project_first(on: bool) -> None:
+    """``models.GIN.GINConv`` with a sum or mean reducer and in_features > out_features runs the first Linear of its MLP BEFORE the
+    aggregation (both are linear: W((1 + eps) x + agg x) + b = (1 + eps) z + agg z + b with z = x W^T), which gathers out_features instead of
+    in_features columns per edge.  On by default; off: aggregate first, as the reference computes it.  Host state, no environment variable."""
+    global _gin_project_first
+    _gin_project_first = bool(on)
+
+
+def gin_project_first() -> bool:
+    return _gin_project_first
+
+
+def _gin_check(x: torch.Tensor, eps: torch.Tensor, plan, mode: str, bias, edge_scale) -> None:
+    if mode not in GIN_MODES:
+        raise ValueError(f"gin_aggregate: mode {mode!r} (one of {sorted(GIN_MODES)})")
+    if x.dim() != 2 or x.shape[0] != plan.num_nodes:
+        raise ValueError(f"gin_aggregate: x must be [{plan.num_nodes}, D] (one row per node of the plan), got {tuple(x.shape)}")
+    if eps.numel() != 1:
+        raise ValueError(f"gin_aggregate: eps holds one value, got {tuple(eps.shape)}")
+    if bias is not None and tuple(bias.shape) != (x.shape[1],):
+        raise ValueError(f"gin_aggregate: bias must be [{x.shape[1]}], got {tuple(bias.shape)}")
+    if edge_scale is not None:
+        _check_edge_scale("gin_aggregate", edge_scale, plan)
+
+
+def gin_aggregate_reference(x: torch.Tensor, eps: torch.Tensor, plan, mode: str, bias: Optional[torch.Tensor] = None,
+                            edge_scale: Optional[torch.Tensor] = None, return_arg: bool = False):
+    """``gin_aggregate`` with tensor operations, in x's dtype on x's device: what the kernels are held against, the CPU path and what
+    ``kernels=False`` runs.  ``max`` takes the FIRST CSR position among equal messages (``return_arg``: also the int32 [n, D] table of
+    those positions, -1 in rows without in-edges) and routes the gradient there."""
+    _gin_check(x, eps, plan, mode, bias, edge_scale)
+    n, D = x.shape
+    dev = x.device
+    rowptr = plan.rowptr.to(dev).long()
+    src = plan.src.to(dev).long()
+    deg = rowptr[1:n + 1] - rowptr[:n]
+    E = int(src.numel())
+    dst = torch.repeat_interleave(torch.arange(n, device=dev), deg, output_size=E)
+    msg = x[src]
+    if edge_scale is not None:
+        msg = msg * edge_scale.to(x.dtype).view(-1, 1)
+    arg = None
+    if mode == "max":
+        m = msg.detach()
+        idx = dst.view(-1, 1).expand(E, D)
+        top = torch.full((n, D), float("-inf"), dtype=x.dtype, device=dev).scatter_reduce(0, idx, m, "amax", include_self=True)
+        pos = torch.arange(E, device=dev).view(-1, 1).expand(E, D)
+        first = torch.full((n, D), E, dtype=torch.int64, device=dev).scatter_reduce(0, idx, torch.where(m == top[dst], pos, E), "amin", include_self=True)
+        chosen = (pos == first[dst]).to(x.dtype)
+        neigh = torch.zeros((n, D), dtype=x.dtype, device=dev).index_add(0, dst, msg * chosen)
+        arg = torch.where(first < E, first, -1).to(torch.int32)
+    else:
+        neigh = torch.zeros((n, D), dtype=x.dtype, device=dev).index_add(0, dst, msg)
+        if mode == "mean":
+            neigh = neigh / deg.clamp(min=1).to(x.dtype).view(-1, 1)
+    out = (1 + eps.to(x.dtype).reshape(())) * x + neigh
+    if bias is not None:
+        out = out + bias.to(x.dtype)
+    return (out, arg) if return_arg else out
+
+
+class _GinAggregate(torch.autograd.Function):
+    """out[w] = (1 + eps) x[w] + reduce_{e: u -> w}(s_e x[u]) (+ bias) on ``wsi_gin_aggregate_fwd``; the backward launches only what is asked
+    for: g_x (``wsi_gin_aggregate_bwd``), g_eps (``wsi_gin_eps_grad``, two launches), g_edge_scale (``wsi_gin_edge_grad``); g_bias = column sums.
+    eps is read by the kernels from its own device storage."""
+
+    @staticmethod
+    def forward(ctx, x, eps, bias, edge_scale, plan, mode: int):
+        N.require_cuda(x, eps, bias, edge_scale)
+        if eps.dtype != torch.float32:
+            raise ValueError("gin_aggregate: eps is an fp32 tensor on the device (the kernels read its storage)")
+        x = x if x.dtype == torch.float32 and x.is_contiguous() else x.to(torch.float32).contiguous()
+        e = eps.detach()
+        b = None if bias is None else bias.detach().to(torch.float32).contiguous()
+        s = None if edge_scale is None else edge_scale.detach().to(torch.float32).contiguous()
+        n, D = x.shape
+        need = ctx.needs_input_grad
+        out = torch.empty((n, D), dtype=torch.float32, device=x.device)
+        arg = torch.empty((n, D), dtype=torch.int32, device=x.device) if mode == N.WSI_GIN_MAX and (need[0] or need[3]) else None
+        N.check(N.load().wsi_gin_aggregate_fwd(N.ptr(x), D, n, D, N.ptr(plan.rowptr), N.ptr(plan.src), N.ptr(s), N.ptr(e), mode, N.ptr(b),
+                                               N.ptr(out), D, N.ptr(arg), N.stream()), "wsi_gin_aggregate_fwd")
+        ctx.plan, ctx.mode, ctx.shape = plan, mode, (n, D)
+        ctx.save_for_backward(x if (need[1] or need[3]) else None, e, s, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, e, s, arg = ctx.saved_tensors
+        plan, mode, (n, D) = ctx.plan, ctx.mode, ctx.shape
+        need = ctx.needs_input_grad
+        gy = gy if gy.dtype == torch.float32 and gy.is_contiguous() else gy.to(torch.float32).contiguous()
+        lib = N.load()
+        gx = ge = gb = gs = None
+        if need[0]:
+            gx = torch.empty((n, D), dtype=torch.float32, device=gy.device)
+            N.check(lib.wsi_gin_aggregate_bwd(N.ptr(gy), D, n, D, N.ptr(plan.rowptr), N.ptr(plan.colptr), N.ptr(plan.csc_eid), N.ptr(plan.csc_dst),
+                                              N.ptr(s), N.ptr(e), mode, N.ptr(arg), N.ptr(gx), D, N.stream()), "wsi_gin_aggregate_bwd")
+        if need[1]:
+            ge = torch.zeros_like(e)
+            if n > 0:
+                partial = torch.empty(lib.wsi_gin_eps_partials(), dtype=torch.float32, device=gy.device)
+                N.check(lib.wsi_gin_eps_grad(N.ptr(gy), D, N.ptr(x), D, n, D, N.ptr(partial), N.ptr(ge), N.stream()), "wsi_gin_eps_grad")
+        if need[2]:
+            gb = gy.sum(0)
+        if need[3]:
+            gs = torch.zeros_like(s)
+            N.check(lib.wsi_gin_edge_grad(N.ptr(gy), D, N.ptr(x), D, n, D, N.ptr(plan.rowptr), N.ptr(plan.src), mode, N.ptr(arg), N.ptr(gs),
+                                          N.stream()), "wsi_gin_edge_grad")
+        return gx, ge, gb, gs, None, None
+
+
+def gin_aggregate(x: torch.Tensor, eps: torch.Tensor, plan, mode: str, bias: Optional[torch.Tensor] = None,
+                  edge_scale: Optional[torch.Tensor] = None, kernels: Optional[bool] = None) -> torch.Tensor:
+    """DGL ``GINConv``'s aggregation as one autograd node: out[w] = (1 + eps) x[w] + reduce_{e: u -> w}(s_e x[u]) (+ bias), reduce = ``mode``
+    in sum | mean | max.  mean divides by the in-degree; a node without in-edges gets 0 from every reducer; under max the scale multiplies the
+    message before the maximum and the first CSR position wins a tie.  ``eps``: one fp32 value on x's device (a Parameter when it is learned:
+    it then receives a gradient; a buffer otherwise: nothing is launched for it).  ``plan``: anything with GraphPlan's rowptr / src / colptr /
+    csc_eid / csc_dst / num_nodes / num_edges (``HomoPlan``, ``EdgeCSR``).  ``edge_scale`` [E] in the plan's CSR order (None: the plain
+    aggregation) receives a gradient (GNNExplainer's sigmoid(edge_mask): ``graph.message_scale``).  g_x is skipped when x needs none.
+    ``kernels=False`` or a CPU tensor: ``gin_aggregate_reference``."""
+    _gin_check(x, eps, plan, mode, bias, edge_scale)
+    use = x.is_cuda if kernels is None else bool(kernels)
+    if not use:
+        return gin_aggregate_reference(x, eps, plan, mode, bias, edge_scale)
+    return _GinAggregate.apply(x, eps, bias, edge_scale, plan, GIN_MODES[mode])
+
+
+# ------------------------------------------------------------------------------------------------
 # ASAPPooling edge kernels (pooling/ASAP.py:158-179)
 # ------------------------------------------------------------------------------------------------
 class EdgeCSR:

@@ -1,6 +1,6 @@
 """Config -> objects, mirroring the reference's ``parser.py`` (same function names, same config keys, same error behaviour):
 
-  parse_gnn_model(cfg["GNN"])      parser.py:48-174   the in-scope branches: GAT, GCN, GCN_NTPool, HetRGCN, HGT, HEAT2, HEAT4
+  parse_gnn_model(cfg["GNN"])      parser.py:48-174   the in-scope branches: GAT, GCN, GCN_NTPool, GIN, HetRGCN, HGT, HEAT2, HEAT4
   parse_optimizer(cfg["optim"], m) parser.py:15-46    adagrad / adadelta / adam / anything else -> SGD (native=True: wsi_hgnn_amd.optim's)
   parse_loss(cfg["train"])         parser.py:176-184  BCE / CE
 
@@ -10,8 +10,10 @@ configs/COAD/HEAT*_staging.yml: orphan configs) raise its ``NotImple
 keys in the reference's order (num_layers, num_heads, num_out_heads, in_dim, hidden_dim, out_dim, feat_drop, attn_drop,
 negative_slope, graph_pooling_type) and always passes ``F.leaky_relu`` and ``residual=False``; a missing key raises
 ``MissingGATKey``, a ``KeyError`` with the reference's message that is also a ``NotImplementedError`` (the package refused GAT
-with the latter before it had the model).  ``GIN`` is the reference's other homogeneous baseline, outside the hot path: it
-raises ``NotImplementedError`` with a message that says so.  tests/test_parser.py replays the calls the REFERENCE function makes on its own configs (tests/golden/
+with the latter before it had the model).  ``GIN`` (:92-102) reads in_dim, hidden_dim, out_dim, num_layers, num_mlp_layers, feat_drop,
+graph_pooling_type and neighbor_pooling_type in that order and leaves ``learn_eps`` at the class default; a missing key raises
+``MissingGINKey``, built the same way (tests/golden/gin/reference_gin.json holds the reference's recorded calls on its two GIN
+configs).  tests/test_parser.py replays the calls the REFERENCE function makes on its own configs (tests/golden/
 reference_surface.json, produced by executing parser.py:48-174 with recording stand-ins for the classes).
 """
 from __future__ import annotations
@@ -19,7 +21,7 @@ from __future__ import annotations
 import torch.nn.functional as F
 from torch import nn, optim
 
-from .models import GAT, GCN, HGT, HEATNet2, HEATNet4, HeteroRGCN, NTPoolGCN
+from .models import GAT, GCN, GIN, HGT, HEATNet2, HEATNet4, HeteroRGCN, NTPoolGCN
 
 
 def parse_optimizer(config_optim, model, native=False):
@@ -54,19 +56,24 @@ class MissingGATKey(KeyError, NotImplementedError):
     as the package's earlier refusal of GAT was."""
 
 
-class _GATConfig:
-    def __init__(self, config_gnn):
-        self._cfg = config_gnn
+class MissingGINKey(KeyError, NotImplementedError):
+    """The same for the GIN branch: the reference's ``KeyError``, and the ``NotImplementedError`` with which the package refused GIN before it
+    had the model."""
+
+
+class _Config:
+    def __init__(self, config_gnn, missing):
+        self._cfg, self._missing = config_gnn, missing
 
     def __getitem__(self, key):
         try:
             return self._cfg[key]
         except KeyError:
-            raise MissingGATKey(key) from None
+            raise self._missing(key) from None
 
 
 def _parse_gat(config_gnn):
-    c = _GATConfig(config_gnn)                                      # parser.py:51-68, keys read in this order
+    c = _Config(config_gnn, MissingGATKey)                          # parser.py:51-68, keys read in this order
     n_layers = c["num_layers"]
     n_heads = c["num_heads"]
     n_out_heads = c["num_out_heads"]
@@ -81,7 +88,10 @@ def parse_gnn_model(config_gnn):
     if gnn_name == "GAT":
         return _parse_gat(config_gnn)
     if gnn_name == "GIN":
-        raise NotImplementedError(f"{gnn_name} is one of the reference's homogeneous baselines, outside the hot path this package rebuilds")
+        c = _Config(config_gnn, MissingGINKey)                      # parser.py:92-102, keys read in this order
+        return GIN(input_dim=c["in_dim"], hidden_dim=c["hidden_dim"], out_dim=c["out_dim"], num_layers=c["num_layers"],
+                   num_mlp_layers=c["num_mlp_layers"], final_dropout=c["feat_drop"], graph_pooling_type=c["graph_pooling_type"],
+                   neighbor_pooling_type=c["neighbor_pooling_type"])
     if gnn_name == "GCN":
         return GCN(in_dim=config_gnn["in_dim"], hidden_dim=config_gnn["hidden_dim"], out_dim=config_gnn["out_dim"],
                    n_layers=config_gnn["num_layers"], activation=F.relu, dropout=config_gnn["feat_drop"],
