@@ -384,7 +384,8 @@ int wsi_col_absmax(const float* x, int64_t ld, int32_t rows, int32_t cols, uint3
  * gradient in colsum_out (the WSI_GEMM_TN form, K <= 32 rows) - the backward of the classifier head behind the readout (head_2 / head_1 / head,
  * linears_prediction: models/HEATNet4.py:219,243-245; HEATNet2.py:183-190), whose levels are one row per graph.  Same group fields, same
  * fp32 fma chains in a fixed order as wsi_gemm_grouped takes for such shapes; n_dx + n_dw <= 16; epilogues: dx BIAS / ACCUMULATE / SCALE_GATE /
- * ADD_R / R_1MG, dw ACCUMULATE / SCALE_GATE.  WSI_ENOSYS when a group is not small (the caller then makes two wsi_gemm_grouped calls). */
+ * ADD_R / R_1MG, dw ACCUMULATE / SCALE_GATE.  WSI_ENOSYS when a group is not small (the caller then makes two wsi_gemm_grouped calls).  Groups
+ * are validated as wsi_gemm_grouped validates them (a negative dimension, ADD_R without R: WSI_EINVAL) before anything is launched. */
 int wsi_gemm_small_pair(const wsi_gemm_group_t* dx, int32_t n_dx, int32_t dx_epilogue,
                         const wsi_gemm_group_t* dw, int32_t n_dw, int32_t dw_epilogue, void* stream);
 

@@ -563,7 +563,7 @@ __device__ __forceinline__ void skinny_rows(const SkinnyDesc& G, int epilogue, i
             for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
             if (lane == 0) {
                 x = (x + bv) * gs;
-                if ((epilogue & WSI_EPI_ADD_R) && G.R) x = fmaf(G.R[(int64_t)m * G.ldr + n], r_scale, x);
+                if (epilogue & WSI_EPI_ADD_R) x = fmaf(G.R[(int64_t)m * G.ldr + n], r_scale, x);
                 float* c = G.C + (int64_t)m * G.ldc + n;
                 if (epilogue & WSI_EPI_ACCUMULATE) x += *c;
                 *c = x;
@@ -603,6 +603,7 @@ static bool launch_skinny(int32_t op, int32_t epilogue, const wsi_gemm_group_t* 
         if (s.K <= 0 || !s.A || !s.B || !s.C || s.c_absmax || s.b_chunk) return false;
         if (op == WSI_GEMM_TN ? (s.K > SKINNY_K) : (s.M > SKINNY_M)) return false;
         if (op != WSI_GEMM_TN && s.colsum_out) return false;
+        if ((epilogue & WSI_EPI_ADD_R) && !s.R) return false;      // nothing launched: the tiled path's validation refuses the call ("ADD_R needs R")
         const int64_t units = (op == WSI_GEMM_TN) ? (int64_t)s.M * s.N : s.N;
         if (units > (1 << 24)) return false;
         SkinnyDesc& d = P.g[P.ngroups++];
@@ -955,8 +956,10 @@ extern "C" int wsi_gemm_small_pair(const wsi_gemm_group_t* dx, int32_t n_dx, int
         const int32_t n = pass ? n_dw : n_dx;
         for (int i = 0; i < n; ++i) {
             const wsi_gemm_group_t& s = gs[i];
-            if (s.M <= 0 || s.N <= 0) continue;
+            if (s.M < 0 || s.N < 0) { set_error("gemm_small_pair: negative dimension in group %d", i); return WSI_EINVAL; }
+            if (s.M == 0 || s.N == 0) continue;
             if (s.K <= 0 || !s.A || !s.B || !s.C || s.c_absmax || s.b_chunk || (!pass && s.colsum_out)) { set_error("gemm_small_pair: group %d: unsupported field", i); return WSI_EINVAL; }
+            if (!pass && (dx_epilogue & WSI_EPI_ADD_R) && !s.R) { set_error("gemm_small_pair: ADD_R needs R (group %d)", i); return WSI_EINVAL; }
             if (pass ? (s.K > SKINNY_K) : (s.M > SKINNY_M)) { set_error("gemm_small_pair: group %d is not small (dX: M <= %d rows, dW: K <= %d rows)", i, SKINNY_M, SKINNY_K); return WSI_ENOSYS; }
             const int64_t units = pass ? (int64_t)s.M * s.N : s.N;
             if (units > (1 << 24)) { set_error("gemm_small_pair: group too wide"); return WSI_ENOSYS; }
