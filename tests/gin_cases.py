@@ -4,29 +4,21 @@ as closed-form tensor expressions that can replay a given ``arg`` - and a float6
 its running statistics included."""
 import torch
 
+from row_group_cases import row_cfg
+
 TOL = 1e-4                         # the project's norm: of the largest float64 entry of each tensor
 N_SINKS = 24                       # nodes without an out-edge
 N_EMPTY = 8                        # nodes without an in-edge
 MODES = ("sum", "mean", "max")
 
 
-# ---------------------------------------------------------------------------------------------------- dispatch rule (csrc/gin.hip: gi_cfg)
+# ---------------------------------------------------------------------------------------------------- dispatch rule (csrc/row_group.h)
 def gin_cfg(D, aligned):
-    """(VEC, G, NK) of a row width: 16-byte chunks when D % 4 == 0 and pointers and strides allow, a group of G lanes covering the chunks,
-    NK chunks per lane beyond 64 lanes."""
-    vec = 4 if (aligned and D % 4 == 0) else 1
-    chunks = D // vec
-    G = 4
-    while G < 64 and G < chunks:
-        G <<= 1
-    need = (chunks + G - 1) // G
-    nk = 1
-    while nk < need:
-        nk <<= 1
-    return vec, G, nk
+    """(VEC, G, NK) of a row width."""
+    return row_cfg(D, D, 1, aligned)
 
 
-# the instantiations csrc/gin.hip's GI_DISPATCH holds
+# the instantiations csrc/gin.hip holds: the narrow cases of csrc/row_group.h (ROW_GROUP_DISPATCH_NARROW)
 GIN_INSTANCES = [(4, 4, 1), (4, 8, 1), (4, 16, 1), (4, 32, 1), (4, 64, 1), (4, 64, 2), (4, 64, 4),
                  (1, 4, 1), (1, 8, 1), (1, 16, 1), (1, 32, 1), (1, 64, 1), (1, 64, 2), (1, 64, 4), (1, 64, 8), (1, 64, 16)]
 # widths that reach each of them through ops (contiguous, allocator-aligned tensors: VEC = 4 exactly when D % 4 == 0)

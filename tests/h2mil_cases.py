@@ -369,8 +369,8 @@ def ra_kernel_graph(seed=0):
 
 
 # ------------------------------------------------------------------------------------------------ the ra_attention dispatch sweep
-# One width per (VEC, G, NK) code of csrc/ra_attn.hip's RA_DISPATCH, none on a boundary of ra_cfg; the two last of each family share
-# a code (a partly filled and a full last chunk).  tests/test_h2mil.py restates ra_cfg and checks the coverage without a GPU.
+# One width per (VEC, G, NK) code of csrc/ra_attn.hip's dispatch (all cases of csrc/row_group.h), none on a boundary of row_cfg; the two last of
+# each family share a code (a partly filled and a full last chunk).  tests/test_h2mil.py restates row_cfg and checks the coverage without a GPU.
 RA_WIDTHS_BEFORE = (1, 3, 4, 32, 256, 260)                   # test_h2mil_kernels_gpu.py's widths before the sweep
 RA_SWEEP_VEC4 = (8, 24, 44, 100, 200, 388, 772, 1284, 2052, 4096)
 RA_SWEEP_VEC1 = (2, 7, 13, 30, 50, 101, 130, 257, 515, 1025, 2050, 4095)

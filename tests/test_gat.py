@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import row_group_cases as R
+
 # configs/COAD/GAT_Kimia_v2.yml, GAT_COAD.yml and GAT_Hover_v2.yml: their ``GNN:`` blocks, inlined
 KIMIA_V2 = {"name": "GAT", "negative_slope": 0.2, "num_layers": 2, "in_dim": 1024, "hidden_dim": 512, "residual": True, "in_drop": 0.2,
             "attn_drop": 0.2, "out_dim": 2, "num_heads": 4, "num_out_heads": 1, "feat_drop": 0.2, "graph_pooling_type": "mean"}
@@ -181,30 +183,17 @@ SDDMM_WIDTHS_ELSEWHERE = [1, 3, 40, 64, 512, 1000]            # test_gnn_explain
 
 
 def ga_cfg(H, D, vec4_ok=True):
-    """csrc/gat_attn.hip's ga_cfg and GA_DISPATCH's code, restated: VEC * 100000 + G * 100 + NK."""
-    vec = 4 if vec4_ok and D % 4 == 0 else 1
-    G = next(g for g in (4, 8, 16, 32, 64) if g == 64 or (g >= H * D // vec and g >= H))
-    NK = next(k for k in (1, 2, 4, 8, 16, 32, 64, 128) if k * G >= H * D // vec)
-    return vec * 100000 + G * 100 + NK
+    """The dispatch code of csrc/gat_attn.hip's call of row_cfg: VEC * 100000 + G * 100 + NK."""
+    return R.code(*R.row_cfg(H * D, D, H, vec4_ok))
 
 
 def ga_group(H, D, vec4_ok=True):
     return ga_cfg(H, D, vec4_ok) // 100 % 1000
 
 
-def _dispatch_codes():
-    import os
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "wsi-hgnn_amd", "csrc", "gat_attn.hip")) as f:
-        text = f.read()
-    table = text[text.index("#define GA_DISPATCH"):text.index("static int ga_check_shape")]
-    return sorted(int(c) for c in re.findall(r"case (\d+):", table))
-
-
 def test_sweeps_reach_every_dispatch_code():
-    codes = _dispatch_codes()
-    assert len(codes) == len(set(codes)) == 20
+    codes = R.family_codes("gat_attn.hip")
+    assert len(codes) == len(set(codes)) == 20 and codes == sorted(sum(R.case_lists(), []))
     reached = {}
     for H, D, _ in GA_SWEEP:
         reached.setdefault(ga_cfg(H, D), []).append((H, D))

@@ -1,5 +1,5 @@
-"""Every instantiation of csrc/gat_attn.hip's dispatch table against float64, on the GPU.  ``ga_cfg(H, D, vec4_ok)`` maps the head count,
-the per-head width and the alignment onto one of 20 (VEC, G, NK) codes; tests/test_gat.py restates the rule and holds the shape table
+"""Every instantiation of csrc/gat_attn.hip's dispatch table against float64, on the GPU.  ``row_cfg(H * D, D, H, vec4_ok)`` (csrc/row_group.h) maps the head
+count, the per-head width and the alignment onto one of 20 (VEC, G, NK) codes; tests/test_gat.py's ``ga_cfg`` restates it and holds the shape table
 (``GA_SWEEP``) that reaches each of them, and checks that without a GPU.  Here:
   1. the table through ``ops.gat_attention`` - scores, forward, every gradient - plain and with the explainer's per-edge message scale;
   2. graphs built for the kernels' edges, one per group size G, with n = 128 * (256 / G) + 37 nodes: the fixed-grid loops of
@@ -231,7 +231,7 @@ _CAPI_REF = {}                     # (H, D) -> (the kink decisions of the run it
 @pytest.mark.parametrize("variant", ["stride", "offset"])
 @pytest.mark.parametrize("H,D", [(4, 8), (4, 512)])
 def test_scalar_fallback_through_the_c_abi(graphs, H, D, variant):
-    """D % 4 == 0 but a row stride that is no multiple of 4, or pointers 4 bytes off a 16-byte boundary: ga_cfg must pick the scalar
+    """D % 4 == 0 but a row stride that is no multiple of 4, or pointers 4 bytes off a 16-byte boundary: row_cfg must pick the scalar
     family (codes 103201 and 106432 here, G = 32 and 64).  Same float64 reference and tolerance; with the strides of F + 1 the column
     after every row of out and g_ft must come back bit for bit - a 16-byte store on this path would overwrite it."""
     from wsi_hgnn_amd import _native as N

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import gin_cases as C
+import row_group_cases as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "gin")
@@ -228,9 +229,9 @@ def test_sweep_reaches_every_instantiation():
     assert all(C.gin_cfg(D, False)[0] == 1 and C.gin_cfg(D, False) in C.GIN_INSTANCES for D in range(1, 1025))
     assert all(C.gin_cfg(D, True) in C.GIN_INSTANCES for D in range(1, 1025))
     assert {C.gin_cfg(D, True)[1] for D in C.GIN_SWEEP} == {4, 8, 16, 32, 64}
-    src = open(os.path.join(ROOT, "wsi-hgnn_amd", "csrc", "gin.hip")).read()
-    table = {(int(v), int(g), int(k)) for g, v, k in re.findall(r"CALL\((\d+), (\d+), (\d+)\)", src)}
-    assert table == set(C.GIN_INSTANCES)
+    codes = R.family_codes("gin.hip")
+    assert codes == sorted(R.case_lists()[0]) and len(codes) == len(set(codes)) == 16
+    assert {(c // 100000, c // 100 % 1000, c % 100) for c in codes} == set(C.GIN_INSTANCES)
 
 
 def _lib():

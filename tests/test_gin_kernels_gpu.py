@@ -1,5 +1,5 @@
-"""Every instantiation of csrc/gin.hip's dispatch table against float64, on the GPU.  ``gin_cfg(D, aligned)`` maps a row width onto one of
-16 (VEC, G, NK) codes; tests/gin_cases.py restates the rule and holds the width table (``GIN_SWEEP``) that reaches each of them
+"""Every instantiation of csrc/gin.hip's dispatch table against float64, on the GPU.  ``row_cfg(D, D, 1, aligned)`` (csrc/row_group.h) maps a row width onto
+one of its 16 narrow (VEC, G, NK) codes; tests/gin_cases.py's ``gin_cfg`` restates it and holds the width table (``GIN_SWEEP``) that reaches each of them
 (tests/test_gin.py checks that without a GPU).  Here:
   1. the table x {sum, mean, max} x {plain, scaled} through ``ops.gin_aggregate``: forward, ``arg``, g_x, g_eps, g_bias, g_edge_scale;
   2. graphs built for the kernels' edges, one per group size G, with n = 128 * (256 / G) + 37 nodes (the last workgroup is partly empty, n is

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import h2mil_cases as C
+import row_group_cases as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "h2mil")
@@ -406,30 +407,18 @@ def test_new_entry_points_refuse_cpu_tensors_and_bad_arguments():
 # What tests/test_h2mil_kernels_gpu.py runs on the GPU is decided and checked here, without one: which kernel instantiation every width
 # reaches, what the sweep graph contains, and that every case leaves the kernels room (tests/h2mil_cases.py: ra_case).
 def ra_cfg(C, vec4_ok=True):
-    """csrc/ra_attn.hip's ra_cfg and RA_DISPATCH's code, restated: (VEC * 100000 + G * 100 + NK, the chunks per lane the width needs)."""
-    vec = 4 if vec4_ok and C % 4 == 0 else 1
-    chunks = C // vec
-    G = next(g for g in (4, 8, 16, 32, 64) if g == 64 or g >= chunks)
-    need = -(-chunks // G)
-    NK = next(k for k in (1, 2, 4, 8, 16, 32, 64, 128) if k >= need)
-    return vec * 100000 + G * 100 + NK, need
+    """The dispatch code of csrc/ra_attn.hip's call of row_cfg, and the chunks per lane the width needs."""
+    vec, G, NK = R.row_cfg(C, C, 1, vec4_ok)
+    return R.code(vec, G, NK), -(-(C // vec) // G)
 
 
 def ra_code(C, vec4_ok=True):
     return ra_cfg(C, vec4_ok)[0]
 
 
-def _ra_dispatch_codes():
-    import re
-    with open(os.path.join(ROOT, "wsi-hgnn_amd", "csrc", "ra_attn.hip")) as f:
-        text = f.read()
-    table = text[text.index("#define RA_DISPATCH"):text.index("static int ra_check_shape")]
-    return sorted(int(c) for c in re.findall(r"case (\d+):", table))
-
-
 def test_ra_sweep_reaches_every_dispatch_code():
-    codes = _ra_dispatch_codes()
-    assert len(codes) == len(set(codes)) == 20
+    codes = R.family_codes("ra_attn.hip")
+    assert len(codes) == len(set(codes)) == 20 and codes == sorted(sum(R.case_lists(), []))
     before = {ra_code(Cw) for Cw in C.RA_WIDTHS_BEFORE}
     assert before == {100401, 400401, 400801, 406401, 406402}
     assert all(Cw % 4 == 0 for Cw in C.RA_SWEEP_VEC4) and all(Cw % 4 for Cw in C.RA_SWEEP_VEC1) and len(set(C.RA_SWEEP)) == len(C.RA_SWEEP) == 22

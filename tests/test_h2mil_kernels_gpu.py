@@ -6,8 +6,8 @@ a wave's worth of edges for every group width), groups of one edge, destinations
 C in {1, 3, 4, 32, 256, 260}; out, g_ft, g_sc and g_bias are each checked.  ihpool_assign: segments of 1, 2, 63, 64, 65 and 300 members under
 1, 2, 7 and 65 seeds and an empty segment, inputs under the margin condition: clusters equal the float64 restatement exactly.
 
-The dispatch sweep.  ``ra_cfg(C, vec4_ok)`` maps the width and the alignment onto one of 20 (VEC, G, NK) codes; tests/test_h2mil.py restates
-the rule, holds the widths (h2mil_cases.RA_SWEEP) to the table and every case below to its conditions without a GPU.  Here, all on
+The dispatch sweep.  ``row_cfg(C, C, 1, vec4_ok)`` (csrc/row_group.h) maps the width and the alignment onto one of 20 (VEC, G, NK) codes;
+tests/test_h2mil.py's ``ra_cfg`` restates it, holds the widths (h2mil_cases.RA_SWEEP) to the table and every case below to its conditions without a GPU.  Here, all on
 h2mil_cases.ra_sweep_graph (n = 333, no multiple of any 256 / G; the destinations above; sources of out-degree >= 17, 65 and 200, so the
 stride loops of ra_bwd_score_kernel and ra_bwd_src_kernel over a source's edges go round again; 24 nodes without an out-edge, one without
 any edge, repeated edges, a self loop):

@@ -186,17 +186,6 @@ __global__ __launch_bounds__(AS_BLOCK) void asap_attend_bwd_src_kernel(const flo
     if (lane == 0) g_b[u] = gb;
 }
 
-#define AS_NV_DISPATCH(D, CALL)                  \
-    {                                            \
-        const int nv_ = ((D) + 63) / 64;         \
-        if (nv_ <= 1) { CALL(1); }               \
-        else if (nv_ <= 2) { CALL(2); }          \
-        else if (nv_ <= 4) { CALL(4); }          \
-        else if (nv_ <= 8) { CALL(8); }          \
-        else if (nv_ <= 16) { CALL(16); }        \
-        else { set_error("feature width %d > 1024 unsupported", (D)); return WSI_ENOSYS; } \
-    }
-
 }  // namespace wsi
 
 using namespace wsi;
@@ -428,7 +417,7 @@ extern "C" int wsi_csr_gather_max_fwd(const float* x, int64_t ldx, int32_t n, in
     const dim3 g((n + AS_WAVES - 1) / AS_WAVES), b(AS_BLOCK);
     hipStream_t st = (hipStream_t)stream;
 #define CALL(NV) hipLaunchKernelGGL((gather_max_fwd_kernel<NV>), g, b, 0, st, x, ldx, n, D, ptr, idx, out, ldo, arg)
-    AS_NV_DISPATCH(D, CALL)
+    WSI_NV_DISPATCH(D, CALL)
 #undef CALL
     return check_launch("csr_gather_max_fwd");
 }
@@ -442,7 +431,7 @@ extern "C" int wsi_csr_gather_max_bwd(const float* g_out, int64_t ldg, const int
     const dim3 g((n_src + AS_WAVES - 1) / AS_WAVES), b(AS_BLOCK);
     hipStream_t st = (hipStream_t)stream;
 #define CALL(NV) hipLaunchKernelGGL((gather_max_bwd_kernel<NV>), g, b, 0, st, g_out, ldg, arg, n_src, D, colptr, csc_eid, csc_dst, gx, ldgx)
-    AS_NV_DISPATCH(D, CALL)
+    WSI_NV_DISPATCH(D, CALL)
 #undef CALL
     return check_launch("csr_gather_max_bwd");
 }
@@ -456,7 +445,7 @@ extern "C" int wsi_asap_attend_fwd(const float* a, const float* b, const float* 
     const dim3 g((n + AS_WAVES - 1) / AS_WAVES), bl(AS_BLOCK);
     hipStream_t st = (hipStream_t)stream;
 #define CALL(NV) hipLaunchKernelGGL((asap_attend_fwd_kernel<NV>), g, bl, 0, st, a, b, x, ldx, n, D, ptr, idx, negative_slope, score, out, ldo)
-    AS_NV_DISPATCH(D, CALL)
+    WSI_NV_DISPATCH(D, CALL)
 #undef CALL
     return check_launch("asap_attend_fwd");
 }
@@ -473,7 +462,7 @@ extern "C" int wsi_asap_attend_bwd(const float* a, const float* b, const float* 
     hipStream_t st = (hipStream_t)stream;
 #define CALL(NV) { hipLaunchKernelGGL((asap_attend_bwd_dst_kernel<NV>), g, bl, 0, st, a, b, x, ldx, n, D, ptr, idx, negative_slope, score, g_out, ldg, gpre, g_a); \
                    hipLaunchKernelGGL((asap_attend_bwd_src_kernel<NV>), g, bl, 0, st, g_out, ldg, n, D, colptr, csc_eid, csc_dst, score, (const float*)gpre, gx, ldgx, g_b); }
-    AS_NV_DISPATCH(D, CALL)
+    WSI_NV_DISPATCH(D, CALL)
 #undef CALL
     return check_launch("asap_attend_bwd");
 }

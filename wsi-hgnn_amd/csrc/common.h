@@ -31,6 +31,18 @@ inline int check_launch(const char* what) {
     return WSI_OK;
 }
 
+// CALL(NV) for a row of D floats held by one wave, NV (a power of two, <= 16) per lane: column c = lane + 64 * i
+#define WSI_NV_DISPATCH(D, CALL)                 \
+    {                                            \
+        const int nv_ = ((D) + 63) / 64;         \
+        if (nv_ <= 1) { CALL(1); }               \
+        else if (nv_ <= 2) { CALL(2); }          \
+        else if (nv_ <= 4) { CALL(4); }          \
+        else if (nv_ <= 8) { CALL(8); }          \
+        else if (nv_ <= 16) { CALL(16); }        \
+        else { set_error("feature width %d > 1024 unsupported", (D)); return WSI_ENOSYS; } \
+    }
+
 // ---------------------------------------------------------------- cross-lane (DPP within a 16-lane row)
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float x) {

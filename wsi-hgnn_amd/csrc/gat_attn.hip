@@ -2,12 +2,11 @@
 //   el | er   = per-head sums of ft * attn_l / attn_r                                   -> wsi_gat_scores
 //   s_e       = leaky_relu(el[u] + er[v]);  a = edge_softmax over v's in-edges (no epsilon);  a = attn_drop(a)
 //   rst[v]    = act(sum_e a_e * ft[u] + bias)                                            -> wsi_gat_attn_fwd
-// Layout: a GROUP of G lanes (4 <= G <= 64, a power of two) owns one row; lane l of the group holds the VEC-wide column
-// chunks c = VEC * (l + G * k), k < NK.  Narrow rows (H*D = 32: G = 8) put 64 / G rows in one wave instead of leaving most
-// lanes idle.  A chunk never straddles two heads (VEC = 4 only when D % 4 == 0), so the head of every chunk is a per-lane
-// constant; the per-(edge, head) softmax weight is computed by lane h of the group and fetched by the others with one
-// ds_bpermute per chunk.  The forward keeps only out and the per-(node, head) log-sum-exp (as max | log of the shifted sum): the
-// backward recomputes every a_e from el, er and lse.  Every reduction runs in a fixed order (no atomics): results are bit-reproducible.
+// Layout: the row groups of row_group.h, a row being the H heads side by side (G >= H).  A chunk never straddles two heads (VEC = 4
+// only when D % 4 == 0), so the head of every chunk is a per-lane constant; the per-(edge, head) softmax weight is computed by lane h
+// of the group and fetched by the others with one ds_bpermute per chunk.  The forward keeps only out and the per-(node, head)
+// log-sum-exp (as max | log of the shifted sum): the backward recomputes every a_e from el, er and lse.  Every reduction runs in a fixed
+// order (no atomics): results are bit-reproducible.
 // Backward (source-major, the shape of the HEAT backward):
 //   prep  g_rst = g_out * act'(out), column partials of g_rst (bias gradient)
 //   A     CSC by source u: g_ft[u] = sum a_e g_rst[w];  g_a[e,h] = g_rst[w]_h . ft[u]_h   (one g_rst row gather per edge)
@@ -20,7 +19,7 @@
 //   A     g_ft[u] = sum a~_e s_e g_rst[w];  g_a keeps the RAW dot r[e,h] = g_rst[w]_h . ft[u]_h
 //   B     d loss / d a~ = s_e r[e,h];  g_scale[e] = sum_h a~_{e,h} r[e,h]  (the lane that owns edge e adds its heads in order)
 // The unscaled instantiations contain none of it.
-#include "common.h"
+#include "row_group.h"
 #include <math.h>
 
 namespace wsi {
@@ -38,7 +37,7 @@ template <int G, int VEC, int NK>
 __device__ __forceinline__ void chunk_heads(int gl, int F, int D, int (&hk)[NK], bool (&ok)[NK]) {
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        const int c = VEC * (gl + G * k);
+        const int c = chunk_col<G, VEC>(gl, k);
         ok[k] = c < F;
         hk[k] = ok[k] ? c / D : 0;
     }
@@ -63,8 +62,7 @@ template <int G, int VEC, int NK>
 __global__ __launch_bounds__(GA_BLOCK) void gat_scores_kernel(const float* __restrict__ ft, int64_t ldf, int n, int H, int D,
                                                               const float* __restrict__ attn_l, const float* __restrict__ attn_r,
                                                               float* __restrict__ eler) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1);
-    const int row = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), row = group_row<G, GA_BLOCK>();
     if (row >= n) return;                                        // group-uniform
     const int F = H * D;
     int hk[NK];
@@ -75,7 +73,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_scores_kernel(const float* __res
     for (int k = 0; k < NK; ++k) {
         pl[k] = pr[k] = 0.f;
         if (ok[k]) {
-            const int c = VEC * (gl + G * k);
+            const int c = chunk_col<G, VEC>(gl, k);
             float x[VEC], al[VEC], ar[VEC];
             load_vec<VEC>(x, ft + (int64_t)row * ldf + c);
             load_vec<VEC>(al, attn_l + c);
@@ -138,8 +136,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
                                                            const float* __restrict__ bias, int act, float act_slope,
                                                            float* __restrict__ out, int64_t ldo, float* __restrict__ lse,
                                                            const float* __restrict__ escale) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
-    const int gi = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), gbase = group_base<G>(), gi = group_row<G, GA_BLOCK>();
     if (gi >= n) return;                                         // group-uniform
     const int v = order ? order[gi] : gi;
     const int F = H * D;
@@ -152,10 +149,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
     const float my_m = softmax_lse<G>(eler, src, v, e0, e1, H, gl, slope, my_ls);
     const float my_er = gl < H ? eler[(int64_t)v * 2 * H + H + gl] : 0.f;
     float acc[NK][VEC];
-#pragma unroll
-    for (int k = 0; k < NK; ++k)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) acc[k][j] = 0.f;
+    zero_chunks(acc);
     for (int e = e0; e < e1; ++e) {
         const int u = src[e];
         float a = 0.f;
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
             const float ak = __shfl(a, gbase + hk[k]);
             if (ok[k]) {
                 float x[VEC];
-                load_vec<VEC>(x, row + VEC * (gl + G * k));
+                load_vec<VEC>(x, row + chunk_col<G, VEC>(gl, k));
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) acc[k][j] = fmaf(ak, x[j], acc[k][j]);
             }
@@ -178,7 +172,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_fwd_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         if (ok[k]) {
-            const int c = VEC * (gl + G * k);
+            const int c = chunk_col<G, VEC>(gl, k);
             float b[VEC];
             if (bias) load_vec<VEC>(b, bias + c);
 #pragma unroll
@@ -197,10 +191,9 @@ template <int G, int VEC, int NK>
 __global__ __launch_bounds__(GA_BLOCK) void gat_act_bwd_kernel(const float* __restrict__ g_out, int64_t ldg, const float* __restrict__ out, int64_t ldo,
                                                                int n, int F, int act, float act_slope, float* __restrict__ g_rst,
                                                                float* __restrict__ part) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1);
-    const int gid = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), gid = group_row<G, GA_BLOCK>();
     const int groups = GA_PART_BLOCKS * (GA_BLOCK / G);
-    float s[NK][VEC];
+    float s[NK][VEC];                                            // (zero_chunks and chunk_col change this kernel's code: spelled out)
 #pragma unroll
     for (int k = 0; k < NK; ++k)
 #pragma unroll
@@ -240,8 +233,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
                                                                const int32_t* __restrict__ order, float slope, GatDrop dr,
                                                                float* __restrict__ g_ft, int64_t ldgf, float* __restrict__ g_a,
                                                                const float* __restrict__ escale) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
-    const int gi = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), gbase = group_base<G>(), gi = group_row<G, GA_BLOCK>();
     if (gi >= n) return;
     const int u = order ? order[gi] : gi;
     const int F = H * D;
@@ -254,7 +246,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
     for (int k = 0; k < NK; ++k) {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { fu[k][j] = 0.f; acc[k][j] = 0.f; }
-        if (ok[k]) load_vec<VEC>(fu[k], ft + (int64_t)u * ldf + VEC * (gl + G * k));
+        if (ok[k]) load_vec<VEC>(fu[k], ft + (int64_t)u * ldf + chunk_col<G, VEC>(gl, k));
     }
     const float my_el = gl < H ? eler[(int64_t)u * 2 * H + gl] : 0.f;
     const int j0 = colptr[u], j1 = colptr[u + 1];
@@ -274,7 +266,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
             p[k] = 0.f;
             if (ok[k]) {
                 float g[VEC];
-                load_vec<VEC>(g, row + VEC * (gl + G * k));
+                load_vec<VEC>(g, row + chunk_col<G, VEC>(gl, k));
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) { acc[k][j] = fmaf(ak, g[j], acc[k][j]); p[k] = fmaf(g[j], fu[k][j], p[k]); }
             }
@@ -284,7 +276,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_src_kernel(const float* __re
     }
 #pragma unroll
     for (int k = 0; k < NK; ++k)
-        if (ok[k]) store_vec<VEC>(g_ft + (int64_t)u * ldgf + VEC * (gl + G * k), acc[k]);
+        if (ok[k]) store_vec<VEC>(g_ft + (int64_t)u * ldgf + chunk_col<G, VEC>(gl, k), acc[k]);
 }
 
 // pass B: one 16-lane group per destination v; in place g_a (d loss / d a~, SCALED: the raw dot r) -> d loss / d a -> g_pre (d loss / d pre-activation score);
@@ -295,8 +287,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_dst_kernel(const float* __re
                                                                float slope, GatDrop dr, float* __restrict__ g_a, float* __restrict__ g_er,
                                                                const float* __restrict__ escale, float* __restrict__ g_scale) {
     constexpr int G = GA_B_LANES;
-    const int gl = threadIdx.x & (G - 1);
-    const int v = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), v = group_row<G, GA_BLOCK>();
     if (v >= n) return;
     const uint32_t seed = dr.seed + (dr.seed_base ? *dr.seed_base : 0u);
     const int e0 = rowptr[v], e1 = rowptr[v + 1];
@@ -341,8 +332,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_attn_kernel(const float* __r
                                                                 const int32_t* __restrict__ colptr, const int32_t* __restrict__ csc_eid,
                                                                 const float* __restrict__ attn_l, const float* __restrict__ attn_r,
                                                                 float* __restrict__ g_ft, int64_t ldgf, float* __restrict__ part) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
-    const int gid = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), gbase = group_base<G>(), gid = group_row<G, GA_BLOCK>();
     const int groups = GA_PART_BLOCKS * (GA_BLOCK / G);
     const int F = H * D;
     int hk[NK];
@@ -354,8 +344,8 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_attn_kernel(const float* __r
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { al[k][j] = ar[k][j] = pl[k][j] = pr[k][j] = 0.f; }
         if (ok[k]) {
-            load_vec<VEC>(al[k], attn_l + VEC * (gl + G * k));
-            load_vec<VEC>(ar[k], attn_r + VEC * (gl + G * k));
+            load_vec<VEC>(al[k], attn_l + chunk_col<G, VEC>(gl, k));
+            load_vec<VEC>(ar[k], attn_r + chunk_col<G, VEC>(gl, k));
         }
     }
     for (int u = gid; u < n; u += groups) {
@@ -372,7 +362,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_attn_kernel(const float* __r
         for (int k = 0; k < NK; ++k) {
             const float lk = __shfl(gel, gbase + hk[k]), rk = __shfl(ger, gbase + hk[k]);
             if (ok[k]) {
-                const int c = VEC * (gl + G * k);
+                const int c = chunk_col<G, VEC>(gl, k);
                 float x[VEC], g[VEC];
                 load_vec<VEC>(x, ft + (int64_t)u * ldf + c);
                 load_vec<VEC>(g, g_ft + (int64_t)u * ldgf + c);
@@ -389,7 +379,7 @@ __global__ __launch_bounds__(GA_BLOCK) void gat_bwd_attn_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         if (ok[k]) {
-            const int c = VEC * (gl + G * k);
+            const int c = chunk_col<G, VEC>(gl, k);
             store_vec<VEC>(part + (int64_t)gid * 3 * F + c, pl[k]);
             store_vec<VEC>(part + (int64_t)gid * 3 * F + F + c, pr[k]);
         }
@@ -415,13 +405,12 @@ __global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __rest
                                                              const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src,
                                                              const float* __restrict__ iscale, const float* __restrict__ oscale,
                                                              const float* __restrict__ relu_ref, int64_t ldref, float* __restrict__ g_w) {
-    const int gl = threadIdx.x & (G - 1);
-    const int w = (int)blockIdx.x * (GA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), w = group_row<G, GA_BLOCK>();
     if (w >= n) return;                                          // group-uniform
     float gw[NK][VEC];
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        const int c = VEC * (gl + G * k);
+        const int c = chunk_col<G, VEC>(gl, k);
 #pragma unroll
         for (int j = 0; j < VEC; ++j) gw[k][j] = 0.f;
         if (c < D) {
@@ -442,7 +431,7 @@ __global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __rest
         float p = 0.f;
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
-            const int c = VEC * (gl + G * k);
+            const int c = chunk_col<G, VEC>(gl, k);
             if (c < D) {
                 float v[VEC];
                 load_vec<VEC>(v, row + c);
@@ -456,40 +445,6 @@ __global__ __launch_bounds__(GA_BLOCK) void sddmm_dot_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-struct GaCfg {
-    int G, VEC, NK;
-};
-
-// VEC = 4 when every row and pointer allows 16-byte accesses and a chunk stays inside one head; G = the smallest power of two
-// (>= 4, >= H, <= 64) that covers the row's chunks, NK the power of two of chunks per lane that covers the rest
-static GaCfg ga_cfg(int H, int D, bool vec4_ok) {
-    GaCfg c;
-    const int F = H * D;
-    c.VEC = (vec4_ok && D % 4 == 0) ? 4 : 1;
-    const int chunks = F / c.VEC;
-    c.G = 4;
-    while (c.G < 64 && (c.G < chunks || c.G < H)) c.G <<= 1;
-    const int need = (chunks + c.G - 1) / c.G;
-    c.NK = 1;
-    while (c.NK < need) c.NK <<= 1;
-    return c;
-}
-
-#define GA_DISPATCH(cfg, CALL)                                                                                              \
-    do {                                                                                                                   \
-        const int code_ = (cfg).VEC * 100000 + (cfg).G * 100 + (cfg).NK;                                                   \
-        switch (code_) {                                                                                                   \
-            case 400401: CALL(4, 4, 1); break;   case 400801: CALL(8, 4, 1); break;   case 401601: CALL(16, 4, 1); break;  \
-            case 403201: CALL(32, 4, 1); break;  case 406401: CALL(64, 4, 1); break;  case 406402: CALL(64, 4, 2); break;  \
-            case 406404: CALL(64, 4, 4); break;  case 406408: CALL(64, 4, 8); break;  case 406416: CALL(64, 4, 16); break; \
-            case 100401: CALL(4, 1, 1); break;   case 100801: CALL(8, 1, 1); break;   case 101601: CALL(16, 1, 1); break;  \
-            case 103201: CALL(32, 1, 1); break;  case 106401: CALL(64, 1, 1); break;  case 106402: CALL(64, 1, 2); break;  \
-            case 106404: CALL(64, 1, 4); break;  case 106408: CALL(64, 1, 8); break;  case 106416: CALL(64, 1, 16); break; \
-            case 106432: CALL(64, 1, 32); break; case 106464: CALL(64, 1, 64); break;                                      \
-            default: set_error("gat: no kernel for G=%d VEC=%d NK=%d", (cfg).G, (cfg).VEC, (cfg).NK); return WSI_ENOSYS;   \
-        }                                                                                                                  \
-    } while (0)
-
 static int ga_check_shape(const char* what, int32_t n, int32_t H, int32_t D) {
     if (n < 0 || H < 1 || H > GA_MAX_HEADS || D < 1 || (int64_t)H * D > GA_MAX_WIDTH) {
         set_error("%s: bad shape n=%d heads=%d D=%d (1 <= heads <= %d, 1 <= heads*D <= %d)", what, n, H, D, GA_MAX_HEADS, GA_MAX_WIDTH);
@@ -510,11 +465,11 @@ extern "C" int wsi_gat_scores(const float* ft, int64_t ldf, int32_t n, int32_t H
     if (ldf < (int64_t)H * D) { set_error("gat_scores: ldf=%lld < heads*D", (long long)ldf); return WSI_EINVAL; }
     if (!ft || !attn_l || !attn_r || !eler) { set_error("gat_scores: null pointer"); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
-    const GaCfg cfg = ga_cfg(H, D, ldf % 4 == 0 && aligned16(ft) && aligned16(attn_l) && aligned16(attn_r));
+    const RowCfg cfg = row_cfg(H * D, D, H, ldf % 4 == 0 && aligned16(ft) && aligned16(attn_l) && aligned16(attn_r));
     hipStream_t st = (hipStream_t)stream;
     const int per = GA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_scores_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, n, H, D, attn_l, attn_r, eler)
-    GA_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_ALL("gat", cfg, CALL);
 #undef CALL
     return check_launch("gat_scores");
 }
@@ -532,13 +487,13 @@ static int ga_fwd(const char* what, const float* ft, int64_t ldf, const float* e
     if (drop_threshold > 65535u) { set_error("%s: drop_threshold %u > 65535", what, drop_threshold); return WSI_EINVAL; }
     if (!ft || !eler || !rowptr || !src || !out || !lse || (SCALED && !edge_scale)) { set_error("%s: null pointer", what); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
-    const GaCfg cfg = ga_cfg(H, D, ldf % 4 == 0 && ldo % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(bias));
+    const RowCfg cfg = row_cfg(H * D, D, H, ldf % 4 == 0 && ldo % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(bias));
     const GatDrop dr{drop_seed, drop_threshold, drop_seed_base, drop_scale};
     hipStream_t st = (hipStream_t)stream;
     const int per = GA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_fwd_kernel<G_, V_, K_, SCALED>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, eler, n, H, D, \
                                             rowptr, src, order_dst, negative_slope, dr, bias, (int)activation, act_slope, out, ldo, lse, edge_scale)
-    GA_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_ALL("gat", cfg, CALL);
 #undef CALL
     return check_launch(what);
 }
@@ -563,8 +518,8 @@ extern "C" int wsi_gat_attn_fwd_scaled(const float* ft, int64_t ldf, const float
 // workspace: g_rst [n, F] (only when activation != none), g_a / g_pre [E, H], g_er [n, H], column partials [rows(G), 3F]
 static int64_t ga_ws_layout(int32_t n, int32_t E, int32_t H, int32_t D, int32_t activation, int64_t* off) {
     const int64_t F = (int64_t)H * D;
-    const GaCfg cfg = ga_cfg(H, D, true);
-    const GaCfg cfg1 = ga_cfg(H, D, false);
+    const RowCfg cfg = row_cfg(H * D, D, H, true);
+    const RowCfg cfg1 = row_cfg(H * D, D, H, false);
     const int rows = ga_part_rows(cfg.G < cfg1.G ? cfg.G : cfg1.G);       // enough for either vector width
     auto up = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
     off[0] = 0;
@@ -615,24 +570,24 @@ static int ga_bwd(const char* what, const float* ft, int64_t ldf, const float* e
     const int64_t ldr = activation ? F : ldg;
     const bool v4 = ldf % 4 == 0 && ldo % 4 == 0 && ldg % 4 == 0 && ldgf % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(g_out) &&
                     aligned16(g_ft) && aligned16(attn_l) && aligned16(attn_r);
-    const GaCfg cfg = ga_cfg(H, D, v4);
+    const RowCfg cfg = row_cfg(H * D, D, H, v4);
     const GatDrop dr{drop_seed, drop_threshold, drop_seed_base, drop_scale};
     const int per = GA_BLOCK / cfg.G;
     if (n > 0) {
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_act_bwd_kernel<G_, V_, K_>), dim3(GA_PART_BLOCKS), dim3(GA_BLOCK), 0, st, g_out, ldg, out, ldo, n, (int)F, \
                                             (int)activation, act_slope, g_rst, part)
-        GA_DISPATCH(cfg, CALL);
+        ROW_GROUP_DISPATCH_ALL("gat", cfg, CALL);
 #undef CALL
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_bwd_src_kernel<G_, V_, K_, SCALED>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, ft, ldf, eler, lse, rst, ldr, \
                                             n, H, D, colptr, csc_eid, csc_dst, order_src, negative_slope, dr, g_ft, ldgf, g_a, edge_scale)
-        GA_DISPATCH(cfg, CALL);
+        ROW_GROUP_DISPATCH_ALL("gat", cfg, CALL);
 #undef CALL
         constexpr int per_b = GA_BLOCK / GA_B_LANES;
         hipLaunchKernelGGL((gat_bwd_dst_kernel<SCALED>), dim3((n + per_b - 1) / per_b), dim3(GA_BLOCK), 0, st, eler, lse, n, H, rowptr, src, negative_slope, dr, g_a, g_er,
                            edge_scale, g_edge_scale);
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gat_bwd_attn_kernel<G_, V_, K_>), dim3(GA_PART_BLOCKS), dim3(GA_BLOCK), 0, st, ft, ldf, (const float*)g_a, \
                                             (const float*)g_er, n, H, D, colptr, csc_eid, attn_l, attn_r, g_ft, ldgf, part)
-        GA_DISPATCH(cfg, CALL);
+        ROW_GROUP_DISPATCH_ALL("gat", cfg, CALL);
 #undef CALL
         hipLaunchKernelGGL(gat_colsum_kernel, dim3((unsigned)((3 * F + 255) / 256)), dim3(256), 0, st, (const float*)part, ga_part_rows(cfg.G), (int)F,
                            g_attn_l, g_attn_r, g_bias);
@@ -676,12 +631,12 @@ extern "C" int wsi_sddmm_dot(const float* g, int64_t ldg, const float* x, int64_
     if (ldg < D || ldx < D || (relu_ref && ldref < D)) { set_error("sddmm_dot: row stride below D"); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
     if (!g || !x || !rowptr || !src || !g_w) { set_error("sddmm_dot: null pointer"); return WSI_EINVAL; }
-    const GaCfg cfg = ga_cfg(1, D, ldg % 4 == 0 && ldx % 4 == 0 && (!relu_ref || ldref % 4 == 0) && aligned16(g) && aligned16(x) && aligned16(relu_ref));
+    const RowCfg cfg = row_cfg(D, D, 1, ldg % 4 == 0 && ldx % 4 == 0 && (!relu_ref || ldref % 4 == 0) && aligned16(g) && aligned16(x) && aligned16(relu_ref));
     hipStream_t st = (hipStream_t)stream;
     const int per = GA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((sddmm_dot_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(GA_BLOCK), 0, st, g, ldg, x, ldx, n, D, \
                                             rowptr, src, iscale, oscale, relu_ref, ldref, g_w)
-    GA_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_ALL("gat", cfg, CALL);
 #undef CALL
     return check_launch("sddmm_dot");
 }

@@ -1,19 +1,17 @@
 // GINConv aggregation (DGL GINConv(apply_func, aggregator_type, init_eps, learn_eps), models/GIN.py:120-121) for gfx950.  Contracts:
 // include/wsi_hgnn.h.
 //   neigh[w] = reduce_{e: u -> w} (s_e x[u]),  reduce = sum | mean | max;   out[w] = (1 + eps) x[w] + neigh[w] (+ bias)
-// Layout (that of gat_attn.hip with one head): a GROUP of G lanes (4 <= G <= 64, a power of two) owns one row, lane l of the group holds
-// the VEC-wide column chunks c = VEC * (l + G * k), k < NK, and 256 / G rows share a workgroup, so narrow rows leave no lane idle.  The
-// edge loop is unrolled over U edges (4 when a lane holds at most 8 floats of a row, else 2): the U gathers are issued before the first
-// is used, and every edge position i mod U has an accumulator of its own.  The accumulators are combined in the order 0 .. U-1, so every
-// sum has one order and the first-position rule of the maximum survives: each accumulator sees its positions in rising order and keeps the
-// first of equal values, and of equal values in two accumulators the lower position wins.
+// Layout: the row groups of row_group.h.  The edge loop is unrolled over U edges (4 when a lane holds at most 8 floats of a row, else 2):
+// the U gathers are issued before the first is used, and every edge position i mod U has an accumulator of its own.  The accumulators
+// are combined in the order 0 .. U-1, so every sum has one order and the first-position rule of the maximum survives: each accumulator
+// sees its positions in rising order and keeps the first of equal values, and of equal values in two accumulators the lower position wins.
 //   forward   CSR by destination w:  the messages of w's in-edges; max also writes arg[w, c] = the CSR position of the first maximum
 //   backward  CSC by source u:       gx[u] = (1 + eps) g[u] + sum_{e: u -> w} s_e c_w [arg[w, c] == e] g[w]   (c_w = 1 / indeg(w) under mean)
 //   edge grad CSR by destination w:  g_s[e] = c_w sum_c [arg[w, c] == e] g[w, c] x[u, c]; g[w] (and arg[w]) stay in the group's registers
 //   eps grad  sum of g * x over the whole table: a fixed grid of partials, then ONE workgroup adds them in order (two launches)
 // MODE and SCALED (edge_s != NULL) are compile-time switches: the unscaled sum contains neither a multiply nor a compare.  eps is read
 // through a device pointer.  No atomics anywhere: identical calls give identical bits.
-#include "common.h"
+#include "row_group.h"
 #include <math.h>
 
 namespace wsi {
@@ -51,12 +49,11 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_fwd_kernel(const float* __restri
                                                            int32_t* __restrict__ arg) {
     constexpr int U = gi_unroll<VEC, NK>::U;
     constexpr bool ISMAX = MODE == WSI_GIN_MAX;
-    const int gl = threadIdx.x & (G - 1);
-    const int w = (int)blockIdx.x * (GI_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), w = group_row<G, GI_BLOCK>();
     if (w >= n) return;                                          // group-uniform
     bool ok[NK];
 #pragma unroll
-    for (int k = 0; k < NK; ++k) ok[k] = VEC * (gl + G * k) < D;
+    for (int k = 0; k < NK; ++k) ok[k] = chunk_col<G, VEC>(gl, k) < D;
     const int e0 = rowptr[w], e1 = rowptr[w + 1];
     float acc[U][NK][VEC];
     int best[ISMAX ? U : 1][NK][VEC];
@@ -81,7 +78,7 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_fwd_kernel(const float* __restri
             for (int k = 0; k < NK; ++k) {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) v[i][k][j] = 0.f;
-                if (live && ok[k]) load_vec<VEC>(v[i][k], row + VEC * (gl + G * k));
+                if (live && ok[k]) load_vec<VEC>(v[i][k], row + chunk_col<G, VEC>(gl, k));
             }
         }
 #pragma unroll
@@ -108,7 +105,7 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_fwd_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         if (ok[k]) {
-            const int c = VEC * (gl + G * k);
+            const int c = chunk_col<G, VEC>(gl, k);
             float xw[VEC], b[VEC], o[VEC];
             int a[VEC];
             load_vec<VEC>(xw, x + (int64_t)w * ldx + c);
@@ -150,19 +147,14 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_bwd_kernel(const float* __restri
     constexpr int U = gi_unroll<VEC, NK>::U;
     constexpr bool ISMAX = MODE == WSI_GIN_MAX;
     constexpr bool COEF = SCALED || MODE == WSI_GIN_MEAN;
-    const int gl = threadIdx.x & (G - 1);
-    const int u = (int)blockIdx.x * (GI_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), u = group_row<G, GI_BLOCK>();
     if (u >= n) return;                                          // group-uniform
     bool ok[NK];
 #pragma unroll
-    for (int k = 0; k < NK; ++k) ok[k] = VEC * (gl + G * k) < D;
+    for (int k = 0; k < NK; ++k) ok[k] = chunk_col<G, VEC>(gl, k) < D;
     float acc[U][NK][VEC];
 #pragma unroll
-    for (int i = 0; i < U; ++i)
-#pragma unroll
-        for (int k = 0; k < NK; ++k)
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) acc[i][k][j] = 0.f;
+    for (int i = 0; i < U; ++i) zero_chunks(acc[i]);
     const int j0 = colptr[u], j1 = colptr[u + 1];
     for (int jj = j0; jj < j1; jj += U) {
         float v[U][NK][VEC], cf[U];
@@ -183,8 +175,8 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_bwd_kernel(const float* __restri
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) v[i][k][j] = 0.f;
                 if (live && ok[k]) {
-                    load_vec<VEC>(v[i][k], row + VEC * (gl + G * k));
-                    if constexpr (ISMAX) load_ivec<VEC>(a[i][k], arg + (int64_t)w * D + VEC * (gl + G * k));
+                    load_vec<VEC>(v[i][k], row + chunk_col<G, VEC>(gl, k));
+                    if constexpr (ISMAX) load_ivec<VEC>(a[i][k], arg + (int64_t)w * D + chunk_col<G, VEC>(gl, k));
                 }
             }
         }
@@ -210,7 +202,7 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_bwd_kernel(const float* __restri
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
         if (ok[k]) {
-            const int c = VEC * (gl + G * k);
+            const int c = chunk_col<G, VEC>(gl, k);
             float gu[VEC], o[VEC];
             load_vec<VEC>(gu, g + (int64_t)u * ldg + c);
 #pragma unroll
@@ -232,15 +224,14 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_edge_grad_kernel(const float* __
                                                                  const int32_t* __restrict__ src, bool mean, const int32_t* __restrict__ arg,
                                                                  float* __restrict__ g_s) {
     constexpr int U = gi_unroll<VEC, NK>::U;
-    const int gl = threadIdx.x & (G - 1);
-    const int w = (int)blockIdx.x * (GI_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), w = group_row<G, GI_BLOCK>();
     if (w >= n) return;                                          // group-uniform
     bool ok[NK];
     float gw[NK][VEC];
     int aw[ISMAX ? NK : 1][VEC];
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        const int c = VEC * (gl + G * k);
+        const int c = chunk_col<G, VEC>(gl, k);
         ok[k] = c < D;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) gw[k][j] = 0.f;
@@ -262,7 +253,7 @@ __global__ __launch_bounds__(GI_BLOCK) void gin_edge_grad_kernel(const float* __
             for (int k = 0; k < NK; ++k) {
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) v[i][k][j] = 0.f;
-                if (live && ok[k]) load_vec<VEC>(v[i][k], row + VEC * (gl + G * k));
+                if (live && ok[k]) load_vec<VEC>(v[i][k], row + chunk_col<G, VEC>(gl, k));
             }
         }
 #pragma unroll
@@ -323,38 +314,6 @@ __global__ __launch_bounds__(GI_EPS_BLOCKS) void gin_eps_finish_kernel(const flo
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-struct GiCfg {
-    int G, VEC, NK;
-};
-
-// VEC = 4 when D % 4 == 0 and every pointer and stride allows 16-byte accesses; G = the smallest power of two (>= 4, <= 64) that covers the
-// row's chunks, NK the power of two of chunks per lane that covers the rest  (tests/test_gin.py restates this rule)
-static GiCfg gi_cfg(int D, bool vec4_ok) {
-    GiCfg c;
-    c.VEC = (vec4_ok && D % 4 == 0) ? 4 : 1;
-    const int chunks = D / c.VEC;
-    c.G = 4;
-    while (c.G < 64 && c.G < chunks) c.G <<= 1;
-    const int need = (chunks + c.G - 1) / c.G;
-    c.NK = 1;
-    while (c.NK < need) c.NK <<= 1;
-    return c;
-}
-
-#define GI_DISPATCH(cfg, CALL)                                                                                              \
-    do {                                                                                                                   \
-        const int code_ = (cfg).VEC * 100000 + (cfg).G * 100 + (cfg).NK;                                                   \
-        switch (code_) {                                                                                                   \
-            case 400401: CALL(4, 4, 1); break;   case 400801: CALL(8, 4, 1); break;   case 401601: CALL(16, 4, 1); break;  \
-            case 403201: CALL(32, 4, 1); break;  case 406401: CALL(64, 4, 1); break;  case 406402: CALL(64, 4, 2); break;  \
-            case 406404: CALL(64, 4, 4); break;                                                                            \
-            case 100401: CALL(4, 1, 1); break;   case 100801: CALL(8, 1, 1); break;   case 101601: CALL(16, 1, 1); break;  \
-            case 103201: CALL(32, 1, 1); break;  case 106401: CALL(64, 1, 1); break;  case 106402: CALL(64, 1, 2); break;  \
-            case 106404: CALL(64, 1, 4); break;  case 106408: CALL(64, 1, 8); break;  case 106416: CALL(64, 1, 16); break; \
-            default: set_error("gin: no kernel for G=%d VEC=%d NK=%d", (cfg).G, (cfg).VEC, (cfg).NK); return WSI_ENOSYS;   \
-        }                                                                                                                  \
-    } while (0)
-
 static int gi_check_shape(const char* what, int32_t n, int32_t D) {
     if (n < 0 || D <= 0) { set_error("%s: bad shape n=%d D=%d", what, n, D); return WSI_EINVAL; }
     if (D > GI_MAX_WIDTH) { set_error("%s: D=%d > %d", what, D, GI_MAX_WIDTH); return WSI_ENOSYS; }
@@ -371,34 +330,34 @@ static int gi_check_mode(const char* what, int32_t mode) {
 
 template <int MODE, bool SCALED>
 static int gi_fwd(const float* x, int64_t ldx, int32_t n, int32_t D, const int32_t* rowptr, const int32_t* src, const float* edge_s,
-                  const float* eps, const float* bias, float* out, int64_t ldo, int32_t* arg, GiCfg cfg, hipStream_t st) {
+                  const float* eps, const float* bias, float* out, int64_t ldo, int32_t* arg, RowCfg cfg, hipStream_t st) {
     const int per = GI_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gin_fwd_kernel<G_, V_, K_, MODE, SCALED>), dim3((n + per - 1) / per), dim3(GI_BLOCK), 0, st, x, ldx, \
                                             (int)n, (int)D, rowptr, src, edge_s, eps, bias, out, ldo, arg)
-    GI_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_NARROW("gin", cfg, CALL);
 #undef CALL
     return WSI_OK;
 }
 
 template <int MODE, bool SCALED>
 static int gi_bwd(const float* g, int64_t ldg, int32_t n, int32_t D, const int32_t* rowptr, const int32_t* colptr, const int32_t* csc_eid,
-                  const int32_t* csc_dst, const float* edge_s, const float* eps, const int32_t* arg, float* gx, int64_t ldgx, GiCfg cfg,
+                  const int32_t* csc_dst, const float* edge_s, const float* eps, const int32_t* arg, float* gx, int64_t ldgx, RowCfg cfg,
                   hipStream_t st) {
     const int per = GI_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gin_bwd_kernel<G_, V_, K_, MODE, SCALED>), dim3((n + per - 1) / per), dim3(GI_BLOCK), 0, st, g, ldg, \
                                             (int)n, (int)D, rowptr, colptr, csc_eid, csc_dst, edge_s, eps, arg, gx, ldgx)
-    GI_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_NARROW("gin", cfg, CALL);
 #undef CALL
     return WSI_OK;
 }
 
 template <bool ISMAX>
 static int gi_edge(const float* g, int64_t ldg, const float* x, int64_t ldx, int32_t n, int32_t D, const int32_t* rowptr, const int32_t* src,
-                   bool mean, const int32_t* arg, float* g_s, GiCfg cfg, hipStream_t st) {
+                   bool mean, const int32_t* arg, float* g_s, RowCfg cfg, hipStream_t st) {
     const int per = GI_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((gin_edge_grad_kernel<G_, V_, K_, ISMAX>), dim3((n + per - 1) / per), dim3(GI_BLOCK), 0, st, g, ldg, \
                                             x, ldx, (int)n, (int)D, rowptr, src, mean, arg, g_s)
-    GI_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_NARROW("gin", cfg, CALL);
 #undef CALL
     return WSI_OK;
 }
@@ -424,7 +383,7 @@ extern "C" int wsi_gin_aggregate_fwd(const float* x, int64_t ldx, int32_t n, int
     if (n == 0) return WSI_OK;
     if (!x || !rowptr || !eps || !out) { set_error("gin_aggregate_fwd: null pointer"); return WSI_EINVAL; }     // (src: NULL for a graph without edges, never read then)
     const bool has_arg = mode == WSI_GIN_MAX && arg;
-    const GiCfg cfg = gi_cfg(D, vec_ok(x, ldx) && vec_ok(out, ldo) && aligned16(bias) && (!has_arg || aligned16(arg)));
+    const RowCfg cfg = row_cfg(D, D, 1, vec_ok(x, ldx) && vec_ok(out, ldo) && aligned16(bias) && (!has_arg || aligned16(arg)));
     int rc;
     GI_BY_MODE(rc, gi_fwd, mode, edge_s != nullptr, x, ldx, n, D, rowptr, src, edge_s, eps, bias, out, ldo, arg, cfg, (hipStream_t)stream);
     if (rc) return rc;
@@ -442,7 +401,7 @@ extern "C" int wsi_gin_aggregate_bwd(const float* g, int64_t ldg, int32_t n, int
         set_error("gin_aggregate_bwd: null pointer");
         return WSI_EINVAL;
     }
-    const GiCfg cfg = gi_cfg(D, vec_ok(g, ldg) && vec_ok(gx, ldgx) && (mode != WSI_GIN_MAX || aligned16(arg)));
+    const RowCfg cfg = row_cfg(D, D, 1, vec_ok(g, ldg) && vec_ok(gx, ldgx) && (mode != WSI_GIN_MAX || aligned16(arg)));
     int rc;
     GI_BY_MODE(rc, gi_bwd, mode, edge_s != nullptr, g, ldg, n, D, rowptr, colptr, csc_eid, csc_dst, edge_s, eps, arg, gx, ldgx, cfg,
                (hipStream_t)stream);
@@ -457,7 +416,7 @@ extern "C" int wsi_gin_edge_grad(const float* g, int64_t ldg, const float* x, in
     if (ldg < D || ldx < D) { set_error("gin_edge_grad: row stride below D"); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
     if (!g || !x || !rowptr || (mode == WSI_GIN_MAX && !arg)) { set_error("gin_edge_grad: null pointer"); return WSI_EINVAL; }   // (src, g_s: NULL without edges)
-    const GiCfg cfg = gi_cfg(D, vec_ok(g, ldg) && vec_ok(x, ldx) && (mode != WSI_GIN_MAX || aligned16(arg)));
+    const RowCfg cfg = row_cfg(D, D, 1, vec_ok(g, ldg) && vec_ok(x, ldx) && (mode != WSI_GIN_MAX || aligned16(arg)));
     const int rc = mode == WSI_GIN_MAX ? gi_edge<true>(g, ldg, x, ldx, n, D, rowptr, src, false, arg, g_s, cfg, (hipStream_t)stream)
                                        : gi_edge<false>(g, ldg, x, ldx, n, D, rowptr, src, mode == WSI_GIN_MEAN, arg, g_s, cfg, (hipStream_t)stream);
     if (rc) return rc;

@@ -5,10 +5,9 @@
 //   out[v]  = sum_e beta_{v,t(e)} a_e ft[u_e] + bias                    (a node without in-edges: out = bias)
 // Both softmaxes subtract the maximum.  torch_geometric's softmax adds 1e-16 to a denominator that is >= 1 after that subtraction,
 // below float64 resolution relative to 1: the kernels omit it.
-// Layout (gat_attn.hip's, one head): a GROUP of G lanes (4 <= G <= 64, a power of two) owns one row, lane l of the group holds the
-// VEC-wide column chunks c = VEC * (l + G * k), k < NK.  The per-edge weight is a scalar: the lanes of a group compute the weights of
-// G consecutive edges at once (one edge each) and hand them round with ds_bpermute while the row gathers run, so an edge costs one
-// expf per group, not one per lane.  The forward keeps out and, per (node, type), max | log of the shifted sum | group count | beta
+// Layout: the row groups of row_group.h.  The per-edge weight is a scalar: the lanes of a group compute the weights of G consecutive
+// edges at once (one edge each) and hand them round with ds_bpermute while the row gathers run, so an edge costs one expf per group,
+// not one per lane.  The forward keeps out and, per (node, type), max | log of the shifted sum | group count | beta
 // (stat [n, 3, 4]); the backward recomputes every edge weight from sc and stat.  Nothing is stored per edge by the forward.
 // Backward (no atomics, every sum in one fixed order):
 //   A  CSC by source u (t(e) is a constant of u): g_ft[u] = sum_e beta a_e g_out[v_e];  r_e = <g_out[v_e], ft[u]>
@@ -16,7 +15,7 @@
 //      g_q_vt = beta_vt (A_vt - sum_t' beta_vt' A_vt') lrelu';  gq[v, t] = g_q_vt / count;  g_pr[v] = sum_t g_q_vt
 //   C  by source u, 16 lanes: g_el[u] = sum g_pre_e;  g_pl[u] = sum gq[v_e, t(u)]
 //   bias: column partials of g_out over a fixed grid, added in order.
-#include "common.h"
+#include "row_group.h"
 #include <math.h>
 
 namespace wsi {
@@ -34,8 +33,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
                                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ src, float slope,
                                                           const float* __restrict__ bias, float* __restrict__ out, int64_t ldo,
                                                           float* __restrict__ stat) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
-    const int v = (int)blockIdx.x * (RA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), gbase = group_base<G>(), v = group_row<G, RA_BLOCK>();
     if (v >= n) return;                                          // group-uniform
     const int e0 = rowptr[v], e1 = rowptr[v + 1];
     const float erv = sc[(int64_t)v * 4 + 1], prv = sc[(int64_t)v * 4 + 3];
@@ -76,7 +74,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < 3; ++k) beta[k] = den > 0.f ? beta[k] / den : 0.f;
 
-    float acc[NK][VEC];
+    float acc[NK][VEC];                                          // (zero_chunks changes this kernel's code: spelled out)
 #pragma unroll
     for (int k = 0; k < NK; ++k)
 #pragma unroll
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
             const float* __restrict__ row = ft + (int64_t)u * ldf;
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
-                const int c = VEC * (gl + G * k);
+                const int c = chunk_col<G, VEC>(gl, k);
                 if (c < C) {
                     float x[VEC];
                     load_vec<VEC>(x, row + c);
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_fwd_kernel(const float* __restric
     }
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        const int c = VEC * (gl + G * k);
+        const int c = chunk_col<G, VEC>(gl, k);
         if (c < C) {
             if (bias) {
                 float b[VEC];
@@ -138,8 +136,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_src_kernel(const float* __res
                                                               const int32_t* __restrict__ colptr, const int32_t* __restrict__ csc_eid,
                                                               const int32_t* __restrict__ csc_dst, float slope,
                                                               float* __restrict__ g_ft, int64_t ldgf, float* __restrict__ r) {
-    const int lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(G - 1);
-    const int u = (int)blockIdx.x * (RA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), gbase = group_base<G>(), u = group_row<G, RA_BLOCK>();
     if (u >= n) return;                                          // group-uniform
     const int t = ra_type(node_type, u);
     const float el = sc[(int64_t)u * 4];
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_src_kernel(const float* __res
     for (int k = 0; k < NK; ++k) {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { fu[k][j] = 0.f; acc[k][j] = 0.f; }
-        const int c = VEC * (gl + G * k);
+        const int c = chunk_col<G, VEC>(gl, k);
         if (c < C) load_vec<VEC>(fu[k], ft + (int64_t)u * ldf + c);
     }
     const int j0 = colptr[u], j1 = colptr[u + 1];
@@ -170,7 +167,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_src_kernel(const float* __res
             float p = 0.f;
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
-                const int c = VEC * (gl + G * k);
+                const int c = chunk_col<G, VEC>(gl, k);
                 if (c < C) {
                     float g[VEC];
                     load_vec<VEC>(g, row + c);
@@ -184,7 +181,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_src_kernel(const float* __res
     }
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-        const int c = VEC * (gl + G * k);
+        const int c = chunk_col<G, VEC>(gl, k);
         if (c < C) store_vec<VEC>(g_ft + (int64_t)u * ldgf + c, acc[k]);
     }
 }
@@ -195,8 +192,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_dst_kernel(const float* __res
                                                               const int32_t* __restrict__ src, float slope, float* __restrict__ r,
                                                               float* __restrict__ gq, float* __restrict__ g_sc) {
     constexpr int G = RA_S_LANES;
-    const int gl = threadIdx.x & (G - 1);
-    const int v = (int)blockIdx.x * (RA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), v = group_row<G, RA_BLOCK>();
     if (v >= n) return;
     const int e0 = rowptr[v], e1 = rowptr[v + 1];
     const float erv = sc[(int64_t)v * 4 + 1], prv = sc[(int64_t)v * 4 + 3];
@@ -257,8 +253,7 @@ __global__ __launch_bounds__(RA_BLOCK) void ra_bwd_score_kernel(const int32_t* _
                                                                 const float* __restrict__ g_pre, const float* __restrict__ gq,
                                                                 float* __restrict__ g_sc) {
     constexpr int G = RA_S_LANES;
-    const int gl = threadIdx.x & (G - 1);
-    const int u = (int)blockIdx.x * (RA_BLOCK / G) + (int)threadIdx.x / G;
+    const int gl = group_lane<G>(), u = group_row<G, RA_BLOCK>();
     if (u >= n) return;
     const int t = ra_type(node_type, u);
     float gel = 0.f, gpl = 0.f;
@@ -292,39 +287,6 @@ __global__ __launch_bounds__(256) void ra_bias_sum_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------- host side
-struct RaCfg {
-    int G, VEC, NK;
-};
-
-// VEC = 4 when every row and pointer allows 16-byte accesses; G = the smallest power of two (>= 4, <= 64) that covers the row's chunks,
-// NK the power of two of chunks per lane that covers the rest
-static RaCfg ra_cfg(int C, bool vec4_ok) {
-    RaCfg c;
-    c.VEC = (vec4_ok && C % 4 == 0) ? 4 : 1;
-    const int chunks = C / c.VEC;
-    c.G = 4;
-    while (c.G < 64 && c.G < chunks) c.G <<= 1;
-    const int need = (chunks + c.G - 1) / c.G;
-    c.NK = 1;
-    while (c.NK < need) c.NK <<= 1;
-    return c;
-}
-
-#define RA_DISPATCH(cfg, CALL)                                                                                              \
-    do {                                                                                                                   \
-        const int code_ = (cfg).VEC * 100000 + (cfg).G * 100 + (cfg).NK;                                                   \
-        switch (code_) {                                                                                                   \
-            case 400401: CALL(4, 4, 1); break;   case 400801: CALL(8, 4, 1); break;   case 401601: CALL(16, 4, 1); break;  \
-            case 403201: CALL(32, 4, 1); break;  case 406401: CALL(64, 4, 1); break;  case 406402: CALL(64, 4, 2); break;  \
-            case 406404: CALL(64, 4, 4); break;  case 406408: CALL(64, 4, 8); break;  case 406416: CALL(64, 4, 16); break; \
-            case 100401: CALL(4, 1, 1); break;   case 100801: CALL(8, 1, 1); break;   case 101601: CALL(16, 1, 1); break;  \
-            case 103201: CALL(32, 1, 1); break;  case 106401: CALL(64, 1, 1); break;  case 106402: CALL(64, 1, 2); break;  \
-            case 106404: CALL(64, 1, 4); break;  case 106408: CALL(64, 1, 8); break;  case 106416: CALL(64, 1, 16); break; \
-            case 106432: CALL(64, 1, 32); break; case 106464: CALL(64, 1, 64); break;                                      \
-            default: set_error("ra_attn: no kernel for G=%d VEC=%d NK=%d", (cfg).G, (cfg).VEC, (cfg).NK); return WSI_ENOSYS; \
-        }                                                                                                                  \
-    } while (0)
-
 static int ra_check_shape(const char* what, int32_t n, int32_t C) {
     if (n < 0 || C < 1 || C > RA_MAX_WIDTH) {
         set_error("%s: bad shape n=%d C=%d (n >= 0, 1 <= C <= %d)", what, n, C, RA_MAX_WIDTH);
@@ -344,12 +306,12 @@ extern "C" int wsi_ra_attn_fwd(const float* ft, int64_t ldf, const float* sc, co
     if (ldf < C || ldo < C) { set_error("ra_attn_fwd: row stride below C"); return WSI_EINVAL; }
     if (n == 0) return WSI_OK;
     if (!ft || !sc || !node_type || !rowptr || !src || !out || !stat) { set_error("ra_attn_fwd: null pointer"); return WSI_EINVAL; }
-    const RaCfg cfg = ra_cfg(C, ldf % 4 == 0 && ldo % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(bias));
+    const RowCfg cfg = row_cfg(C, C, 1, ldf % 4 == 0 && ldo % 4 == 0 && aligned16(ft) && aligned16(out) && aligned16(bias));
     hipStream_t st = (hipStream_t)stream;
     const int per = RA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((ra_fwd_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(RA_BLOCK), 0, st, ft, ldf, sc, node_type, n, C, \
                                             rowptr, src, negative_slope, bias, out, ldo, stat)
-    RA_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_ALL("ra_attn", cfg, CALL);
 #undef CALL
     return check_launch("ra_attn_fwd");
 }
@@ -372,11 +334,11 @@ extern "C" int wsi_ra_attn_bwd(const float* ft, int64_t ldf, const float* sc, co
         set_error("ra_attn_bwd: null pointer");
         return WSI_EINVAL;
     }
-    const RaCfg cfg = ra_cfg(C, ldf % 4 == 0 && ldg % 4 == 0 && ldgf % 4 == 0 && aligned16(ft) && aligned16(g_out) && aligned16(g_ft));
+    const RowCfg cfg = row_cfg(C, C, 1, ldf % 4 == 0 && ldg % 4 == 0 && ldgf % 4 == 0 && aligned16(ft) && aligned16(g_out) && aligned16(g_ft));
     const int per = RA_BLOCK / cfg.G;
 #define CALL(G_, V_, K_) hipLaunchKernelGGL((ra_bwd_src_kernel<G_, V_, K_>), dim3((n + per - 1) / per), dim3(RA_BLOCK), 0, st, ft, ldf, sc, node_type, stat, \
                                             g_out, ldg, n, C, colptr, csc_eid, csc_dst, negative_slope, g_ft, ldgf, edge_ws)
-    RA_DISPATCH(cfg, CALL);
+    ROW_GROUP_DISPATCH_ALL("ra_attn", cfg, CALL);
 #undef CALL
     constexpr int per_s = RA_BLOCK / RA_S_LANES;
     hipLaunchKernelGGL(ra_bwd_dst_kernel, dim3((n + per_s - 1) / per_s), dim3(RA_BLOCK), 0, st, sc, node_type, stat, n, rowptr, src, negative_slope,

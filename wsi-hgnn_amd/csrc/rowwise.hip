@@ -136,17 +136,6 @@ __global__ __launch_bounds__(RW_BLOCK) void spmm_sum_kernel(const float* __restr
     }
 }
 
-#define WSI_NV_DISPATCH(D, CALL)                 \
-    {                                            \
-        const int nv_ = ((D) + 63) / 64;         \
-        if (nv_ <= 1) { CALL(1); }               \
-        else if (nv_ <= 2) { CALL(2); }          \
-        else if (nv_ <= 4) { CALL(4); }          \
-        else if (nv_ <= 8) { CALL(8); }          \
-        else if (nv_ <= 16) { CALL(16); }        \
-        else { set_error("feature width %d > 1024 unsupported", (D)); return WSI_ENOSYS; } \
-    }
-
 }  // namespace wsi
 
 using namespace wsi;
