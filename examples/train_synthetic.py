@@ -11,6 +11,7 @@ Run on one GPU:            python examples/train_synthetic.py --epochs 2        
                            add --type-mask: slots that also replay batches lacking a node type, DESIGN 3.29;
                            --model GCN --pooling att --captured-slots 3 --captured-eval --optimizer adam: the homogeneous baseline with the
                            attention readout, replayed over homogeneous slots, DESIGN 3.30;
+                           --model GIN --captured-slots 3 --captured-eval --optimizer adam: GIN the same way, DESIGN 3.33;
                            --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers)
 Run data-parallel on N:    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_synthetic.py
 """
@@ -39,7 +40,7 @@ def main(argv=None):
                          "--captured-eval its slots carry the per-relation-source plan, re-derived on the device behind every fill (DESIGN 3.27).  "
                          "GCN: the homogeneous baseline over graph.to_homogeneous slides with self-loops; its slots keep GraphConv's degree norms "
                          "current on the device (DESIGN 3.30).  GIN: the reference's GIN_COAD shape (2 layers, 2-layer MLPs, mean neighbours) over "
-                         "the same homogeneous slides, on the eager path only (DESIGN 3.32)")
+                         "the same homogeneous slides; its slots also keep the live rows and their count on the device, for its BatchNorms (DESIGN 3.33)")
     ap.add_argument("--pooling", choices=("mean", "sum", "max", "att"), default="mean",
                     help="graph_pooling_type.  att: the attention readout - in captured slots one pass over the slot's readout tables (DESIGN 3.30); "
                          "HEATNet4 and HGT apply its first gate, sized for --in-dim, to --hidden-wide states: they need --hidden == --in-dim")
@@ -91,8 +92,6 @@ def main(argv=None):
         td.barrier(device_ids=[local])
     mine = dist.shard(paths, rank, world)                                   # WSI-sharded data parallelism
     graphs = [io.load_graph(p) for p in mine]
-    if args.model == "GIN" and (args.captured_slots or args.captured_eval):
-        raise SystemExit("--model GIN runs on the eager path only (no captured slots: DESIGN 3.32)")
     if args.model in ("GCN", "GIN"):                                        # the reference's homogeneous data set: one node type, self-loops added
         from wsi_hgnn_amd import graph as graph_mod
         graphs = [graph_mod.to_homogeneous(g, add_self_loop=True) for g in graphs]

@@ -708,6 +708,16 @@ int wsi_type_present(const float* seg_nonempty, int32_t T, int32_t graphs, int32
  * float32 device tensor gives (models/GCN.py HomoPlan): the same bits. */
 int wsi_degree_norms(const int32_t* rowptr, const int32_t* colptr, int32_t n, float* in_norm, float* out_norm, void* stream);
 
+/* The live rows of a homogeneous slot (an addition to ABI 26; one node type, so readout segment = graph; models/GIN.py's BatchNorm, DESIGN
+ * 3.33), re-derived behind every fill as wsi_type_present is:
+ *   live[i] = row_seg[i] < b_cap ? 1.0 : 0.0 for the n rows (the filler's rows are dead; the empty graphs have none), and
+ *   live_rows[0] = seg_counts[0] + ... + seg_counts[b_cap - 1], added in index order by one lane (integers below 2^24: exact).
+ * row_seg int32 [n] and seg_counts float [graphs]: the slot's readout tables as wsi_slot_fill / wsi_slot_aug_* have just written them on
+ * `stream`.  One launch, plain loads and vector stores, no atomics, no read-back; every word of live [n] and live_rows [1] is written, and
+ * n == 0 still writes live_rows.  0 <= n, 0 <= b_cap <= graphs. */
+int wsi_slot_live_rows(const int32_t* row_seg, const float* seg_counts, int32_t n, int32_t graphs, int32_t b_cap,
+                       float* live, float* live_rows, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Row-wise kernels of the HGT / GCN siblings of the path.
  *
@@ -1291,6 +1301,21 @@ int wsi_masked_bn_fwd(const float* x, int64_t ldx, int32_t rows, int32_t C, cons
 int wsi_masked_bn_bwd(const float* gy, int64_t ldg, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live,
                       const float* live_rows, const float* gamma, const float* stats, int32_t training, float* partial,
                       float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream);
+
+/* BatchNorm1d + ReLU over the live rows in the same passes (an addition to ABI 26; ops.masked_batch_norm(relu=True), models/GIN.py, DESIGN
+ * 3.33).  With y = fmaf((x - mean) rstd, gamma, beta) exactly as wsi_masked_bn_fwd computes it:
+ *   wsi_masked_bn_relu_fwd writes y > 0 ? y : 0 in live rows and 0 in dead rows (y == 0 is on the zero side); statistics, running
+ *     statistics, stats, workspace and eval mode are those of wsi_masked_bn_fwd - the ReLU enters no statistic.
+ *   wsi_masked_bn_relu_bwd is wsi_masked_bn_bwd with g read as g [y > 0], in the sums and in dx.  It recomputes y from x, the saved stats,
+ *     gamma and beta through the one device function the forward calls, so the sign is the forward's bit for bit; no y and no mask is
+ *     stored or read.  That is why it takes `beta` (NULL: 0), which wsi_masked_bn_bwd has no use for; dbeta is still an output.
+ * Both give the bits of the unfused entry followed / preceded by the elementwise ReLU: the same sums in the same order. */
+int wsi_masked_bn_relu_fwd(const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live, const float* live_rows,
+                           const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t training,
+                           float momentum, float eps, float* partial, float* stats, float* y, int64_t ldy, void* stream);
+int wsi_masked_bn_relu_bwd(const float* gy, int64_t ldg, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live,
+                           const float* live_rows, const float* gamma, const float* beta, const float* stats, int32_t training,
+                           float* partial, float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream);
 
 /* The per-relation-source plan derived from a base plan (an addition to ABI 26; graph.plan_by_relation): the plan HGT's
  * attention runs on, whose source rows are numbered per (relation, source node): row(r, u) = rel_lo[r] + (u - type_off[source type of r]).

@@ -12,6 +12,11 @@
 //   backward   : the same two-level shape for dbeta = sum g and dgamma = sum g xhat (plain sums in one fixed order), then an elementwise pass
 //                dx = gamma rstd (g - dbeta / n - xhat dgamma / n), 0 in dead rows.
 // No atomics; every sum has one order, so identical calls give identical bits.
+//
+// BatchNorm + ReLU in the same passes (wsi_masked_bn_relu_fwd / _bwd; models/GIN.py): a `bool RELU` parameter on the normalise,
+// gradient-sum and dx kernels.  With y = mb_affine(x, mean, rstd, gamma, beta), forward writes y > 0 ? y : 0 and both backward kernels
+// read g as g [y > 0], recomputing y from x and the saved stats through the SAME function: the sign backward sees is the sign forward used,
+// bit for bit, and neither y nor a mask is stored.  y == 0 is on the zero side.  The statistics kernels do not know about the ReLU.
 #include "common.h"
 #include <math.h>
 #include <initializer_list>
@@ -107,8 +112,13 @@ __global__ __launch_bounds__(64) void masked_bn_eval_stats_kernel(const float* _
     if (c < C) { stats[c] = running_mean[c]; stats[C + c] = 1.f / sqrtf(running_var[c] + eps); }
 }
 
-// y = live ? (x - mean) rstd gamma + beta : 0
-template <int V>
+// the affine output of one entry: the one expression forward and (RELU) both backward kernels evaluate
+__device__ __forceinline__ float mb_affine(float x, float mean, float rstd, float gamma, float beta) {
+    return fmaf((x - mean) * rstd, gamma, beta);
+}
+
+// y = live ? (x - mean) rstd gamma + beta : 0;  RELU: max(y, 0), y == 0 and dead rows giving 0
+template <int V, bool RELU>
 __global__ __launch_bounds__(MB_THREADS) void masked_bn_apply_kernel(const float* __restrict__ x, int64_t ldx, int rows, int C,
                                                                      const float* __restrict__ live, const float* __restrict__ gamma,
                                                                      const float* __restrict__ beta, const float* __restrict__ stats,
@@ -121,15 +131,19 @@ __global__ __launch_bounds__(MB_THREADS) void masked_bn_apply_kernel(const float
         const bool alive = live[r] != 0.f;
         if (alive) load_vec<V>(v, x + (int64_t)r * ldx + c);
 #pragma unroll
-        for (int k = 0; k < V; ++k)
-            o[k] = alive ? fmaf((v[k] - stats[c + k]) * stats[C + c + k], gamma ? gamma[c + k] : 1.f, beta ? beta[c + k] : 0.f) : 0.f;
+        for (int k = 0; k < V; ++k) {
+            const float yk = mb_affine(v[k], stats[c + k], stats[C + c + k], gamma ? gamma[c + k] : 1.f, beta ? beta[c + k] : 0.f);
+            o[k] = alive && (!RELU || yk > 0.f) ? yk : 0.f;
+        }
         store_vec<V>(y + (int64_t)r * ldy + c, o);
     }
 }
 
-// chunk partials of dbeta = sum g and dgamma = sum g xhat over the live rows
+// chunk partials of dbeta = sum g and dgamma = sum g xhat over the live rows;  RELU: g counts where the forward's y was > 0
+template <bool RELU>
 __global__ __launch_bounds__(MB_THREADS) void masked_bn_grad_sums_kernel(const float* __restrict__ gy, int64_t ldg, const float* __restrict__ x,
                                                                          int64_t ldx, int rows, int C, const float* __restrict__ live,
+                                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                          const float* __restrict__ stats, float* __restrict__ partial) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -138,6 +152,7 @@ __global__ __launch_bounds__(MB_THREADS) void masked_bn_grad_sums_kernel(const f
     const int r0 = (int)blockIdx.x * MB_CHUNK;
     const int r1 = r0 + MB_CHUNK < rows ? r0 + MB_CHUNK : rows;
     const float mean = has ? stats[c] : 0.f, rstd = has ? stats[C + c] : 0.f;
+    const float gam = (RELU && has && gamma) ? gamma[c] : 1.f, bet = (RELU && has && beta) ? beta[c] : 0.f;
     float sg = 0.f, sgx = 0.f;
     for (int rb = r0 + wave; rb < r1; rb += 4 * MB_UNROLL) {
         float xv[MB_UNROLL], gv[MB_UNROLL];
@@ -147,6 +162,7 @@ __global__ __launch_bounds__(MB_THREADS) void masked_bn_grad_sums_kernel(const f
             const bool ok = r < r1 && has && live[r] != 0.f;
             xv[k] = ok ? x[(int64_t)r * ldx + c] : mean;
             gv[k] = ok ? gy[(int64_t)r * ldg + c] : 0.f;
+            if (RELU) gv[k] = mb_affine(xv[k], mean, rstd, gam, bet) > 0.f ? gv[k] : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < MB_UNROLL; ++k) {
@@ -176,13 +192,15 @@ __global__ __launch_bounds__(64) void masked_bn_grad_finish_kernel(const float* 
     if (lane == 0) { dbeta[c] = sg; dgamma[c] = sgx; }
 }
 
-// training: dx = gamma rstd (g - dbeta / n - xhat dgamma / n);  eval (the statistics are constants): dx = gamma rstd g;  0 in dead rows
-template <int V>
+// training: dx = gamma rstd (g - dbeta / n - xhat dgamma / n);  eval (the statistics are constants): dx = gamma rstd g;  0 in dead rows.
+// RELU: g is taken as 0 where the forward's y was <= 0 (beta is read for that alone)
+template <int V, bool RELU>
 __global__ __launch_bounds__(MB_THREADS) void masked_bn_dx_kernel(const float* __restrict__ gy, int64_t ldg, const float* __restrict__ x, int64_t ldx,
                                                                   int rows, int C, const float* __restrict__ live, const float* __restrict__ live_rows,
-                                                                  const float* __restrict__ gamma, const float* __restrict__ stats,
-                                                                  const float* __restrict__ dgamma, const float* __restrict__ dbeta, bool training,
-                                                                  float* __restrict__ dx, int64_t lddx) {
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ stats, const float* __restrict__ dgamma,
+                                                                  const float* __restrict__ dbeta, bool training, float* __restrict__ dx,
+                                                                  int64_t lddx) {
     const int cv = (C + V - 1) / V;
     const int64_t total = (int64_t)rows * cv;
     const float inv_n = training ? 1.f / live_rows[0] : 0.f;
@@ -195,7 +213,9 @@ __global__ __launch_bounds__(MB_THREADS) void masked_bn_dx_kernel(const float* _
         for (int k = 0; k < V; ++k) {
             if (alive) {
                 const float rstd = stats[C + c + k], xhat = (v[k] - stats[c + k]) * rstd;
-                const float t = training ? g[k] - dbeta[c + k] * inv_n - xhat * (dgamma[c + k] * inv_n) : g[k];
+                float gk = g[k];
+                if (RELU) gk = mb_affine(v[k], stats[c + k], rstd, gamma ? gamma[c + k] : 1.f, beta ? beta[c + k] : 0.f) > 0.f ? gk : 0.f;
+                const float t = training ? gk - dbeta[c + k] * inv_n - xhat * (dgamma[c + k] * inv_n) : gk;
                 o[k] = (gamma ? gamma[c + k] : 1.f) * rstd * t;
             } else o[k] = 0.f;
         }
@@ -223,13 +243,14 @@ using namespace wsi;
 
 extern "C" int32_t wsi_masked_bn_chunks(int32_t rows) { return mb_chunks(rows); }
 
-extern "C" int wsi_masked_bn_fwd(const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live, const float* live_rows,
-                                 const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t training,
-                                 float momentum, float eps, float* partial, float* stats, float* y, int64_t ldy, void* stream) {
-    if (rows < 0 || C <= 0 || ldx < C || ldy < C || !(eps >= 0.f)) { set_error("masked_bn_fwd: bad argument"); return WSI_EINVAL; }
+template <bool RELU>
+static int masked_bn_fwd(const char* who, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live, const float* live_rows,
+                         const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t training, float momentum,
+                         float eps, float* partial, float* stats, float* y, int64_t ldy, void* stream) {
+    if (rows < 0 || C <= 0 || ldx < C || ldy < C || !(eps >= 0.f)) { set_error("%s: bad argument", who); return WSI_EINVAL; }
     if (rows == 0) return WSI_OK;
     if (!x || !live || !stats || !y || (training && (!live_rows || !partial)) || (!training && (!running_mean || !running_var))) {
-        set_error("masked_bn_fwd: null pointer"); return WSI_EINVAL;
+        set_error("%s: null pointer", who); return WSI_EINVAL;
     }
     hipStream_t st = (hipStream_t)stream;
     if (training) {
@@ -242,35 +263,66 @@ extern "C" int wsi_masked_bn_fwd(const float* x, int64_t ldx, int32_t rows, int3
                            (int)C, eps, stats);
     }
     if (mb_vec4(C, {x, y}, {ldx, ldy}))
-        hipLaunchKernelGGL((masked_bn_apply_kernel<4>), dim3(mb_stream_blocks((int64_t)rows * (C / 4))), dim3(MB_THREADS), 0, st, x, ldx, (int)rows,
-                           (int)C, live, gamma, beta, (const float*)stats, y, ldy);
+        hipLaunchKernelGGL((masked_bn_apply_kernel<4, RELU>), dim3(mb_stream_blocks((int64_t)rows * (C / 4))), dim3(MB_THREADS), 0, st, x, ldx,
+                           (int)rows, (int)C, live, gamma, beta, (const float*)stats, y, ldy);
     else
-        hipLaunchKernelGGL((masked_bn_apply_kernel<1>), dim3(mb_stream_blocks((int64_t)rows * C)), dim3(MB_THREADS), 0, st, x, ldx, (int)rows,
-                           (int)C, live, gamma, beta, (const float*)stats, y, ldy);
-    return check_launch("masked_bn_fwd");
+        hipLaunchKernelGGL((masked_bn_apply_kernel<1, RELU>), dim3(mb_stream_blocks((int64_t)rows * C)), dim3(MB_THREADS), 0, st, x, ldx,
+                           (int)rows, (int)C, live, gamma, beta, (const float*)stats, y, ldy);
+    return check_launch(who);
+}
+
+template <bool RELU>
+static int masked_bn_bwd(const char* who, const float* gy, int64_t ldg, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live,
+                         const float* live_rows, const float* gamma, const float* beta, const float* stats, int32_t training, float* partial,
+                         float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream) {
+    if (rows < 0 || C <= 0 || ldg < C || ldx < C || lddx < C) { set_error("%s: bad argument", who); return WSI_EINVAL; }
+    if (!dgamma || !dbeta) { set_error("%s: null pointer", who); return WSI_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = mb_chunks(rows);
+    if (rows > 0 && (!gy || !x || !live || !stats || !partial || !dx || (training && !live_rows))) {
+        set_error("%s: null pointer", who); return WSI_EINVAL;
+    }
+    if (rows > 0)
+        hipLaunchKernelGGL(masked_bn_grad_sums_kernel<RELU>, dim3(chunks, (C + 63) / 64), dim3(MB_THREADS), 0, st, gy, ldg, x, ldx, (int)rows, (int)C,
+                           live, gamma, beta, stats, partial);
+    hipLaunchKernelGGL(masked_bn_grad_finish_kernel, dim3(C), dim3(64), 0, st, (const float*)partial, chunks, (int)C, dgamma, dbeta);
+    if (rows > 0) {
+        if (mb_vec4(C, {gy, x, dx}, {ldg, ldx, lddx}))
+            hipLaunchKernelGGL((masked_bn_dx_kernel<4, RELU>), dim3(mb_stream_blocks((int64_t)rows * (C / 4))), dim3(MB_THREADS), 0, st, gy, ldg, x,
+                               ldx, (int)rows, (int)C, live, live_rows, gamma, beta, stats, (const float*)dgamma, (const float*)dbeta, training != 0,
+                               dx, lddx);
+        else
+            hipLaunchKernelGGL((masked_bn_dx_kernel<1, RELU>), dim3(mb_stream_blocks((int64_t)rows * C)), dim3(MB_THREADS), 0, st, gy, ldg, x, ldx,
+                               (int)rows, (int)C, live, live_rows, gamma, beta, stats, (const float*)dgamma, (const float*)dbeta, training != 0,
+                               dx, lddx);
+    }
+    return check_launch(who);
+}
+
+extern "C" int wsi_masked_bn_fwd(const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live, const float* live_rows,
+                                 const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t training,
+                                 float momentum, float eps, float* partial, float* stats, float* y, int64_t ldy, void* stream) {
+    return masked_bn_fwd<false>("masked_bn_fwd", x, ldx, rows, C, live, live_rows, gamma, beta, running_mean, running_var, training, momentum, eps,
+                                partial, stats, y, ldy, stream);
 }
 
 extern "C" int wsi_masked_bn_bwd(const float* gy, int64_t ldg, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live,
                                  const float* live_rows, const float* gamma, const float* stats, int32_t training, float* partial,
                                  float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream) {
-    if (rows < 0 || C <= 0 || ldg < C || ldx < C || lddx < C) { set_error("masked_bn_bwd: bad argument"); return WSI_EINVAL; }
-    if (!dgamma || !dbeta) { set_error("masked_bn_bwd: null pointer"); return WSI_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    const int chunks = mb_chunks(rows);
-    if (rows > 0 && (!gy || !x || !live || !stats || !partial || !dx || (training && !live_rows))) {
-        set_error("masked_bn_bwd: null pointer"); return WSI_EINVAL;
-    }
-    if (rows > 0)
-        hipLaunchKernelGGL(masked_bn_grad_sums_kernel, dim3(chunks, (C + 63) / 64), dim3(MB_THREADS), 0, st, gy, ldg, x, ldx, (int)rows, (int)C, live,
-                           stats, partial);
-    hipLaunchKernelGGL(masked_bn_grad_finish_kernel, dim3(C), dim3(64), 0, st, (const float*)partial, chunks, (int)C, dgamma, dbeta);
-    if (rows > 0) {
-        if (mb_vec4(C, {gy, x, dx}, {ldg, ldx, lddx}))
-            hipLaunchKernelGGL((masked_bn_dx_kernel<4>), dim3(mb_stream_blocks((int64_t)rows * (C / 4))), dim3(MB_THREADS), 0, st, gy, ldg, x, ldx,
-                               (int)rows, (int)C, live, live_rows, gamma, stats, (const float*)dgamma, (const float*)dbeta, training != 0, dx, lddx);
-        else
-            hipLaunchKernelGGL((masked_bn_dx_kernel<1>), dim3(mb_stream_blocks((int64_t)rows * C)), dim3(MB_THREADS), 0, st, gy, ldg, x, ldx,
-                               (int)rows, (int)C, live, live_rows, gamma, stats, (const float*)dgamma, (const float*)dbeta, training != 0, dx, lddx);
-    }
-    return check_launch("masked_bn_bwd");
+    return masked_bn_bwd<false>("masked_bn_bwd", gy, ldg, x, ldx, rows, C, live, live_rows, gamma, nullptr, stats, training, partial, dgamma, dbeta,
+                                dx, lddx, stream);
+}
+
+extern "C" int wsi_masked_bn_relu_fwd(const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live, const float* live_rows,
+                                      const float* gamma, const float* beta, float* running_mean, float* running_var, int32_t training,
+                                      float momentum, float eps, float* partial, float* stats, float* y, int64_t ldy, void* stream) {
+    return masked_bn_fwd<true>("masked_bn_relu_fwd", x, ldx, rows, C, live, live_rows, gamma, beta, running_mean, running_var, training, momentum,
+                               eps, partial, stats, y, ldy, stream);
+}
+
+extern "C" int wsi_masked_bn_relu_bwd(const float* gy, int64_t ldg, const float* x, int64_t ldx, int32_t rows, int32_t C, const float* live,
+                                      const float* live_rows, const float* gamma, const float* beta, const float* stats, int32_t training,
+                                      float* partial, float* dgamma, float* dbeta, float* dx, int64_t lddx, void* stream) {
+    return masked_bn_bwd<true>("masked_bn_relu_bwd", gy, ldg, x, ldx, rows, C, live, live_rows, gamma, beta, stats, training, partial, dgamma,
+                               dbeta, dx, lddx, stream);
 }

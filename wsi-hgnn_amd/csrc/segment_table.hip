@@ -129,6 +129,19 @@ __global__ __launch_bounds__(256) void degree_norms_kernel(const int32_t* __rest
     out_norm[i] = degree_norm(colptr[i + 1] - colptr[i]);
 }
 
+// Which rows of a filled homogeneous slot belong to its real slides, and how many they are (wsi_slot_live_rows): thread i reads one word of
+// row_seg; thread 0 of the grid adds the b_cap counts in index order (integers below 2^24 as fp32: the sum is exact).
+__global__ __launch_bounds__(256) void slot_live_rows_kernel(const int32_t* __restrict__ row_seg, const float* __restrict__ seg_counts, int n,
+                                                             int b_cap, float* __restrict__ live, float* __restrict__ live_rows) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) live[i] = row_seg[i] < b_cap ? 1.f : 0.f;
+    if (i == 0) {
+        float s = 0.f;
+        for (int b = 0; b < b_cap; ++b) s += seg_counts[b];
+        live_rows[0] = s;
+    }
+}
+
 static int launch_segment_table(const char* who, const int64_t* desc, int32_t nsegs, int32_t total_blocks, void* stream) {
     if (nsegs < 0 || total_blocks < 0) { set_error("%s: bad argument", who); return WSI_EINVAL; }
     if (nsegs == 0 || total_blocks == 0) return WSI_OK;
@@ -162,4 +175,13 @@ extern "C" int wsi_degree_norms(const int32_t* rowptr, const int32_t* colptr, in
     if (!rowptr || !colptr || !in_norm || !out_norm) { set_error("degree_norms: null pointer"); return WSI_EINVAL; }
     hipLaunchKernelGGL(degree_norms_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rowptr, colptr, (int)n, in_norm, out_norm);
     return check_launch("degree_norms");
+}
+
+extern "C" int wsi_slot_live_rows(const int32_t* row_seg, const float* seg_counts, int32_t n, int32_t graphs, int32_t b_cap, float* live,
+                                  float* live_rows, void* stream) {
+    if (n < 0 || graphs < 0 || b_cap < 0 || b_cap > graphs) { set_error("slot_live_rows: bad argument"); return WSI_EINVAL; }
+    if (!live_rows || (!seg_counts && b_cap > 0) || (n > 0 && (!row_seg || !live))) { set_error("slot_live_rows: null pointer"); return WSI_EINVAL; }
+    hipLaunchKernelGGL(slot_live_rows_kernel, dim3(n > 0 ? (n + 255) / 256 : 1), dim3(256), 0, (hipStream_t)stream, row_seg, seg_counts, (int)n,
+                       (int)b_cap, live, live_rows);
+    return check_launch("slot_live_rows");
 }

@@ -456,7 +456,11 @@ class BatchSlot:
     attached to the graph as ``slot.graph._type_present``, where the models' heads read it in place of their host-side test
     (``h[k].shape[0] > 0``) and ``optim``'s gate reads it in place of a ``None`` gradient.  A float32 ``[T]`` device tensor instead of
     ``True`` makes the slot write the caller's table (several slots then share one: ``share_type_table``).  Such a slot takes batches in
-    which NO slide has a node of some type, and an augmented one drops the ``p ** n`` rule of ``fits``.  ``False``: today's slot."""
+    which NO slide has a node of some type, and an augmented one drops the ``p ** n`` rule of ``fits``.  ``False``: today's slot.
+
+    A homogeneous slot (one node type, one relation: ``graph.to_homogeneous`` slides) also keeps, re-derived on the device behind every fill,
+    GraphConv's degree norms and ``live_rows`` = (float32 ``[N]`` 1 / 0 by row, the number of live rows as one float32 word):
+    the rows of the real slides, over which ``models.GIN``'s BatchNorms take their statistics."""
 
     def __init__(self, loader: GraphBatchLoader, capacity=None, bucket: int = 0, per_relation_src: bool = False, quota=None, type_mask=False):
         if not loader.resident:
@@ -552,6 +556,13 @@ class BatchSlot:
             mk = lambda: torch.empty(lay.N, dtype=torch.float32, device=self.device)
             self.degree_norms = self.bufs["in_norm"], self.bufs["out_norm"] = mk(), mk()
             G.__dict__["_homo_plan"] = HomoPlan.over_tables(plan, lay.N, lay.E, *self.degree_norms)
+        # ... and which rows belong to the real slides, with their count: what models.GIN's BatchNorms normalise over - the
+        # filler's rows, often most of the table, enter no statistic - installed where models.GIN.live_rows looks
+        self.live_rows = None
+        if T == 1 and len(rels) == 1:
+            self.live_rows = self.bufs["live"], self.bufs["live_rows"] = (torch.ones(lay.N, dtype=torch.float32, device=self.device),
+                                                                          torch.full((1,), float(lay.N), dtype=torch.float32, device=self.device))
+            G.__dict__["_gin_live"] = self.live_rows
 
     def share_type_table(self, table: torch.Tensor) -> None:
         """Make ``table`` (float32 ``[T]`` on the slot's device) this slot's presence table: every later fill writes it, and the slot graph
@@ -573,6 +584,8 @@ class BatchSlot:
             _graph_mod.derive_type_present(self.layout, self.bufs, self.type_present)
         if self.degree_norms is not None:
             _graph_mod.derive_degree_norms(self.layout, self.bufs, *self.degree_norms)
+        if self.live_rows is not None:
+            _graph_mod.derive_live_rows(self.layout, self.bufs, *self.live_rows)
 
     def quota_of(self, idx: int):
         """``(qn, qe)`` of the loader's slide ``idx`` under this slot's quota rule, never above the stored counts (cached)."""

@@ -1278,6 +1278,29 @@ def derive_degree_norms(lay: SlotLayout, bufs: Dict[str, torch.Tensor], in_norm:
     N.check(N.load().wsi_degree_norms(N.ptr(rowptr), N.ptr(colptr), n, N.ptr(in_norm), N.ptr(out_norm), N.stream()), "wsi_degree_norms")
 
 
+def derive_live_rows(lay: SlotLayout, bufs: Dict[str, torch.Tensor], live: torch.Tensor, live_rows: torch.Tensor) -> None:
+    """The live rows of the batch just filled into a HOMOGENEOUS slot's ``bufs`` (one node type: readout segment = graph), for a BatchNorm
+    that must not see the filler (``models.GIN``, DESIGN 3.33): ``live[i] = 1.0`` where row i belongs to a real slide (``row_seg[i] < b_cap``;
+    the empty graphs have no rows, the filler's are dead), else 0.0, and ``live_rows[0]`` = the number of those rows, the sum of the first
+    ``b_cap`` words of ``seg_counts`` in index order (integers: exact in fp32).  On the current stream behind the fill: ``wsi_slot_live_rows``
+    on the GPU (one launch, no read-back - an augmented slot's counts exist on the device only), the same tensor operations on the CPU (the
+    kernel's oracle)."""
+    if lay.T != 1:
+        raise ValueError("derive_live_rows: a homogeneous slot (one node type)")
+    n, row_seg, counts = lay.N, bufs["row_seg"], bufs["seg_counts"]
+    if (tuple(live.shape) != (n,) or tuple(live_rows.shape) != (1,) or any(t.dtype != torch.float32 or t.device != row_seg.device or
+                                                                           not t.is_contiguous() for t in (live, live_rows))):
+        raise ValueError(f"derive_live_rows: the tables are contiguous float32 [{n}] and [1] tensors on the slot's device")
+    if row_seg.device.type != "cuda":
+        with torch.no_grad():
+            live.copy_((row_seg < lay.b_cap).to(torch.float32))
+            live_rows.copy_(counts.reshape(-1)[:lay.b_cap].sum().reshape(1))      # (integers below 2^24: exact in any order)
+        return
+    from . import _native as N
+    N.check(N.load().wsi_slot_live_rows(N.ptr(row_seg), N.ptr(counts), n, lay.graphs, lay.b_cap, N.ptr(live), N.ptr(live_rows), N.stream()),
+            "wsi_slot_live_rows")
+
+
 def slot_fill_torch(lay: SlotLayout, pieces: Sequence[PlanPieces], labels: Sequence[int], feats: Sequence[Sequence[torch.Tensor]],
                     scales: Optional[Sequence[Sequence[torch.Tensor]]] = None, device="cpu", allow_empty_type: bool = False) -> Dict[str, object]:
     """``slot_fill`` as tensor operations: the CPU path and the kernel's test oracle (the GPU test compares the two bit for bit).  The real

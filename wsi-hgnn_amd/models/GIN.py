@@ -3,7 +3,9 @@
 ``GINConv`` = ``ops.gin_aggregate`` (HIP ``wsi_gin_aggregate_*``: (1 + eps) x + sum | mean | max of the in-neighbours, eps read from its own
 device storage, ``graph.message_scale`` honoured) followed by ``apply_func``.  With a sum or mean reducer and in_features > out_features the
 first Linear of the MLP runs BEFORE the aggregation (both are linear; ``ops.set_gin_project_first``), as ``GraphConv`` does; max always
-aggregates first.  BatchNorm1d is ``ops.masked_batch_norm`` over a table whose rows are all live; Linears are ``ops.linear``.  Classes,
+aggregates first.  BatchNorm1d is ``ops.masked_batch_norm`` over the graph's live rows - all of them, except on the padded batch of a
+``data.BatchSlot``, whose filler rows are dead (the slot keeps the table and the count on the device, ``graph.derive_live_rows``) - and the
+ReLU behind each of the three BatchNorms runs inside its passes (``relu=True``: the composite's bits); Linears are ``ops.linear``.  Classes,
 constructor signatures, parameter creation order and state_dict keys are the reference's.
 
 One deliberate deviation: ``GIN.py:160`` calls ``self.dropout``, which does not exist (``:123`` defines ``self.drop``), so the reference raises
@@ -52,7 +54,8 @@ def _readout(pool: nn.Module, g, h: torch.Tensor) -> torch.Tensor:
 
 
 def live_rows(g, n: int, device):
-    """(live [n] of ones, the row count as one fp32 word) for ``ops.masked_batch_norm``, kept on the graph next to ``_homo_plan``."""
+    """(live [n], the number of live rows as one fp32 word) for ``ops.masked_batch_norm``, kept on the graph next to ``_homo_plan``: ones and
+    n, unless the graph is a homogeneous ``data.BatchSlot``'s, which installs its own device tables here and rewrites them behind every fill."""
     c = g.__dict__.get("_gin_live") if g is not None else None
     if c is None or c[0].device != device or c[0].numel() != n:
         c = (torch.ones(n, dtype=torch.float32, device=device), torch.full((1,), float(n), dtype=torch.float32, device=device))
@@ -62,14 +65,15 @@ def live_rows(g, n: int, device):
 
 
 class BatchNorm1d(nn.BatchNorm1d):
-    """``nn.BatchNorm1d`` (same parameters, buffers and defaults) whose forward is ``ops.masked_batch_norm`` with every row live."""
+    """``nn.BatchNorm1d`` (same parameters, buffers and defaults) whose forward is ``ops.masked_batch_norm`` over the rows ``live`` names
+    (``live_rows``; None: every row).  ``relu=True``: followed by ReLU, inside the same passes on the GPU."""
 
-    def forward(self, x, live=None):
+    def forward(self, x, live=None, relu: bool = False):
         if self.training and x.shape[0] < 2:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
         live = live if live is not None else live_rows(None, x.shape[0], x.device)
         return ops.masked_batch_norm(x, live[0], live[1], self.weight, self.bias, self.running_mean, self.running_var, self.training,
-                                     self.momentum, self.eps, self.num_batches_tracked)
+                                     self.momentum, self.eps, self.num_batches_tracked, relu=relu)
 
 
 class ApplyNodeFunc(nn.Module):
@@ -85,8 +89,7 @@ class ApplyNodeFunc(nn.Module):
 
     def forward(self, h, live=None, projected: bool = False):
         h = self.mlp(h, live, projected)
-        h = self.bn(h, live)
-        return F.relu(h)
+        return self.bn(h, live, relu=True)
 
 
 class MLP(nn.Module):
@@ -118,7 +121,7 @@ class MLP(nn.Module):
         h = x
         for i in range(self.num_layers - 1):
             z = h if (projected and i == 0) else _linear(self.linears[i], h)
-            h = F.relu(self.batch_norms[i](z, live))
+            h = self.batch_norms[i](z, live, relu=True)
         return _linear(self.linears[-1], h)
 
 

@@ -3481,9 +3481,24 @@ def mincut_pool_products(s: torch.Tensor, x: torch.Tensor, rp: ReducePlan):
 # ------------------------------------------------------------------------------------------------
 # BatchNorm1d over the live rows of a padded table (wsi_masked_bn_fwd / _bwd: gtn.GCNBlock on a gtn.GraphSlot)
 # ------------------------------------------------------------------------------------------------
+_FUSED_BN_RELU = {"enabled": True}
+
+
+def set_fused_bn_relu(on: bool) -> None:
+    """On (default): ``masked_batch_norm(relu=True)`` on the GPU is ``wsi_masked_bn_relu_fwd`` / ``_bwd`` - the ReLU inside the normalise,
+    gradient-sum and dx passes.  Off: the composite, ``wsi_masked_bn_fwd`` followed by ``F.relu`` - the same bits, one more read
+    and write of the table forward, two reads and one write backward; for A/B measurements.  Host state, no environment variable."""
+    _FUSED_BN_RELU["enabled"] = bool(on)
+
+
+def fused_bn_relu() -> bool:
+    return _FUSED_BN_RELU["enabled"]
+
+
 class _MaskedBatchNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, y, live, live_rows, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float):
+    def forward(ctx, y, live, live_rows, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float,
+                relu: bool = False):
         N.require_cuda(y, live, live_rows, weight, bias, running_mean, running_var)
         x = y if y.dtype == torch.float32 and (y.shape[1] == 1 or y.stride(1) == 1) and y.stride(0) >= y.shape[1] else y.to(torch.float32).contiguous()
         rows, C = x.shape
@@ -3493,16 +3508,17 @@ class _MaskedBatchNorm(torch.autograd.Function):
         out = torch.empty((rows, C), dtype=torch.float32, device=dev)
         stats = torch.empty((2, C), dtype=torch.float32, device=dev)
         partial = torch.empty(max(3 * lib.wsi_masked_bn_chunks(rows) * C, 1), dtype=torch.float32, device=dev) if training else None
-        N.check(lib.wsi_masked_bn_fwd(N.ptr(x), x.stride(0) if rows > 1 else C, rows, C, N.ptr(live), N.ptr(live_rows), N.ptr(w), N.ptr(b),
-                                      N.ptr(running_mean), N.ptr(running_var), 1 if training else 0, float(momentum), float(eps), N.ptr(partial),
-                                      N.ptr(stats), N.ptr(out), C, N.stream()), "wsi_masked_bn_fwd")
-        ctx.training, ctx.has_w, ctx.has_b = training, weight is not None, bias is not None
-        ctx.save_for_backward(x, live, live_rows, w, stats)
+        fwd = lib.wsi_masked_bn_relu_fwd if relu else lib.wsi_masked_bn_fwd
+        N.check(fwd(N.ptr(x), x.stride(0) if rows > 1 else C, rows, C, N.ptr(live), N.ptr(live_rows), N.ptr(w), N.ptr(b),
+                    N.ptr(running_mean), N.ptr(running_var), 1 if training else 0, float(momentum), float(eps), N.ptr(partial),
+                    N.ptr(stats), N.ptr(out), C, N.stream()), "wsi_masked_bn_relu_fwd" if relu else "wsi_masked_bn_fwd")
+        ctx.training, ctx.has_w, ctx.has_b, ctx.relu = training, weight is not None, bias is not None, relu
+        ctx.save_for_backward(x, live, live_rows, w, stats, b if relu else None)      # (relu: the backward recomputes y's sign, which needs beta)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        x, live, live_rows, w, stats = ctx.saved_tensors
+        x, live, live_rows, w, stats, b = ctx.saved_tensors
         rows, C = x.shape
         dev, lib = x.device, N.load()
         g = g if (C == 1 or g.stride(1) == 1) and g.stride(0) >= C else g.contiguous()
@@ -3510,10 +3526,13 @@ class _MaskedBatchNorm(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=dev)
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         partial = torch.empty(max(2 * lib.wsi_masked_bn_chunks(rows) * C, 1), dtype=torch.float32, device=dev)
-        N.check(lib.wsi_masked_bn_bwd(N.ptr(g), g.stride(0) if rows > 1 else C, N.ptr(x), x.stride(0) if rows > 1 else C, rows, C, N.ptr(live),
-                                      N.ptr(live_rows), N.ptr(w), N.ptr(stats), 1 if ctx.training else 0, N.ptr(partial), N.ptr(dgamma),
-                                      N.ptr(dbeta), N.ptr(dx), C, N.stream()), "wsi_masked_bn_bwd")
-        return dx, None, None, (dgamma if ctx.has_w else None), (dbeta if ctx.has_b else None), None, None, None, None, None
+        head = (N.ptr(g), g.stride(0) if rows > 1 else C, N.ptr(x), x.stride(0) if rows > 1 else C, rows, C, N.ptr(live), N.ptr(live_rows), N.ptr(w))
+        tail = (N.ptr(stats), 1 if ctx.training else 0, N.ptr(partial), N.ptr(dgamma), N.ptr(dbeta), N.ptr(dx), C, N.stream())
+        if ctx.relu:
+            N.check(lib.wsi_masked_bn_relu_bwd(*head, N.ptr(b), *tail), "wsi_masked_bn_relu_bwd")
+        else:
+            N.check(lib.wsi_masked_bn_bwd(*head, *tail), "wsi_masked_bn_bwd")
+        return dx, None, None, (dgamma if ctx.has_w else None), (dbeta if ctx.has_b else None), None, None, None, None, None, None
 
 
 def masked_batch_norm_tensor(y, live, live_rows, weight, bias, running_mean, running_var, training: bool, momentum: float, eps: float):
@@ -3541,14 +3560,19 @@ def masked_batch_norm_tensor(y, live, live_rows, weight, bias, running_mean, run
 
 def masked_batch_norm(y: torch.Tensor, live: torch.Tensor, live_rows: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
                       running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor], training: bool, momentum: Optional[float] = 0.1,
-                      eps: float = 1e-5, num_batches_tracked: Optional[torch.Tensor] = None, kernels: Optional[bool] = None) -> torch.Tensor:
+                      eps: float = 1e-5, num_batches_tracked: Optional[torch.Tensor] = None, kernels: Optional[bool] = None,
+                      relu: bool = False) -> torch.Tensor:
     """``torch.nn.functional.batch_norm`` of the rows of ``y`` [rows, C] with ``live`` [rows] = 1 - and 0 in the others, which enter no
     statistic and receive no gradient.  ``live_rows``: a one-element tensor on y's device holding the number of live rows (at least 2 in
     training - the caller checks: the device cannot raise); no host value of the batch enters, so the call can be recorded.  In training the
     running statistics are updated in place as torch updates them (unbiased variance) and ``num_batches_tracked`` (if given) is incremented;
     in eval mode the running statistics normalise.  ``momentum=None`` (torch's cumulative average) is refused: it needs a host count.
     On the GPU two small launches and one streaming pass each way (``wsi_masked_bn_fwd`` / ``_bwd``; identical calls give identical bits);
-    ``kernels=False`` or a CPU tensor: ``masked_batch_norm_tensor``."""
+    ``kernels=False`` or a CPU tensor: ``masked_batch_norm_tensor``.
+
+    ``relu=True``: ``F.relu`` of the above - on the GPU inside the same passes (``wsi_masked_bn_relu_fwd`` / ``_bwd``: the backward
+    recomputes the sign from y's own expression, no mask and no pre-activation is kept), with the bits of the composite, which
+    ``set_fused_bn_relu(False)`` restores; on the CPU or with ``kernels=False`` the composite itself."""
     if momentum is None:
         raise ValueError("masked_batch_norm: momentum=None (a cumulative moving average) needs a host count of the batches; pass a number")
     if y.dim() != 2 or live.shape != y.shape[:1] or live_rows.numel() != 1:
@@ -3559,10 +3583,14 @@ def masked_batch_norm(y: torch.Tensor, live: torch.Tensor, live_rows: torch.Tens
         num_batches_tracked.add_(1)
     use = y.is_cuda if kernels is None else bool(kernels)
     if not use:
-        return masked_batch_norm_tensor(y, live, live_rows, weight, bias, running_mean, running_var, training, momentum, eps)
+        out = masked_batch_norm_tensor(y, live, live_rows, weight, bias, running_mean, running_var, training, momentum, eps)
+        return torch.relu(out) if relu else out
     if live.dtype != torch.float32 or live_rows.dtype != torch.float32:
         raise ValueError("masked_batch_norm: live and live_rows are fp32 tensors")
-    return _MaskedBatchNorm.apply(y, live.contiguous(), live_rows, weight, bias, running_mean, running_var, bool(training), float(momentum), float(eps))
+    fuse = bool(relu) and fused_bn_relu()
+    out = _MaskedBatchNorm.apply(y, live.contiguous(), live_rows, weight, bias, running_mean, running_var, bool(training), float(momentum),
+                                 float(eps), fuse)
+    return torch.relu(out) if relu and not fuse else out
 
 
 def seq_attention_supported(n: int, head_dim: int) -> bool:

@@ -133,8 +133,8 @@ class CapturedStep:
 
 def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
     """What a capture over batch slots needs of the model and the slots (``CapturedSlotStep``, ``CapturedSlotEval``): a HEAT trunk, HGT over
-    slots that carry the per-relation-source plan, or GCN over homogeneous slots (one node type, one relation: the slot then keeps GraphConv's
-    degree norms current), with any readout ('att' runs from the slot's device tables, ``ops.attention_readout``); slots on the
+    slots that carry the per-relation-source plan, or GCN / GIN over homogeneous slots (one node type, one relation: the slot then keeps
+    GraphConv's degree norms and, for GIN's BatchNorms, the live rows and their count current), with any readout ('att' runs from the slot's device tables, ``ops.attention_readout``); slots on the
     GPU fed by one loader.  Returns (slots as a list, their loader, its device)."""
     from .data import BatchSlot
     from .models.heat_net import HEATTrunk
@@ -145,9 +145,17 @@ def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
         raise ValueError(f"{who}: slots with and without type_mask are mixed - the slots of one capture share one presence table (DESIGN 3.29): "
                          "build all of them with BatchSlot(..., type_mask=True), or none")
     from .models.GCN import GCN
+    from .models.GIN import GIN
     from .models.HGT import HGT
     from .pooling import GlobalAttentionPooling
-    if type(gnn) is GCN:
+    if type(gnn) is GIN:
+        # GIN's BatchNorms take their statistics over the live rows the slot derives on the device behind every fill
+        if not all(getattr(s, "live_rows", None) is not None for s in slots):
+            raise RuntimeError(f"{who}: GIN needs homogeneous slots - a loader of graph.to_homogeneous slides (one node type, one relation) - "
+                               f"or {verb} it eagerly")
+        if any(s.type_mask for s in slots):
+            raise ValueError(f"{who}: type_mask tells the heads of a heterogeneous model which node types a batch holds; GIN has one")
+    elif type(gnn) is GCN:
         if not all(s.degree_norms is not None for s in slots):
             raise RuntimeError(f"{who}: GCN needs homogeneous slots - a loader of graph.to_homogeneous slides (one node type, one relation) - "
                                f"or {verb} it eagerly")
@@ -161,9 +169,9 @@ def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
                                f"BatchSlot(loader, capacity, per_relation_src=True) - or {verb} it eagerly")
     elif not isinstance(gnn, HEATTrunk):
         raise RuntimeError(f"{who}: {type(gnn).__name__} is not supported - HEATNet2 / HEATNet4, HGT over slots built with "
-                           f"per_relation_src=True and GCN over homogeneous slots (HGT + ASAP and HeteroRGCN rebuild host-side structure per "
+                           f"per_relation_src=True and GCN / GIN over homogeneous slots (HGT + ASAP and HeteroRGCN rebuild host-side structure per "
                            f"batch); {verb} it eagerly")
-    if type(gnn) is not GCN and isinstance(gnn.pools[0], GlobalAttentionPooling) and gnn.pools[0].gate_nn.in_features != gnn.n_hid:
+    if type(gnn) not in (GCN, GIN) and isinstance(gnn.pools[0], GlobalAttentionPooling) and gnn.pools[0].gate_nn.in_features != gnn.n_hid:
         # (the reference sizes pools[0]'s gate for in_dim and applies it to hidden_dim-wide node states, models/HEATNet4.py:182-187 and :219)
         raise RuntimeError(f"{who}: the attention readout's first gate reads {gnn.pools[0].gate_nn.in_features} columns but the node states it "
                            f"pools have {gnn.n_hid}: 'att' needs in_dim == hidden_dim; use a sum / mean / max readout")
@@ -173,6 +181,24 @@ def _check_slots(who: str, verb: str, gnn: torch.nn.Module, slots):
     if loader.device.type != "cuda":
         raise RuntimeError(f"{who}: the slots must live on the GPU")
     return slots, loader, loader.device
+
+
+def two_live_rows(slot, idxs: Sequence[int]) -> bool:
+    """Will the batch ``idxs`` (one that fits) leave ``slot`` at least two live rows, which a train-mode BatchNorm over them needs (GIN; the
+    device cannot raise)?  Plain slot: the stored node count n >= 2.  Augmented slot that drops nodes with probability p: fewer than two of n
+    survive with probability p^n + n (1 - p) p^(n - 1), which must stay at or under 2 ** -32, the bound ``BatchSlot.fits`` holds its own
+    rule to (n >= 38 at p = 0.5).  Quota slot: the node quotas must also sum to 2 or more."""
+    n = sum(sum(slot.loader.items[i].num_nodes) for i in idxs)
+    if n < 2:
+        return False
+    spec = slot.spec
+    if spec is not None and spec.node_thr > 0:
+        p = spec.node_thr / 65536.0
+        if p ** n + n * (1.0 - p) * p ** (n - 1) > 2.0 ** -32:
+            return False
+    if slot.quota is not None and sum(sum(slot.quota_of(i)[0]) for i in idxs) < 2:
+        return False
+    return True
 
 
 def _share_type_table(slots):
@@ -203,9 +229,9 @@ def _gate_by_type(who: str, gnn: torch.nn.Module, optimizer, table: torch.Tensor
             optimizer.gate(params, table, t)
 
 
-def _first_slide(who: str, i: int, slot):
-    """The default warm-up batch of slot ``i``: the first slide of the data set that fits it alone."""
-    first = next(([j] for j in sorted(slot.members) if slot.fits([j])), None)
+def _first_slide(who: str, i: int, slot, also=None):
+    """The default warm-up batch of slot ``i``: the first slide of the data set that fits it alone (and passes ``also(slot, [j])``)."""
+    first = next(([j] for j in sorted(slot.members) if slot.fits([j]) and (also is None or also(slot, [j]))), None)
     if first is None:
         raise ValueError(f"{who}: no slide of the data set fits slot {i}")
     return first
@@ -221,10 +247,13 @@ class CapturedSlotStep:
     ``step(idxs)`` takes the smallest slot (fewest node rows) that fits.  A batch no slot fits runs eagerly through the loader's ordinary
     assembly.  Protocol: ``capture.py``; slot by slot the ``warmup`` (1) optimisation steps run on ``warmup_batches[i]`` (default: the slot's
     first fitting batch of one slide) and the slot is captured before the next one warms up; train-mode dropout may be the HEAT and the HGT
-    layers' counter-based draw (all slots advance ONE device word).  HEATNet2 / HEATNet4, and HGT over
-    slots built with ``per_relation_src=True`` (the slot re-derives HGT's plan on the device behind every fill), with a sum / mean /
-    max readout or the attention readout ('att': one pass over the slot's readout tables); HGT + ASAP and HeteroRGCN rebuild
-    host-side structure - those are refused.
+    layers' counter-based draw, GCN's or GIN's inter-layer one (all slots advance ONE device word).  HEATNet2 / HEATNet4, HGT over
+    slots built with ``per_relation_src=True`` (the slot re-derives HGT's plan on the device behind every fill), and GCN / GIN
+    over homogeneous slots, with a sum / mean / max readout or the attention readout ('att': one pass over the slot's
+    readout tables); HGT + ASAP and HeteroRGCN rebuild host-side structure - those are refused.
+
+    GIN in train mode: its BatchNorms run over the slot's live rows, counted on the device, and need two of them - the device cannot raise,
+    so ``slot_for`` sends a batch that might leave fewer to the eager route (``two_live_rows``).
 
     Slots over a loader with a slot-compatible ``transform=`` (``data.slot_augment_spec``) are AUGMENTED: every ``step`` fills its slot with a fresh
     draw taken on the device (no read-back) in front of the replay, a batch no slot fits goes through ``loader._augmented``, and either way the
@@ -248,20 +277,24 @@ class CapturedSlotStep:
         from .models.heat_layer import HEATLayer
         from .models.HGT import HGTLayer
         from .models.GCN import GCN
+        from .models.GIN import GIN
         capture.require_capturable("CapturedSlotStep", optimizer)
         # slots with a presence table: one table for all of them, and the optimizer gated on it
         self.type_table = _share_type_table(self.slots)
         if self.type_table is not None:
             _gate_by_type("CapturedSlotStep", gnn, optimizer, self.type_table)
-        # (an HGTLayer, and GCN's inter-layer dropout, draw counter-based whenever a seed base is active, which it is throughout this class's steps)
-        self.seed_base = capture.new_seed_word(dev) if capture.counter_dropout_only("CapturedSlotStep", gnn, (HEATLayer, HGTLayer, GCN)) else None
+        # (an HGTLayer, and GCN's and GIN's inter-layer dropout, draw counter-based whenever a seed base is active, which it is throughout this
+        # class's steps)
+        self.seed_base = capture.new_seed_word(dev) if capture.counter_dropout_only("CapturedSlotStep", gnn, (HEATLayer, HGTLayer, GCN, GIN)) else None
+        self.two_rows = type(gnn) is GIN
         self.gnn, self.optimizer, self.loss_fcn = gnn, optimizer, loss_fcn
         self.slots, warmup_batches = capture.smallest_first(self.slots, lambda s: s.layout.N, warmup_batches)
         self.params = capture.trainable_params(optimizer)
         self.steps_taken, self.replays, self.eager_steps = 0, 0, 0
         self.graphs, self.outputs = [], []
         for i, slot in enumerate(self.slots):
-            slot.load(list(warmup_batches[i]) if warmup_batches is not None else _first_slide("CapturedSlotStep", i, slot))
+            slot.load(list(warmup_batches[i]) if warmup_batches is not None else
+                      _first_slide("CapturedSlotStep", i, slot, two_live_rows if self.two_rows and gnn.training else None))
             body = lambda: self._eager(slot.graph, slot.labels)
             capture.warm_up(dev, warmup, body)
             self.steps_taken += max(1, warmup)
@@ -280,7 +313,11 @@ class CapturedSlotStep:
         return loss, pred
 
     def slot_for(self, idxs: Sequence[int]):
-        """Index of the smallest slot the batch fits, or None."""
+        """Index of the smallest slot the batch fits, or None.  GIN in train mode: of the slots that leave its BatchNorms two live rows
+        (``two_live_rows``)."""
+        if self.two_rows and self.gnn.training:
+            idxs = list(idxs)
+            return next((i for i, slot in enumerate(self.slots) if slot.fits(idxs) and two_live_rows(slot, idxs)), None)
         return capture.first_fit(self.slots, idxs)
 
     def overflows(self) -> int:
