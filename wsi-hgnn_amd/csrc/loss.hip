@@ -17,6 +17,7 @@ namespace wsi {
 // Any other label outside [0, C) - torch's device assert - sets *bad (if given), zeroes its gradient row and turns the loss into NaN: the failure is
 // visible in the result itself, without a host read.  One workgroup; B * C <= 65536.
 constexpr int64_t CE_IGNORE_INDEX = -100;
+constexpr int CE_BLOCK = 32;
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int B, int C,
                                                             float* __restrict__ loss, float* __restrict__ dlogits, int* __restrict__ bad) {
     __shared__ float part[256];
@@ -47,8 +48,18 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
         }
         float mx = -INFINITY;
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, row[c]);
-        float den = 0.f;
-        for (int c = 0; c < C; ++c) den += expf(row[c] - mx);
+        // the denominator in blocks of CE_BLOCK columns, the block sums added with a compensated sum: in one serial chain a wide row's
+        // partial sum swallows the small terms one by one (C = 65536, logits 3 * randn: 7e-5 of the denominator lost).  C <= CE_BLOCK is
+        // the one chain it always was, bit for bit.
+        float den = 0.f, lost = 0.f;
+        for (int c0 = 0; c0 < C; c0 += CE_BLOCK) {
+            const int c1 = min(c0 + CE_BLOCK, C);
+            float blk = 0.f;
+            for (int c = c0; c < c1; ++c) blk += expf(row[c] - mx);
+            const float add = blk - lost, t = den + add;
+            lost = (t - den) - add;
+            den = t;
+        }
         acc += (logf(den) + mx) - row[y];
         const float inv = 1.f / den;
         for (int c = 0; c < C; ++c) dlogits[(int64_t)b * C + c] = (expf(row[c] - mx) * inv - (c == y ? 1.f : 0.f)) * invB;

@@ -1599,8 +1599,25 @@ def gemm_tn_fp32(groups: Sequence[dict], device) -> None:
 # ------------------------------------------------------------------------------------------------
 # segment dot (skip-gate gradient)
 # ------------------------------------------------------------------------------------------------
+def _unit_columns(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself where the kernels can walk it by a row stride alone (adjacent columns, rows a non-negative stride apart), else a copy."""
+    if (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]):
+        return t
+    return t.contiguous()
+
+
 def segment_dot_diff(g: torch.Tensor, a: torch.Tensor, b: torch.Tensor, rp: "ReducePlan") -> torch.Tensor:
-    """out[s] = sum over rows of segment s and all columns of g * (a - b)."""
+    """out[s] = sum over rows of segment s and all columns of g * (a - b).  g, a, b: [rows, D] float32 on the GPU, rows >= the plan's last
+    row.  A row-strided view (a column slice of a wider table) is read in place; a view whose columns are not adjacent is copied first."""
+    N.require_cuda(g, a, b)
+    for name, t in (("g", g), ("a", a), ("b", b)):
+        if t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError(f"segment_dot_diff: {name} must be a 2-D float32 tensor, got {tuple(t.shape)} {t.dtype}")
+        if t.shape != g.shape or t.device != g.device:
+            raise ValueError(f"segment_dot_diff: {name} is {tuple(t.shape)} on {t.device}, g is {tuple(g.shape)} on {g.device}")
+    if g.shape[1] < 1 or g.shape[0] < rp.first_row + rp.num_rows:
+        raise ValueError(f"segment_dot_diff: the plan covers rows [{rp.first_row}, {rp.first_row + rp.num_rows}) but the tensors are {tuple(g.shape)}")
+    g, a, b = _unit_columns(g), _unit_columns(a), _unit_columns(b)
     lib = N.load()
     D = g.shape[1]
     out = torch.empty(rp.num_segs, dtype=torch.float32, device=g.device)
