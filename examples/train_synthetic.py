@@ -12,7 +12,9 @@ Run on one GPU:            python examples/train_synthetic.py --epochs 2        
                            --model GCN --pooling att --captured-slots 3 --captured-eval --optimizer adam: the homogeneous baseline with the
                            attention readout, replayed over homogeneous slots, DESIGN 3.30;
                            --model GIN --captured-slots 3 --captured-eval --optimizer adam: GIN the same way, DESIGN 3.33;
-                           --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers)
+                           --optimizer sgd|adagrad|adadelta|adam: the package's one-launch optimizers;
+                           --captured-slots 3 --optimizer adam --cosine-lr: CosineAnnealingLR stepped once per epoch on a learning rate kept
+                           as a device word, which every replay reads - nothing is recorded again)
 Run data-parallel on N:    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_synthetic.py
 """
 import argparse
@@ -61,6 +63,10 @@ def main(argv=None):
     ap.add_argument("--quota", action="store_true",
                     help="with --captured-slots and --augment: size the slots for the draw instead of for the stored slides - survivor quotas "
                          "(data.BatchSlot(quota=\"bound\"), DESIGN 3.28); the epoch line then reports in how many fills a quota bound (expected 0)")
+    ap.add_argument("--cosine-lr", action="store_true",
+                    help="step torch.optim.lr_scheduler.CosineAnnealingLR(opt, epochs, 5e-6) once per epoch, as the reference's one-item-per-step "
+                         "baselines do.  With --captured-slots the optimizer is built with the rate as a device word (optim.lr_word, DESIGN 3.34): "
+                         "the scheduler fill_s it and the captured steps follow; without, the rate is a float, as ever")
     ap.add_argument("--captured-eval", action="store_true",
                     help="evaluate through trainer.CapturedSlotEval (DESIGN 3.17): one captured forward per slot, the epoch's metrics accumulated on the "
                          "device and read back once; with --captured-slots the training metrics of the epoch come from the captured step as well")
@@ -135,7 +141,9 @@ def main(argv=None):
     if args.captured_slots:
         if world > 1 or args.optimizer not in ("adam", "sgd", "adadelta"):
             raise SystemExit("--captured-slots: single process and --optimizer adam | sgd | adadelta")
-        if args.optimizer == "adam":
+        if args.cosine_lr:                                                   # the rate a device word (and Adam's count on the device)
+            opt = parser.parse_optimizer({"opt_method": args.optimizer, "lr": 1e-5, "weight_decay": 5e-3}, gnn, native=True, device_lr=True)
+        elif args.optimizer == "adam":
             from wsi_hgnn_amd import optim
             opt = optim.Adam(gnn.parameters(), lr=1e-5, weight_decay=5e-3, capturable=True)         # the step count on the device
         # slot k holds any `batch` slides out of the smallest (k + 1) / K of the data set; the last one every batch
@@ -159,6 +167,10 @@ def main(argv=None):
                                                                                     type_mask=args.type_mask) for c in caps],
                                              metrics=train_metrics)
 
+    # the reference's baselines: CosineAnnealingLR(optimizer, num_epochs, 5e-6), stepped once per epoch.  On a word it ends in a fill_, which
+    # the captured steps read at their next replay; on a float it assigns group["lr"], which an eager step reads
+    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(opt, args.epochs, 5e-6) if args.cosine_lr else None
+
     # 3. epochs
     for epoch in range(args.epochs):
         gnn.train()
@@ -172,12 +184,16 @@ def main(argv=None):
         for G, y in (loader if slot_step is None else ()):
             loss, acc, *_ = trainer.train_one_step(gnn, opt, loss_fn, G, y, dev, bucket=bucket, sync=True)
             tot, n = tot + loss, n + 1
+        if scheduler is not None:
+            scheduler.step()
         gnn.eval()
         metrics = io.evaluate(gnn, eval_loader) if slot_eval is None else slot_eval.evaluate()
         if rank == 0:
             print(f"epoch {epoch}: train loss {tot / max(n, 1):.4f}  eval {metrics}")
             if slot_step is not None:
                 print(f"epoch {epoch}: {slot_step.replays} steps replayed, {slot_step.eager_steps} stepped eagerly so far")
+            if scheduler is not None:
+                print(f"epoch {epoch}: lr for the next epoch {float(opt.param_groups[0]['lr']):.3e}" + (" (a device word)" if slot_step is not None else ""))
             if slot_step is not None and args.quota:                            # one read-back per slot and epoch
                 print(f"epoch {epoch}: fills truncated by a quota so far {slot_step.overflows()} of {slot_step.replays} replayed steps")
             if train_metrics is not None:                                       # train_gnn.py:104-108, one read-back per epoch

@@ -609,6 +609,18 @@ int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t coun
 int wsi_optim_step_gated(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
                          const int32_t* gate_index, const float* gate_table, int32_t gate_len, void* stream);
 
+/* wsi_optim_step_gated with the LEARNING RATE read on the device (an addition to ABI 26; optim.lr_word).  lr_word == NULL: exactly
+ * wsi_optim_step_gated.  Otherwise lr_word is an 8-byte aligned DEVICE pointer to one double, read when the launch runs (lane 0 of every
+ * workgroup loads it next to the count and forms from it in double, in the host's order, what is made of lr: the (float)lr of SGD and
+ * Adadelta, Adam's step_size, Adagrad's clr); hyper->lr is then ignored and not range-checked, and neither host nor kernel checks the word, as
+ * torch checks no tensor lr.  With the double v in the word every output bit (p, s0, s1, step and ticket words) equals those of the same
+ * call with lr_word == NULL and hyper->lr == v.  A rule that reads t takes a word only with a `step` word per tensor: a host count has its
+ * factors taken on the host, which cannot read the word (WSI_EINVAL; torch's tensor lr needs capturable=True for the same reason).  The word
+ * is written by the caller on the same stream between launches (a fill_), never by the library.  The gate arguments as above (NULL, NULL, 0:
+ * nobody is gated). */
+int wsi_optim_step_lr(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
+                      const int32_t* gate_index, const float* gate_table, int32_t gate_len, const double* lr_word, void* stream);
+
 /* Mean cross entropy of logits [B, C] against int64 labels and its gradient factor in ONE launch (torch.nn.CrossEntropyLoss() with its
  * defaults, parser.py:182-183, applied at trainer/train_gnn.py:67):  *loss = mean over the VALID rows b of (logsumexp(logits[b]) - logits[b, y_b]);
  * dlogits[b, c] = (softmax(logits[b])[c] - [c == y_b]) / #valid  (the caller multiplies it by the incoming gradient of the loss).

@@ -24,8 +24,12 @@
   7. Per batch, ``first_fit`` takes the smallest slot that fits (the slots are kept sorted, smallest first); the class fills it, replays its
      graph and returns the recorded outputs cut to the real items.  A batch no slot fits runs the same body eagerly, through the ordinary
      assembly.
-  8. A host hyper-parameter such as ``lr`` is frozen into a capture; the classes with a ``recapture()`` record their graphs again, without
-     stepping, after it changes.
+  8. The learning rate.  A FLOAT ``lr`` is a host value and is frozen into a capture; the classes with a ``recapture()`` record their graphs
+     again, without stepping, after it changes.  A tensor ``lr`` - ``optim.lr_word(value, device)``, a float64 device word - is
+     read by every replay when it runs: change it with ``fill_`` and the next replay steps at the new rate, nothing is recorded again.
+     ``torch.optim.lr_scheduler.*`` work on it unchanged: they ``fill_`` a tensor ``lr`` in place, and with one their arithmetic ends in one
+     ``.item()`` per scheduler step, outside any capture.  Never REBIND ``group["lr"]`` under a captured class: the graph holds the word's
+     pointer.  The other hyper-parameters stay host values.
 
 ``eval_mode`` is what the evaluation classes and the eager evaluators record and run under.
 """
@@ -38,11 +42,20 @@ import torch
 
 
 def require_capturable(who: str, optimizer: torch.optim.Optimizer) -> None:
-    """Every parameter group of ``optimizer`` carries ``capturable=True`` (``optim.SGD`` and ``optim.Adadelta`` read no count and set it)."""
+    """Every parameter group of ``optimizer`` carries ``capturable=True`` (``optim.SGD`` and ``optim.Adadelta`` read no count and set it).  A
+    tensor ``lr`` of the package's own optimizers is a float64 word on the device of the group's parameters (their constructors and first
+    step check the same; a group rebound since is caught here, before it is recorded); ``torch.optim``'s optimizers take a tensor ``lr`` as
+    torch accepts it."""
+    from . import optim
     for group in optimizer.param_groups:
         if not group.get("capturable", False):
             raise RuntimeError(f"{who}: the optimizer must be capturable (wsi_hgnn_amd.optim.Adam(..., capturable=True)): "
                                "its step count has to live on the device, a host count would be frozen into the graph")
+        lr = group.get("lr")
+        if isinstance(lr, torch.Tensor) and isinstance(optimizer, optim._OneLaunch):
+            if lr.dtype != torch.float64 or lr.numel() != 1 or any(p.device != lr.device for p in group["params"]):
+                raise RuntimeError(f"{who}: a tensor lr is a float64 one-element tensor on the parameters' device "
+                                   "(wsi_hgnn_amd.optim.lr_word(value, device)): the recorded step reads it there")
 
 
 def counter_dropout_only(who: str, model: torch.nn.Module, counter_based: Sequence[type] = ()) -> bool:

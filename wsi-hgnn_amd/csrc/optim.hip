@@ -13,6 +13,13 @@
 // draws the last one stores old + 1 and swaps the ticket back to 0.  Nobody waits for anybody: a workgroup has CONSUMED its load of the count
 // (it went through LDS and a barrier) before its add issues, so the one store of the new count comes after every load of the old one, and
 // what this launch writes (elements, count, ticket) is read by the next kernel only - no fence.
+//
+// The learning rate as a device word (wsi_optim_step_lr).  The kernel template has a second parameter, WORD: the five WORD = false instances
+// are the kernels of wsi_optim_step / wsi_optim_step_gated, instruction for instruction what they were before the word existed (T.lr stays a
+// scalar load of the kernel arguments, SGD without a step word stays without a barrier); the five WORD = true instances let the lane that
+// loads the count load the 8-byte word too and form from it, in double and in optim_factors' order, what is made of lr - the (float)lr of
+// SGD and Adadelta, Adam's step_size, Adagrad's clr - and hand it over in the LDS word that carries f0.  The word is written by the host's
+// fill_ on the same stream between launches and only read here: a plain load.
 #include "common.h"
 #include <math.h>
 #include <cmath>
@@ -40,6 +47,7 @@ struct OptimTable {
     float f0, f1;                                         // the factors for t = host_step: Adam step_size, bc2_sqrt; Adagrad clr
     int32_t nesterov;
     const float* gate_table;                              // device words, read by every workgroup of a gated tensor
+    const double* lr_word;                                // wsi_optim_step_lr: one device double read by lane 0 of every workgroup in place of lr_d / lr (else null)
 };
 static_assert(sizeof(OptimTable) <= 5680, "the table travels in the kernel arguments: no larger than the largest argument block this library has "
                                           "launched with (5680 bytes: the 128-tensor table of the Adam kernel this template replaced)");
@@ -60,14 +68,14 @@ __host__ __device__ __forceinline__ void optim_factors(double t, double lr, doub
 
 // one element, torch's order of operations (products that torch rounds on their own in a kernel of their own are rounded here too)
 template <int RULE>
-__device__ __forceinline__ void optim_one(float& p, float g, float& a, float& b, const OptimTable& T, float f0, float f1, bool first) {
+__device__ __forceinline__ void optim_one(float& p, float g, float& a, float& b, const OptimTable& T, float lr, float f0, float f1, bool first) {
     g = fmaf(T.weight_decay, p, g);                                        // every rule: L2 penalty added to the gradient
     if (RULE == R_SGD) {
-        p = fmaf(-T.lr, g, p);
+        p = fmaf(-lr, g, p);
     } else if (RULE == R_SGD_MOMENTUM) {
         a = first ? g : fmaf(T.omd, g, __fmul_rn(T.momentum, a));          // buf.mul_(momentum).add_(grad, alpha=1 - dampening); first step: buf = grad
         g = T.nesterov ? fmaf(T.momentum, a, g) : a;
-        p = fmaf(-T.lr, g, p);
+        p = fmaf(-lr, g, p);
     } else if (RULE == R_ADAGRAD) {
         a = fmaf(g, g, a);                                                 // state_sum.addcmul_(grad, grad, value=1)
         p = fmaf(-f0, g / (sqrtf(a) + T.eps), p);                          // param.addcdiv_(grad, sqrt(sum) + eps, value=-clr)
@@ -75,7 +83,7 @@ __device__ __forceinline__ void optim_one(float& p, float g, float& a, float& b,
         a = fmaf(__fmul_rn(T.omr, g), g, __fmul_rn(T.rho, a));             // square_avg.mul_(rho).addcmul_(grad, grad, value=1 - rho)
         const float d = __fmul_rn(sqrtf(b + T.eps) / sqrtf(a + T.eps), g); // delta = sqrt(acc_delta + eps) / sqrt(square_avg + eps) * grad
         b = fmaf(__fmul_rn(T.omr, d), d, __fmul_rn(T.rho, b));             // acc_delta.mul_(rho).addcmul_(delta, delta, value=1 - rho)
-        p = fmaf(-T.lr, d, p);
+        p = fmaf(-lr, d, p);
     } else {                                                               // Adam: step_size = f0, bc2_sqrt = f1
         a = fmaf(T.omb1, g - a, a);
         b = fmaf(T.beta2, b, T.omb2 * g * g);
@@ -84,7 +92,7 @@ __device__ __forceinline__ void optim_one(float& p, float g, float& a, float& b,
     }
 }
 
-template <int RULE>
+template <int RULE, bool WORD>
 __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
     constexpr int NS = RULE == R_SGD ? 0 : (RULE == R_SGD_MOMENTUM || RULE == R_ADAGRAD) ? 1 : 2;        // state tensors of the rule
     __shared__ float s_t[3];                                               // old count, f0, f1 of this workgroup's tensor
@@ -106,18 +114,21 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
     const bool first = (T.flags[t] & WSI_OPTIM_FIRST) != 0;
     constexpr bool COUNTS = RULE == R_ADAM || RULE == R_ADAGRAD;             // the rules that read t
     float f0 = 0.f, f1 = 0.f, old = 0.f;
-    if (COUNTS || step) {                                                  // (block-uniform; the factors reach the lanes through LDS on both paths:
+    if (WORD || COUNTS || step) {                                          // (block-uniform; the factors reach the lanes through LDS on both paths:
         if (threadIdx.x == 0) {                                            //  a choice between an LDS word and a kernel argument would cost a copy of the table)
             float a0 = T.f0, a1 = T.f1;                                    // t = host_step: taken on the host
+            const double lr_d = WORD ? *T.lr_word : T.lr_d;                // (a rule that reads t takes a word with a step word only: the host checked)
             if (step) {
                 old = __hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                optim_factors<RULE>((double)old + 1.0, T.lr_d, T.lr_decay_d, T.beta1_d, T.beta2_d, a0, a1);
+                optim_factors<RULE>((double)old + 1.0, lr_d, T.lr_decay_d, T.beta1_d, T.beta2_d, a0, a1);
             }
+            if (WORD && !COUNTS) a0 = (float)lr_d;                         // SGD, Adadelta: what the host puts into T.lr, rounded the same way
             s_t[0] = old; s_t[1] = a0; s_t[2] = a1;
         }
         __syncthreads();
         f0 = s_t[1]; f1 = s_t[2];
     }
+    const float lr = WORD ? f0 : T.lr;                                     // (read by SGD and Adadelta only)
     uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g);
     if (NS >= 1) bits |= reinterpret_cast<uintptr_t>(s0);
     if (NS >= 2) bits |= reinterpret_cast<uintptr_t>(s1);
@@ -132,8 +143,8 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
             float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
             if (NS >= 1 && !(RULE == R_SGD_MOMENTUM && first)) av = *reinterpret_cast<const float4*>(s0 + i);
             if (NS >= 2) bv = *reinterpret_cast<const float4*>(s1 + i);
-            optim_one<RULE>(pv.x, gv.x, av.x, bv.x, T, f0, f1, first); optim_one<RULE>(pv.y, gv.y, av.y, bv.y, T, f0, f1, first);
-            optim_one<RULE>(pv.z, gv.z, av.z, bv.z, T, f0, f1, first); optim_one<RULE>(pv.w, gv.w, av.w, bv.w, T, f0, f1, first);
+            optim_one<RULE>(pv.x, gv.x, av.x, bv.x, T, lr, f0, f1, first); optim_one<RULE>(pv.y, gv.y, av.y, bv.y, T, lr, f0, f1, first);
+            optim_one<RULE>(pv.z, gv.z, av.z, bv.z, T, lr, f0, f1, first); optim_one<RULE>(pv.w, gv.w, av.w, bv.w, T, lr, f0, f1, first);
             *reinterpret_cast<float4*>(p + i) = pv;
             if (NS >= 1) *reinterpret_cast<float4*>(s0 + i) = av;
             if (NS >= 2) *reinterpret_cast<float4*>(s1 + i) = bv;
@@ -142,7 +153,7 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
                 float pk = p[i + k], ak = 0.f, bk = 0.f;
                 if (NS >= 1 && !(RULE == R_SGD_MOMENTUM && first)) ak = s0[i + k];
                 if (NS >= 2) bk = s1[i + k];
-                optim_one<RULE>(pk, g[i + k], ak, bk, T, f0, f1, first);
+                optim_one<RULE>(pk, g[i + k], ak, bk, T, lr, f0, f1, first);
                 p[i + k] = pk;
                 if (NS >= 1) s0[i + k] = ak;
                 if (NS >= 2) s1[i + k] = bk;
@@ -161,7 +172,8 @@ __global__ __launch_bounds__(256) void optim_step_kernel(const OptimTable T) {
 
 template <int RULE>
 static void optim_launch(const OptimTable& T, unsigned blocks, hipStream_t st) {
-    hipLaunchKernelGGL(optim_step_kernel<RULE>, dim3(blocks), dim3(256), 0, st, T);
+    if (T.lr_word) hipLaunchKernelGGL((optim_step_kernel<RULE, true>), dim3(blocks), dim3(256), 0, st, T);
+    else hipLaunchKernelGGL((optim_step_kernel<RULE, false>), dim3(blocks), dim3(256), 0, st, T);
 }
 
 }  // namespace wsi
@@ -177,7 +189,7 @@ static int optim_states(int inst) { return inst == R_SGD ? 0 : (inst == R_SGD_MO
 // What the entry points do once every argument is checked: the hyper-parameters into the table, then one launch per OPTIM_MAX non-empty tensors.
 // gate_index: per tensor 0 (no gate) or the 1-based word of gate_table; null: no tensor is gated.
 static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t& H, hipStream_t st,
-                           const int32_t* gate_index = nullptr, const float* gate_table = nullptr) {
+                           const int32_t* gate_index = nullptr, const float* gate_table = nullptr, const double* lr_word = nullptr) {
     const int inst = optim_instance(rule, H), ns = optim_states(inst);
     OptimTable T;
     T.lr_d = H.lr; T.lr_decay_d = H.lr_decay; T.beta1_d = H.beta1; T.beta2_d = H.beta2;
@@ -188,6 +200,7 @@ static void optim_launches(int32_t rule, const wsi_optim_tensor_t* tensors, int3
     T.nesterov = H.nesterov != 0.0;
     T.f0 = T.f1 = 0.f;
     T.gate_table = gate_table;
+    T.lr_word = lr_word;
     if (H.host_step >= 1.0) {
         if (inst == R_ADAM) optim_factors<R_ADAM>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
         if (inst == R_ADAGRAD) optim_factors<R_ADAGRAD>(H.host_step, H.lr, H.lr_decay, H.beta1, H.beta2, T.f0, T.f1);
@@ -248,14 +261,14 @@ extern "C" int wsi_adam_step(const wsi_adam_tensor_t* tensors, int32_t count, do
 }
 
 static int optim_step_checked(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
-                              const int32_t* gate_index, const float* gate_table, void* stream) {
+                              const int32_t* gate_index, const float* gate_table, const double* lr_word, void* stream) {
     // every argument is checked before the first launch: a bad tensor 200 must not leave tensors 0..87 stepped
     if (rule != WSI_OPTIM_SGD && rule != WSI_OPTIM_ADAGRAD && rule != WSI_OPTIM_ADADELTA && rule != WSI_OPTIM_ADAM) { set_error("optim_step: unknown rule %d", rule); return WSI_EINVAL; }
     if (count < 0) { set_error("optim_step: negative tensor count"); return WSI_EINVAL; }
     if (!hyper) { set_error("optim_step: null hyper-parameters"); return WSI_EINVAL; }
     const wsi_optim_hyper_t& H = *hyper;
-    const bool fin = std::isfinite(H.lr) && std::isfinite(H.weight_decay);
-    bool ok = fin && H.lr >= 0.0 && H.weight_decay >= 0.0;
+    // with a word, hyper->lr is ignored: the rate is on the device, where the host cannot look (and the kernel does not, as torch checks no tensor lr)
+    bool ok = (lr_word || (std::isfinite(H.lr) && H.lr >= 0.0)) && std::isfinite(H.weight_decay) && H.weight_decay >= 0.0;
     if (rule == WSI_OPTIM_SGD)
         ok = ok && std::isfinite(H.momentum) && H.momentum >= 0.0 && std::isfinite(H.dampening) && (H.nesterov == 0.0 || H.nesterov == 1.0) &&
              (H.nesterov == 0.0 || (H.momentum > 0.0 && H.dampening == 0.0));
@@ -278,20 +291,21 @@ static int optim_step_checked(int32_t rule, const wsi_optim_tensor_t* tensors, i
         if (a.n == 0) continue;
         ++nonempty;
         if (!a.p || !a.g || (ns >= 1 && !a.s0) || (ns >= 2 && !a.s1)) { set_error("optim_step: tensor %d: null pointer (p, g or a state tensor of the rule)", i); return WSI_EINVAL; }
+        if (counts && !a.step && lr_word) { set_error("optim_step_lr: tensor %d has no step word: with a host count the factors are taken on the host, which cannot read the lr word", i); return WSI_EINVAL; }
         if (counts && !a.step && !(H.host_step >= 1.0 && std::isfinite(H.host_step))) { set_error("optim_step: tensor %d has no step word and host_step is not a count >= 1", i); return WSI_EINVAL; }
         if (counts && !a.step && gate_index && gate_index[i]) { set_error("optim_step_gated: tensor %d is gated and has no step word (a host count advances whether it is stepped or not)", i); return WSI_EINVAL; }
     }
     if (nonempty == 0) return WSI_OK;                  // zero-element tensors only: nothing to launch (and no HIP call)
-    optim_launches(rule, tensors, count, H, (hipStream_t)stream, gate_index, gate_table);
+    optim_launches(rule, tensors, count, H, (hipStream_t)stream, gate_index, gate_table, lr_word);
     return check_launch("optim_step");
 }
 
 extern "C" int wsi_optim_step(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper, void* stream) {
-    return optim_step_checked(rule, tensors, count, hyper, nullptr, nullptr, stream);
+    return optim_step_checked(rule, tensors, count, hyper, nullptr, nullptr, nullptr, stream);
 }
 
-extern "C" int wsi_optim_step_gated(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
-                                    const int32_t* gate_index, const float* gate_table, int32_t gate_len, void* stream) {
+extern "C" int wsi_optim_step_lr(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
+                                 const int32_t* gate_index, const float* gate_table, int32_t gate_len, const double* lr_word, void* stream) {
     if (gate_len < 0 || gate_len > 255) { set_error("optim_step_gated: gate_len %d outside 0..255", gate_len); return WSI_EINVAL; }
     bool any = false;
     for (int32_t i = 0; gate_index && i < count; ++i) {
@@ -299,5 +313,11 @@ extern "C" int wsi_optim_step_gated(int32_t rule, const wsi_optim_tensor_t* tens
         any = any || gate_index[i] != 0;
     }
     if (any && !gate_table) { set_error("optim_step_gated: null gate table"); return WSI_EINVAL; }
-    return optim_step_checked(rule, tensors, count, hyper, any ? gate_index : nullptr, gate_table, stream);
+    if (reinterpret_cast<uintptr_t>(lr_word) & 7) { set_error("optim_step_lr: the lr word is not 8-byte aligned"); return WSI_EINVAL; }
+    return optim_step_checked(rule, tensors, count, hyper, any ? gate_index : nullptr, gate_table, lr_word, stream);
+}
+
+extern "C" int wsi_optim_step_gated(int32_t rule, const wsi_optim_tensor_t* tensors, int32_t count, const wsi_optim_hyper_t* hyper,
+                                    const int32_t* gate_index, const float* gate_table, int32_t gate_len, void* stream) {
+    return wsi_optim_step_lr(rule, tensors, count, hyper, gate_index, gate_table, gate_len, nullptr, stream);
 }

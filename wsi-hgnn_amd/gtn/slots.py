@@ -238,8 +238,11 @@ class CapturedGraphStep:
     itself), as for the other captured steps; no queue setting is touched.
 
     ``step(slides, idxs, labels)`` loads the smallest slot (fewest rows) that fits and replays; a batch no slot fits runs eagerly through
-    ``gtn.train_one_step`` on ``slides.batch(idxs)`` and is counted in ``eager_steps``.  ``recapture()`` records the graphs again without
-    stepping: the optimizer's ``lr`` is a host value frozen into a capture, and the reference steps a ``CosineAnnealingLR`` every epoch."""
+    ``gtn.train_one_step`` on ``slides.batch(idxs)`` and is counted in ``eager_steps``.  The reference steps a ``CosineAnnealingLR`` every epoch
+    (``main_kfold*.py:118-157``).  A FLOAT ``lr`` is a host value frozen into a capture: ``recapture()`` records the graphs again, without
+    stepping, after it changes.  A word - ``optim.Adam(..., lr=optim.lr_word(1e-3, device), capturable=True)`` - is read by every replay:
+    ``torch.optim.lr_scheduler.*`` work on it unchanged (they ``fill_`` a tensor ``lr``; their arithmetic ends in one ``.item()`` per
+    scheduler step, outside any capture) and nothing is recorded again.  Never rebind ``group["lr"]`` here (``capture.py``, point 8)."""
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, slots, warmup: int = 1, warmup_batches=None):
         from .GraphTransformer import Classifier

@@ -324,9 +324,11 @@ class CapturedBagStep:
     is refused: these models draw no counter-based dropout.
 
     ``step(bags, labels)`` loads the smallest slot (fewest rows) that fits and replays; a batch no slot fits runs eagerly through
-    ``mil.train_one_step`` - after ``mil.dropout_patches`` if the slots drop - and is counted in ``eager_steps``.  ``recapture()`` records the
-    graphs again without stepping: the optimizer's ``lr`` is a host value frozen into a capture, and the reference steps a
-    ``CosineAnnealingLR`` every epoch.
+    ``mil.train_one_step`` - after ``mil.dropout_patches`` if the slots drop - and is counted in ``eager_steps``.  The reference steps a
+    ``CosineAnnealingLR`` every epoch.  A FLOAT ``lr`` is a host value frozen into a capture: ``recapture()`` records the graphs again,
+    without stepping, after it changes.  A word - ``optim.Adam(..., lr=optim.lr_word(2e-4, device), capturable=True)`` - is read by every
+    replay: ``torch.optim.lr_scheduler.*`` work on it unchanged (they ``fill_`` a tensor ``lr``; their arithmetic ends in one ``.item()`` per
+    scheduler step, outside any capture) and nothing is recorded again.  Never rebind ``group["lr"]`` here (``capture.py``, point 8).
 
     ReMix needs nothing more - a slot loads from any device tensor::
 

@@ -13,6 +13,15 @@ Adam and Adagrad read the step count.  By default ``state["step"]`` is a Python 
 are taken on the host.  ``capturable=True`` keeps it as a 0-dim fp32 device word, torch's capturable layout, which the kernel itself reads and
 advances: that is what ``trainer.CapturedStep`` needs to replay the step from a hipGraph.  SGD and Adadelta never read a count, so their groups
 always carry ``capturable=True``.
+
+The learning rate may be a device word too: ``lr`` a float64 one-element tensor on the parameters' device, what
+:func:`lr_word` returns and what ``torch.optim`` itself accepts as a tensor ``lr``.  The launch then goes through ``wsi_optim_step_lr`` and the
+kernel reads the rate when it RUNS: no step reads the tensor back, and a step recorded into a hipGraph follows every later ``fill_`` of the word -
+which is how ``torch.optim.lr_scheduler.*`` change a tensor ``lr``.  So under a captured class the rate is changed with ``fill_`` (or by a torch
+scheduler) and ``group["lr"]`` is NEVER rebound: the capture holds the word's pointer.  An eager step follows a rebound ``group["lr"]`` at the
+next step (the cached descriptor table is keyed on the word's ``data_ptr``).  With the double ``v`` in the word a step gives the bits of the
+same step with the float ``lr = v``.  Adam and Adagrad take a word under ``capturable=True`` only: a host count has its factors taken on the
+host, which cannot see the word (torch draws the same line).  All groups that were given the same tensor share one rate.
 """
 from __future__ import annotations
 
@@ -29,6 +38,40 @@ def _refuse(name: str, **unsupported) -> None:
     for k, v in unsupported.items():
         if v:
             raise ValueError(f"wsi_hgnn_amd.optim.{name} has one implementation (one HIP launch) and one algorithm: {k}={v!r} is not supported")
+
+
+def lr_word(value: float, device=None) -> torch.Tensor:
+    """A learning rate the kernels read on the device: a 0-dim float64 tensor on ``device`` holding ``value`` (float64, so that a Python float
+    a scheduler ``fill_``s in is held exactly).  Pass it as ``lr=`` to the optimizers of this module."""
+    return torch.full((), float(value), dtype=torch.float64, device=device)
+
+
+def _check_lr(name: str, lr, reads_count: bool = False, capturable: bool = True) -> None:
+    """The constructors' check of ``lr``: a float is >= 0; a tensor is a device word (never read back here - torch checks no tensor lr either)."""
+    if isinstance(lr, torch.Tensor):
+        if lr.dtype != torch.float64 or lr.numel() != 1:
+            raise ValueError(f"{name}: a tensor lr is a float64 tensor of exactly one element on the parameters' device (got {lr.dtype}, "
+                             f"{lr.numel()} elements): make one with wsi_hgnn_amd.optim.lr_word(value, device)")
+        if reads_count and not capturable:
+            raise ValueError(f"{name}: a tensor lr needs capturable=True - this rule's factors depend on the step count, and with a count kept on "
+                             "the host they are taken on the host, where the word cannot be read without a synchronisation")
+    elif lr < 0.0:
+        raise ValueError(f"{name}: invalid hyper-parameter")
+
+
+def _host_lr(group: dict) -> float:
+    """``hyper->lr``: the float rate, or 0.0 beside a word (wsi_optim_step_lr ignores it) - a tensor is never read back."""
+    lr = group["lr"]
+    return 0.0 if isinstance(lr, torch.Tensor) else float(lr)
+
+
+def _load_into(kept: torch.Tensor, value) -> torch.Tensor:
+    """``kept`` holding ``value`` (a number or a one-element tensor): the object and its ``data_ptr`` stay, which a capture depends on."""
+    if isinstance(value, torch.Tensor):
+        kept.copy_(value.detach().reshape(kept.shape))
+    else:
+        kept.fill_(float(value))
+    return kept
 
 
 def _check_param(name: str, p: torch.Tensor) -> None:
@@ -125,23 +168,55 @@ class _OneLaunch(torch.optim.Optimizer):
     def load_state_dict(self, state_dict) -> None:
         # torch replaces the groups by the saved ones and keeps a saved count as it finds it: where the count lives is this OBJECT'S choice
         # (a checkpoint written by torch.optim, host counts, loads into a capturable optimizer and the other way round)
+        # So is whether the rate is a word: an optimizer built with one keeps THAT tensor (a capture holds its pointer) and fills it with the
+        # loaded value, float or tensor; one built with a float takes float(value).  `initial_lr`, which schedulers add, likewise - a tensor
+        # of its own on the device, never an alias of lr.
         capturable = [g["capturable"] for g in self.param_groups]
+        # The state tensors this object already steps are kept as well where the loaded ones have their shape, dtype and device, and take the
+        # loaded values: a recorded step reads and writes THEM, so a checkpoint loaded under a captured class is what its next replay sees.
+        rates = [(g["lr"], g.get("initial_lr")) for g in self.param_groups]
+        kept = {p: dict(self.state[p]) for g in self.param_groups for p in g["params"] if p in self.state}
         super().load_state_dict(state_dict)
-        for group, cap in zip(self.param_groups, capturable):
+        for group, cap, (lr, initial) in zip(self.param_groups, capturable, rates):
             group["capturable"] = cap
+            if isinstance(lr, torch.Tensor):
+                group["lr"] = _load_into(lr, group["lr"])
+                if "initial_lr" in group:
+                    group["initial_lr"] = _load_into(initial if isinstance(initial, torch.Tensor) else torch.empty_like(lr), group["initial_lr"])
+                elif isinstance(initial, torch.Tensor):
+                    group["initial_lr"] = initial
+            else:
+                group["lr"] = float(group["lr"])
+                if isinstance(group.get("initial_lr"), torch.Tensor):
+                    group["initial_lr"] = float(group["initial_lr"])
             for p in group["params"]:
                 st = self.state.get(p)
-                if st and "step" in st:
+                if not st:
+                    continue
+                old = kept.get(p, {})
+                if "step" in st:
                     if cap:
-                        st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32).reshape(()).to(p.device)
+                        word = old.get("step")
+                        if isinstance(word, torch.Tensor) and word.dtype == torch.float32 and word.dim() == 0 and word.device == p.device:
+                            st["step"] = _load_into(word, st["step"])
+                        else:
+                            st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32).reshape(()).to(p.device)
                     else:
                         st["step"] = int(st["step"])
+                for k, new in st.items():
+                    was = old.get(k)
+                    if (k != "step" and isinstance(new, torch.Tensor) and isinstance(was, torch.Tensor) and was is not new
+                            and (was.shape, was.dtype, was.device, was.is_contiguous()) == (new.shape, new.dtype, new.device, True)):
+                        st[k] = was.copy_(new)
         self.__dict__.pop("_wsi_tables", None)
 
     def _step_group(self, lib, gi: int, group: dict) -> None:
         name = type(self).__name__
         cap = group["capturable"]
         host_counts = self.READS_COUNT and not cap
+        word = group["lr"] if isinstance(group["lr"], torch.Tensor) else None
+        if word is not None and host_counts:
+            raise ValueError(f"{name}: a tensor lr needs capturable=True (the host takes this rule's factors for a host count, and cannot read the word)")
         keys = self._state_keys(group)
         by_step = {}
         for p in group["params"]:
@@ -171,9 +246,14 @@ class _OneLaunch(torch.optim.Optimizer):
         for t, items in by_step.items():                        # (one launch when every parameter has been stepped equally often, or counts on the device)
             # the descriptor table is kept between steps and only the pointers that move are refreshed: the parameter's and the gradient's.  The
             # state tensors, step words included, are replaced by _new_state and load_state_dict only, and both drop the table
-            key = tuple(id(p) for p, _, _, _ in items)
+            key = (tuple(id(p) for p, _, _, _ in items), None if word is None else word.data_ptr())        # (a rebound group["lr"] is followed)
             cached = tables.get(gi)
             if cached is None or cached[0] != key:
+                if word is not None:                            # (the constructor's check again: the group's lr may have been rebound since)
+                    _check_lr(name, word)
+                    if word.device != items[0][0].device:
+                        raise ValueError(f"{name}: the lr tensor lives on {word.device}, the parameters on {items[0][0].device}: make it with "
+                                         "wsi_hgnn_amd.optim.lr_word(value, device)")
                 arr = (N.OptimTensor * len(items))()
                 tick = self._tickets(items[0][0].device)
                 written, empty = [], []                        # every tensor the launch writes; the step words of zero-element tensors
@@ -199,10 +279,14 @@ class _OneLaunch(torch.optim.Optimizer):
             _, arr, arr_p, written, empty, gidx, gtable = cached
             for a, (p, g, _, flags) in zip(arr, items):
                 a.p, a.g, a.flags = p.data_ptr(), g.data_ptr(), flags
-            for word, gate in empty:                             # (no workgroup of the launch covers a zero-element tensor; torch counts its steps too -
-                word += 1 if gate is None else (gate != 0).to(torch.float32)      # those of a gated one where its gate word says so, on the device)
+            for count, gate in empty:                             # (no workgroup of the launch covers a zero-element tensor; torch counts its steps too -
+                count += 1 if gate is None else (gate != 0).to(torch.float32)      # those of a gated one where its gate word says so, on the device)
             hyper.host_step = float(t)
-            if gtable is None:
+            if word is not None:                                 # the rate is read by the launch, on the device: no read-back, nothing a capture freezes
+                N.check(lib.wsi_optim_step_lr(self.RULE, arr_p, len(items), ctypes.addressof(hyper),
+                                              None if gtable is None else ctypes.cast(gidx, ctypes.c_void_p), N.ptr(gtable),
+                                              0 if gtable is None else gtable.numel(), word.data_ptr(), N.stream()), "wsi_optim_step_lr")
+            elif gtable is None:
                 N.check(lib.wsi_optim_step(self.RULE, arr_p, len(items), ctypes.addressof(hyper), N.stream()), "wsi_optim_step")
             else:
                 N.check(lib.wsi_optim_step_gated(self.RULE, arr_p, len(items), ctypes.addressof(hyper), ctypes.cast(gidx, ctypes.c_void_p),
@@ -233,7 +317,8 @@ class SGD(_OneLaunch):
     def __init__(self, params: Iterable, lr: float = 1e-3, momentum: float = 0, dampening: float = 0, weight_decay: float = 0,
                  nesterov: bool = False, *, maximize: bool = False, foreach=None, differentiable: bool = False, fused=None):
         _refuse("SGD", maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
-        if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
+        _check_lr("SGD", lr)
+        if momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("SGD: invalid hyper-parameter")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
@@ -276,7 +361,7 @@ class SGD(_OneLaunch):
         super()._step_group(lib, gi, group)
 
     def _hyper(self, group, h):
-        h.lr, h.weight_decay, h.momentum = float(group["lr"]), float(group["weight_decay"]), float(group["momentum"])
+        h.lr, h.weight_decay, h.momentum = _host_lr(group), float(group["weight_decay"]), float(group["momentum"])
         h.dampening, h.nesterov = float(group["dampening"]), float(bool(group["nesterov"]))
 
 
@@ -289,7 +374,8 @@ class Adagrad(_OneLaunch):
     def __init__(self, params: Iterable, lr: float = 1e-2, lr_decay: float = 0, weight_decay: float = 0, initial_accumulator_value: float = 0,
                  eps: float = 1e-10, foreach=None, *, maximize: bool = False, differentiable: bool = False, fused=None, capturable: bool = False):
         _refuse("Adagrad", maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
-        if lr < 0.0 or lr_decay < 0.0 or weight_decay < 0.0 or initial_accumulator_value < 0.0 or eps < 0.0:
+        _check_lr("Adagrad", lr, True, bool(capturable))
+        if lr_decay < 0.0 or weight_decay < 0.0 or initial_accumulator_value < 0.0 or eps < 0.0:
             raise ValueError("Adagrad: invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, lr_decay=lr_decay, eps=eps, weight_decay=weight_decay,
                                       initial_accumulator_value=initial_accumulator_value, capturable=bool(capturable),
@@ -305,7 +391,7 @@ class Adagrad(_OneLaunch):
         return st
 
     def _hyper(self, group, h):
-        h.lr, h.weight_decay, h.lr_decay, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["lr_decay"]), float(group["eps"])
+        h.lr, h.weight_decay, h.lr_decay, h.eps = _host_lr(group), float(group["weight_decay"]), float(group["lr_decay"]), float(group["eps"])
 
 
 class Adadelta(_OneLaunch):
@@ -318,13 +404,14 @@ class Adadelta(_OneLaunch):
         _refuse("Adadelta", maximize=maximize, foreach=foreach, differentiable=differentiable)
         if not capturable:
             raise ValueError("Adadelta: the count is kept on the device and the rule never reads it - there is no non-capturable form")
-        if lr < 0.0 or not (0.0 <= rho <= 1.0) or eps < 0.0 or weight_decay < 0.0:
+        _check_lr("Adadelta", lr)
+        if not (0.0 <= rho <= 1.0) or eps < 0.0 or weight_decay < 0.0:
             raise ValueError("Adadelta: invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, rho=rho, eps=eps, weight_decay=weight_decay, capturable=True,      # (always: no count is read)
                                       maximize=False, foreach=None, differentiable=False))
 
     def _hyper(self, group, h):
-        h.lr, h.weight_decay, h.rho, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["rho"]), float(group["eps"])
+        h.lr, h.weight_decay, h.rho, h.eps = _host_lr(group), float(group["weight_decay"]), float(group["rho"]), float(group["eps"])
 
 
 class Adam(_OneLaunch):
@@ -338,11 +425,12 @@ class Adam(_OneLaunch):
                  fused=None, decoupled_weight_decay: bool = False):
         _refuse("Adam", amsgrad=amsgrad, foreach=foreach, maximize=maximize, differentiable=differentiable, fused=fused,
                 decoupled_weight_decay=decoupled_weight_decay)
-        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
+        _check_lr("Adam", lr, True, bool(capturable))
+        if eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
             raise ValueError("Adam: invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, capturable=bool(capturable),
                                       amsgrad=False, maximize=False, foreach=None, differentiable=False, fused=None, decoupled_weight_decay=False))
 
     def _hyper(self, group, h):
-        h.lr, h.weight_decay, h.eps = float(group["lr"]), float(group["weight_decay"]), float(group["eps"])
+        h.lr, h.weight_decay, h.eps = _host_lr(group), float(group["weight_decay"]), float(group["eps"])
         h.beta1, h.beta2 = float(group["betas"][0]), float(group["betas"][1])

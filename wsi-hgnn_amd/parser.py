@@ -24,9 +24,11 @@ from torch import nn, optim
 from .models import GAT, GCN, GIN, HGT, HEATNet2, HEATNet4, HeteroRGCN, NTPoolGCN
 
 
-def parse_optimizer(config_optim, model, native=False):
+def parse_optimizer(config_optim, model, native=False, device_lr=False):
     """parser.py:15-46.  ``native=False``: the ``torch.optim`` classes, as the reference builds them.  ``native=True``: the same branch with the
-    same arguments from ``wsi_hgnn_amd.optim`` - every parameter of the model stepped in one HIP launch."""
+    same arguments from ``wsi_hgnn_amd.optim`` - every parameter of the model stepped in one HIP launch.  ``device_lr=True`` (with
+    ``native=True`` only): the rate is ``optim.lr_word(lr, device of the model's parameters)``, read by the launch on the device, and Adam and
+    Adagrad are built ``capturable=True`` - what a captured step needs to follow a ``torch.optim.lr_scheduler`` without being recorded again."""
     opt_method = config_optim["opt_method"].lower()
     alpha = config_optim["lr"]
     weight_decay = config_optim["weight_decay"]
@@ -34,12 +36,20 @@ def parse_optimizer(config_optim, model, native=False):
         from . import optim as O
     else:
         O = optim
+    counts = {}
+    if device_lr:
+        if not native:
+            raise ValueError("parse_optimizer: device_lr=True builds wsi_hgnn_amd.optim's classes (native=True); torch.optim's own optimizers "
+                             "take a tensor lr themselves (lr=torch.tensor(...), capturable=True)")
+        first = next(iter(model.parameters()), None)
+        alpha = O.lr_word(alpha, None if first is None else first.device)
+        counts = {"capturable": True}                               # (the rules that read the count take a word with a device count only)
     if opt_method == "adagrad":
-        return O.Adagrad(model.parameters(), lr=alpha, lr_decay=weight_decay, weight_decay=weight_decay)    # (lr_decay = weight_decay: parser.py:23)
+        return O.Adagrad(model.parameters(), lr=alpha, lr_decay=weight_decay, weight_decay=weight_decay, **counts)    # (lr_decay = weight_decay: parser.py:23)
     if opt_method == "adadelta":
         return O.Adadelta(model.parameters(), lr=alpha, weight_decay=weight_decay)
     if opt_method == "adam":
-        return O.Adam(model.parameters(), lr=alpha, weight_decay=weight_decay)
+        return O.Adam(model.parameters(), lr=alpha, weight_decay=weight_decay, **counts)
     return O.SGD(model.parameters(), lr=alpha, weight_decay=weight_decay)
 
 
